@@ -17,21 +17,27 @@ stream of the batch in one decode call) is timed beside it and reported as `uppe
 value = pixels of all images of all ranks / wall time (Mpixels/s).  N > 1: one process per GPU, each rank codes its own
 24 images (weak scaling); the only exchange is one RCCL all-gather of the per-stream byte lengths per step.
 
-One JSON line is printed by rank 0; besides the driver's contract it carries
+A plain run sets up, warms up, times the --steps steps, checks the last step's result (decode == round(y)), writes that step's
+outputs with --dump-outputs DIR, and prints one JSON line from rank 0: the driver's contract (`ms_per_step` = milliseconds of
+one timed step) and two figures taken from the timed steps themselves:
   roofline         the symtab (encode-side GMM-CDF) kernel: algorithmic bytes (56 B/coded symbol) over its
                    launch duration measured here with HIP events on the stream it runs on, against 8 TB/s HBM
   roofline_decode  the decode-side table kernel against both of its rooflines (VALU issue, HBM), edges per latent
+  ranks            per-rank step times and the all-gather's share (N > 1)
+Everything else is measured with --full only (implied by --diag and --baseline-extras), which also writes the whole result to
+bench_detail.json and stderr:
   cpu_baseline     the REAL reference extension (oracle/_ref, built from /root/reference in the build container; kind
                    "reference"), or this repo's C restatement (kind "port"), timed on this box's host cores on the same
                    images: one core (`value`), and every core this process may use, one stream per process (`all_cores`)
   latency_ms       one image (two bitstreams), encode + decode, as the codec schedules it and all at once
   upper_bound      the step with every stream in one decode call
-  ranks            per-rank step times and the all-gather's share (N > 1)
+  reference_md5    the first four bitstreams against the reference's md5s (tests/golden/ka1.json)
   modes            BASELINE configs[2] in the same run (N = 1): the A&S and logistic approximations on the same batch, a few steps each,
                    the first four bitstreams checked against the reference's md5s (tests/golden/ka1.json: fixtures made from the
                    compiled reference)
   elic4k           BASELINE configs[4] in the same run (N = 1): sixteen 4K images in flight, fp16 parameter planes, a few steps
   checkpointed     the step on checkpointed bitstreams (segments decoded on the GPU), every rank, max over ranks
+  head_fused       the parameter head's last layer fused with the encode-side CDF kernel (N = 1)
 """
 from __future__ import annotations
 
@@ -1083,13 +1089,74 @@ def ka1_check(leg: Leg, res):
     return {"streams": n, "md5_equal_reference": got == want, "md5": got, "source": "tests/golden/ka1.json"}
 
 
+DUMP_MAX_ELEMS = 1 << 22  # --dump-outputs: a larger array is written as a seeded sample of this many elements (16 MB in float32)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_sample(n: int):
+    """fixed positions of an array of n > DUMP_MAX_ELEMS elements: one per equal slice of it, drawn by a seeded generator
+    (the same positions in every run, and for every array of that length), ascending -> int64 array, or None (everything)"""
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    edges = np.arange(DUMP_MAX_ELEMS + 1, dtype=np.int64) * n // DUMP_MAX_ELEMS
+    return edges[:-1] + np.random.default_rng(20240611).integers(0, edges[1:] - edges[:-1])
+
+
+def dump_outputs(path: str, leg: Leg) -> dict:
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, as DIR/<name>.npy - streams in coding order
+    (image-major, stage-minor), each array flattened stream after stream:
+      y_hat              decompress: the decoded latents (float32)
+      y_q                compress: round(y) as the encoder returns it (float32)
+      bitstreams         compress: the bytes of every bitstream, concatenated (float32, 0..255)
+      bitstream_lengths  compress: bytes per bitstream (float64)
+      abs_max            compress: each bitstream's abs_max (float64)
+      zero_bitmaps       compress: each bitstream's per-channel flags, concatenated (float32)
+    An array of more than DUMP_MAX_ELEMS elements is written as the sample _dump_sample picks (the same positions in every run).
+    -> {name: elements written}"""
+    res, outs = leg.last["res"], leg.last["outs"]
+    if leg.stacked:  # outs: one [N', 1, M, h, w] tensor per decode call, call s = every len(outs)-th stream from s
+        strings, abs_max, zb, y_q = res.strings, res.abs_maxes, res.zero_bitmaps.reshape(-1), res.y_q.reshape(-1)
+        y_hat = torch.empty_like(res.y_q)
+        for s, o in enumerate(outs):
+            y_hat[s::len(outs)] = o
+        y_hat = y_hat.reshape(-1)
+    else:
+        strings, abs_max = [r[0][0] for r in res], [r[0][1] for r in res]
+        zb = torch.cat([r[0][2].reshape(-1).cpu() for r in res])
+        y_q = torch.cat([r[1].reshape(-1) for r in res])
+        y_hat = torch.cat([o.reshape(-1) for o in outs])
+
+    def sampled(t):
+        idx = _dump_sample(t.numel())
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.to(torch.float32).cpu().numpy()
+
+    blob = np.frombuffer(b"".join(bytes(b) for b in strings), np.uint8)
+    idx = _dump_sample(blob.size)
+    arrays = {"y_hat": sampled(y_hat), "y_q": sampled(y_q),
+              "bitstreams": (blob if idx is None else blob[idx]).astype(np.float32),
+              "bitstream_lengths": np.array([len(b) for b in strings], np.float64),
+              "abs_max": np.array(abs_max, np.float64), "zero_bitmaps": sampled(zb)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {name: int(arr.size) for name, arr in arrays.items()}
+
+
 def main(argv=None):
     t_bench0 = time.perf_counter()
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the extra legs and sub-legs, the CPU baseline, the comparisons with the reference, "
+                         "the whole result to bench_detail.json and stderr (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--workload", default="kodak24", choices=["kodak24", "elic4k"])
     ap.add_argument("--images", type=int, default=None, help="images per GPU (default 24 for kodak24, 16 for elic4k)")
     ap.add_argument("--param-dtype", default=None, choices=["f32", "f16"], help="default f32 (kodak24) / f16 (elic4k)")
@@ -1127,6 +1194,9 @@ def main(argv=None):
     ap.add_argument("--no-sublegs", action="store_true",
                     help="skip the `modes` (configs[2]) and `elic4k` (configs[4]) legs of the default kodak24 line")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    a.full = a.full or a.diag or a.baseline_extras  # (their legs are part of the full run)
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(a, argv)
@@ -1217,6 +1287,7 @@ def main(argv=None):
         leg.step(a.schedule)
     dt, step_ms = leg.timed(a.schedule, a.steps, record=True)
     res = leg.check_last()
+    dumped = dump_outputs(a.dump_outputs, leg) if a.dump_outputs and rank == 0 else None
     n_coded = leg.coded_symbols(res)
     total_bytes = sum(len(r[0][0]) for r in res)
     enc_table_bytes = _lib.ctx_stat(local_rank, 0)
@@ -1230,7 +1301,7 @@ def main(argv=None):
         per_rank_threads = [int(t[1].item()) for t in gathered]
         checked = int(sum(t[2].item() for t in gathered))
         dt = max(per_rank)
-    ka1 = ka1_check(leg, res)
+    ka1 = ka1_check(leg, res) if a.full else None
 
     extras = {}
     if perf is not None and perf.ok and rank == 0:
@@ -1251,7 +1322,7 @@ def main(argv=None):
                           "note": "perf_event_open, user space, all threads of the process (host workers, calling thread, the runtime's own), per coded "
                                   "symbol of the batch; cycles / instructions / last-level-cache references and misses"}
     payload_ms = None
-    if world > 1:
+    if world > 1 and a.full:
         # the containers themselves, once per run (the timed step exchanges the LENGTHS; a deployment that assembles every
         # image's container on every rank would pay this as well): rank r owns the images r, r + world, ...
         local = [Cn.pack([res[i * spi + s][0] for s in range(spi)], {"y": list(leg.shapes1[0])}) for i in range(a.images)]
@@ -1261,7 +1332,7 @@ def main(argv=None):
         allc = P.gather_containers(local, a.images * world, device=coll_dev)
         payload_ms = env.max_over_ranks((time.perf_counter() - t0) * 1e3)
         assert len(allc) == a.images * world and allc[rank] == local[0]
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         other = "all-at-once" if a.schedule == "codec" else "codec"
         n_ub = max(3, min(a.steps, 10))
         leg.step(other)
@@ -1349,7 +1420,7 @@ def main(argv=None):
             _lib.set_threads(local_rank, threads)
 
     # ---- BASELINE configs[2] and configs[4] in the default line (N = 1): a few steps each, so that the driver's own run witnesses them
-    sublegs = world == 1 and a.workload == "kodak24" and a.mode == "polya" and not f16 and not a.no_sublegs and not a.no_extras and not leg.real
+    sublegs = a.full and world == 1 and a.workload == "kodak24" and a.mode == "polya" and not f16 and not a.no_sublegs and not a.no_extras and not leg.real
     if sublegs:
         t_sub = time.perf_counter()
         modes = {}
@@ -1505,12 +1576,14 @@ def main(argv=None):
                       "allgather_payload_ms": round(payload_ms, 4) if payload_ms is not None else None},
             "reference_md5": ka1,
         }
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": a.dump_outputs, "elements": dumped}
         out.update(extras)
         out["host_throttled"] = bool(step_ms.get("nr_throttled", 0))
         if out["host_throttled"]:
             print(f"[bench] THE CGROUP'S CPU CONTROLLER THROTTLED THIS PROCESS DURING THE TIMED REGION ({step_ms.get('cpu_throttled')}): `value` "
                   f"measures the quota, not the path - fewer host workers (--host-threads, FGMM_WORKERS_PER_CPU) or a larger quota", file=sys.stderr)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cb = cpu_baseline(leg.host, leg.shapes1, pix_per_image, spi, rank, f16, hip_bytes=[bytes(r[0][0]) for r in res], from_seeds=not leg.real,
                               extras=a.baseline_extras)
             if "one_host_thread" in extras and cb.get("value"):
@@ -1538,7 +1611,7 @@ def main(argv=None):
                               "halves decode one after the other: 0.5 + 2 x 1.5 ms against the reference's 42 ms is 12x at best")
             out["cpu_baseline"] = cb
         out["bench_s"] = round(time.perf_counter() - t_bench0, 1)  # this process, argument parsing to here (imports excluded)
-        emit(out)
+        emit(out, detail=a.full)
     if dist:
         dist.destroy_process_group()
 

@@ -1,5 +1,5 @@
 for r in 1 2; do for v in 49 41 33 25; do
-env FGMM_EF_MIN_ROWS=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-sublegs > /tmp/ab_line.json 2>/dev/null
+env FGMM_EF_MIN_ROWS=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-sublegs > /tmp/ab_line.json 2>/dev/null
 python - "ef_min=$v" <<'PY'
 import json, sys, statistics as st
 d = json.load(open("/tmp/ab_detail.json")); sm = d["step_ms"]; ph = sm.get("phases_ms") or {}

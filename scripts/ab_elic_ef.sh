@@ -1,5 +1,5 @@
 for r in 1 2; do for v in 49 33; do
-env FGMM_EF_MIN_ROWS=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --workload elic4k --images 8 --steps 4 --warmup 2 --no-cpu-baseline --no-extras > /tmp/ab_line.json 2>/dev/null
+env FGMM_EF_MIN_ROWS=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --full --workload elic4k --images 8 --steps 4 --warmup 2 --no-cpu-baseline --no-extras > /tmp/ab_line.json 2>/dev/null
 python - "elic ef_min=$v" <<'PY'
 import json, sys, statistics as st
 d = json.load(open("/tmp/ab_detail.json")); sm = d["step_ms"]
@@ -7,7 +7,7 @@ print(f"{sys.argv[1]:16s} value {d['value']:7.1f}  median {sm['median']:7.2f}  c
 PY
 done; done
 for v in 0 6 10 12; do
-env FGMM_PIECES=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-sublegs > /tmp/ab_line.json 2>/dev/null
+env FGMM_PIECES=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-sublegs > /tmp/ab_line.json 2>/dev/null
 python - "pieces=$v" <<'PY'
 import json, sys, statistics as st
 d = json.load(open("/tmp/ab_detail.json")); sm = d["step_ms"]; ph = sm.get("phases_ms") or {}

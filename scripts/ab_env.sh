@@ -5,7 +5,7 @@ set -u
 name=$1; a=$2; b=$3; rounds=${4:-3}
 for r in $(seq 1 $rounds); do
   for v in "$a" "$b"; do
-    env $name=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-sublegs > /tmp/ab_line.json 2>/dev/null
+    env $name=$v FGMM_BENCH_DETAIL=/tmp/ab_detail.json python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-sublegs > /tmp/ab_line.json 2>/dev/null
     python - "$name=$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_detail.json"))

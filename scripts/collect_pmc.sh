@@ -10,8 +10,8 @@ workload=${3:-kodak24}
 steps=${4:-4}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$out/pmc_fetch" "$out/pmc_write"
-FGMM_BENCH_DETAIL="$out/pmc_fetch/detail.json" rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- python3 bench.py --steps $steps --warmup 1 --mode "$mode" --workload "$workload" --no-cpu-baseline --no-extras --schedule all-at-once > "$out/pmc_fetch/bench.json" 2> "$out/pmc_fetch/err.txt"
-FGMM_BENCH_DETAIL="$out/pmc_write/detail.json" rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write" -- python3 bench.py --steps $steps --warmup 1 --mode "$mode" --workload "$workload" --no-cpu-baseline --no-extras --schedule all-at-once > "$out/pmc_write/bench.json" 2> "$out/pmc_write/err.txt"
+FGMM_BENCH_DETAIL="$out/pmc_fetch/detail.json" rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- python3 bench.py --full --steps $steps --warmup 1 --mode "$mode" --workload "$workload" --no-cpu-baseline --no-extras --schedule all-at-once > "$out/pmc_fetch/bench.json" 2> "$out/pmc_fetch/err.txt"
+FGMM_BENCH_DETAIL="$out/pmc_write/detail.json" rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write" -- python3 bench.py --full --steps $steps --warmup 1 --mode "$mode" --workload "$workload" --no-cpu-baseline --no-extras --schedule all-at-once > "$out/pmc_write/bench.json" 2> "$out/pmc_write/err.txt"
 python3 - "$out" "$mode" "$workload" "$steps" <<'PY'
 import csv, glob, json, sys
 out, mode, workload, steps = sys.argv[1], sys.argv[2], sys.argv[3], int(sys.argv[4])

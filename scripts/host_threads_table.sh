@@ -3,7 +3,7 @@
 # host (a 16-CPU quota for the node leaves a rank ~6 workers), plain and checkpointed schedules
 set -u
 for t in ${THREADS:-2 4 6 8 12 16 24 48}; do
-  FGMM_BENCH_DETAIL=/tmp/ht_detail.json python bench.py --steps 12 --warmup 3 --host-threads $t --no-cpu-baseline --no-sublegs > /tmp/ht_line.json 2>/dev/null
+  FGMM_BENCH_DETAIL=/tmp/ht_detail.json python bench.py --full --steps 12 --warmup 3 --host-threads $t --no-cpu-baseline --no-sublegs > /tmp/ht_line.json 2>/dev/null
   python - $t <<'PY'
 import json, sys, statistics as st
 d = json.load(open("/tmp/ht_detail.json")); sm = d["step_ms"]

@@ -4,8 +4,8 @@ set -euo pipefail
 out=${1:-gpurun_out/sweep}
 mkdir -p "$out"
 for m in polya as logistic; do
-  python bench.py --steps 15 --warmup 3 --mode $m --no-cpu-baseline > "$out/kodak24_$m.json"
+  python bench.py --full --steps 15 --warmup 3 --mode $m --no-cpu-baseline > "$out/kodak24_$m.json"
   cat "$out/kodak24_$m.json"
 done
-python bench.py --workload elic4k --steps 5 --warmup 2 --no-cpu-baseline > "$out/elic4k_f16_polya.json"
+python bench.py --full --workload elic4k --steps 5 --warmup 2 --no-cpu-baseline > "$out/elic4k_f16_polya.json"
 cat "$out/elic4k_f16_polya.json"

@@ -291,3 +291,35 @@ def test_a_line_that_would_not_fit_is_refused(monkeypatch, tmp_path):
     full["cpu_baseline"]["sample"] = "x" * 5000
     with pytest.raises(AssertionError, match="driver's window"):
         bench.emit(full)
+
+
+def test_dump_outputs_writes_the_last_step_in_coding_order(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): the last timed step's results as the caller got them - stacked batches decoded in
+    stage-major calls are put back in coding order, list-form batches are concatenated stream after stream; every file is
+    float32 / float64; an array above DUMP_MAX_ELEMS is a sample at fixed, ascending positions, one per equal slice"""
+    import types
+
+    import numpy as np
+    import torch
+    from flashgmm_amd.entropy_models import CompressedBatch
+
+    bench = _load_bench()
+    y_q = torch.arange(4 * 3 * 2 * 2, dtype=torch.float32).reshape(4, 1, 3, 2, 2) - 20
+    strings = [bytes([k]) * (k + 2) for k in range(4)]
+    zb = torch.tensor([[1, 0, 1], [1, 1, 1], [0, 0, 1], [1, 1, 0]])
+    stacked = types.SimpleNamespace(stacked=True, last={"res": CompressedBatch(strings, [5, 6, 7, 8], zb, y_q), "outs": [y_q[0::2], y_q[1::2]]})
+    listed = types.SimpleNamespace(stacked=False, last={"res": [((strings[k], 5 + k, zb[k]), y_q[k]) for k in range(4)], "outs": list(y_q)})
+    for k, leg in enumerate((stacked, listed)):
+        n = bench.dump_outputs(str(tmp_path / str(k)), leg)
+        got = {f: np.load(tmp_path / str(k) / f"{f}.npy") for f in n}
+        assert n == {f: a.size for f, a in got.items()} and set(n) == {"y_hat", "y_q", "bitstreams", "bitstream_lengths", "abs_max", "zero_bitmaps"}
+        assert np.array_equal(got["y_hat"], y_q.reshape(-1).numpy()) and np.array_equal(got["y_q"], got["y_hat"]) and got["y_hat"].dtype == np.float32
+        assert got["bitstreams"].dtype == np.float32 and got["bitstreams"].astype(np.uint8).tobytes() == b"".join(strings)
+        assert got["bitstream_lengths"].tolist() == [2, 3, 4, 5] and got["abs_max"].tolist() == [5, 6, 7, 8]
+        assert got["abs_max"].dtype == np.float64 and np.array_equal(got["zero_bitmaps"], zb.reshape(-1).numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 5)
+    idx = bench._dump_sample(48)
+    assert np.array_equal(idx, bench._dump_sample(48)) and bench._dump_sample(5) is None
+    assert len(idx) == 5 and all(i * 48 // 5 <= v < (i + 1) * 48 // 5 for i, v in enumerate(idx))
+    n = bench.dump_outputs(str(tmp_path / "s"), stacked)
+    assert n["y_hat"] == 5 and np.array_equal(np.load(tmp_path / "s" / "y_hat.npy"), y_q.reshape(-1).numpy()[idx])

@@ -1515,7 +1515,7 @@ def test_bench_two_ranks_rehearsed_on_one_device(tmp_path):
         env.pop(k, None)
     torch.cuda.synchronize()
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--images", "4", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--launch-timeout", "400"], env=env, capture_output=True, text=True, timeout=480)
+                        "--full", "--no-cpu-baseline", "--launch-timeout", "400"], env=env, capture_output=True, text=True, timeout=480)
     assert r.returncode == 0, r.stderr[-3000:]
     line, d = _bench_line_and_detail(r, tmp_path / "detail.json")
     assert line["n_gpus"] == 2 and line["ranks"]["backend"] == "gloo" and len(line["ranks"]["ms_per_step"]) == 2 and line["checkpointed"]["value"] > 0
@@ -1564,7 +1564,7 @@ def test_bench_latents_dir_hook(tmp_path):
         img.append({"pixels": 128 * 192})
         torch.save(img, tmp_path / f"image_{i:02d}.pt")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--latents-dir", str(tmp_path), "--steps", "2", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--latents-dir", str(tmp_path), "--steps", "2", "--warmup", "1", "--full", "--no-extras",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=dict(os.environ, FGMM_BENCH_DETAIL=str(tmp_path / "detail.json")))
     assert r.returncode == 0, r.stderr[-3000:]
     line, d = _bench_line_and_detail(r, tmp_path / "detail.json")
@@ -1577,6 +1577,44 @@ def test_bench_latents_dir_hook(tmp_path):
     assert ph["steps"] == 2 and {"call0_encode.bus", "call1_decode.head", "call2_decode.host_tail", "between_calls"} <= set(ph)
     in_calls = sum(v for k, v in ph.items() if k.endswith((".head", ".bus", ".host_tail", ".end")))
     assert 0 <= ph["between_calls"] and in_calls < d["step_ms"]["max"] * 1.05
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, prints the headline line without the extra legs, writes no
+    detail file, and with --dump-outputs writes what its last timed step returned: two Kodak images = the KA-1 streams (seeds 0..3),
+    so the bitstreams are the reference's bytes (tests/golden/ka1.json) and the decoded latents round(y), in coding order."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir, detail = tmp_path / "out", tmp_path / "detail.json"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--images", "2", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, FGMM_BENCH_DETAIL=str(detail)))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Mpixels/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and len(line["step_ms"]) >= 4
+    assert not {"cpu_baseline", "upper_bound", "checkpointed", "latency_ms", "modes", "elic4k", "head_fused", "detail"} & set(line)
+    assert not detail.exists()
+    got = {n: np.load(out_dir / f"{n}.npy") for n in ("y_hat", "y_q", "bitstreams", "bitstream_lengths", "abs_max", "zero_bitmaps")}
+    assert all(got[n].dtype == np.float32 for n in ("y_hat", "y_q", "bitstreams", "zero_bitmaps"))
+    assert got["bitstream_lengths"].dtype == got["abs_max"].dtype == np.float64
+    ka = json.load(open(os.path.join(GOLD, "ka1.json")))["polya"]
+    blob, at = got["bitstreams"].astype(np.uint8).tobytes(), 0
+    assert len(blob) == int(got["bitstream_lengths"].sum()) and len(got["bitstream_lengths"]) == 4
+    want_y, want_zb = [], []
+    for k, n in enumerate(got["bitstream_lengths"].astype(int)):
+        assert hashlib.md5(blob[at:at + n]).hexdigest() == ka[str(k)]["md5"], k
+        at += n
+        y, sg, mu, pi = T.make_latent(k)
+        sym, s, m, w, abs_max, zb, yq = T.to_coder_inputs(y, sg, mu, pi)
+        assert got["abs_max"][k] == abs_max
+        want_y.append(yq.reshape(-1)), want_zb.append(zb.reshape(-1))
+    assert np.array_equal(got["y_hat"], np.concatenate(want_y)) and np.array_equal(got["y_q"], got["y_hat"])
+    assert np.array_equal(got["zero_bitmaps"], np.concatenate(want_zb).astype(np.float32))
 
 
 def test_a_failed_call_leaves_nothing_in_flight(ctx_options):
