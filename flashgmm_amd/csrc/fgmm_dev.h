@@ -12,14 +12,18 @@ constexpr int kBlock = 256;
 // ---------------------------------------------------------------------------------------------------------
 // wave / block helpers (wave64)
 // ---------------------------------------------------------------------------------------------------------
+// min / max that KEEP NaN, as torch.min / torch.max do (fminf / fmaxf drop it): y.max() of a latent with one NaN is NaN, and
+// abs_max is then 1 (entropy_models.py:834-837) - the channel census must carry the NaN to the host
+__device__ __forceinline__ float min_nan(float a, float b) { return (a < b || a != a) ? a : b; }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  for (int o = 32; o > 0; o >>= 1) v = min_nan(v, __shfl_xor(v, o, 64));
   return v;
 }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
   return v;
 }
 

@@ -424,23 +424,22 @@ struct EncodeCall {
       const int32_t *nz = reinterpret_cast<const int32_t *>(ctx->h_ws + it.o_nz);
       float gmin = INFINITY, gmax = -INFINITY;
       int n_nz = 0;
-      for (int c = 0; c < it.M; ++c) {
-        gmin = fminf(gmin, mn[c]);
-        gmax = fmaxf(gmax, mx[c]);
+      for (int c = 0; c < it.M; ++c) { // NaN is kept, as torch.min / torch.max keep it (quant_stats_kernel's census does too)
+        gmin = (mn[c] < gmin || mn[c] != mn[c]) ? mn[c] : gmin;
+        gmax = (mx[c] > gmax || mx[c] != mx[c]) ? mx[c] : gmax;
         n_nz += nz[c] != 0;
         if (it.zero_bitmap) it.zero_bitmap[c] = nz[c] != 0;
       }
       // max(torch.abs(y.max()).int(), torch.abs(y.min()).int()) + 1, floored at 1   (entropy_models.py:834-837)
-      auto trunc_abs = [](float v) -> int64_t {
-        const float a = fabsf(v);
-        if (!(a < 2147483648.0f)) return INT32_MIN; // torch .int() of an out-of-range float: x86 cvttss2si
-        return (int64_t)(int32_t)a;
-      };
-      int64_t am = (it.M * it.hw) ? std::max(trunc_abs(gmax), trunc_abs(gmin)) + 1 : 1;
+      int64_t am = (it.M * it.hw) ? std::max((int64_t)cvtt_i32(fabsf(gmax)), (int64_t)cvtt_i32(fabsf(gmin))) + 1 : 1;
       if (am < 1) am = 1;
       it.abs_max = (int32_t)am;
       n = (int64_t)n_nz * it.hw;
-      if (n_bypass && am > 32767) {
+      // a latent that is NaN, infinite or beyond int32 is the symbol INT32_MIN (torch's .int()), bypass-coded whatever abs_max is:
+      // its two CDF abscissae are the same float (NaN, +-inf, or |v| >= 2^31 where floats are >= 128 apart: v - 0.5 + 1 == v - 0.5),
+      // here at rint(y) as in the reference at (float)INT32_MIN, so both edges are one evaluation, pmf == 0 and n_bypass > 0
+      const bool out_of_range = !(fabsf(gmax) < 2147483648.0f && fabsf(gmin) < 2147483648.0f);
+      if (n_bypass && (am > 32767 || out_of_range)) {
         // a bypassed symbol may not fit the 16 bits the table carries: fetch the GPU-rounded latents (y_q, written by
         // quant_stats_kernel) and convert them to the int32 symbols - an integer conversion, no arithmetic.  Without a y_q buffer
         // the raw latents are fetched and rounded to nearest-even here (rintf semantics).
@@ -451,7 +450,7 @@ struct EncodeCall {
           if (nz[c])
             for (int64_t p = 0; p < it.hw; ++p) {
               const float v = yv[(size_t)c * it.hw + p];
-              wide_syms[(size_t)i].push_back((int32_t)(it.yq ? v : nearbyintf(v)));
+              wide_syms[(size_t)i].push_back(cvtt_i32(it.yq ? v : nearbyintf(v)));
             }
         syms_for_bypass = wide_syms[(size_t)i].data();
       }

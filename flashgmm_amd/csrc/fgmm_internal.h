@@ -166,6 +166,11 @@ constexpr uint32_t kTabEfDefault = 33;     // ... and are, by default, in the ba
                                            // round 6: with the decoders on a pool of their own, one hardware thread per core, the rows of 33-48 entries
                                            // pay as Elias-Fano too - 57.6 -> 56.6 B/latent, step median 8.83 -> 8.72 ms, CPU per step +2 %)
 constexpr uint32_t kHdr2Escape = 255;
+// torch's .int() of a float as x86-64 does it (cvttss2si): truncation toward zero, INT32_MIN for NaN and out-of-range values.
+// A plain C++ cast of such a float is undefined (and the GPU's v_cvt_i32_f32 saturates instead): make the answer explicit.
+FGMM_HD static inline int32_t cvtt_i32(float f) {
+  return (f > -2147483904.0f && f < 2147483648.0f) ? (int32_t)f : INT32_MIN;
+}
 FGMM_HD static inline uint32_t tab_hdr_pack(int32_t a, uint32_t cnt, uint32_t nonmono) {
   return (uint32_t)(uint16_t)(int16_t)a | ((cnt & 0x7FFFu) << 16) | (nonmono << 31);
 }

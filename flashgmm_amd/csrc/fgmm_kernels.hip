@@ -37,8 +37,8 @@ __global__ __launch_bounds__(kBlock) void quant_stats_kernel(const EncDesc *__re
       const float4 v = *reinterpret_cast<const float4 *>(y + p);
       float4 q;
       q.x = __builtin_rintf(v.x); q.y = __builtin_rintf(v.y); q.z = __builtin_rintf(v.z); q.w = __builtin_rintf(v.w);
-      mn = fminf(fminf(mn, v.x), fminf(fminf(v.y, v.z), v.w));
-      mx = fmaxf(fmaxf(mx, v.x), fmaxf(fmaxf(v.y, v.z), v.w));
+      mn = min_nan(min_nan(mn, v.x), min_nan(min_nan(v.y, v.z), v.w));
+      mx = max_nan(max_nan(mx, v.x), max_nan(max_nan(v.y, v.z), v.w));
       nz |= (q.x != 0.0f) | (q.y != 0.0f) | (q.z != 0.0f) | (q.w != 0.0f);
       if (yq) *reinterpret_cast<float4 *>(yq + p) = q;
     }
@@ -46,8 +46,8 @@ __global__ __launch_bounds__(kBlock) void quant_stats_kernel(const EncDesc *__re
     for (int64_t p = threadIdx.x; p < hw; p += kBlock) {
       const float v = y[p];
       const float q = __builtin_rintf(v); // round-half-even == torch.round
-      mn = fminf(mn, v);
-      mx = fmaxf(mx, v);
+      mn = min_nan(mn, v);
+      mx = max_nan(mx, v);
       nz |= (q != 0.0f);
       if (yq) yq[p] = q;
     }
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void quant_stats_kernel(const EncDesc *__re
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int i = 1; i < kBlock / 64; ++i) {
-      mn = fminf(mn, s_mn[i]); mx = fmaxf(mx, s_mx[i]); nz |= s_nz[i];
+      mn = min_nan(mn, s_mn[i]); mx = max_nan(mx, s_mx[i]); nz |= s_nz[i];
     }
     d.chan_min[c] = mn;
     d.chan_max[c] = mx;

@@ -1,0 +1,402 @@
+"""The edge corpus shared by tests/test_reference_edges_cpu.py and tests/test_gpu_reference_edges.py: seeded generators of
+the inputs where a GMM coder goes wrong, each family a named case so that a failure names its family.  Data only (numpy):
+the expected answers are computed by the compiled reference (tests/ref_worker.py), never stored.
+
+  PARAM_FAMILIES   (sigma, mu, pi) rows [n, 4] float32, plus symbols v and abscissae x1 < x2 for every row
+  FP16_FAMILIES    the same as float16 planes (the device widens them; the reference is fed the widened floats)
+  LATENT_FAMILIES  latents y [1, M, h, w] float32 with ordinary parameters: ties, -0.0, NaN / inf, |y| >= 2^31, and the values
+                   that put abs_max at the limits of the coder's paths
+  STREAM_FAMILIES  what a decoder is given instead of its bitstream: random bytes, truncations, a flipped word
+"""
+from __future__ import annotations
+
+import numpy as np
+
+F32 = np.float32
+I32_MIN, I32_MAX = -(2**31), 2**31 - 1
+
+
+def _rng(name: str, seed: int = 0) -> np.random.Generator:
+    return np.random.default_rng([seed, *name.encode()])
+
+
+def _ordinary(rng, n):
+    """KA-1-like rows: per-row scale e, sigma in [0.11, 2.1] e, mu ~ N(0, e), pi Dirichlet(1)"""
+    e = np.exp(rng.uniform(-2, 2, n))[:, None]
+    sg = (rng.uniform(0, 2, (n, 4)) + 0.11) * e
+    mu = rng.standard_normal((n, 4)) * e
+    pi = rng.dirichlet(np.ones(4), n)
+    return sg.astype(F32), mu.astype(F32), pi.astype(F32)
+
+
+def _spots(rng, n, frac=0.25):
+    """(rows, components) of a random subset of the entries"""
+    m = rng.random((n, 4)) < frac
+    m[rng.integers(0, n, max(1, n // 8)), rng.integers(0, 4, max(1, n // 8))] = True
+    return m
+
+
+def _with(a, mask, vals):
+    a = a.copy()
+    a[mask] = np.resize(np.asarray(vals, F32), int(mask.sum()))
+    return a
+
+
+def _p_wide_sigma(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    return np.exp(rng.uniform(np.log(1e-5), np.log(3e3), (n, 4))).astype(F32), mu, pi
+
+
+def _p_neg_sigma(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    m = _spots(rng, n)
+    return _with(sg, m, -sg[m]), mu, pi
+
+
+def _p_zero_sigma(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    return _with(sg, _spots(rng, n), [0.0, -0.0]), mu, pi
+
+
+def _p_subnormal_sigma(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    sub = np.array([1e-45, 1e-40, 1.1754942e-38, -1e-42, 1.17549435e-38], F32)
+    return _with(sg, _spots(rng, n), sub), mu, pi
+
+
+def _p_nonfinite_sigma(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    return _with(sg, _spots(rng, n, 0.15), [np.inf, -np.inf, np.nan]), mu, pi
+
+
+def _p_huge_mu(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    return sg, _with(mu, _spots(rng, n), [1e30, -1e30, 3e38, -3e38, 3.4028235e38]), pi
+
+
+def _p_nonfinite_mu(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    return sg, _with(mu, _spots(rng, n, 0.15), [np.inf, -np.inf, np.nan]), pi
+
+
+def _p_neg_weights(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    m = _spots(rng, n)
+    return sg, mu, _with(pi, m, -pi[m] * F32(0.7))
+
+
+def _p_weights_over_one(rng, n):
+    """rows whose weights sum above 1 by one ulp .. 1e-4 (the largest component grows)"""
+    sg, mu, pi = _ordinary(rng, n)
+    pi = pi.copy()
+    k = pi.argmax(1)
+    ex = np.where(rng.random(n) < 0.5, np.spacing(F32(1)) * rng.integers(1, 4, n), rng.uniform(1e-7, 1e-4, n)).astype(F32)
+    pi[np.arange(n), k] += ex
+    return sg, mu, pi
+
+
+def _p_nan_weights(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    return sg, mu, _with(pi, _spots(rng, n, 0.1), [np.nan, np.inf, -np.inf])
+
+
+def _p_zero_weights(rng, n):
+    sg, mu, pi = _ordinary(rng, n)
+    pi = pi.copy()
+    pi[rng.random(n) < 0.5] = 0.0
+    return sg, mu, pi
+
+
+def _p_tiny_and_huge_sigma(rng, n):
+    """tiny and huge sigma in the same row"""
+    sg, mu, pi = _ordinary(rng, n)
+    sg = sg.copy()
+    sg[:, 0] = np.exp(rng.uniform(np.log(1e-6), np.log(1e-2), n))
+    sg[:, 3] = np.exp(rng.uniform(np.log(1e2), np.log(1e5), n))
+    return sg, mu, pi
+
+
+def _p_dip_weights(rng, n):
+    """half the rows: 0.6 at -a, -0.3 at 0, 0.35 + 0.35 at +a - a CDF that rises, falls across several edges and rises to 1
+    again: it decreases in the middle of its window only (monotone into both saturated tails)"""
+    sg, mu, pi = _ordinary(rng, n)
+    sg, mu, pi = sg.copy(), mu.copy(), pi.copy()
+    d = rng.random(n) < 0.5
+    a = rng.uniform(6, 12, n)
+    mu[d] = np.stack([-a, rng.uniform(-1, 1, n), a, a + rng.uniform(0, 2, n)], 1)[d]
+    sg[d] = np.stack([np.ones(n), rng.uniform(0.5, 1.5, n), np.ones(n), np.ones(n)], 1)[d]
+    pi[d] = np.array([0.6, -0.3, 0.35, 0.35], F32)
+    return sg, mu, pi
+
+
+PARAM_FAMILIES = {
+    "wide_sigma": _p_wide_sigma,
+    "neg_sigma": _p_neg_sigma,
+    "zero_sigma": _p_zero_sigma,
+    "subnormal_sigma": _p_subnormal_sigma,
+    "nonfinite_sigma": _p_nonfinite_sigma,
+    "huge_mu": _p_huge_mu,
+    "nonfinite_mu": _p_nonfinite_mu,
+    "neg_weights": _p_neg_weights,
+    "weights_over_one": _p_weights_over_one,
+    "nan_weights": _p_nan_weights,
+    "zero_weights": _p_zero_weights,
+    "tiny_and_huge_sigma": _p_tiny_and_huge_sigma,
+    "dip_weights": _p_dip_weights,
+}
+
+
+def symbols_for(rng, mu, n):
+    """symbols: mostly near the row's first mean (the coded range), some anywhere in int32 and at its ends"""
+    near = np.clip(np.nan_to_num(mu[:, 0], nan=0.0, posinf=0.0, neginf=0.0), -40, 40)
+    v = np.rint(near + rng.standard_normal(n) * 4).astype(np.int64)
+    far = rng.random(n) < 0.1
+    v[far] = rng.integers(I32_MIN, I32_MAX, int(far.sum()), endpoint=True)
+    ends = rng.random(n) < 0.02
+    v[ends] = rng.choice([I32_MIN, I32_MIN + 1, I32_MAX, -32768, 32767, 2**31 - 128, -(2**31) + 128], int(ends.sum()))
+    return v.astype(np.int32)
+
+
+def abscissae_for(rng, n):
+    """arbitrary float abscissae x1 < x2 (any distance, far tails, the int32 ends)"""
+    x1 = (rng.standard_normal(n) * np.exp(rng.uniform(-3, 25, n))).astype(F32)
+    x2 = (x1 + np.exp(rng.uniform(-10, 10, n))).astype(F32)
+    return x1, x2
+
+
+def param_case(family: str, n: int = 4096, seed: int = 0):
+    """-> dict(s, m, w [n, 4] float32; v int32 [n]; x1, x2 float32 [n])"""
+    rng = _rng(family, seed)
+    s, m, w = PARAM_FAMILIES[family](rng, n)
+    v = symbols_for(rng, m, n)
+    x1, x2 = abscissae_for(rng, n)
+    return {"s": np.ascontiguousarray(s, F32), "m": np.ascontiguousarray(m, F32), "w": np.ascontiguousarray(w, F32),
+            "v": v, "x1": x1, "x2": x2}
+
+
+def param_case_after(family: str, n: int, n_head: int, seed: int = 0):
+    """param_case whose first n_head rows are ordinary ones: the family's rows only from n_head on (a checkpointed stream's
+    last segment holds them alone, so no note downstream of them can catch a wrong symbol there)"""
+    c = param_case(family, n, seed)
+    s, m, w = _ordinary(_rng(family + "/head", seed), n_head)
+    c["s"][:n_head], c["m"][:n_head], c["w"][:n_head] = s, m, w
+    return c
+
+
+# ---- fp16 planes ------------------------------------------------------------------------------------------------------
+def _h_subnormal(rng, n):
+    s, m, w = _ordinary(rng, n)
+    s16, m16, w16 = s.astype(np.float16), m.astype(np.float16), w.astype(np.float16)
+    sub = np.array([6e-8, 1e-6, 3e-5, 6.1e-5], np.float16)  # the subnormal halves (the smallest normal one is 6.104e-5)
+    mk = _spots(rng, n)
+    s16[mk] = np.resize(sub, int(mk.sum()))
+    mk = _spots(rng, n)
+    m16[mk] = np.resize(-sub, int(mk.sum()))
+    return s16, m16, w16
+
+
+def _h_max(rng, n):
+    s, m, w = _ordinary(rng, n)
+    s16, m16, w16 = s.astype(np.float16), m.astype(np.float16), w.astype(np.float16)
+    mk = _spots(rng, n)
+    m16[mk] = np.resize(np.array([65504, -65504], np.float16), int(mk.sum()))
+    sk = _spots(rng, n, 0.1)
+    s16[sk] = np.float16(65504)
+    return s16, m16, w16
+
+
+def _h_inf(rng, n):
+    s, m, w = _ordinary(rng, n)
+    s16, m16, w16 = s.astype(np.float16), m.astype(np.float16), w.astype(np.float16)
+    for a in (s16, m16):
+        mk = _spots(rng, n, 0.08)
+        a[mk] = np.resize(np.array([np.inf, -np.inf], np.float16), int(mk.sum()))
+    return s16, m16, w16
+
+
+def _h_weights_nearest(rng, n):
+    """weights rounded to NEAREST (tests/synth.py's helper rounds toward zero): some rows sum above 1"""
+    s, m, w = _ordinary(rng, n)
+    return s.astype(np.float16), m.astype(np.float16), w.astype(np.float16)
+
+
+FP16_FAMILIES = {
+    "f16_subnormal": _h_subnormal,
+    "f16_max": _h_max,
+    "f16_inf": _h_inf,
+    "f16_weights_nearest": _h_weights_nearest,
+}
+
+
+def fp16_case(family: str, M: int = 8, h: int = 8, w: int = 12, seed: int = 0):
+    """-> (y [1, M, h, w] float32, sigma, mu, pi planes [1, 4M, h, w] float16)"""
+    rng = _rng(family, seed)
+    n = M * h * w
+    s16, m16, w16 = FP16_FAMILIES[family](rng, n)
+    e = np.exp(rng.uniform(-1, 1.5, M)).astype(F32)
+    y = (rng.standard_normal((1, M, h, w)) * 1.5 * e[None, :, None, None]).astype(F32)
+
+    def planes(a):  # rows are (channel, position) in order, component k -> channel k*M + c
+        return np.ascontiguousarray(a.reshape(M, h, w, 4).transpose(3, 0, 1, 2).reshape(1, 4 * M, h, w))
+
+    return y, planes(s16), planes(m16), planes(w16)
+
+
+# ---- latents -----------------------------------------------------------------------------------------------------------
+def _l_base(rng, M, h, w):
+    e = np.exp(rng.uniform(-1, 1.5, M)).astype(F32)
+    return (rng.standard_normal((1, M, h, w)) * 1.5 * e[None, :, None, None]).astype(F32)
+
+
+def _put(y, rng, vals):
+    """the values at distinct random places of y (in place)"""
+    flat = y.reshape(-1)
+    at = rng.choice(flat.size, len(vals), replace=False)
+    flat[at] = np.asarray(vals, F32)
+    return y
+
+
+def _l_ties(rng, M, h, w):
+    y = _l_base(rng, M, h, w)
+    k = rng.integers(-6, 6, y.size)
+    half = rng.random(y.size) < 0.5
+    y.reshape(-1)[half] = (k[half] + 0.5).astype(F32)
+    return y
+
+
+def _l_neg_zero(rng, M, h, w):
+    y = _l_base(rng, M, h, w)
+    y[0, 1] = -0.0
+    y[0, 2] = np.where(rng.random((h, w)) < 0.5, F32(-0.0), F32(-0.4))
+    return _put(y, rng, [-0.0] * 7)
+
+
+def _l_all_negative(rng, M, h, w):
+    return -np.abs(_l_base(rng, M, h, w)) - F32(0.6)
+
+
+def _l_one_nan(rng, M, h, w):
+    return _put(_l_base(rng, M, h, w), rng, [np.nan])
+
+
+def _l_one_posinf(rng, M, h, w):
+    return _put(_l_base(rng, M, h, w), rng, [np.inf])
+
+
+def _l_one_neginf(rng, M, h, w):
+    return _put(_l_base(rng, M, h, w), rng, [-np.inf])
+
+
+def _l_beyond_int32(rng, M, h, w):
+    return _put(_l_base(rng, M, h, w), rng, [2147483648.0, -2147483904.0, 3e9, -5e12, 1e38])
+
+
+def _l_beyond_int32_mean_there(rng, M, h, w):
+    return _put(_l_base(rng, M, h, w), rng, [np.nan, np.inf, -np.inf, 3e9, -2147483904.0, 2147483648.0])
+
+
+def _l_near_int32_end(rng, M, h, w):
+    """just below and above 2^31 - 128 (the last float below 2^31), and the int32 minimum"""
+    return _put(_l_base(rng, M, h, w), rng, [2147483520.0, np.nextafter(F32(2147483520.0), F32(0)), -2147483520.0,
+                                             -2147483648.0, 2147483392.0])
+
+
+def _abs_max_at(am):
+    def make(rng, M, h, w):
+        y = np.clip(_l_base(rng, M, h, w), -(am - 1), am - 1)
+        return _put(y, rng, [am - 1 + 0.25, -(am - 1) - 0.4])  # max(|trunc|) = am - 1 -> abs_max = am
+    return make
+
+
+LATENT_FAMILIES = {
+    "ties_half": _l_ties,
+    "neg_zero": _l_neg_zero,
+    "all_negative": _l_all_negative,
+    "one_nan": _l_one_nan,
+    "one_posinf": _l_one_posinf,
+    "one_neginf": _l_one_neginf,
+    "beyond_int32": _l_beyond_int32,
+    "beyond_int32_mean_there": _l_beyond_int32_mean_there,  # (latent_case puts means at -2^31 and at the latent itself)
+    "near_int32_end": _l_near_int32_end,
+    "abs_max_32767": _abs_max_at(32767),
+    "abs_max_32768": _abs_max_at(32768),
+    "hdr2_max_bs_126": _abs_max_at(125),     # abs_max + 1 = 126: 2-byte headers (tests/helpers.py:hdr_form)
+    "hdr4_max_bs_127": _abs_max_at(126),     # 127: 4-byte headers
+    "hdr4_max_bs_16382": _abs_max_at(16381),  # MAX_BS_H4: the last 4-byte form
+    "hdr8_max_bs_16383": _abs_max_at(16382),
+    "segdec_am_1022": _abs_max_at(1022),     # 2 * (am + 1) + 2 = 2048: the GPU segment decoder's last width
+    "segdec_am_1023": _abs_max_at(1023),     # 2050: beyond it
+}
+# the segment decoder takes checkpointed items only: these families are drawn with LATENT_SHAPE (seven notes at stride 256
+# per channel group of 512 latents), the others with latent_case's default shape
+LATENT_SHAPE = {"segdec_am_1022": (12, 16, 32), "segdec_am_1023": (12, 16, 32)}
+
+
+def latent_case(family: str, M: int = 12, h: int = 8, w: int = 16, seed: int = 0):
+    """-> (y [1, M, h, w], sigma, mu, pi [1, 4M, h, w]) float32, ordinary parameters (sigma scaled with the channel's latents).
+    (M, h, w) is LATENT_SHAPE's where the family has one there."""
+    M, h, w = LATENT_SHAPE.get(family, (M, h, w))
+    rng = _rng(family, seed)
+    y = LATENT_FAMILIES[family](rng, M, h, w)
+    n = M * h * w
+    s, m, p = _ordinary(rng, n)
+    if family == "beyond_int32_mean_there":  # a mixture centred where the out-of-range latent's symbol INT32_MIN lies, and
+        far = ~(np.abs(y.reshape(-1)) < 2**31)  # one at the latent itself (finite ones): both edges are still the same float
+        m[far, 0] = F32(-2147483648.0)
+        m[far, 1] = np.where(np.isfinite(y.reshape(-1)[far]), y.reshape(-1)[far], F32(0))
+        s[far, :2] = F32(1.0)
+
+    def planes(a):
+        return np.ascontiguousarray(a.reshape(M, h, w, 4).transpose(3, 0, 1, 2).reshape(1, 4 * M, h, w))
+
+    return np.ascontiguousarray(y, F32), planes(s), planes(m), planes(p)
+
+
+# ---- streams -----------------------------------------------------------------------------------------------------------
+STREAM_FAMILIES = ("random", "truncated", "flipped")
+
+
+def stream_cases(family: str, valid: bytes, n: int, seed: int = 0, tail_from: int = 0):
+    """-> [(tag, bytes)] of one family, derived from a valid stream for n symbols (lengths multiples of 4, >= 8).
+    tail_from > 0 (a byte offset): "flipped" also corrupts only the words from there on - a checkpointed stream's last
+    segment, which no note verifies"""
+    rng = _rng(family, seed)
+    if family == "random":
+        return [(f"random{k}", rng.integers(0, 256, L, dtype=np.uint8).tobytes())
+                for k, L in enumerate((8, 4 * (n // 4 + 8), 4 * (n + 64)))]
+    if family == "truncated":  # every multiple of 4 in a short window below the full length, and a few far shorter
+        L = len(valid)
+        cuts = sorted({c for c in range(max(8, L - 40), L, 4)} | {8, max(8, (L // 8) * 4)})
+        return [(f"cut{c}", valid[:c]) for c in cuts]
+    assert family == "flipped"
+    out = []
+    for k in range(4):
+        b = bytearray(valid)
+        wi = int(rng.integers(0, len(valid) // 4))
+        b[4 * wi: 4 * wi + 4] = (int.from_bytes(b[4 * wi: 4 * wi + 4], "little") ^ int(rng.integers(1, 2**32))).to_bytes(4, "little")
+        out.append((f"flip{k}@{wi}", bytes(b)))
+    if tail_from:
+        for k in range(3):
+            b = bytearray(valid)
+            k0 = (tail_from + 4 * int(rng.integers(0, max(1, (len(valid) - tail_from) // 8)))) & ~3
+            b[k0:] = rng.integers(0, 256, len(valid) - k0, dtype=np.uint8).tobytes()
+            out.append((f"tail{k}@{k0}", bytes(b)))
+    return out
+
+
+# pmfs of pmf_to_quantized_cdf (compressai._CXX): degenerate ones
+PMF_CASES = {
+    "len1": [1.0],
+    "len1_tiny": [1e-9],
+    "len1_zero": [0.0],
+    "len2": [0.3, 0.7],
+    "len2_one_zero": [1.0, 0.0],
+    "len2_tiny": [1e-5, 0.0],
+    "all_zeros": [0.0] * 5,
+    "one_entry": [0.0, 0.0, 1.0, 0.0],
+    "with_nan": [0.5, float("nan"), 0.5],
+    "with_inf": [0.5, float("inf")],
+    "negative": [0.6, -0.1, 0.5],
+    "unnormalised": [3.0, 1.0, 0.0, 7.5],
+    "many_tiny": [1e-7] * 40 + [1.0],
+}

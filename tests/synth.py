@@ -45,20 +45,30 @@ def make_latent(seed: int, M: int = 192, h: int = 32, w: int = 24, K: int = 4, *
     )
 
 
+def torch_int(a) -> np.ndarray:
+    """float32 -> int32 as torch's ``.int()`` does it on x86-64 (cvttss2si): truncation toward zero, INT32_MIN for NaN, +-inf
+    and every value outside [-2^31, 2^31).  numpy's ``astype`` leaves those cases undefined."""
+    a = np.asarray(a, dtype=np.float32)
+    ok = (a > np.float32(-2147483904.0)) & (a < np.float32(2147483648.0))
+    with np.errstate(invalid="ignore"):
+        return np.where(ok, np.trunc(np.where(ok, a, 0)).astype(np.int32), np.int32(np.iinfo(np.int32).min)).astype(np.int32)
+
+
 def to_coder_inputs(y, scales, means, weights, K: int = 4, clamp: bool = True):
     """numpy restatement of what GaussianMixtureConditional.compress hands the coder
     (entropy_models.py:834-846, :810-828): (symbols int32[n], scales/means/weights (n,K) views with strides
     (1, n) elements, abs_max, zero_bitmap int64[M], y_q)."""
     B, M, h, w = y.shape
     assert B == 1
-    ymax, ymin = float(y.max()), float(y.min())
-    # torch.abs(y.max()).int().item(): truncation toward zero of |max|, |min|   (:834-837)
-    abs_max = max(int(abs(ymax)), int(abs(ymin))) + 1
+    y = np.asarray(y, dtype=np.float32)
+    # torch.abs(y.max()).int().item(): truncation toward zero of |max|, |min|   (:834-837).  y.max() / y.min() keep NaN, and .int()
+    # of NaN, of +-inf or of |v| >= 2^31 is INT32_MIN: one NaN anywhere gives abs_max = 1
+    abs_max = max(int(torch_int(np.abs(y.max()))), int(torch_int(np.abs(y.min())))) + 1
     abs_max = 1 if abs_max < 1 else abs_max
     yq = np.round(y)  # round-half-even, as torch.round
-    zero_bitmap = (np.abs(yq).sum((3, 2))[0] != 0).astype(np.int64)
+    zero_bitmap = (np.abs(yq).sum((3, 2))[0] != 0).astype(np.int64)  # a NaN sum is not 0: the channel is coded
     nz = np.nonzero(zero_bitmap)[0]
-    symbols = yq[0, nz].reshape(-1).astype(np.int32)
+    symbols = torch_int(yq[0, nz].reshape(-1))
 
     def rs(p):
         return p.reshape(K, M, h * w)[:, nz].reshape(K, -1).T  # (n, K) view-like, strides (1, n) after copy
