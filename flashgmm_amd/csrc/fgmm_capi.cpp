@@ -464,17 +464,21 @@ struct fgmm_head {
   int device = 0;
   float *packed = nullptr; // [wp | bp]
   fgmm::HeadW w{};
+  // bf16x6: the exact form's packing as well [wp | bp | a flag word], for the items with a feature outside the bf16x6 domain
+  float *packed32 = nullptr;
+  fgmm::HeadW w32{};
   // bf16x6: the features' split copy of the call in progress (grown on demand; calls are serialised by the context's lock)
   mutable void *xs = nullptr;
   mutable size_t xs_cap = 0;
 };
 
 // FGMM_HEAD_BF16X6: split the features of a call's items into their three bf16 parts (fgmm_head16.hip) -> the pointers the kernels'
-// descriptors carry as `x`.  One launch when the items are evenly spaced and of one size (stacked tensors), one per item otherwise.
-static int head16_split(const fgmm_head *head, void *stream, const float *const *x, const int64_t *hw, int count, std::vector<const float *> &out) {
+// descriptors carry as `xs`, each followed by the item's domain word (head16_oob_word: 1 = a feature outside the bf16x6 domain, the
+// exact kernels take that item).  One launch when the items are evenly spaced and of one size (stacked tensors), one per item otherwise.
+static int head16_split(const fgmm_head *head, void *stream, const float *const *x, const int64_t *hw, int count, std::vector<const void *> &out) {
   out.assign((size_t)count, nullptr);
   std::vector<size_t> at((size_t)count + 1, 0);
-  for (int i = 0; i < count; ++i) at[(size_t)i + 1] = at[(size_t)i] + head16_split_elems(head->w.c_in, hw[i]);
+  for (int i = 0; i < count; ++i) at[(size_t)i + 1] = at[(size_t)i] + head16_split_elems(head->w.c_in, hw[i]) + kHead16FlagElems;
   const size_t bytes = at[(size_t)count] * sizeof(uint16_t);
   if (bytes > head->xs_cap) {
     if (head->xs) (void)dev::free_device(head->xs);
@@ -484,7 +488,7 @@ static int head16_split(const fgmm_head *head, void *stream, const float *const 
     head->xs = p, head->xs_cap = bytes;
   }
   uint16_t *base = static_cast<uint16_t *>(head->xs);
-  for (int i = 0; i < count; ++i) out[(size_t)i] = reinterpret_cast<const float *>(base + at[(size_t)i]);
+  for (int i = 0; i < count; ++i) out[(size_t)i] = base + at[(size_t)i];
   bool even = count > 0;
   for (int i = 1; i < count && even; ++i) even = hw[i] == hw[0] && x[i] - x[i - 1] == x[1] - x[0];
   if (even && hw[0] > 0) {
@@ -504,7 +508,8 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   std::vector<EncItem> v((size_t)count);
-  std::vector<const float *> xsplit;
+  std::vector<const void *> xsplit;
+  fgmm::HeadW heads[2] = {head ? head->w : fgmm::HeadW{}, head ? head->w32 : fgmm::HeadW{}}; // (bf16x6: the head, its exact form)
   if (head && head->w.arith == FGMM_HEAD_BF16X6 && count) { // the features' three bf16 parts, once for all of the call's blocks
     std::vector<int64_t> hws((size_t)count);
     for (int i = 0; i < count; ++i) {
@@ -512,7 +517,7 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
       hws[(size_t)i] = (int64_t)items[i].M * items[i].hw ? items[i].hw : 0;
     }
     if (int rc = head16_split(head, stream, x, hws.data(), count, xsplit)) return rc;
-    x = xsplit.data();
+    heads[0].oob = heads[1].oob = 1;
   }
   for (int i = 0; i < count; ++i) {
     const fgmm_item &s = items[i];
@@ -523,6 +528,7 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
       if (s.M != head->w.M) return fail(FGMM_ERR_INVALID, "item %d: M = %d, the head was made for M = %d", i, s.M, head->w.M);
       if (s.hw < 0 || (s.M * s.hw && (!s.y || !x[i]))) return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
       e.x = x[i];
+      e.xs = xsplit.empty() ? nullptr : xsplit[(size_t)i];
       e.prm = fgmm_params{};
       e.prm.dtype = FGMM_F32;
       e.prm.flags = FGMM_PARAMS_LOGITS;
@@ -545,7 +551,7 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
       return fail(FGMM_ERR_INVALID, "item %d: ckpt_stride must be 0 or a power of two >= 256, the same for a whole batch", i);
     e.ckpt_stride = s.ckpt_stride;
   }
-  const int rc = encode_batch(ctx, (dev::Stream)stream, v, mode, head ? &head->w : nullptr, sink);
+  const int rc = encode_batch(ctx, (dev::Stream)stream, v, mode, head ? heads : nullptr, sink);
   if (rc != FGMM_OK) // a failed call returns no buffer: what the bitstreams that had finished hold is released here, not leaked by a
     for (auto &e : v) { // binding that raises on the status
       if (!sink) free(e.bytes); // (a sink's storage is the caller's)
@@ -591,8 +597,9 @@ int fgmm_head_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const 
   const size_t floats = head_packed_floats(M, c_in), bias_floats = (size_t)h->w.n_cg * 12 * kHeadCG;
   const bool b16 = (flags & FGMM_HEAD_BF16X6) != 0;
   const size_t bytes = b16 ? head16_packed_bytes(M, c_in) : floats * sizeof(float);
-  void *p = nullptr;
-  if (dev::malloc_device(&p, bytes) != 0) {
+  void *p = nullptr, *p32 = nullptr;
+  if (dev::malloc_device(&p, bytes + (b16 ? 16 : 0)) != 0 || (b16 && dev::malloc_device(&p32, floats * sizeof(float)) != 0)) {
+    if (p) (void)dev::free_device(p);
     delete h;
     return fail(FGMM_ERR_NOMEM, "%zu bytes of device memory for the packed weights", bytes);
   }
@@ -600,11 +607,27 @@ int fgmm_head_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const 
   h->w.arith = b16 ? FGMM_HEAD_BF16X6 : 0;
   h->w.wp = p;
   h->w.bp = b16 ? reinterpret_cast<const float *>(static_cast<const char *>(p) + (bytes - bias_floats * sizeof(float))) : h->packed + (floats - bias_floats);
-  int e = b16 ? launch_head16_pack(weight, bias, M, c_in, p, stream) : launch_head_pack(weight, bias, M, c_in, h->packed, h->packed + (floats - bias_floats), stream);
-  if (!e) e = dev::stream_sync((dev::Stream)stream); // (the caller may free or overwrite its weights on return)
-  if (e) {
+  int e;
+  uint32_t bad = 0;
+  if (b16) { // the bf16x6 packing, which flags weights outside its domain (the word after it), and the exact form's (the items with
+             // features outside it)
+    h->packed32 = static_cast<float *>(p32);
+    h->w32 = h->w;
+    h->w32.arith = 0, h->w32.wp = h->packed32, h->w32.bp = h->packed32 + (floats - bias_floats);
+    const uint32_t *d_bad = reinterpret_cast<const uint32_t *>(static_cast<const char *>(p) + bytes);
+    e = launch_head16_pack(weight, bias, M, c_in, p, stream);
+    if (!e) e = launch_head_pack(weight, bias, M, c_in, h->packed32, h->packed32 + (floats - bias_floats), stream);
+    if (!e) e = dev::stream_sync((dev::Stream)stream); // (the caller may free or overwrite its weights on return)
+    if (!e) e = dev::copy_sync(&bad, d_bad, sizeof(uint32_t), dev::kD2H);
+  } else {
+    e = launch_head_pack(weight, bias, M, c_in, h->packed, h->packed + (floats - bias_floats), stream);
+    if (!e) e = dev::stream_sync((dev::Stream)stream); // (the caller may free or overwrite its weights on return)
+  }
+  if (e || bad) {
     (void)dev::free_device(p);
+    if (p32) (void)dev::free_device(p32);
     delete h;
+    if (bad) return fail(FGMM_ERR_INVALID, "FGMM_HEAD_BF16X6: a weight is not finite or |w| >= 0x1.FFp127 (outside the bf16x6 domain)");
     return fail(FGMM_ERR_HIP, "packing the head's weights: %s", dev::error_string(e));
   }
   *out = h;
@@ -616,6 +639,7 @@ void fgmm_head_destroy(fgmm_head *h) {
   {
     DeviceGuard g(h->device);
     (void)dev::free_device(h->packed);
+    if (h->packed32) (void)dev::free_device(h->packed32);
     if (h->xs) (void)dev::free_device(h->xs);
   }
   delete h;
@@ -636,19 +660,23 @@ int fgmm_head_params_batch(fgmm_ctx *ctx, void *stream, const fgmm_head *head, c
   bool vec = true;
   for (int i = 0; i < count; ++i)
     if (hw[i] < 0 || (hw[i] && (!x[i] || !out[i]))) return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
-  std::vector<const float *> xsplit;
-  if (head->w.arith == FGMM_HEAD_BF16X6) {
-    if ((rc = head16_split(head, stream, x, hw, count, xsplit))) return rc;
-    x = xsplit.data();
-  }
+  std::vector<const void *> xsplit;
+  if (head->w.arith == FGMM_HEAD_BF16X6 && (rc = head16_split(head, stream, x, hw, count, xsplit))) return rc;
   for (int i = 0; i < count; ++i) {
-    hd[i] = HeadDesc{x[i], out[i], hw[i]};
+    hd[i] = HeadDesc{x[i], xsplit.empty() ? nullptr : xsplit[(size_t)i], out[i], hw[i]};
     hw_max = std::max(hw_max, hw[i]);
     vec = vec && (hw[i] & 3) == 0 && (reinterpret_cast<uintptr_t>(x[i]) & 15) == 0;
   }
   DEV_TRY(dev::copy_async(ctx->d_ws, hd, bytes, dev::kH2D, (dev::Stream)stream));
-  if (head->w.arith == FGMM_HEAD_BF16X6) LAUNCH_TRY(launch_head16_params(reinterpret_cast<const HeadDesc *>(ctx->d_ws), head->w, count, hw_max, stream));
-  else LAUNCH_TRY(launch_head_params(reinterpret_cast<const HeadDesc *>(ctx->d_ws), head->w, count, hw_max, vec, stream));
+  const HeadDesc *dd = reinterpret_cast<const HeadDesc *>(ctx->d_ws);
+  if (head->w.arith == FGMM_HEAD_BF16X6) { // then the exact form, for the items with a feature outside the bf16x6 domain
+    HeadW w16 = head->w, w32 = head->w32;
+    w16.oob = w32.oob = 1;
+    LAUNCH_TRY(launch_head16_params(dd, w16, count, hw_max, stream));
+    LAUNCH_TRY(launch_head_params(dd, w32, count, hw_max, vec, stream));
+  } else {
+    LAUNCH_TRY(launch_head_params(dd, head->w, count, hw_max, vec, stream));
+  }
   DEV_TRY(dev::stream_sync((dev::Stream)stream)); // (the descriptors' staging area belongs to the next call)
   return FGMM_OK;
 }

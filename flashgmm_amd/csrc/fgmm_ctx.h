@@ -390,6 +390,7 @@ struct EncItem {
   bool latent = false;               // latent-codec layout (y [M, hw], per-channel statistics, channel compaction) - also when M * hw == 0 and y is null
   const float *y = nullptr;          // device
   const float *x = nullptr;          // device: the parameter head's input features [c_in, hw] (fused head: encode_batch's `head`)
+  const void *xs = nullptr;          // device: bf16x6 head, their split copy
   const int32_t *sym_dev = nullptr;  // device (raw boundary)
   const int32_t *sym_host = nullptr; // host copy of the raw symbols when the caller has one
   fgmm_params prm{};
@@ -418,6 +419,7 @@ struct EncItem {
   int64_t job_n = 0, job_bypass = 0;
   double t_sub = 0, t_start = 0, t_end = 0, t_waited = 0, t_lastland = 0; // job timeline (the call log; trace level 2)
 };
+// head: the fused parameter head; a bf16x6 head is head[0] and its exact form head[1] (for the items whose domain word is set)
 int encode_batch(fgmm_ctx *ctx, dev::Stream stream, std::vector<EncItem> &items, int mode, const HeadW *head = nullptr, const fgmm_sink *sink = nullptr);
 
 // ---- one bitstream of a batched decode --------------------------------------------------------------------------------------

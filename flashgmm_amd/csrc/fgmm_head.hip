@@ -96,6 +96,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
   }
   const int64_t P0 = (int64_t)pt * kPB;
   if (P0 >= hw || cg * kCG >= M) return;
+  if (hw_.oob && !*head16_oob_word(FUSED ? edescs[item].xs : hdescs[item].xs, hw_.c_in, hw)) return; // a bf16x6 call: only the items
+                                                                                                      // outside its domain are this kernel's
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
   if constexpr (FUSED) {
     // compact (coded) channel of each of the block's 16 channels, -1 = no coded symbol: a prefix sum over quant_stats' census
@@ -157,7 +159,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
   const float *wp = static_cast<const float *>(hw_.wp) + (int64_t)cg * n_kt * (kRows * kBK);
   // Staging, branch-free (the K loop is ONE basic block, so that the instruction order below is the order issued): a load that would
   // fall outside the features (input channels past c_in in the last tile, positions past hw in the last position tile) reads a valid
-  // address instead and is replaced by zero; the packed weights are zero there as well.
+  // address instead and is replaced by -0; the packed weights are +0 there.  +0 * -0 = -0 adds nothing to any accumulator, -0
+  // included (+0 + -0 = +0 would turn a chain that ends at -0 into +0): the padded channels leave the chain's bits as they are.
   float4_t ra[6], rb[4];
   unsigned rb_ok = 0; // bit 4 j + e: element e of rb[j] lies inside the features (applied when the tile is WRITTEN: a select right after
                       // the load would wait for it, and the loads are there to be in flight under a tile's products)
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
       const int f = tid + 256 * j;
       float4_t v = rb[j];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (rb_ok >> (4 * j + e)) & 1u ? v[e] : 0.0f;
+      for (int e = 0; e < 4; ++e) v[e] = (rb_ok >> (4 * j + e)) & 1u ? v[e] : -0.0f;
       *reinterpret_cast<float4_t *>(&sB[(f >> 5) * kBLd + (f & 31) * 4]) = v;
     }
   };

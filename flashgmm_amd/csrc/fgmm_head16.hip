@@ -24,7 +24,7 @@
 namespace fgmm {
 namespace {
 
-constexpr int kCG = kHeadCG, kRows = 12 * kCG, kBK = 16, kPB = 256; // (K tiles of SIXTEEN input channels here: one matrix step)
+constexpr int kCG = kHeadCG, kRows = 12 * kCG, kBK = kHead16BK, kPB = 256; // (K tiles of SIXTEEN input channels here: one matrix step)
 constexpr int kPitch = 24;                                           // bf16 per LDS row (48 bytes)
 constexpr int kA16 = 3 * kRows * kPitch, kB16 = 3 * kPB * kPitch;    // bf16 elements of the W tile / x tile in LDS
 constexpr int kBuf16 = kA16 + kB16;                                  // one staged (W tile, x tile) pair: 64 512 bytes
@@ -47,9 +47,13 @@ __device__ __forceinline__ Split3 split3(float v) {
   return Split3{{bf_bits(a), bf_bits(b), bf_bits(c)}};
 }
 
+// the operands whose three bfloat16 parts carry them: finite, and not rounding to an infinite first part (|v| < 0x1.FFp127; NaN fails
+// the test).  Beyond, split3 gives (+-inf, NaN, NaN), and the six part products turn an infinite or a finite exact result into NaN.
+__device__ __forceinline__ bool in_domain(float v) { return __builtin_fabsf(v) < 0x1.FFp127f; }
+
 // packed weights: bf16 [channel group][K tile of 16][part 3][192 rows][16 input channels in natural order]; bias as in fgmm_head.hip
 __global__ __launch_bounds__(256) void head16_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, int M, int c_in, int n_cg, int n_kt,
-                                                          uint16_t *__restrict__ wp, float *__restrict__ bp) {
+                                                          uint16_t *__restrict__ wp, float *__restrict__ bp, uint32_t *__restrict__ bad) {
   const int64_t total = (int64_t)n_cg * n_kt * kRows * kBK;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total + (int64_t)n_cg * kRows; i += (int64_t)gridDim.x * 256) {
     const bool is_bias = i >= total;
@@ -66,7 +70,9 @@ __global__ __launch_bounds__(256) void head16_pack_kernel(const float *__restric
       bp[e] = (c < M && bias) ? bias[o] : 0.0f;
     } else {
       const int kin = kt * kBK + q;
-      const Split3 s = split3((c < M && kin < c_in) ? w[o * c_in + kin] : 0.0f);
+      const float v = (c < M && kin < c_in) ? w[o * c_in + kin] : 0.0f;
+      if (!in_domain(v)) *bad = 1u;
+      const Split3 s = split3(v);
       const int64_t base = ((int64_t)cg * n_kt + kt) * 3 * (kRows * kBK) + (int64_t)r * kBK + q;
 #pragma unroll
       for (int part = 0; part < 3; ++part) wp[base + (int64_t)part * (kRows * kBK)] = s.p[part];
@@ -84,12 +90,16 @@ __global__ __launch_bounds__(256) void head16_split_kernel(const float *__restri
   const int64_t pos = (int64_t)blockIdx.x * 128 + (threadIdx.x >> 1);
   if (pos >= hw) return;
   uint16_t parts[3][8];
+  bool ok = true;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int kin = kt * kBK + 8 * g8 + j;
-    const Split3 s = split3(kin < c_in ? ldg<float>(x + (int64_t)kin * hw + pos) : 0.0f);
+    const float v = kin < c_in ? ldg<float>(x + (int64_t)kin * hw + pos) : 0.0f;
+    ok = ok && in_domain(v);
+    const Split3 s = split3(v);
     parts[0][j] = s.p[0], parts[1][j] = s.p[1], parts[2][j] = s.p[2];
   }
+  if (!ok) *const_cast<uint32_t *>(head16_oob_word(xs, c_in, hw)) = 1u; // the item goes to the exact kernel (every writer writes 1)
 #pragma unroll
   for (int part = 0; part < 3; ++part) {
     u4_t v;
@@ -97,6 +107,12 @@ __global__ __launch_bounds__(256) void head16_split_kernel(const float *__restri
     for (int e = 0; e < 4; ++e) v[e] = (uint32_t)parts[part][2 * e] | ((uint32_t)parts[part][2 * e + 1] << 16);
     stg<u4_t>(xs + (((int64_t)kt * 3 + part) * hw + pos) * kBK + 8 * g8, v);
   }
+}
+
+// the domain words of `count` evenly spaced split copies, zeroed before head16_split_kernel flags them
+__global__ __launch_bounds__(256) void head16_oob_clear_kernel(uint16_t *__restrict__ xs0, int64_t hw, int c_in, int count, int64_t xs_stride) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i < count) *const_cast<uint32_t *>(head16_oob_word(xs0 + (int64_t)i * xs_stride, c_in, hw)) = 0u;
 }
 
 // 512 threads = 8 waves, two per SIMD (each within 256 registers): wave = (row half rh, position quarter pq) = 96 rows (the three
@@ -114,16 +130,17 @@ __global__ __launch_bounds__(kThreads) void head16_kernel(const EncDesc *__restr
   const int item = L / (pt_max * cg_max);
   const int rem = L - item * (pt_max * cg_max);
   const int pt = rem / cg_max, cg = rem - pt * cg_max;
-  const uint16_t *xs; // the item's features, split by head16_split_kernel (the descriptor's x points at that copy)
+  const uint16_t *xs; // the item's features, split by head16_split_kernel (the descriptor's xs)
   int64_t hw;
   int M;
   if constexpr (FUSED) {
-    xs = reinterpret_cast<const uint16_t *>(edescs[item].x), hw = edescs[item].hw, M = edescs[item].M;
+    xs = static_cast<const uint16_t *>(edescs[item].xs), hw = edescs[item].hw, M = edescs[item].M;
   } else {
-    xs = reinterpret_cast<const uint16_t *>(hdescs[item].x), hw = hdescs[item].hw, M = hw_.M;
+    xs = static_cast<const uint16_t *>(hdescs[item].xs), hw = hdescs[item].hw, M = hw_.M;
   }
   const int64_t P0 = (int64_t)pt * kPB;
   if (P0 >= hw || cg * kCG >= M) return;
+  if (hw_.oob && *head16_oob_word(xs, hw_.c_in, hw)) return; // a feature outside the domain: the exact kernel, launched next, takes it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
   const int rh = wave & 1, pq = wave >> 1;
   if constexpr (FUSED) { // the compact channel of each of the block's 16 channels (fgmm_head.hip; chunks of 512 channels here)
@@ -339,8 +356,10 @@ int launch_head16_pack(const float *w, const float *bias, int M, int c_in, void 
   const int64_t total = (int64_t)n_cg * n_kt * kRows * kBK + (int64_t)n_cg * kRows;
   uint16_t *wp = static_cast<uint16_t *>(packed);
   float *bp = reinterpret_cast<float *>(wp + (size_t)n_cg * n_kt * 3 * kRows * kBK);
+  uint32_t *bad = reinterpret_cast<uint32_t *>(static_cast<char *>(packed) + head16_packed_bytes(M, c_in));
+  if (int e = (int)hipMemsetAsync(bad, 0, sizeof(uint32_t), (hipStream_t)stream)) return e;
   hipLaunchKernelGGL(head16_pack_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, bias, M, c_in, n_cg, n_kt,
-                     wp, bp);
+                     wp, bp, bad);
   return (int)hipGetLastError();
 }
 
@@ -350,6 +369,8 @@ size_t head16_split_elems(int c_in, int64_t hw) { return (size_t)((c_in + kBK - 
 int launch_head16_split(const float *x0, void *xs0, int64_t hw, int c_in, int count, int64_t x_stride, int64_t xs_stride, void *stream) {
   if (count <= 0 || hw <= 0) return 0;
   const int n_kt = (c_in + kBK - 1) / kBK;
+  hipLaunchKernelGGL(head16_oob_clear_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, static_cast<uint16_t *>(xs0), hw, c_in,
+                     count, xs_stride);
   hipLaunchKernelGGL(head16_split_kernel, dim3((unsigned)((hw + 127) / 128), (unsigned)n_kt, (unsigned)count), dim3(256), 0, (hipStream_t)stream, x0,
                      static_cast<uint16_t *>(xs0), hw, c_in, n_kt, x_stride, xs_stride);
   return (int)hipGetLastError();

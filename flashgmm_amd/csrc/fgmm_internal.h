@@ -28,6 +28,7 @@ struct EncDesc {
   int32_t logits;        // the weights planes hold LOGITS: pi = softmax4 over K in the kernel (fgmm_math.h)
   uint32_t meta_slots;   // entries of `meta`
   const float *x;        // fused parameter head (fgmm_head.hip): the head's input features [c_in, hw]; the planes above are unused
+  const void *xs;        // ... bf16x6 (fgmm_head16.hip): their three bfloat16 parts, written by head16_split_kernel
   // outputs (device)
   float *yq;             // [M*hw] round(y), or null
   float *chan_min;       // [M]  min over the channel of y
@@ -90,10 +91,14 @@ struct HeadW {              // the PACKED weights of a head (device): see head_p
   const void *wp;           // exact form: float [n_cg][n_kt][12 * kHeadCG][kHeadBK]; bf16x6: bf16 [n_cg][n_kt][3][12 * kHeadCG][kHeadBK]
   const float *bp;          // [n_cg][12 * kHeadCG]
   int32_t M, c_in, n_cg, n_kt;
-  int32_t arith, pad_;      // 0: binary32 on v_mfma_f32_32x32x2_f32 (fgmm_head.hip); FGMM_HEAD_BF16X6: fgmm_head16.hip
+  int32_t arith;            // 0: binary32 on v_mfma_f32_32x32x2_f32 (fgmm_head.hip); FGMM_HEAD_BF16X6: fgmm_head16.hip
+  // 1: a bf16x6 call - every item's split copy (descriptor `xs`) is followed by its domain word (head16_oob_word): the bf16x6 kernels
+  // skip the items it flags, the exact kernels launched after them take only those.  0: every item is the kernel's
+  int32_t oob;
 };
 struct HeadDesc { // one item of the un-fused form
   const float *x; // device [c_in, hw]
+  const void *xs; // bf16x6: the split copy of x (head16_split_kernel)
   float *out;     // device [3 * 4 * M, hw]: scales | means | logits planes, channel k * M + c
   int64_t hw;
 };
@@ -104,10 +109,18 @@ static inline size_t head_packed_floats(int M, int c_in) {
 int launch_head_pack(const float *w, const float *bias_or_null, int M, int c_in, float *wp, float *bp, void *stream);
 // the bf16x6 form (fgmm_head16.hip): `packed` holds the three bf16 parts of the weights, then the bias
 size_t head16_packed_bytes(int M, int c_in);
+// `packed` has room for head16_packed_bytes + 4: that last word becomes 1 when a weight is outside the bf16x6 domain (|w| >= 0x1.FFp127,
+// inf, NaN)
 int launch_head16_pack(const float *w, const float *bias_or_null, int M, int c_in, void *packed, void *stream);
-// the features' split copy: head16_split_elems bf16 per item, written by launch_head16_split; the kernels' descriptors then carry THAT
-// pointer as `x`
+// the features' split copy: head16_split_elems bf16 per item, written by launch_head16_split; the kernels' descriptors carry it as `xs`.
+// Each item's copy is followed by kHead16FlagElems bf16 of room: its domain word (head16_oob_word), 1 when a feature of the item is
+// outside the bf16x6 domain (non-finite or |x| >= 0x1.FFp127), else 0 (launch_head16_split writes both)
+constexpr int kHead16BK = 16;       // input channels per K tile of the bf16x6 form
+constexpr int kHead16FlagElems = 8; // (16 bytes: the next item's copy stays 16-byte aligned)
 size_t head16_split_elems(int c_in, int64_t hw);
+FGMM_HD static inline const uint32_t *head16_oob_word(const void *xs, int c_in, int64_t hw) {
+  return reinterpret_cast<const uint32_t *>(static_cast<const uint16_t *>(xs) + (int64_t)((c_in + kHead16BK - 1) / kHead16BK) * 3 * hw * kHead16BK);
+}
 int launch_head16_split(const float *x0, void *xs0, int64_t hw, int c_in, int count, int64_t x_stride, int64_t xs_stride, void *stream);
 int launch_head16_params(const HeadDesc *d_descs, const HeadW &w, int count, int64_t hw_max, void *stream);
 int launch_head16_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_max, int64_t hw_max, int mode, bool clamped, void *stream);

@@ -161,7 +161,11 @@ class ParameterHead:
         y_hat = gmc.decompress_batch(res.strings, res.abs_maxes, res.zero_bitmaps, scales, means, logits, weights_are_logits=True)
 
     Encoder and decoder then derive identical parameters from identical weights whatever BLAS / MIOpen version either side
-    runs - the reference relies on that silently.  The weights are packed once, here."""
+    runs - the reference relies on that silently.  The weights are packed once, here.
+
+    ``arithmetic="bf16x6"`` is within ``R (sum_k |w x| + |b|) + 2^-133 sum_k (|w_k| + |x_k|) + 6 n16 2^-150`` of the exact result,
+    ``n16 = ceil(c_in / 16)``, ``R = 2^-23 (1 + 2^-6) + 6 n16 2^-24 (1 + 2^-7)``, on its domain: finite operands below 0x1.FFp127.
+    Weights outside it raise here; an item whose features leave it is computed by the exact form (the fmaf chain, bit for bit)."""
 
     def __init__(self, conv, K: int = 4, arithmetic: str = "f32"):
         # arithmetic: "f32" (the default: binary32 products and sums on v_mfma_f32_32x32x2_f32, bit for bit an fmaf chain) or "bf16x6"

@@ -296,7 +296,8 @@ int fgmm_gmc_compress_batch_to(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
  *    c_in = 640, M = 192 there), the chunk(3, 1) into scales | means | weights and the softmax over K
  *    (compressai/latent_codecs/gaussian_mixture_conditional.py:183-202).
  *    out[o][p] = bias[o] + sum_k weight[o][k] * x[k][p], o = t * K*M + k * M + c (t: scales, means, logits), computed on
- *    v_mfma_f32_32x32x2_f32 in ONE fixed order - bit for bit  acc = bias[o]; for k ascending: acc = fmaf(weight[o][k], x[k][p], acc)  -
+ *    v_mfma_f32_32x32x2_f32 in ONE fixed order - bit for bit, signs of zero, infinities and NaN included,
+ *    acc = bias[o] (+0 without a bias); for k ascending: acc = fmaf(weight[o][k], x[k][p], acc)  -
  *    so that encoder and decoder derive identical parameters from identical weights on any ROCm / torch / MIOpen version (a
  *    BLAS's or MIOpen's summation order is not part of any contract; the reference silently relies on it being the same on both
  *    sides).  Streams coded from these parameters decode from these parameters.
@@ -306,10 +307,15 @@ typedef struct fgmm_head fgmm_head; /* a head's weights, packed for the kernel, 
  * The weights are copied (packed) before the call returns. */
 int fgmm_head_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int K, int c_in, fgmm_head **out);
 /* ... with flags.  FGMM_HEAD_BF16X6: the same layer on the BF16 matrix cores with binary32 accuracy - weights and features split into
- * three bfloat16 parts each, six part products per product, accumulated in binary32 (fgmm_head16.hip): within ~2e-7 * sum |w x| of the
- * exact sum at a third of the matrix-pipe cycles.  Deterministic on gfx950 (the same inputs give the same parameters on every launch,
- * fused or not), but NOT the fmaf chain of the default form and not restatable bit for bit on a CPU: encoder and decoder must both use
- * it, on MI355X. */
+ * three bfloat16 parts each, six part products per product, accumulated in binary32 (fgmm_head16.hip), at a third of the matrix-pipe
+ * cycles.  Bound, per output, with n16 = ceil(c_in / 16):
+ *     |out - exact| <= R (sum_k |w x| + |b|) + 2^-133 sum_k (|w_k| + |x_k|) + 6 n16 2^-150,   R = 2^-23 (1 + 2^-6) + 6 n16 2^-24 (1 + 2^-7)
+ * (the three dropped part products; the bfloat16 subnormal grid, where a third part is rounded; one binary32 rounding per matrix
+ * step) - on data of order one the error is ~2e-7 sum |w x|.  Domain: finite operands with |v| < 0x1.FFp127 (whose first bfloat16
+ * part is finite).  Weights outside it are refused here (FGMM_ERR_INVALID).  An item with a feature outside it is computed by the
+ * exact form instead, bit for bit the fmaf chain above (IEEE infinities and NaN included).  Deterministic on gfx950 (the same inputs
+ * give the same parameters on every launch, fused or not), but NOT the fmaf chain of the default form and not restatable bit for bit
+ * on a CPU: encoder and decoder must both use it, on MI355X. */
 #define FGMM_HEAD_BF16X6 1
 int fgmm_head_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int K, int c_in, int flags,
                         fgmm_head **out);

@@ -400,3 +400,151 @@ PMF_CASES = {
     "unnormalised": [3.0, 1.0, 0.0, 7.5],
     "many_tiny": [1e-7] * 40 + [1.0],
 }
+
+
+# ---- the parameter head's last layer (fgmm_head.hip, fgmm_head16.hip) ----------------------------------------------------
+# Every family returns (W [12 M, c_in], b [12 M], x [c_in, hw]) float32 for a given shape.  The finite families keep every partial
+# sum of the fmaf chain within binary32 (no overflow in any order): sum |w x| + |b| <= 2^126.
+F32_MAX = float(np.finfo(F32).max)
+BF16_OVERFLOW = float.fromhex("0x1.FFp127")  # the smallest binary32 that rounds to an infinite bfloat16 (to nearest even)
+
+
+def _pow2(rng, lo, hi, shape):
+    """mixed signs, log-uniform magnitudes in [2^lo, 2^hi)"""
+    return (np.where(rng.random(shape) < 0.5, -1.0, 1.0) * np.exp2(rng.uniform(lo, hi, shape))).astype(F32)
+
+
+def _fit(W, b, x, limit):
+    """x scaled by a power of two (exactly) so that sum |w x| + |b| <= limit everywhere"""
+    s = (np.abs(W.astype(np.float64)) @ np.abs(x.astype(np.float64)) + np.abs(b.astype(np.float64))[:, None]).max()
+    k = max(0, int(np.ceil(np.log2(s / limit)))) if s > limit else 0
+    return W, b, (x * F32(2.0**-k)).astype(F32)
+
+
+def _hd_ordinary(rng, M, c_in, hw):
+    W = (rng.standard_normal((12 * M, c_in)) / np.sqrt(c_in)).astype(F32)
+    b = rng.standard_normal(12 * M).astype(F32)
+    x = rng.standard_normal((c_in, hw)).astype(F32)
+    return W, b, np.where(x > 0, x, F32(0.01) * x).astype(F32)
+
+
+def _hd_wide_range(rng, M, c_in, hw):
+    W, b, x = _pow2(rng, -60, 60, (12 * M, c_in)), _pow2(rng, -60, 60, 12 * M), _pow2(rng, -60, 60, (c_in, hw))
+    return _fit(W, b, x, 2.0**120)
+
+
+def _hd_cancellation(rng, M, c_in, hw):
+    """bias = -(sum w x) of position 0 rounded to binary32, and other positions near it: results far below sum |w x|"""
+    W, _, x = _hd_ordinary(rng, M, c_in, hw)
+    x = (x[:, :1] + F32(1e-3) * x).astype(F32)
+    b = (-(W.astype(np.float64) @ x[:, 0].astype(np.float64))).astype(F32)
+    return W, b, x
+
+
+def _hd_huge(rng, M, c_in, hw):
+    """one or two products per output near 2^125 (features of 2^61 .. 2^63 at two channels of each position), the rest ordinary"""
+    W = _pow2(rng, 60, 62, (12 * M, c_in))
+    x = _pow2(rng, -70, -60, (c_in, hw))
+    for p in range(hw):
+        x[rng.choice(c_in, min(2, c_in), replace=False), p] = _pow2(rng, 61, 63, min(2, c_in))
+    return _fit(W, _pow2(rng, 100, 124, 12 * M), x, 2.0**126)
+
+
+def _hd_near_bf16_overflow_features(rng, M, c_in, hw):
+    """a few |x| in [0x1.FFp127, FLT_MAX] - finite, but their first bfloat16 part is infinite - at channel c_in - 1, at the last
+    position, and elsewhere; weights <= 2^-4, at most one such feature per position"""
+    W = (_pow2(rng, -30, -4, (12 * M, c_in))).astype(F32)
+    x = _hd_ordinary(rng, M, c_in, hw)[2]
+    big = np.exp2(rng.uniform(np.log2(BF16_OVERFLOW), np.log2(F32_MAX), 4)).astype(F32)
+    big = np.minimum(big, F32(F32_MAX)) * np.array([1, -1, 1, -1], F32)
+    big[0] = F32(BF16_OVERFLOW)
+    places = [(c_in - 1, hw - 1), (0, 0), (int(rng.integers(c_in)), hw // 2), (c_in - 1, hw // 3)]
+    used = set()
+    for (k, p), v in zip(places, big):
+        if p not in used:
+            x[k, p] = v
+            used.add(p)
+    return W, (rng.standard_normal(12 * M) * 1e3).astype(F32), x
+
+
+def _hd_subnormal(rng, M, c_in, hw):
+    """subnormal features and weights beside ordinary ones: products between 2^-150 and 2^-100 among them"""
+    W, b, x = _hd_ordinary(rng, M, c_in, hw)
+    mx, mw = rng.random(x.shape) < 0.5, rng.random(W.shape) < 0.3
+    x[mx] = _pow2(rng, -149, -126, int(mx.sum()))
+    W[mw] = _pow2(rng, -149, -126, int(mw.sum()))
+    return W, (b * F32(2.0**-120)).astype(F32), x
+
+
+def _hd_tiny_products(rng, M, c_in, hw):
+    """w x between 2^-150 and 2^-100 everywhere: the result is mostly subnormal"""
+    W, x = _pow2(rng, -75, -50, (12 * M, c_in)), _pow2(rng, -75, -50, (c_in, hw))
+    return W, _pow2(rng, -150, -110, 12 * M), x
+
+
+def _hd_signed_zeros(rng, M, c_in, hw):
+    """+-0 in the weights, the features and the bias, rows of zero weights, negative features: many chains end at -0"""
+    W, b, x = _hd_ordinary(rng, M, c_in, hw)
+    W[rng.random(W.shape) < 0.5] = 0.0
+    W[rng.random(W.shape) < 0.3] = -0.0
+    W[rng.random(12 * M) < 0.6] = np.where(rng.random(c_in) < 0.5, F32(0.0), F32(-0.0))  # zero rows, both signs
+    b = np.where(rng.random(12 * M) < 0.5, F32(-0.0), F32(0.0)).astype(F32)
+    x = -np.abs(x)
+    x[rng.random(x.shape) < 0.2] = -0.0
+    x[rng.random(x.shape) < 0.1] = 0.0
+    return W, b, x
+
+
+def _hd_dead_rows(rng, M, c_in, hw):
+    W, b, x = _hd_ordinary(rng, M, c_in, hw)
+    dead = rng.random(12 * M) < 0.4
+    W[dead] = 0.0
+    b[dead[: 12 * M] & (rng.random(12 * M) < 0.5)] = 0.0
+    return W, b, x
+
+
+def _hd_nonfinite_features(rng, M, c_in, hw):
+    """NaN and +-inf features, at input channel c_in - 1, at the last position (a last, partial position tile) and elsewhere"""
+    W, b, x = _hd_ordinary(rng, M, c_in, hw)
+    vals = [np.nan, np.inf, -np.inf]
+    x[c_in - 1, hw - 1] = np.inf
+    x[0, 0] = np.nan
+    if hw > 2:
+        x[c_in - 1, 1] = -np.inf
+        x[int(rng.integers(c_in)), hw // 2] = vals[int(rng.integers(3))]
+    return W, b, x
+
+
+def _hd_nonfinite_weights(rng, M, c_in, hw):
+    """NaN and +-inf weights (column c_in - 1 included) and one infinite bias"""
+    W, b, x = _hd_ordinary(rng, M, c_in, hw)
+    W[0, c_in - 1] = np.inf
+    W[12 * M - 1, 0] = np.nan
+    W[int(rng.integers(12 * M)), int(rng.integers(c_in))] = -np.inf
+    b[6 * M] = -np.inf
+    return W, b, x
+
+
+HEAD_FAMILIES = {
+    "ordinary": _hd_ordinary,
+    "wide_range": _hd_wide_range,
+    "cancellation": _hd_cancellation,
+    "huge": _hd_huge,
+    "near_bf16_overflow_features": _hd_near_bf16_overflow_features,
+    "subnormal": _hd_subnormal,
+    "tiny_products": _hd_tiny_products,
+    "signed_zeros": _hd_signed_zeros,
+    "dead_rows": _hd_dead_rows,
+    "nonfinite_features": _hd_nonfinite_features,
+    "nonfinite_weights": _hd_nonfinite_weights,
+}
+HEAD_NONFINITE = ("nonfinite_features", "nonfinite_weights")  # the exact result is NaN or +-inf somewhere
+# outside the bf16x6 form's domain (include/flashgmm_amd.h FGMM_HEAD_BF16X6): features it hands to the exact form, weights it refuses
+HEAD_BF16_FEATURES_OUT = ("near_bf16_overflow_features", "nonfinite_features")
+HEAD_BF16_WEIGHTS_OUT = ("nonfinite_weights",)
+
+
+def head_case(family: str, M: int, c_in: int, hw: int, seed: int = 0):
+    """-> (W [12 M, c_in], b [12 M], x [c_in, hw]) float32, contiguous"""
+    W, b, x = HEAD_FAMILIES[family](_rng(f"head/{family}/{M}/{c_in}/{hw}", seed), M, c_in, hw)
+    return tuple(np.ascontiguousarray(a, F32) for a in (W, b, x))
