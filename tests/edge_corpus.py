@@ -7,6 +7,8 @@ the expected answers are computed by the compiled reference (tests/ref_worker.py
   LATENT_FAMILIES  latents y [1, M, h, w] float32 with ordinary parameters: ties, -0.0, NaN / inf, |y| >= 2^31, and the values
                    that put abs_max at the limits of the coder's paths
   STREAM_FAMILIES  what a decoder is given instead of its bitstream: random bytes, truncations, a flipped word
+  CLAMP_FAMILIES   rows (v, sigma, mu, pi) aimed at the guards of the clamped-sigma fast paths (flashgmm_amd/csrc/fgmm_math.h,
+                   fgmm_tab.hip), each with a numpy predicate that restates its guard on the inputs (CLAMP_GUARDS)
 """
 from __future__ import annotations
 
@@ -350,6 +352,326 @@ def latent_case(family: str, M: int = 12, h: int = 8, w: int = 16, seed: int = 0
         return np.ascontiguousarray(a.reshape(M, h, w, 4).transpose(3, 0, 1, 2).reshape(1, 4 * M, h, w))
 
     return np.ascontiguousarray(y, F32), planes(s), planes(m), planes(p)
+
+
+# ---- the clamped-sigma fast paths ------------------------------------------------------------------------------------------
+# With clamp_scales=True (every real caller) the kernels run packed-fp32 fast sequences behind guards and hand back to the IEEE
+# sequence outside them.  Every family below is a function of (rng, n) -> (v int32 [n], sigma, mu, pi [n, 4] float32): rows that
+# lie on both sides of one guard, the constants taken from the line that holds the guard.  |v| stays small enough for every
+# decoder (abs_max + 1 far below 40000), and sigma is given PRE-clamp.
+GUARD_A = 2048.0                      # fgmm_math.h mix4_clamped2: `fabsf(a.x) < 0x1p11f`, a.x = (v - 0.5) - mu_k
+RCP_TAME = 2.0**60                    # fgmm_math.h tame(): `fabsf(a) < 0x1p60f`, Phi2<MODE_LOGISTIC>'s per-half guard on d = 1 + e
+LOGISTIC_C = F32(1.702)               # fgmm_math.h Phi<MODE_LOGISTIC>: e = exp(-1.0f * (1.702f * z))
+EXP_HI = 88.3762626647949             # fgmm_math.h exp_ref: the upper clamp of the argument
+SIGMA_LO, SIGMA_HI = F32(0.11), F32(256.0)  # fgmm_math.h clamp_scale / Sigma4::set (entropy_models.py:817)
+SAT_Z = {"polya": (5.25, 5.0), "as": (5.45, 5.45), "logistic": (8.2, 9.8)}  # fgmm_math.h Sat<MODE>::ZL, ZR
+SEGDEC_AM = 1022                      # fgmm_decode_gpu.cpp: the segment decoder takes 2 * (abs_max + 1) + 2 <= 2048
+# the distances mix4_clamped2's compare is probed at (both signs); beyond the issue's list a few far ones below 2^40, where
+# exp_nonpos2's un-clamped argument (valid to -2^30) would leave its domain if the compare let them through
+GUARD_BELOW = (2047.0, 2047.5, float(np.nextafter(F32(2048), F32(0))))
+GUARD_ABOVE = (2048.0, float(np.nextafter(F32(2048), F32(4096))), 2048.5, 2049.0, 4096.0, 2.0**16, 2.0**24, 2.0**32, 2.0**39)
+
+
+def clamp_sigma(s):
+    """torch.clamp(s, 0.11, 256) on float32: NaN kept, -0 / negative / -inf -> 0.11, +inf -> 256"""
+    with np.errstate(invalid="ignore"):
+        return np.clip(np.asarray(s, F32), SIGMA_LO, SIGMA_HI)
+
+
+def _near_symbols(rng, n, lim=40):
+    return rng.integers(-lim, lim, n, endpoint=True).astype(np.int32)
+
+
+def _ordinary_at(rng, v):
+    """ordinary rows whose means lie near the row's symbol"""
+    n = len(v)
+    sg, mu, pi = _ordinary(rng, n)
+    return sg, (mu + v[:, None].astype(F32)).astype(F32), pi
+
+
+def _c_guard_2048(rng, n):
+    """(v - 0.5) - mu_k exactly on +-GUARD_BELOW / +-GUARD_ABOVE in one, two or all four components (fgmm_math.h mix4_clamped2,
+    the 0x1p11f compare).  The symbol's sign is chosen so that mu = x - a is a binary32 and x - mu gives a back exactly: for
+    2048 - ulp the mean must stay below 2048 in magnitude (x and a of one sign), for 2048 + ulp above it (opposite signs)."""
+    below = rng.random(n) < 0.45
+    a = np.where(below, rng.choice(GUARD_BELOW, n), rng.choice(GUARD_ABOVE, n))
+    sa = np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    sx = np.where(a < 2048, sa, -sa)
+    v = (sx * rng.integers(1, 40, n, endpoint=True)).astype(np.int32)
+    sg, mu, pi = _ordinary_at(rng, v)
+    x = v.astype(np.float64) - 0.5
+    far = (x - sa * a).astype(F32)
+    how = rng.integers(0, 3, n)  # one, two, all four components
+    k0 = rng.integers(0, 4, n)
+    hit = np.zeros((n, 4), bool)
+    hit[np.arange(n), k0] = True
+    hit[np.arange(n), (k0 + 1) % 4] |= how >= 1
+    hit[how == 2] = True
+    mu = np.where(hit, far[:, None], mu).astype(F32)
+    # sigma of the far components: both ends of the clamp and beyond, so that z = a / sigma runs from 8 to 2^39 / 0.11
+    sg = np.where(hit, rng.choice(np.array([0.05, 0.11, 1.0, 200.0, 256.0, 1000.0], F32), (n, 4)), sg).astype(F32)
+    return v, sg, mu, pi
+
+
+def _spread(rng, n, lim, lo0, hi0, gap_lo, gap_hi):
+    """mu_0 in [lo0, hi0], mu_1 = mu_0 + [gap_lo, gap_hi] (more than 2^11 and less than 2^12 apart: some edges are within 2^11
+    of all four means, others are not), mu_2, mu_3 between them; wide sigma so that the far components are not saturated
+    everywhere; symbols anywhere in [-lim, lim]"""
+    mu = np.empty((n, 4))
+    mu[:, 0] = rng.uniform(lo0, hi0, n)
+    mu[:, 1] = mu[:, 0] + rng.uniform(gap_lo, gap_hi, n)
+    mu[:, 2:] = mu[:, :1] + rng.uniform(0, 1, (n, 2)) * (mu[:, 1:2] - mu[:, :1])
+    sg = np.exp(rng.uniform(np.log(0.05), np.log(600.0), (n, 4)))
+    sg[:, :2] = rng.uniform(60, 300, (n, 2))
+    pi = rng.dirichlet(np.ones(4), n)
+    near = mu[np.arange(n), rng.integers(0, 4, n)] + rng.standard_normal(n) * 30
+    v = np.clip(np.rint(np.where(rng.random(n) < 0.5, near, rng.uniform(-lim, lim, n))), -lim, lim).astype(np.int32)
+    v[:2] = (lim, -lim)
+    return v, sg.astype(F32), mu.astype(F32), pi.astype(F32)
+
+
+def _c_spread_means(rng, n):
+    """means inside the coded range, abs_max of about three thousand (4-byte headers): fgmm_tab.hip tab_kernel phase 2 decides
+    fast / slow per pair of edges, and a row's window spans both kinds"""
+    return _spread(rng, n, 3000, -1900.0, -1100.0, 2100.0, 3900.0)
+
+
+def _c_spread_means_1022(rng, n):
+    """spread_means' second shape: abs_max <= SEGDEC_AM (the GPU segment decoder's width limit) with mu_0 and mu_1 OUTSIDE
+    the coded range, about -1500 and +1500: |x - mu_k| still crosses 2^11 inside the row (fgmm_tab.hip segdec_kernel)"""
+    return _spread(rng, n, SEGDEC_AM - 1, -1900.0, -1300.0, 2950.0, 3500.0)
+
+
+def _c_spread_means_510(rng, n):
+    """the same with abs_max <= 510: 2 * 511 + 2 = 1024 edges, the widest row the single-pass table kernel takes (fgmm_internal.h
+    tab_tl: at least 16 latents per block of 16384 edges), so that tab_kernel's phase 2 sees mixed rows in a decode too"""
+    return _spread(rng, n, 509, -1900.0, -1300.0, 2950.0, 3500.0)
+
+
+def _c_nan_sigma_one(rng, n):
+    """NaN in exactly one, two, three and four sigmas of half the rows, the others ordinary (fgmm_math.h Sigma4::set: `tame`)"""
+    v = _near_symbols(rng, n)
+    sg, mu, pi = _ordinary_at(rng, v)
+    cnt = np.where(rng.random(n) < 0.5, 0, rng.integers(1, 4, n, endpoint=True))
+    order = np.argsort(rng.random((n, 4)), 1)
+    sg = sg.copy()
+    sg[np.argsort(order, 1) < cnt[:, None]] = np.nan
+    return v, sg, mu, pi
+
+
+SIGMA_AT_CLAMP = np.array([np.nextafter(SIGMA_LO, F32(0)), SIGMA_LO, np.nextafter(SIGMA_LO, F32(1)), np.nextafter(SIGMA_HI, F32(0)),
+                           SIGMA_HI, np.nextafter(SIGMA_HI, F32(1e3)), 0.0, -0.0, 1e-40, -1.5, -np.inf, np.inf,
+                           np.finfo(F32).max], F32)
+
+
+def _c_sigma_at_clamp(rng, n):
+    """sigma at, one ulp inside and one ulp outside both ends of the clamp, and the values only the clamp makes legal
+    (fgmm_math.h Sigma4::set's v_med3_f32 against clamp_scale)"""
+    v = _near_symbols(rng, n)
+    sg, mu, pi = _ordinary_at(rng, v)
+    m = _spots(rng, n, 0.3)
+    m[rng.random(n) < 0.3] = False
+    sg = sg.copy()
+    sg[m] = rng.choice(SIGMA_AT_CLAMP, int(m.sum()))
+    return v, sg, mu, pi
+
+
+def _c_logistic_rcp_guard(rng, n):
+    """z with 1 + exp(-1.702 z) just below, at and above 2^60 (fgmm_math.h Phi2<MODE_LOGISTIC>, tame(d.x) && tame(d.y)) in one or
+    all four components: every binary32 within 64 ulp of the threshold z = -60 ln 2 / 1.702 (sigma 1: z = x - mu exactly), a
+    band around it, and sigma 0.11 with x - mu down to -2047 (the exponential at its upper clamp)"""
+    v = _near_symbols(rng, n, 8)
+    sg, mu, pi = _ordinary_at(rng, v)
+    x = v.astype(np.float64) - 0.5
+    zt = F32(-60.0 * np.log(2.0) / 1.702)
+    kind = rng.integers(0, 4, n)
+    z = np.where(kind == 0, zt + rng.integers(-64, 64, n, endpoint=True) * np.spacing(zt),
+                 np.where(kind == 1, rng.uniform(-60, -24.5, n), np.where(kind == 2, rng.uniform(-24.4, -10, n), 0.0)))
+    s_hit = np.where(kind == 3, SIGMA_LO, F32(1.0)).astype(F32)
+    a = np.where(kind == 3, np.where(rng.random(n) < 0.2, -2047.0, -np.exp(rng.uniform(np.log(1.0), np.log(2047.0), n))), z)
+    hit = np.zeros((n, 4), bool)
+    hit[np.arange(n), rng.integers(0, 4, n)] = True
+    hit[rng.random(n) < 0.3] = True
+    mu = np.where(hit, (x - a)[:, None], mu).astype(F32)
+    sg = np.where(hit, s_hit[:, None], sg).astype(F32)
+    return v, sg, mu, pi
+
+
+def _c_sat_edges(rng, n):
+    """(v - 0.5 - mu_k) / sigma_k within a few ulp of -ZL and +ZR of each mode at a v inside the range, for one component and for
+    all four, sigma 0.11 and 256 among them (fgmm_tab.hip tab_window: the rounding of vL / vR and their - 1.0f / + 1.0f)"""
+    v = _near_symbols(rng, n)
+    sg, mu, pi = _ordinary_at(rng, v)
+    zs = np.array([c for zl, zr in SAT_Z.values() for c in (-zl, zr)], F32)
+    z = rng.choice(zs, n)
+    s_hit = rng.choice(np.array([0.11, 0.25, 1.0, 3.0, 17.5, 256.0], F32), n)
+    vt = rng.integers(-30, 30, n, endpoint=True)
+    m_hit = ((vt - 0.5).astype(F32) - z * s_hit).astype(F32)  # z(vt) = (vt - 0.5 - mu) / sigma ~ z
+    m_hit = (m_hit + rng.integers(-3, 3, n, endpoint=True) * np.spacing(m_hit)).astype(F32)
+    hit = np.zeros((n, 4), bool)
+    hit[np.arange(n), rng.integers(0, 4, n)] = True
+    hit[rng.random(n) < 0.4] = True
+    return v, np.where(hit, s_hit[:, None], sg).astype(F32), np.where(hit, m_hit[:, None], mu).astype(F32), pi
+
+
+def _c_window_weights(rng, n):
+    """weights for which tab_window must refuse the pruning lemma (fgmm_math.h Sat<MODE>::weight_ok) or T_sat = quant16(sum pi)
+    is unusual (fgmm_tab.hip tab_window): 1 + ulp, -0.0, tiny negative, a sum above one whose quant16 wraps past 65535, a sum
+    below one, all zero, one NaN, +inf, and a weight of tens to millions"""
+    v = _near_symbols(rng, n)
+    sg, mu, pi = _ordinary_at(rng, v)
+    pi = pi.copy()
+    kind = rng.integers(0, 12, n)
+    k = rng.integers(0, 4, n)
+    r = np.arange(n)
+    one_hot = np.zeros((n, 4), F32)
+    one_hot[r, k] = 1.0
+    sel = kind == 0  # one weight of 1 + ulp, the others +0
+    pi[sel] = one_hot[sel] * np.nextafter(F32(1), F32(2))
+    sel = kind == 1  # -0.0 beside ordinary weights
+    pi[r[sel], k[sel]] = -0.0
+    sel = kind == 2  # tiny negative
+    pi[r[sel], k[sel]] = rng.choice(np.array([-1e-45, -1e-30, -1e-8], F32), int(sel.sum()))
+    sel = kind == 3  # a sum above one: (sum pi) * 65535 >= 65536 wraps in 16 bits
+    pi[sel] = (pi[sel] * rng.uniform(1.1, 3.0, (int(sel.sum()), 1))).astype(F32)
+    sel = kind == 4  # a sum below one
+    pi[sel] = (pi[sel] * rng.uniform(0.05, 0.98, (int(sel.sum()), 1))).astype(F32)
+    pi[kind == 5] = 0.0
+    sel = (kind == 6) | (kind == 10)
+    pi[r[sel], k[sel]] = np.nan
+    sel = (kind == 7) | (kind == 11)
+    pi[r[sel], k[sel]] = np.inf
+    sel = kind == 8  # exactly one: a weight of 1.0f and three +0 (weight_ok's upper end, inside)
+    pi[sel] = one_hot[sel]
+    sel = kind == 9  # far outside [0, 1]: the logistic left tail's 2^-20 bound times such a weight is a whole count of the 16-bit CDF
+    pi[r[sel], k[sel]] = rng.choice(np.array([20.0, 1000.0, 1e6, -50.0, -4000.0], F32), int(sel.sum()))
+    return v, sg, mu, pi
+
+
+CLAMP_FAMILIES = {
+    "guard_2048": _c_guard_2048,
+    "spread_means": _c_spread_means,
+    "spread_means_1022": _c_spread_means_1022,
+    "spread_means_510": _c_spread_means_510,
+    "nan_sigma_one": _c_nan_sigma_one,
+    "sigma_at_clamp": _c_sigma_at_clamp,
+    "logistic_rcp_guard": _c_logistic_rcp_guard,
+    "sat_edges": _c_sat_edges,
+    "window_weights": _c_window_weights,
+}
+# Families that keep their character as float16 planes (rounded to nearest): NaN sigmas and the weights' NaN / inf / -0.0 / sums
+# above one survive as they are; guard_2048's means near +-2048 round to even integers, so |x - mu| still lies on both sides of
+# 2^11, no longer at the listed distances.  The others do not: 0.11 +- ulp, the 64-ulp band of logistic_rcp_guard and the few
+# ulp of sat_edges collapse, and spread_means' sigma and means lose what separates its rows from wide_sigma's.
+CLAMP_FP16_FAMILIES = ("guard_2048", "nan_sigma_one", "window_weights")
+# Families whose rows can decrease under the clamp (negative, NaN or infinite weights): the ones the segment decoder must hand back
+CLAMP_NONMONO_FAMILIES = ("neg_weights", "nan_weights", "dip_weights", "window_weights")
+
+
+def clamp_case(family: str, n: int = 2304, seed: int = 0):
+    """-> dict(v int32 [n]; s, m, w [n, 4] float32, sigma PRE-clamp) of a CLAMP_FAMILIES family"""
+    v, s, m, w = CLAMP_FAMILIES[family](_rng("clamp/" + family, seed), n)
+    return {"v": np.ascontiguousarray(v, np.int32), "s": np.ascontiguousarray(s, F32), "m": np.ascontiguousarray(m, F32),
+            "w": np.ascontiguousarray(w, F32)}
+
+
+def clamp_case_after(family: str, n: int, n_head: int, seed: int = 0):
+    """a family of CLAMP_FAMILIES or PARAM_FAMILIES whose first n_head rows are ordinary ones (param_case_after's construction),
+    symbols within +-40"""
+    if family in CLAMP_FAMILIES:
+        c = clamp_case(family, n, seed)
+    else:
+        c = {k: a for k, a in param_case(family, n, seed).items() if k in ("v", "s", "m", "w")}
+        c["v"] = np.clip(c["v"], -40, 40).astype(np.int32)
+    s, m, w = _ordinary(_rng(family + "/head", seed), n_head)
+    c["s"][:n_head], c["m"][:n_head], c["w"][:n_head] = s, m, w
+    c["v"][:n_head] = np.clip(c["v"][:n_head], -40, 40)
+    return c
+
+
+# ---- the guards, restated on the inputs: each -> bool [n], True where the row stays on the FAST side -----------------------
+def _a_of(c):
+    """(v - 0.5) - mu_k as the kernels compute it: binary32, one rounding"""
+    x = (c["v"].astype(F32) - F32(0.5)).astype(F32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (x[:, None] - c["m"]).astype(F32)
+
+
+def guard_tame_sigma(c):
+    """Sigma4::set: no sigma is NaN"""
+    return ~np.isnan(c["s"]).any(1)
+
+
+def guard_near_means(c):
+    """sym_entry's fast path: Sigma4::tame and every |(v - 0.5) - mu_k| < 2^11 (False for NaN / inf)"""
+    with np.errstate(invalid="ignore"):
+        return guard_tame_sigma(c) & (np.abs(_a_of(c)) < F32(GUARD_A)).all(1)
+
+
+def guard_clamp_idle(c):
+    """the clamp changes no sigma of the row"""
+    with np.errstate(invalid="ignore"):
+        return (clamp_sigma(c["s"]).view(np.uint32) == c["s"].view(np.uint32)).all(1)
+
+
+def guard_logistic_rcp(c):
+    """Phi2<MODE_LOGISTIC>: d = 1 + exp(-1.702 z) < 2^60 in both halves (x = v - 0.5 and x + 1) of every component.  z and the
+    exponential's argument in binary32 as the kernel rounds them; the exponential itself in double (rows within the last ulp of
+    the threshold may fall on either side here: the split that is asserted counts quarters)"""
+    ok = np.ones(len(c["v"]), bool)
+    s = clamp_sigma(c["s"])
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for a in (_a_of(c), (_a_of(c) + F32(1)).astype(F32)):
+            z = (a / s).astype(F32)
+            arg = -(LOGISTIC_C * z).astype(F32)
+            d = 1.0 + np.exp(np.minimum(arg.astype(np.float64), EXP_HI))
+            ok &= (d < RCP_TAME).all(1)
+    return ok
+
+
+def guard_weights_logistic(c):
+    """Sat<MODE_LOGISTIC>::weight_ok for all four: 0 <= pi <= 1 (-0.0 passes, NaN does not)"""
+    with np.errstate(invalid="ignore"):
+        return ((c["w"] >= 0) & (c["w"] <= 1)).all(1)
+
+
+def guard_weights_finite(c):
+    """Sat<MODE_POLYA / MODE_AS>::weight_ok for all four: finite"""
+    return np.isfinite(c["w"]).all(1)
+
+
+def near_sat_edge(c, max_bs: int, ulps: int = 8):
+    """rows where some component's z at some edge v - 0.5, v in [-max_bs, max_bs + 1], lies within `ulps` of a -ZL or +ZR"""
+    s = clamp_sigma(c["s"])
+    hit = np.zeros(len(c["v"]), bool)
+    x = (np.arange(-max_bs, max_bs + 2).astype(F32) - F32(0.5)).astype(F32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        z = ((x[None, :, None] - c["m"][:, None, :]) / s[:, None, :]).astype(F32)
+        for zl, zr in SAT_Z.values():
+            for t in (F32(-zl), F32(zr)):
+                hit |= (np.abs(z - t) <= ulps * np.spacing(np.abs(t))).any((1, 2))
+    return hit
+
+
+def window_pair_kinds(c, max_bs: int):
+    """-> (fast [n], slow [n]): the number of integer v in [-max_bs, max_bs] between the row's smallest and largest mean - edges
+    every mode's evaluation window holds, since z changes sign there - whose edge v - 0.5 is within 2^11 of all four means, and
+    the number where it is not"""
+    vv = np.arange(-max_bs, max_bs + 1)
+    x = (vv.astype(F32) - F32(0.5)).astype(F32)
+    inside = (vv[None, :] >= np.ceil(c["m"].min(1))[:, None]) & (vv[None, :] <= np.floor(c["m"].max(1))[:, None])
+    near = (np.abs((x[None, :, None] - c["m"][:, None, :]).astype(F32)) < F32(GUARD_A)).all(2)
+    return (inside & near).sum(1), (inside & ~near).sum(1)
+
+
+# family -> the guards it names: at least a quarter of its rows lie on each side of every one of them
+CLAMP_GUARDS = {
+    "guard_2048": (guard_near_means,),
+    "nan_sigma_one": (guard_tame_sigma,),
+    "sigma_at_clamp": (guard_clamp_idle,),
+    "logistic_rcp_guard": (guard_logistic_rcp,),
+    "window_weights": (guard_weights_logistic, guard_weights_finite),
+}
 
 
 # ---- streams -----------------------------------------------------------------------------------------------------------

@@ -233,7 +233,10 @@ const char *error_string(int e) { return e == kErrUnsupported ? "fake device: ke
 // ================================================================================================================ the "kernels"
 namespace {
 
-inline float clamp_sigma(float s) { return fminf(fmaxf(s, 0.11f), 256.0f); } // entropy_models.py:817 (NaN behaviour not exercised here)
+inline float clamp_sigma(float s) { // entropy_models.py:817: torch.clamp keeps NaN, as clamp_scale does (fgmm_math.h); fminf / fmaxf would drop it
+  s = (s < 0.11f) ? 0.11f : s;
+  return (s > 256.0f) ? 256.0f : s;
+}
 
 // (hw, 4) rows of one channel of an item's planar parameters, sigma clamped when asked
 struct Rows {

@@ -2,6 +2,7 @@
 // (fake_device.cpp), meant to run under ThreadSanitizer / AddressSanitizer + UBSan (scripts/tsan_host.sh).  Every batch:
 //   fgmm_gmc_compress_batch   -> each bitstream == the oracle's encoder on the same symbols and parameters (fgo_encode_gmm), bit for bit
 //   fgmm_gmc_decompress_batch -> y_hat == round(y) for every item
+// (sigma un-clamped, a NaN sigma and a mean beyond 2^11 in some items: the clamped path with its hand-backs, against the oracle)
 // under random pipeline options (pieces, first launch, Elias-Fano threshold, encoder ways, whole / segmented encode
 // tables, scatter rounds, checkpointed streams decoded in host segments / handed to the "GPU" and partly handed back, a tiny staging
 // budget that forces overflow re-runs, an LDS budget that sends items to the generic kernels) and random worker counts; now and then a
@@ -56,6 +57,12 @@ struct Item {
   std::vector<int64_t> zb;
 };
 
+// torch.clamp(s, 0.11, 256): NaN stays NaN (fminf / fmaxf would turn it into 0.11)
+static float clamp_sigma(float s) {
+  s = (s < 0.11f) ? 0.11f : s;
+  return (s > 256.0f) ? 256.0f : s;
+}
+
 static void make_item(Item &it, int M, int64_t hw, double zero_frac) {
   it.M = M, it.hw = hw;
   const size_t n = (size_t)M * (size_t)hw;
@@ -76,6 +83,13 @@ static void make_item(Item &it, int M, int64_t hw, double zero_frac) {
       }
     }
   }
+  // one item in three: what the clamped kernels' fast evaluation hands back to the IEEE one - a NaN sigma (the clamp keeps it:
+  // Sigma4::set's `tame`) and a mean more than 2^11 from the latent (mix4_clamped2's compare) - in a few latents each
+  if (n > 0 && rnd() % 3 == 0)
+    for (int r = 0; r < 1 + (int)(n / 64); ++r) {
+      it.sg[(size_t)(rnd() % 4) * n + (size_t)(rnd() % n)] = NAN;
+      it.mu[(size_t)(rnd() % 4) * n + (size_t)(rnd() % n)] = (float)((rnd() % 2 ? 1.0 : -1.0) * (2040.0 + 40.0 * uni() + (rnd() % 4 ? 0.0 : 1e6 * uni())));
+    }
 }
 
 // one coded channel of an item through the raw (n, 4) boundary, host memory, the reference's view strides (1, n)
@@ -90,7 +104,7 @@ static void raw_boundary(fgmm_ctx *ctx, const Item &it, int mode) {
     sym[(size_t)p] = (int32_t)nearbyintf(it.y[(size_t)c * it.hw + p]);
     amax = std::max(amax, std::abs(sym[(size_t)p]));
     for (int k = 0; k < 4; ++k) {
-      s[(size_t)k * n + p] = fminf(fmaxf(it.sg[(size_t)k * n_all + (size_t)c * it.hw + p], 0.11f), 256.0f);
+      s[(size_t)k * n + p] = clamp_sigma(it.sg[(size_t)k * n_all + (size_t)c * it.hw + p]);
       m[(size_t)k * n + p] = it.mu[(size_t)k * n_all + (size_t)c * it.hw + p];
       w[(size_t)k * n + p] = it.pi[(size_t)k * n_all + (size_t)c * it.hw + p];
     }
@@ -129,7 +143,7 @@ static void coded_rows(const Item &it, std::vector<int32_t> &sym, std::vector<fl
       const size_t at = (size_t)c * it.hw + p;
       sym.push_back((int32_t)nearbyintf(it.y[at]));
       for (int k = 0; k < 4; ++k) {
-        s.push_back(fminf(fmaxf(it.sg[(size_t)k * n_all + at], 0.11f), 256.0f));
+        s.push_back(clamp_sigma(it.sg[(size_t)k * n_all + at]));
         m.push_back(it.mu[(size_t)k * n_all + at]);
         w.push_back(it.pi[(size_t)k * n_all + at]);
       }
