@@ -50,23 +50,32 @@ class fgmm_item(C.Structure):
                 ("ckpt", C.c_void_p), ("n_ckpt", C.c_int64)]
 
 
-def _item_dtype():
+class fgmm_rate_item(C.Structure):
+    """one item of fgmm_gmc_estimate_batch (include/flashgmm_amd.h section 3b)"""
+    _fields_ = [("y", C.c_void_p), ("params", fgmm_params), ("M", C.c_int32), ("K", C.c_int32), ("hw", C.c_int64),
+                ("zero_bitmap", C.c_void_p), ("chan_bits_q", C.c_void_p), ("bits_map", C.c_void_p), ("abs_max", C.c_int32),
+                ("status", C.c_int32), ("n_symbols", C.c_int64), ("n_bypass", C.c_int64), ("bits_q", C.c_uint64), ("bytes_pred", C.c_uint64)]
+
+
+def _item_dtype(struct=fgmm_item):
     """numpy view of ``fgmm_item[]`` (offsets taken from the ctypes declaration): lets a batch be filled column by
     column instead of field by field."""
     import numpy as np
     names, formats, offsets = [], [], []
-    kinds = {C.c_void_p: "<u8", C.c_int64: "<i8", C.c_int32: "<i4", C.c_size_t: "<u8"}
-    for name, typ in fgmm_item._fields_:
-        base = getattr(fgmm_item, name).offset
+    kinds = {C.c_void_p: "<u8", C.c_int64: "<i8", C.c_int32: "<i4", C.c_size_t: "<u8", C.c_uint64: "<u8"}
+    for name, typ in struct._fields_:
+        base = getattr(struct, name).offset
         if typ is fgmm_params:
             for pn, pt in fgmm_params._fields_:
                 names.append(pn); formats.append(kinds[pt]); offsets.append(base + getattr(fgmm_params, pn).offset)
         else:
             names.append(name); formats.append(kinds[typ]); offsets.append(base)
-    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": C.sizeof(fgmm_item)})
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": C.sizeof(struct)})
 
 
 ITEM_DTYPE = _item_dtype()
+RATE_ITEM_DTYPE = _item_dtype(fgmm_rate_item)
+FGMM_RATE_Q = 24  # unit of the size estimate's costs: 2^-24 bit
 
 SINK_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)  # fgmm_sink.alloc(user, item, nbytes) -> address
 
@@ -125,6 +134,10 @@ SIGNATURES = {
     "fgmm_rans_encode_symtab_segs": (_i, [_p, _i, _i64, _p, _i64, _i64, _pp, _psz, _p]),
     "fgmm_rans_decode_cdftab": (_i, [_p, _sz, _p, _p, C.c_uint64, _i64, _i32, _i, _p]),
     "fgmm_rans_decode_tab": (_i, [_p, _sz, _p, _i, _p, _i32, _p, C.c_uint64, _i64, _i32, _i, _p]),
+    "fgmm_symtab_bits": (_i, [_p, _p, _i64, _p, C.POINTER(C.c_uint64), C.POINTER(_i64)]),
+    "fgmm_rate_stream_bytes": (C.c_uint64, [C.c_uint64]),
+    "fgmm_symtab_bits_hip": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p]),
+    "fgmm_gmc_estimate_batch": (_i, [_p, _p, C.POINTER(fgmm_rate_item), _i, _i, _i]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

@@ -103,6 +103,8 @@ void fgmm_ctx::trim() {
   if (d_ws) (void)dev::free_device(d_ws);
   if (h_ws) (void)dev::free_pinned(h_ws);
   if (d_stage) (void)dev::free_device(d_stage);
+  if (d_rate_log2) (void)dev::free_device(d_rate_log2);
+  d_rate_log2 = nullptr;
   for (auto &c : chunks) (void)dev::free_pinned(c.p);
   chunks.clear();
   d_ws = h_ws = d_stage = nullptr;

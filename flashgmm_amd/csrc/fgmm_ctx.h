@@ -358,6 +358,7 @@ struct fgmm_ctx {
   char *d_stage = nullptr;
   size_t d_stage_cap = 0;
   int ensure_stage(size_t bytes);
+  uint32_t *d_rate_log2 = nullptr; // device copy of rate_log2_table() (fgmm_estimate.cpp uploads it on first use; trim() releases it)
   size_t stage_budget() const; // bytes the staging area may take
   int ensure_streams();
   int ensure_device(size_t bytes);

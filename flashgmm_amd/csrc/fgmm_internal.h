@@ -265,6 +265,34 @@ int launch_fastmath_selftest(int which, unsigned long long n, unsigned long long
 // exhaustive check of the saturation lemmas behind the pruning; *n_bad (device) receives the number of violations
 int launch_saturation_selftest(int mode, unsigned long long *n_bad, void *stream);
 
+// ---- coded size without coding (fgmm_rate_host.cpp, fgmm_rate.hip, fgmm_estimate.cpp) ----------------------------
+// One entry's cost in units of 2^-FGMM_RATE_Q bit, the same integer arithmetic on the host and in the kernels (derivation:
+// include/flashgmm_amd.h section 3b).  L = rate_log2_table() or its device copy; `symbol` is only looked at for a bypass entry.
+FGMM_HD static inline int32_t rate_entry_symbol(uint32_t entry) { // what fgmm_rans_encode_symtab codes for a bypass entry without `symbols`
+  return (int32_t)(int16_t)(uint16_t)(entry & 0xFFFFu);
+}
+FGMM_HD static inline uint32_t rate_nibbles(int32_t symbol) { // nibbles of the uint32 bit pattern up to its leading one: 0 for 0, 8 for any negative symbol
+  const uint32_t raw = (uint32_t)symbol;
+  return raw ? (uint32_t)(32 - __builtin_clz(raw) + 3) >> 2 : 0u;
+}
+FGMM_HD static inline uint32_t rate_cost_q(uint32_t entry, int32_t symbol, const uint32_t *L) {
+  const uint32_t range = entry >> 16;
+  return range ? (16u << FGMM_RATE_Q) - L[range] : (16u + 4u * (1u + rate_nibbles(symbol))) << FGMM_RATE_Q;
+}
+FGMM_HD static inline uint64_t rate_stream_bytes(uint64_t bits_q) { return 4ull * ((bits_q + (64ull << FGMM_RATE_Q)) >> (FGMM_RATE_Q + 5)); }
+const uint32_t *rate_log2_table(); // host uint32[65536]: L[r] = round(2^FGMM_RATE_Q * log2 r), built once
+struct RateDesc {                  // item i of a rate_kernel launch, beside its EncDesc
+  unsigned long long *chan_bits;   // device [M], zeroed by the host: sum of the costs of channel c's symbols (0: not coded)
+  unsigned long long *chan_bypass; // device [M], zeroed by the host: its bypass symbols
+  float *bits_map;                 // device [M * hw] or null: cost_q * 2^-FGMM_RATE_Q per latent of the coded channels
+};
+// the arithmetic of launch_symtab ending in a reduction instead of a table: vec = 4 (everything 16-byte aligned) or 1
+int launch_rate(const EncDesc *d_descs, const RateDesc *d_rdescs, const uint32_t *d_log2, int count, int M_max, int64_t hw_max,
+                int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
+// table -> cost: bits_q / n_bypass (device, single words) are ADDED to
+int launch_symtab_bits(const uint32_t *packed, const int32_t *symbols_or_null, int64_t n, const uint32_t *d_log2, uint32_t *cost_q_or_null,
+                       unsigned long long *bits_q, unsigned long long *n_bypass, void *stream);
+
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the
 // encoder asks it for storage of the stream's exact size once that is known and copies the stream there out of its scratch: the

@@ -27,7 +27,7 @@ from torch import Tensor
 
 from . import _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -108,6 +108,38 @@ class CompressedBatch(Sequence):
 
     def __radd__(self, other):
         return list(other) + list(self)
+
+
+class RateEstimate:
+    """The coded size of one latent, computed on the GPU WITHOUT running the coder (``GaussianMixtureConditional.estimate_bits`` /
+    ``estimate_bits_batch``; include/flashgmm_amd.h section 3b):
+
+    ``bits_q``       exact ideal code length of the symbols ``compress`` would code, in units of 2^-24 bit (an integer: the same
+                     on every run);  ``bits`` = ``bits_q / 2**24``
+    ``nbytes``       predicted ``len(bytes)`` of the bitstream: ``4 * ((bits_q + (64 << 24)) >> 29)`` - the stream's length, except
+                     where ``bits`` lies within the coder's accumulated rounding of a multiple of 32 (then 4 bytes off)
+    ``n_symbols``    symbols coded (coded channels x h x w);  ``n_bypass``: those that take the bypass escape
+    ``abs_max``, ``zero_bitmap``   what ``compress`` returns (``zero_bitmap``: int64 ``[M]`` CPU tensor)
+    ``channel_bits_q`` / ``channel_bits``   per channel, int64 / float64 ``[M]`` CPU tensors (``per_channel=True``; else None)
+    ``latent_bits``  float32 ``[1, M, h, w]`` on the inputs' device: bits per latent, 0 in the channels that are not coded
+                     (``per_latent=True``; else None)"""
+
+    __slots__ = ("bits_q", "nbytes", "n_symbols", "n_bypass", "abs_max", "zero_bitmap", "channel_bits_q", "latent_bits")
+
+    def __init__(self, bits_q, nbytes, n_symbols, n_bypass, abs_max, zero_bitmap, channel_bits_q=None, latent_bits=None):
+        self.bits_q, self.nbytes, self.n_symbols, self.n_bypass = int(bits_q), int(nbytes), int(n_symbols), int(n_bypass)
+        self.abs_max, self.zero_bitmap, self.channel_bits_q, self.latent_bits = int(abs_max), zero_bitmap, channel_bits_q, latent_bits
+
+    @property
+    def bits(self) -> float:
+        return self.bits_q / float(1 << _lib.FGMM_RATE_Q)
+
+    @property
+    def channel_bits(self):
+        return None if self.channel_bits_q is None else self.channel_bits_q.to(torch.float64) / float(1 << _lib.FGMM_RATE_Q)
+
+    def __repr__(self) -> str:
+        return f"RateEstimate(bits={self.bits:.3f}, nbytes={self.nbytes}, n_symbols={self.n_symbols}, n_bypass={self.n_bypass}, abs_max={self.abs_max})"
 
 
 def _take_ckpts_many(device: int, ptrs, counts):
@@ -291,7 +323,7 @@ class GaussianMixtureConditional(nn.Module):
             keep.append(yc)
         return yp, s.data_ptr(), m.data_ptr(), w.data_ptr(), M, hw, sk, sc, s.device, s.dtype
 
-    def _stacked_items(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, flags: int = 0):
+    def _stacked_items(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, flags: int = 0, dtype=None):
         """``fgmm_item[N]`` (as a numpy record array) for N items given as ONE tensor each: y ``[N, M, h, w]``,
         parameters ``[N, K*M, h, w]``.  One validation and one set of strides for the whole batch; the item
         pointers are the batch-dimension offsets."""
@@ -312,7 +344,7 @@ class GaussianMixtureConditional(nn.Module):
         M = KM // self.K
         sc = st[1] if KM > 1 else hw
         esz = scales.element_size()
-        items = np.zeros(N, _lib.ITEM_DTYPE)
+        items = np.zeros(N, _lib.ITEM_DTYPE if dtype is None else dtype)  # (fgmm_item[], or fgmm_rate_item[]: the same input fields)
         step = np.arange(N, dtype=np.uint64) * np.uint64(st[0] * esz)
         items["scales"] = np.uint64(scales.data_ptr()) + step
         items["means"] = np.uint64(means.data_ptr()) + step
@@ -569,6 +601,74 @@ class GaussianMixtureConditional(nn.Module):
             cks = _take_ckpts_many(di, items["ckpt"].tolist(), items["n_ckpt"].tolist())
             datas = [CheckpointedBytes._adopt(d, ck[0], self.checkpoint_stride, ck[1]) for d, ck in zip(datas, cks)]
         return CompressedBatch(datas, items["abs_max"].tolist(), zb, yq)
+
+    def estimate_bits_batch(self, ys, scales, means, weights, *, weights_are_logits: bool = False, per_channel: bool = False,
+                            per_latent: bool = False) -> List[RateEstimate]:
+        """The size of what ``compress_batch`` would return for the same arguments, WITHOUT coding: one kernel does the encode-side
+        CDF kernel's arithmetic and sums the exact code length (no table, nothing but a few KB across PCIe, no host coder).
+        Inputs as ``compress_batch`` takes them - sequences of ``[1, M, h, w]`` / ``[1, K*M, h, w]`` tensors, or stacked.
+        -> one ``RateEstimate`` per item; ``per_channel`` / ``per_latent`` add the per-channel sums and the per-latent map."""
+        if self.K != _lib.FGMM_K:
+            raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
+        flags = _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0
+        if isinstance(ys, Tensor):
+            items, keep, N, M, h, w, dev = self._stacked_items(ys, scales, means, weights, flags, _lib.RATE_ITEM_DTYPE)
+            if N == 0:
+                return []
+            rng = np.arange(N, dtype=np.uint64)
+            zb = torch.empty((N, M), dtype=torch.int64)
+            items["zero_bitmap"] = np.uint64(zb.data_ptr()) + rng * np.uint64(M * 8)
+            bitmaps = zb.unbind(0)
+            chans = maps = [None] * N
+            if per_channel:
+                cb = torch.empty((N, M), dtype=torch.int64)
+                items["chan_bits_q"] = np.uint64(cb.data_ptr()) + rng * np.uint64(M * 8)
+                chans = cb.unbind(0)
+            if per_latent:
+                lm = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
+                items["bits_map"] = np.uint64(lm.data_ptr()) + rng * np.uint64(M * h * w * 4)
+                maps = lm.unbind(0)
+            ptr = C.cast(items.ctypes.data, C.POINTER(_lib.fgmm_rate_item))
+        else:
+            N = len(ys)
+            if N == 0:
+                return []
+            arr = (_lib.fgmm_rate_item * N)()
+            keep, bitmaps, chans, maps, dev = [], [], [], [], None
+            for i in range(N):
+                yp, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
+                dev = dev or d
+                if d != dev:
+                    raise RuntimeError("all items of a batch must be on one device")
+                it = arr[i]
+                it.y = yp
+                it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
+                it.M, it.K, it.hw = M, self.K, hw
+                zb = torch.empty(M, dtype=torch.int64)
+                it.zero_bitmap = zb.data_ptr()
+                bitmaps.append(zb)
+                cb = torch.empty(M, dtype=torch.int64) if per_channel else None
+                if cb is not None:
+                    it.chan_bits_q = cb.data_ptr()
+                chans.append(cb)
+                lm = torch.empty((1, M) + tuple(ys[i].shape[2:]), dtype=torch.float32, device=d) if per_latent else None
+                if lm is not None:
+                    it.bits_map = lm.data_ptr()
+                maps.append(lm)
+            items = np.frombuffer(arr, dtype=_lib.RATE_ITEM_DTYPE)
+            ptr = arr
+        di = dev.index if dev.index is not None else -1
+        rc = _lib.lib().fgmm_gmc_estimate_batch(_lib.ctx(di), torch.cuda.current_stream(dev).cuda_stream, ptr, N, self._mode(), int(self.clamp_scales))
+        _lib.check(rc, "GaussianMixtureConditional.estimate_bits")
+        cols = zip(items["bits_q"].tolist(), items["bytes_pred"].tolist(), items["n_symbols"].tolist(), items["n_bypass"].tolist(),
+                   items["abs_max"].tolist(), bitmaps, chans, maps)
+        return [RateEstimate(*c) for c in cols]
+
+    def estimate_bits(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, weights_are_logits: bool = False,
+                      per_channel: bool = False, per_latent: bool = False) -> RateEstimate:
+        """-> the ``RateEstimate`` of ``compress(y, scales, means, weights)``: its size, without coding"""
+        return self.estimate_bits_batch([y], [scales], [means], [weights], weights_are_logits=weights_are_logits, per_channel=per_channel,
+                                        per_latent=per_latent)[0]
 
     def compress(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, weights_are_logits: bool = False):
         """-> ((bytes, abs_max, zero_bitmap), y_quantized)     (entropy_models.py:833-867)"""

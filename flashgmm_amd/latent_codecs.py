@@ -126,6 +126,12 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         return [{"strings": [(b, a, zb.to(y.device))], "shape": y.shape[2:4], "y_hat": yq}
                 for ((b, a, zb), yq), y in zip(res, ys)]
 
+    def estimate_many(self, prepared: List[Tuple[Tensor, Tensor, Tensor, Tensor]], **kwargs: Any):
+        """the sizes of what ``compress_many`` would return for the same ``coder_inputs`` results, without coding them: a list of
+        ``RateEstimate`` (``GaussianMixtureConditional.estimate_bits_batch``; ``per_channel`` / ``per_latent`` are passed on)"""
+        ys, ss, ms, ws = zip(*prepared)
+        return self.gaussian_mixture_conditional.estimate_bits_batch(list(ys), list(ss), list(ms), list(ws), weights_are_logits=self.fuse_softmax, **kwargs)
+
     def decompress(self, strings: List[Any], shape: Tuple[int, int], ctx_params: Tensor, **kwargs: Any) -> Dict[str, Any]:
         (y_strings,) = strings
         scales_hat, means_hat, weights = self._params(ctx_params)
@@ -287,6 +293,23 @@ class CheckerboardLatentCodec(nn.Module):
         if self.fuse_head:
             return self.finish(self.latent_codec["y"].compress_many_head(prepared, self._head_parts()[1]), y_hat)
         return self.finish(self.latent_codec["y"].compress_many(prepared), y_hat)
+
+    def estimate(self, y: Tensor, side_params: Tensor, **kwargs: Any) -> Dict[str, Any]:
+        """The size of ``compress(y, side_params)``'s two bitstreams without coding them: ``prepare`` (the networks run as for
+        ``compress``), then one size-estimate call for both halves.  -> ``{"estimates": [anchors, non-anchors] (RateEstimate),
+        "bits_q", "bits", "nbytes"}``, the last three summed over the halves.  With ``fuse_head`` the parameters are the head's
+        (``ParameterHead.params``, logits) - the ones its fused encode kernel codes with."""
+        prepared, _ = self.prepare(y, side_params)
+        codec = self.latent_codec["y"]
+        if self.fuse_head:
+            codec._check_head()
+            ys, feats = zip(*prepared)
+            scales, means, logits = self._head_parts()[1].params(torch.cat(list(feats)))
+            est = codec.gaussian_mixture_conditional.estimate_bits_batch(torch.cat(list(ys)), scales, means, logits, weights_are_logits=True, **kwargs)
+        else:
+            est = codec.estimate_many(prepared, **kwargs)
+        bits_q = sum(e.bits_q for e in est)
+        return {"estimates": est, "bits_q": bits_q, "bits": bits_q / float(1 << 24), "nbytes": sum(e.nbytes for e in est)}
 
     def decompress(self, strings: List[Any], shape: Tuple[int, ...], side_params: Tensor, **kwargs: Any) -> Dict[str, Any]:
         n = 1

@@ -40,7 +40,8 @@ extern "C" {
 
 #define FGMM_ABI_VERSION 6 /* 6: + the parameter head (fgmm_head_*, fgmm_gmc_compress_head_batch); + fgmm_sink and the _to forms of the batched
                               compress calls; FGMM_WORKER_CPUS that cannot be honoured fails fgmm_ctx_create.  5: + fgmm_ctx_call_log; REMOVED (measured, lost, pruned): options tab_place /
-                              tab_spin / copy_engine / dec_pair / dec_group, fgmm_rans_decode_tab2 + fgmm_tab_ref, fgmm_ctx_stat index 6 */
+                              tab_spin / copy_engine / dec_pair / dec_group, fgmm_rans_decode_tab2 + fgmm_tab_ref, fgmm_ctx_stat index 6.
+                              Added since without a bump (nothing existing changed): section 3b, the coded size without running the coder */
 
 typedef enum {
   FGMM_OK = 0,
@@ -458,6 +459,61 @@ int fgmm_rans_decode_tab(const uint8_t *encoded, size_t encoded_len, const void 
 int fgmm_rans_decode_tab_ckpt(const uint8_t *encoded, size_t encoded_len, const void *hdr, int hdr_form, const uint32_t *blk_off,
                               int32_t tl, const uint8_t *rows, uint64_t rows_len, int64_t n, int32_t max_bs, int flags,
                               const fgmm_ckpt *ckpt, int64_t n_ckpt, int64_t stride, int32_t *out_symbols, int32_t *verified_out);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3b. The coded size WITHOUT running the coder (rate control, byte budgets, bpp, per-latent rate maps).
+ *    The stream's length is a closed form of the encode-side table.  With 16-bit frequencies
+ *      - a coded symbol of range r costs 16 - log2 r bits;
+ *      - a bypass symbol v costs 16 + 4 * (1 + nib(v)) bits: the {65535, 1} sentinel, one count nibble, and nib(v) nibbles -
+ *        those of v's uint32 bit pattern up to its leading one: 0 for v = 0, 8 for every negative v (rans_interface.cpp:524-551).
+ *    The coder's state starts at 2^31, ends in [2^31, 2^63) and is flushed as 8 bytes; Rans64EncPut departs from x * 2^16 / r
+ *    by a relative 2^-15 per symbol at worst (about 2^-31 in practice: the state is rarely at its floor).  So with B = sum of the
+ *    costs, 8 * len - B lies in (32, 64], and len being a multiple of 4,
+ *        len = 4 * floor((B + 64) / 32)                                       (the empty stream: 8 bytes)
+ *    - exact unless B lies within the accumulated departure of a multiple of 32, then 4 bytes off.
+ *    Costs are fixed point in units of 2^-FGMM_RATE_Q bit: (16 << 24) - L[r] with L[r] = 2^24 * log2 r rounded to nearest (exact
+ *    at powers of two), one table built by the host and shared with the kernels, so host and GPU agree bit for bit on every
+ *    symbol; sums are uint64 - independent of order, identical from run to run.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FGMM_RATE_Q 24
+/* Host, integer only: table -> cost, the counterpart of fgmm_rans_encode_symtab (table -> bytes).  cost_q_or_null: uint32[n], the
+ * cost of every entry; *bits_q_out their sum; *n_bypass_out the entries with range == 0 (any out-pointer may be NULL).  A bypass
+ * entry is priced by symbols_or_null[i] - or, without symbols, by what fgmm_rans_encode_symtab would code then: the entry's low 16
+ * bits sign-extended (right whenever abs(symbol) < 32768). */
+int fgmm_symtab_bits(const uint32_t *packed, const int32_t *symbols_or_null, int64_t n, uint32_t *cost_q_or_null, uint64_t *bits_q_out,
+                     int64_t *n_bypass_out);
+/* bytes of the flushed stream whose symbols cost bits_q: 4 * ((bits_q + (64 << 24)) >> 29) */
+uint64_t fgmm_rate_stream_bytes(uint64_t bits_q);
+/* GPU: the same from a table in device memory - with fgmm_build_symtab_hip a per-latent rate map for the (n, 4) layout.  All
+ * pointers device; cost_q_or_null uint32[n]; bits_q_dev / n_bypass_dev uint64[1] each (overwritten; either may be NULL).  Every
+ * value equals fgmm_symtab_bits'. */
+int fgmm_symtab_bits_hip(fgmm_ctx *ctx, void *stream, const uint32_t *packed, const int32_t *symbols_or_null, int64_t n,
+                         uint32_t *cost_q_or_null, uint64_t *bits_q_dev, uint64_t *n_bypass_dev);
+
+/* The fused form at the entropy-model level: what fgmm_gmc_compress_batch WOULD return for these items, priced by one kernel that
+ * does the encode-side CDF kernel's arithmetic on the same inputs (same addressing, same Phi, same softmax over K with
+ * FGMM_PARAMS_LOGITS, float32 or float16 planes) and ends in a reduction instead of a table: no table, no table traffic over
+ * PCIe, no host coder.  Per item:
+ *   abs_max, zero_bitmap   as fgmm_gmc_compress_batch returns them
+ *   n_symbols              symbols it would code (coded channels * hw);  n_bypass: those that take the bypass escape
+ *   bits_q                 their exact cost, units of 2^-FGMM_RATE_Q bit;  chan_bits_q[c]: channel c's part (0: not coded)
+ *   bytes_pred             fgmm_rate_stream_bytes of bits_q: the length of the bitstream (see above for when it is 4 off)
+ *   bits_map               cost_q * 2^-24 as float32 per latent, 0 in the channels that are not coded
+ * Arguments are validated as by the compress call (K != 4, null tensors, negative sizes, mixed dtypes: FGMM_ERR_INVALID; an
+ * item with M * hw == 0 is the empty stream, 8 bytes).  Returns with every output complete. */
+typedef struct {
+  const float *y;          /* device [M*hw] */
+  fgmm_params params;
+  int32_t M, K;
+  int64_t hw;
+  int64_t *zero_bitmap;    /* HOST int64[M] out, may be NULL */
+  uint64_t *chan_bits_q;   /* HOST uint64[M] out, may be NULL */
+  float *bits_map;         /* DEVICE float32[M*hw] out, may be NULL */
+  int32_t abs_max, status; /* out */
+  int64_t n_symbols, n_bypass; /* out */
+  uint64_t bits_q, bytes_pred; /* out */
+} fgmm_rate_item;
+int fgmm_gmc_estimate_batch(fgmm_ctx *ctx, void *stream, fgmm_rate_item *items, int count, int mode, int clamp_scales);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
