@@ -57,6 +57,13 @@ class fgmm_rate_item(C.Structure):
                 ("status", C.c_int32), ("n_symbols", C.c_int64), ("n_bypass", C.c_int64), ("bits_q", C.c_uint64), ("bytes_pred", C.c_uint64)]
 
 
+class fgmm_rdoq_item(C.Structure):
+    """one item of fgmm_gmc_rdoq_batch (include/flashgmm_amd.h section 3c)"""
+    _fields_ = [("y", C.c_void_p), ("params", fgmm_params), ("M", C.c_int32), ("K", C.c_int32), ("hw", C.c_int64),
+                ("y_rdo", C.c_void_p), ("zero_bitmap", C.c_void_p), ("chan_bits_q_after", C.c_void_p), ("abs_max", C.c_int32),
+                ("status", C.c_int32), ("n_changed", C.c_int64), ("bits_q_before", C.c_uint64), ("bits_q_after", C.c_uint64)]
+
+
 def _item_dtype(struct=fgmm_item):
     """numpy view of ``fgmm_item[]`` (offsets taken from the ctypes declaration): lets a batch be filled column by
     column instead of field by field."""
@@ -75,6 +82,7 @@ def _item_dtype(struct=fgmm_item):
 
 ITEM_DTYPE = _item_dtype()
 RATE_ITEM_DTYPE = _item_dtype(fgmm_rate_item)
+RDOQ_ITEM_DTYPE = _item_dtype(fgmm_rdoq_item)
 FGMM_RATE_Q = 24  # unit of the size estimate's costs: 2^-24 bit
 
 SINK_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)  # fgmm_sink.alloc(user, item, nbytes) -> address
@@ -138,6 +146,7 @@ SIGNATURES = {
     "fgmm_rate_stream_bytes": (C.c_uint64, [C.c_uint64]),
     "fgmm_symtab_bits_hip": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p]),
     "fgmm_gmc_estimate_batch": (_i, [_p, _p, C.POINTER(fgmm_rate_item), _i, _i, _i]),
+    "fgmm_gmc_rdoq_batch": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.c_double]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

@@ -289,6 +289,20 @@ struct Arena {
   }
 };
 
+// ---- fgmm_estimate.cpp: what the estimate call (3b) and the RDOQ call (3c) share ------------------------------------------------
+int ensure_rate_table(fgmm_ctx *ctx); // the context's device copy of rate_log2_table(), uploaded on first use
+struct CensusOff {                    // workspace offsets of one item's census: per channel min | max | any non-zero, the compact list
+  size_t o_min, o_max, o_nz, o_list;
+};
+CensusOff census_take(Arena &ar, int M);
+// the EncDesc of an item without a table: its latent, its census arrays at `o`, and (params non-null) its parameter planes
+void census_desc(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o, const float *y, const fgmm_params *params_or_null, int M, int64_t hw,
+                 int clamp);
+// can every load of an item, and the store to `out` (may be null), be 4 positions wide?
+bool census_vec4_ok(const EncDesc &d, const void *out, bool f16);
+// from the census copied back to the host: abs_max as the compress call returns it, zero_bitmap (may be null); the coded channels' count
+int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap_or_null, int32_t *abs_max_out);
+
 struct DeviceGuard {
   int prev = -1;
   bool ok = false;

@@ -1,4 +1,4 @@
-// fgmm_dev.h — device helpers shared by fgmm_kernels.hip (encode side, misc) and fgmm_tab.hip (decode-side tables).
+// fgmm_dev.h — device helpers shared by fgmm_kernels.hip (encode side, misc), fgmm_tab.hip (decode-side tables), fgmm_rate.hip and fgmm_rdoq.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,6 +70,12 @@ template <typename PT, int N> __device__ __forceinline__ void ldv(const void *ba
 // One entry of the encode-side table: both CDF edges of a symbol as one packed-fp32 pair, 16-bit quantisation, pmf == 0 -> the
 // reference's bypass escape (rans_interface.cpp:498-517).  Shared by symtab_kernel (parameters from planes) and the fused parameter
 // head (parameters straight from the MFMA accumulators, fgmm_head.hip).
+// the entry of symbol vi from its two quantised edges                                      (rans_interface.cpp:512-517)
+__device__ __forceinline__ uint32_t entry_from_edges(uint32_t lo, uint32_t hi, int vi, int &bypass) {
+  const uint32_t pmf = (hi - lo) & 0xFFFFu; // uint16_t pmf = next - value                (:512)
+  bypass = (pmf == 0);
+  return pmf ? (lo | (pmf << 16)) : ((uint32_t)vi & 0xFFFFu); // bypass: low 16 bits of the int32 symbol
+}
 template <int MODE, bool CLAMPED>
 __device__ __forceinline__ uint32_t sym_entry(float vq, int vi, const float (&mu)[4], const float (&sg)[4], const float (&pi)[4],
                                               int &bypass) {
@@ -93,9 +99,53 @@ __device__ __forceinline__ uint32_t sym_entry(float vq, int vi, const float (&mu
     lo = quant16(mix4<MODE>(x1, mu, sg, pi));
     hi = quant16(mix4<MODE>(x2, mu, sg, pi));
   }
-  const uint32_t pmf = (hi - lo) & 0xFFFFu; // uint16_t pmf = next - value                (:512)
-  bypass = (pmf == 0);
-  return pmf ? (lo | (pmf << 16)) : ((uint32_t)vi & 0xFFFFu); // bypass: low 16 bits of the int32 symbol
+  return entry_from_edges(lo, hi, vi, bypass);
+}
+
+// The quantised CDF at the FOUR edges vq - 1.5, vq - 0.5, vq + 0.5, vq + 1.5 of a latent with |vq| <= 2^20 (rdoq_kernel, fgmm_rdoq.hip):
+// there every edge is exact in binary32, so q[j], q[j + 1] are the `lo`, `hi` sym_entry computes for the symbol vq - 1 + j (its
+// float(v) - 0.5f and float(v) - 0.5f + 1.0f are these numbers), and entry_from_edges(q[j], q[j + 1], v) is its entry.  Clamped: two
+// packed pairs that share one Sigma4; a pair outside the fast cores' domain takes the IEEE evaluation edge by edge, as sym_entry's does
+// (inside the domain the two agree bit for bit, so it does not matter which pair an edge falls in).
+template <int MODE, bool CLAMPED>
+__device__ __forceinline__ void sym_edges4(float vq, const float (&mu)[4], const float (&sg)[4], const float (&pi)[4], uint32_t (&q)[4]) {
+  const float x[4] = {vq - 1.5f, vq - 0.5f, vq + 0.5f, vq + 1.5f};
+  float c[4];
+  if constexpr (CLAMPED) {
+    Sigma4 S;
+    S.set(sg[0], sg[1], sg[2], sg[3]);
+    bool ok_a = S.tame, ok_b = S.tame;
+    const f2 a = mix4_clamped2<MODE>((f2){x[0], x[1]}, mu, S, pi, ok_a);
+    const f2 b = mix4_clamped2<MODE>((f2){x[2], x[3]}, mu, S, pi, ok_b);
+    c[0] = a.x; c[1] = a.y; c[2] = b.x; c[3] = b.y;
+    if (__builtin_expect(!(ok_a && ok_b), 0)) {
+      const float s0 = clamp_scale(sg[0]), s1 = clamp_scale(sg[1]), s2 = clamp_scale(sg[2]), s3 = clamp_scale(sg[3]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (!(j < 2 ? ok_a : ok_b)) c[j] = mix4_slow<MODE>(x[j], mu[0], mu[1], mu[2], mu[3], s0, s1, s2, s3, pi[0], pi[1], pi[2], pi[3]);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c[j] = mix4<MODE>(x[j], mu, sg, pi);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) q[j] = quant16(c[j]);
+}
+
+// ---- exact code lengths (fgmm_rate.hip, fgmm_rdoq.hip): integer costs, summed in uint64 across the wave, one atomic per wave ----------
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ void add64(unsigned long long *p, unsigned long long v) { // no value returned: the wave does not wait for it
+  (void)__hip_atomic_fetch_add((FGMM_GLOBAL unsigned long long *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the symbol a bypass entry codes: the raw symbol, or the rounded latent converted as the host converts it (torch's .int():
+// INT32_MIN for NaN, infinities and everything beyond int32 - fgmm_encode.cpp side_info)
+__device__ __forceinline__ uint32_t entry_cost(uint32_t ent, float vq, int vi, bool from_y, const uint32_t *__restrict__ L) {
+  if (__builtin_expect((ent >> 16) != 0, 1)) return (16u << FGMM_RATE_Q) - L[ent >> 16];
+  return rate_cost_q(0u, from_y ? cvtt_i32(vq) : vi, L);
 }
 
 __device__ __forceinline__ uint32_t block_reduce_add(uint32_t v, uint32_t *s_tmp) { // kBlock threads, result in all

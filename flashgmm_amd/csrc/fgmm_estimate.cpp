@@ -7,17 +7,7 @@
 
 using namespace fgmm;
 
-namespace {
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// can every load (and the map's store) of an item be 4 positions wide?
-bool rate_vec4_ok(const EncDesc &d, const RateDesc &r, bool f16) {
-  const uintptr_t pm = f16 ? 7 : 15; // 4 parameters per load: 8 B (fp16) or 16 B (fp32)
-  auto al = [pm](const void *p) { return (reinterpret_cast<uintptr_t>(p) & pm) == 0; };
-  return d.stride_p == 1 && (d.hw & 3) == 0 && (d.stride_c & 3) == 0 && (d.stride_k & 3) == 0 && al(d.scales) && al(d.means) &&
-         al(d.weights) && aligned16(d.y) && aligned16(r.bits_map);
-}
-
+namespace fgmm {
 // the context's device copy of L[r] = round(2^24 * log2 r): uploaded on first use (256 KB), kept until fgmm_ctx_trim
 int ensure_rate_table(fgmm_ctx *ctx) {
   if (ctx->d_rate_log2) return FGMM_OK;
@@ -32,8 +22,69 @@ int ensure_rate_table(fgmm_ctx *ctx) {
   return FGMM_OK;
 }
 
+CensusOff census_take(Arena &ar, int M) {
+  CensusOff o;
+  o.o_min = ar.take(sizeof(float) * M, 16);
+  o.o_max = ar.take(sizeof(float) * M, 16);
+  o.o_nz = ar.take(sizeof(int32_t) * M, 16);
+  o.o_list = ar.take(sizeof(int32_t) * ((size_t)M + 1), 16);
+  return o;
+}
+
+void census_desc(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o, const float *y, const fgmm_params *params, int M, int64_t hw, int clamp) {
+  memset(&d, 0, sizeof d);
+  d.y = y;
+  if (params) { // (quant_stats_kernel and chan_compact_kernel read nothing but y, hw and M)
+    d.scales = params->scales;
+    d.means = params->means;
+    d.weights = params->weights;
+    d.stride_k = params->stride_k;
+    d.stride_c = params->stride_c;
+    d.logits = (params->flags & FGMM_PARAMS_LOGITS) ? 1 : 0;
+  }
+  d.stride_p = 1;
+  d.hw = hw;
+  d.M = M;
+  d.clamp = clamp;
+  d.chan_min = reinterpret_cast<float *>(ctx->d_ws + o.o_min);
+  d.chan_max = reinterpret_cast<float *>(ctx->d_ws + o.o_max);
+  d.chan_nz = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_nz);
+  d.chan_list = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_list);
+  d.seg_b[0] = d.seg_b[1] = d.seg_b[2] = INT32_MAX; // (no table: `packed` and `meta` stay null, neither kernel touches them)
+}
+
+bool census_vec4_ok(const EncDesc &d, const void *out, bool f16) {
+  const uintptr_t pm = f16 ? 7 : 15; // 4 parameters per load: 8 B (fp16) or 16 B (fp32)
+  auto al = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
+  return d.stride_p == 1 && (d.hw & 3) == 0 && (d.stride_c & 3) == 0 && (d.stride_k & 3) == 0 && al(d.scales, pm) && al(d.means, pm) &&
+         al(d.weights, pm) && al(d.y, 15) && al(out, 15);
+}
+
+int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap, int32_t *abs_max_out) {
+  const float *mn = reinterpret_cast<const float *>(ctx->h_ws + o.o_min);
+  const float *mx = reinterpret_cast<const float *>(ctx->h_ws + o.o_max);
+  const int32_t *nz = reinterpret_cast<const int32_t *>(ctx->h_ws + o.o_nz);
+  float gmin = INFINITY, gmax = -INFINITY;
+  int n_nz = 0;
+  for (int c = 0; c < M; ++c) { // NaN is kept, as torch.min / torch.max keep it
+    gmin = (mn[c] < gmin || mn[c] != mn[c]) ? mn[c] : gmin;
+    gmax = (mx[c] > gmax || mx[c] != mx[c]) ? mx[c] : gmax;
+    n_nz += nz[c] != 0;
+    if (zero_bitmap) zero_bitmap[c] = nz[c] != 0;
+  }
+  // max(torch.abs(y.max()).int(), torch.abs(y.min()).int()) + 1, floored at 1   (entropy_models.py:834-837)
+  int64_t am = ((int64_t)M * hw) ? std::max((int64_t)cvtt_i32(fabsf(gmax)), (int64_t)cvtt_i32(fabsf(gmin))) + 1 : 1;
+  if (am < 1) am = 1;
+  *abs_max_out = (int32_t)am;
+  return n_nz;
+}
+} // namespace fgmm
+
+namespace {
+
 struct RateOff { // workspace offsets of one item
-  size_t o_min, o_max, o_nz, o_list, o_bits, o_byp;
+  CensusOff census;
+  size_t o_bits, o_byp;
 };
 
 int estimate_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rate_item *items, int count, int mode, int clamp) {
@@ -50,10 +101,7 @@ int estimate_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rate_item *items, int
   for (int i = 0; i < count; ++i) {
     const fgmm_rate_item &it = items[i];
     RateOff &o = off[(size_t)i];
-    o.o_min = ar.take(sizeof(float) * it.M, 16);
-    o.o_max = ar.take(sizeof(float) * it.M, 16);
-    o.o_nz = ar.take(sizeof(int32_t) * it.M, 16);
-    o.o_list = ar.take(sizeof(int32_t) * ((size_t)it.M + 1), 16);
+    o.census = census_take(ar, it.M);
     o.o_bits = ar.take(sizeof(unsigned long long) * it.M, 16);
     o.o_byp = ar.take(sizeof(unsigned long long) * it.M, 16);
     M_max = std::max(M_max, it.M);
@@ -71,28 +119,12 @@ int estimate_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rate_item *items, int
     const fgmm_rate_item &it = items[i];
     const RateOff &o = off[(size_t)i];
     EncDesc &d = hd[i];
-    memset(&d, 0, sizeof d);
-    d.y = it.y;
-    d.scales = it.params.scales;
-    d.means = it.params.means;
-    d.weights = it.params.weights;
-    d.stride_k = it.params.stride_k;
-    d.stride_c = it.params.stride_c;
-    d.stride_p = 1;
-    d.hw = it.hw;
-    d.M = it.M;
-    d.clamp = clamp;
-    d.logits = (it.params.flags & FGMM_PARAMS_LOGITS) ? 1 : 0;
-    d.chan_min = reinterpret_cast<float *>(ctx->d_ws + o.o_min);
-    d.chan_max = reinterpret_cast<float *>(ctx->d_ws + o.o_max);
-    d.chan_nz = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_nz);
-    d.chan_list = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_list);
-    d.seg_b[0] = d.seg_b[1] = d.seg_b[2] = INT32_MAX; // (no table: `packed` and `meta` stay null, rate_kernel touches neither)
+    census_desc(d, ctx, o.census, it.y, &it.params, it.M, it.hw, clamp);
     RateDesc &r = hr[i];
     r.chan_bits = reinterpret_cast<unsigned long long *>(ctx->d_ws + o.o_bits);
     r.chan_bypass = reinterpret_cast<unsigned long long *>(ctx->d_ws + o.o_byp);
     r.bits_map = (int64_t)it.M * it.hw ? it.bits_map : nullptr;
-    vec4 = vec4 && rate_vec4_ok(d, r, f16);
+    vec4 = vec4 && census_vec4_ok(d, r.bits_map, f16);
   }
   const int vec = vec4 ? 4 : 1;
   for (int i = 0; i < count; ++i) linear = linear && items[i].hw % (64 * vec) == 0;
@@ -112,27 +144,15 @@ int estimate_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rate_item *items, int
   for (int i = 0; i < count; ++i) {
     fgmm_rate_item &it = items[i];
     const RateOff &o = off[(size_t)i];
-    const float *mn = reinterpret_cast<const float *>(ctx->h_ws + o.o_min);
-    const float *mx = reinterpret_cast<const float *>(ctx->h_ws + o.o_max);
-    const int32_t *nz = reinterpret_cast<const int32_t *>(ctx->h_ws + o.o_nz);
     const unsigned long long *cb = reinterpret_cast<const unsigned long long *>(ctx->h_ws + o.o_bits);
     const unsigned long long *cy = reinterpret_cast<const unsigned long long *>(ctx->h_ws + o.o_byp);
-    float gmin = INFINITY, gmax = -INFINITY;
-    int n_nz = 0;
+    const int n_nz = census_side_info(ctx, o.census, it.M, it.hw, it.zero_bitmap, &it.abs_max);
     uint64_t bits = 0, byp = 0;
-    for (int c = 0; c < it.M; ++c) { // NaN is kept, as torch.min / torch.max keep it
-      gmin = (mn[c] < gmin || mn[c] != mn[c]) ? mn[c] : gmin;
-      gmax = (mx[c] > gmax || mx[c] != mx[c]) ? mx[c] : gmax;
-      n_nz += nz[c] != 0;
-      if (it.zero_bitmap) it.zero_bitmap[c] = nz[c] != 0;
+    for (int c = 0; c < it.M; ++c) {
       if (it.chan_bits_q) it.chan_bits_q[c] = cb[c];
       bits += cb[c];
       byp += cy[c];
     }
-    // max(torch.abs(y.max()).int(), torch.abs(y.min()).int()) + 1, floored at 1   (entropy_models.py:834-837)
-    int64_t am = ((int64_t)it.M * it.hw) ? std::max((int64_t)cvtt_i32(fabsf(gmax)), (int64_t)cvtt_i32(fabsf(gmin))) + 1 : 1;
-    if (am < 1) am = 1;
-    it.abs_max = (int32_t)am;
     it.n_symbols = (int64_t)n_nz * it.hw;
     it.n_bypass = (int64_t)byp;
     it.bits_q = bits;

@@ -293,6 +293,17 @@ int launch_rate(const EncDesc *d_descs, const RateDesc *d_rdescs, const uint32_t
 int launch_symtab_bits(const uint32_t *packed, const int32_t *symbols_or_null, int64_t n, const uint32_t *d_log2, uint32_t *cost_q_or_null,
                        unsigned long long *bits_q, unsigned long long *n_bypass, void *stream);
 
+// ---- rate-distortion optimised quantisation (fgmm_rdoq.hip, fgmm_rdoq.cpp; include/flashgmm_amd.h section 3c) ----------------
+struct RdoqDesc {                   // item i of an rdoq_kernel launch, beside its EncDesc
+  float *y_out;                     // device [M * hw], zeroed by the host: the chosen symbols of the coded channels as floats
+  unsigned long long *chan_before;  // device [M], zeroed by the host: sum of cost_q(round(y)) over channel c (0: not coded)
+  unsigned long long *chan_after;   // device [M], zeroed by the host: sum of cost_q(chosen symbol)
+  unsigned long long *chan_changed; // device [M], zeroed by the host: latents whose symbol is not round(y)
+};
+// the addressing of launch_rate; lam_q = lambda * 2^-FGMM_RATE_Q (the objective is in units of one squared quantisation step)
+int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, double lam_q, int count, int M_max, int64_t hw_max,
+                int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
+
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the
 // encoder asks it for storage of the stream's exact size once that is known and copies the stream there out of its scratch: the

@@ -5,7 +5,7 @@
 // numpy record arrays), the GIL is released across the native call - the reference holds it (no gil_scoped_release anywhere in its
 // module) - and the bitstreams come back as `bytes` objects allocated at their final size and filled by the encoders' flush
 // (fgmm_sink: no buffer of the library's, no copy after the call).  Nothing here computes: every function is argument plumbing around
-// fgmm_gmc_compress_batch / fgmm_gmc_decompress_batch / fgmm_gmc_compress_head_batch.  flashgmm_amd/_lib.py (ctypes) binds the same
+// fgmm_gmc_compress_batch / fgmm_gmc_decompress_batch / fgmm_gmc_compress_head_batch / fgmm_gmc_rdoq_batch.  flashgmm_amd/_lib.py (ctypes) binds the same
 // ABI and stays the fallback.
 #include <pybind11/pybind11.h>
 
@@ -240,6 +240,41 @@ void decompress_stacked(uintptr_t ctx_, uintptr_t stream, py::sequence strings, 
   if (rc) raise("GaussianMixtureConditional.decompress", rc);
 }
 
+// GaussianMixtureConditional.quantize_rdo for N stacked items (fgmm_gmc_rdoq_batch, header section 3c): y_rdo (device float32 [N, M, hw]),
+// the zero bitmaps and - chan_after != 0 - the per-channel costs (HOST int64 [N, M]) are written through;
+//   -> (n_changed, bits_q_before, bits_q_after, abs_max), a list of N integers each
+py::tuple rdoq_stacked(uintptr_t ctx_, uintptr_t stream, uintptr_t y, uintptr_t scales, uintptr_t means, uintptr_t weights, int N, int M, int64_t hw,
+                       int64_t item_stride, int64_t stride_k, int64_t stride_c, int dtype, int flags, int mode, int clamp_scales, double lambda,
+                       uintptr_t y_rdo, uintptr_t zero_bitmap, uintptr_t chan_after) {
+  fgmm_ctx *ctx = ptr<fgmm_ctx>(ctx_);
+  std::vector<fgmm_item> in((size_t)N);
+  fill_items(in, Stacked{scales, means, weights, item_stride, stride_k, stride_c, dtype, flags, N, M, hw});
+  std::vector<fgmm_rdoq_item> it((size_t)N);
+  for (int i = 0; i < N; ++i) {
+    fgmm_rdoq_item &f = it[(size_t)i];
+    std::memset(&f, 0, sizeof f);
+    f.params = in[(size_t)i].params;
+    f.M = M, f.K = FGMM_K, f.hw = hw;
+    f.y = ptr<const float>(y) + (size_t)i * (size_t)M * (size_t)hw;
+    f.y_rdo = ptr<float>(y_rdo) + (size_t)i * (size_t)M * (size_t)hw;
+    f.zero_bitmap = ptr<int64_t>(zero_bitmap) + (size_t)i * (size_t)M;
+    if (chan_after) f.chan_bits_q_after = ptr<uint64_t>(chan_after) + (size_t)i * (size_t)M;
+  }
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = fgmm_gmc_rdoq_batch(ctx, ptr<void>(stream), it.data(), N, mode, clamp_scales, lambda);
+  }
+  if (rc) raise("GaussianMixtureConditional.quantize_rdo", rc);
+  py::list changed((size_t)N), before((size_t)N), after((size_t)N), abs_max((size_t)N);
+  for (int i = 0; i < N; ++i) {
+    const fgmm_rdoq_item &f = it[(size_t)i];
+    changed[(size_t)i] = py::int_(f.n_changed), before[(size_t)i] = py::int_(f.bits_q_before), after[(size_t)i] = py::int_(f.bits_q_after);
+    abs_max[(size_t)i] = py::int_(f.abs_max);
+  }
+  return py::make_tuple(changed, before, after, abs_max);
+}
+
 // ---- items of any mix of shapes (the sequence form of compress_batch / decompress_batch: ELIC's ten groups per image) --------------
 // one item = a tuple of integers; compress: (y, scales, means, weights, M, hw, stride_k, stride_c, yq, zero_bitmap),
 // decompress: (scales, means, weights, M, hw, stride_k, stride_c, y_hat, zero_bitmap): device addresses, HOST zero bitmap
@@ -324,6 +359,8 @@ PYBIND11_MODULE(_native, m) {
         "stride_c"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "ckpt_stride"_a, "yq"_a, "zero_bitmap"_a, "bytes_cls"_a = py::none());
   m.def("compress_head_stacked", &compress_head_stacked, "ctx"_a, "stream"_a, "y"_a, "x"_a, "head"_a, "N"_a, "M"_a, "c_in"_a, "hw"_a, "mode"_a, "clamp_scales"_a,
         "ckpt_stride"_a, "yq"_a, "zero_bitmap"_a, "bytes_cls"_a = py::none());
+  m.def("rdoq_stacked", &rdoq_stacked, "ctx"_a, "stream"_a, "y"_a, "scales"_a, "means"_a, "weights"_a, "N"_a, "M"_a, "hw"_a, "item_stride"_a, "stride_k"_a,
+        "stride_c"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "lambda"_a, "y_rdo"_a, "zero_bitmap"_a, "chan_after"_a = 0);
   m.def("compress_items", &compress_items, "ctx"_a, "stream"_a, "items"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "ckpt_stride"_a, "bytes_cls"_a = py::none());
   m.def("decompress_items", &decompress_items, "ctx"_a, "stream"_a, "strings"_a, "abs_maxes"_a, "items"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a,
         "ckpt_cls"_a = py::none());

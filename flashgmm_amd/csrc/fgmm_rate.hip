@@ -18,21 +18,6 @@
 
 namespace fgmm {
 
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ void add64(unsigned long long *p, unsigned long long v) { // no value returned: the wave does not wait for it
-  (void)__hip_atomic_fetch_add((FGMM_GLOBAL unsigned long long *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the symbol a bypass entry codes: the raw symbol, or the rounded latent converted as the host converts it (torch's .int():
-// INT32_MIN for NaN, infinities and everything beyond int32 - fgmm_encode.cpp side_info)
-__device__ __forceinline__ uint32_t entry_cost(uint32_t ent, float vq, int vi, bool from_y, const uint32_t *__restrict__ L) {
-  if (__builtin_expect((ent >> 16) != 0, 1)) return (16u << FGMM_RATE_Q) - L[ent >> 16];
-  return rate_cost_q(0u, from_y ? cvtt_i32(vq) : vi, L);
-}
-
 #ifndef FGMM_RATE_WAVES
 #define FGMM_RATE_WAVES 5 // min waves per SIMD the register allocator must leave room for, as symtab_kernel's (<= 96 VGPRs)
 #endif

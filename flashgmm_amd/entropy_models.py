@@ -27,7 +27,7 @@ from torch import Tensor
 
 from . import _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -140,6 +140,36 @@ class RateEstimate:
 
     def __repr__(self) -> str:
         return f"RateEstimate(bits={self.bits:.3f}, nbytes={self.nbytes}, n_symbols={self.n_symbols}, n_bypass={self.n_bypass}, abs_max={self.abs_max})"
+
+
+class RdoQuantized:
+    """A latent quantised with rate-distortion optimisation (``GaussianMixtureConditional.quantize_rdo`` / ``quantize_rdo_batch``;
+    include/flashgmm_amd.h section 3c): per latent of a coded channel ``round(y)`` or one of its two neighbours, whichever minimises
+    ``(y - v)**2 + lam * bits(v)`` under the coder's own exact cost.
+
+    ``y``            float32 ``[1, M, h, w]`` on the inputs' device, integer-valued: ``compress(result.y, ...)`` codes it unchanged
+    ``n_changed``    latents whose symbol is not ``round(y)``
+    ``bits_q_before`` / ``bits_q_after``   exact cost of ``round(y)`` / of the chosen symbols over the channels coded for the input, in
+                     units of 2^-24 bit (integers: the same on every run);  ``bits_before`` / ``bits_after`` in bits
+    ``abs_max``, ``zero_bitmap``   what ``compress(result.y, ...)`` returns (``zero_bitmap``: int64 ``[M]`` CPU tensor)
+    ``channel_bits_q_after``   per channel, int64 ``[M]`` CPU tensor (``per_channel=True``; else None)"""
+
+    __slots__ = ("y", "n_changed", "bits_q_before", "bits_q_after", "abs_max", "zero_bitmap", "channel_bits_q_after")
+
+    def __init__(self, y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after=None):
+        self.y, self.n_changed, self.bits_q_before, self.bits_q_after = y, int(n_changed), int(bits_q_before), int(bits_q_after)
+        self.abs_max, self.zero_bitmap, self.channel_bits_q_after = int(abs_max), zero_bitmap, channel_bits_q_after
+
+    @property
+    def bits_before(self) -> float:
+        return self.bits_q_before / float(1 << _lib.FGMM_RATE_Q)
+
+    @property
+    def bits_after(self) -> float:
+        return self.bits_q_after / float(1 << _lib.FGMM_RATE_Q)
+
+    def __repr__(self) -> str:
+        return f"RdoQuantized(n_changed={self.n_changed}, bits_before={self.bits_before:.3f}, bits_after={self.bits_after:.3f}, abs_max={self.abs_max})"
 
 
 def _take_ckpts_many(device: int, ptrs, counts):
@@ -669,6 +699,89 @@ class GaussianMixtureConditional(nn.Module):
         """-> the ``RateEstimate`` of ``compress(y, scales, means, weights)``: its size, without coding"""
         return self.estimate_bits_batch([y], [scales], [means], [weights], weights_are_logits=weights_are_logits, per_channel=per_channel,
                                         per_latent=per_latent)[0]
+
+    def quantize_rdo_batch(self, ys, scales, means, weights, lam: float, *, weights_are_logits: bool = False,
+                           per_channel: bool = False) -> List[RdoQuantized]:
+        """Rate-distortion optimised quantisation: per latent of a channel ``compress_batch`` would code, ``round(y)`` or one of its
+        two neighbours, whichever minimises ``(y - v)**2 + lam * bits(v)`` - ``bits`` the coder's own exact cost of ``v`` under that
+        latent's mixture (the rule, exactly: include/flashgmm_amd.h section 3c).  One kernel; nothing is coded.  Inputs as
+        ``compress_batch`` takes them - sequences of ``[1, M, h, w]`` / ``[1, K*M, h, w]`` tensors, or stacked; ``lam`` finite, >= 0
+        (0 returns ``round(y)``).  -> one ``RdoQuantized`` per item; ``compress(result.y, ...)`` then codes it through the unchanged
+        encode path."""
+        if self.K != _lib.FGMM_K:
+            raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
+        lam = float(lam)
+        if not (0.0 <= lam < float("inf")):
+            raise ValueError(f"lam = {lam!r}: must be finite and >= 0")
+        flags = _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0
+        nat = _lib.native()
+        if isinstance(ys, Tensor) and nat is not None and scales.dim() == 4 and scales.shape[0] > 0:  # the compiled boundary: items built in C++
+            y, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(ys, scales, means, weights)
+            dev = scales.device
+            out = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
+            zb = torch.empty((N, M), dtype=torch.int64)
+            cb = torch.empty((N, M), dtype=torch.int64) if per_channel else None
+            di = dev.index if dev.index is not None else -1
+            ch, before, after, am = nat.rdoq_stacked(_lib.ctx_addr(di), torch.cuda.current_stream(dev).cuda_stream, y.data_ptr(), scales.data_ptr(),
+                                                     means.data_ptr(), weights.data_ptr(), N, M, h * w, s_item, M * sc, sc,
+                                                     _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32, flags, self._mode(),
+                                                     int(self.clamp_scales), lam, out.data_ptr(), zb.data_ptr(), cb.data_ptr() if per_channel else 0)
+            return [RdoQuantized(*c) for c in zip(out.unbind(0), ch, before, after, am, zb.unbind(0), cb.unbind(0) if per_channel else [None] * N)]
+        if isinstance(ys, Tensor):
+            items, keep, N, M, h, w, dev = self._stacked_items(ys, scales, means, weights, flags, _lib.RDOQ_ITEM_DTYPE)
+            if N == 0:
+                return []
+            rng = np.arange(N, dtype=np.uint64)
+            out = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
+            items["y_rdo"] = np.uint64(out.data_ptr()) + rng * np.uint64(M * h * w * 4)
+            outs = out.unbind(0)
+            zb = torch.empty((N, M), dtype=torch.int64)
+            items["zero_bitmap"] = np.uint64(zb.data_ptr()) + rng * np.uint64(M * 8)
+            bitmaps = zb.unbind(0)
+            chans = [None] * N
+            if per_channel:
+                cb = torch.empty((N, M), dtype=torch.int64)
+                items["chan_bits_q_after"] = np.uint64(cb.data_ptr()) + rng * np.uint64(M * 8)
+                chans = cb.unbind(0)
+            ptr = C.cast(items.ctypes.data, C.POINTER(_lib.fgmm_rdoq_item))
+        else:
+            N = len(ys)
+            if N == 0:
+                return []
+            arr = (_lib.fgmm_rdoq_item * N)()
+            keep, outs, bitmaps, chans, dev = [], [], [], [], None
+            for i in range(N):
+                yp, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
+                dev = dev or d
+                if d != dev:
+                    raise RuntimeError("all items of a batch must be on one device")
+                it = arr[i]
+                it.y = yp
+                it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
+                it.M, it.K, it.hw = M, self.K, hw
+                out = torch.empty((1, M) + tuple(ys[i].shape[2:]), dtype=torch.float32, device=d)
+                it.y_rdo = out.data_ptr()
+                outs.append(out)
+                zb = torch.empty(M, dtype=torch.int64)
+                it.zero_bitmap = zb.data_ptr()
+                bitmaps.append(zb)
+                cb = torch.empty(M, dtype=torch.int64) if per_channel else None
+                if cb is not None:
+                    it.chan_bits_q_after = cb.data_ptr()
+                chans.append(cb)
+            items = np.frombuffer(arr, dtype=_lib.RDOQ_ITEM_DTYPE)
+            ptr = arr
+        di = dev.index if dev.index is not None else -1
+        rc = _lib.lib().fgmm_gmc_rdoq_batch(_lib.ctx(di), torch.cuda.current_stream(dev).cuda_stream, ptr, N, self._mode(), int(self.clamp_scales), lam)
+        _lib.check(rc, "GaussianMixtureConditional.quantize_rdo")
+        cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
+                   bitmaps, chans)
+        return [RdoQuantized(*c) for c in cols]
+
+    def quantize_rdo(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lam: float, *, weights_are_logits: bool = False,
+                     per_channel: bool = False) -> RdoQuantized:
+        """-> the ``RdoQuantized`` of one latent (``quantize_rdo_batch``)"""
+        return self.quantize_rdo_batch([y], [scales], [means], [weights], lam, weights_are_logits=weights_are_logits, per_channel=per_channel)[0]
 
     def compress(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, weights_are_logits: bool = False):
         """-> ((bytes, abs_max, zero_bitmap), y_quantized)     (entropy_models.py:833-867)"""

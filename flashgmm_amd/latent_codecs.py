@@ -37,12 +37,23 @@ __all__ = ["GaussianMixtureConditionalLatentCodec", "CheckerboardLatentCodec", "
            "HyperpriorLatentCodec"]
 
 
+def _check_rdo_lambda(lam) -> float:
+    lam = float(lam)
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError(f"rdo_lambda = {lam!r}: must be finite and >= 0")
+    return lam
+
+
 class GaussianMixtureConditionalLatentCodec(nn.Module):
     def __init__(self, K: int = 4, gaussian_mixture_conditional: Optional[GaussianMixtureConditional] = None,
                  entropy_parameters: Optional[nn.Module] = None, quantizer: str = "noise",
                  chunks: Tuple[str, ...] = ("scales", "means", "weights"), mode=None, param_dtype: torch.dtype = torch.float32,
-                 fuse_softmax: bool = False, checkpoint_stride: int = 0, **kwargs: Any):
+                 fuse_softmax: bool = False, checkpoint_stride: int = 0, rdo_lambda: float = 0.0, **kwargs: Any):
         super().__init__()
+        # rdo_lambda > 0: rate-distortion optimised quantisation (GaussianMixtureConditional.quantize_rdo) - what is coded is, per latent,
+        # round(.) or one of its two neighbours, whichever minimises (y - v)^2 + rdo_lambda * bits(v).  An encoder-side choice: the
+        # decoder needs no switch.  0: plain rounding, no extra launch
+        self.rdo_lambda = _check_rdo_lambda(rdo_lambda)
         if param_dtype not in (torch.float32, torch.float16):
             raise ValueError("param_dtype must be torch.float32 or torch.float16")
         self.param_dtype = param_dtype  # float16: BASELINE configs[4], "fp16 (mu, sigma, pi) with fp32 CDF accumulate"
@@ -101,14 +112,29 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         weighted_sum = torch.sum(me * we, dim=1)
         return weighted_sum, (me - weighted_sum.unsqueeze(1)).reshape(B, KM, H, W)
 
+    def _rdo(self, y_code: Tensor, planes, lam: float):
+        """(y_to_code, planes) with y_to_code replaced by its rate-distortion optimised quantisation (integer-valued: the encode path
+        then rounds it to itself)"""
+        q = self.gaussian_mixture_conditional.quantize_rdo(y_code, *planes, lam, weights_are_logits=self.fuse_softmax)
+        return (q.y, *planes)
+
     def coder_inputs(self, y: Tensor, ctx_params: Tensor):
         """What ``compress`` hands the entropy model: ``(y_to_code, scales, means, weights)``.  ``round(y_to_code)`` is
-        the ``y_hat`` that ``compress`` returns (:127-149) — known before any coding happens."""
+        the ``y_hat`` that ``compress`` returns (:127-149) — known before any coding happens.  With the codec's ``rdo_lambda`` > 0
+        ``y_to_code`` is the RDOQ result of what would be rounded."""
+        return self.coder_inputs_rdo(y, ctx_params, self.rdo_lambda)
+
+    def coder_inputs_rdo(self, y: Tensor, ctx_params: Tensor, rdo_lambda: float):
+        """``coder_inputs`` with a given ``rdo_lambda`` in place of the codec's own (0: plain rounding, no extra launch)"""
+        lam = _check_rdo_lambda(rdo_lambda)
         scales_hat, means_hat, weights = self._params(ctx_params)
         if self.quantizer == "noise":
-            return (y, *self._planes(scales_hat, means_hat, weights))
+            planes = self._planes(scales_hat, means_hat, weights)
+            return self._rdo(y, planes, lam) if lam > 0 else (y, *planes)
         weighted_sum, means_rel = self._recentre(means_hat, weights)
         d = y - weighted_sum
+        if lam > 0:
+            return self._rdo(d, self._planes(scales_hat, means_rel, weights), lam)
         # quantize_ste (compressai/ops/ops.py:66-80) is (round(d) - d) + d: the value of round(d), but +0.0 where
         # round(d) is -0.0 — kept, so that the returned y_hat has the reference's bits
         return ((torch.round(d) - d) + d, *self._planes(scales_hat, means_rel, weights))
@@ -207,8 +233,15 @@ class CheckerboardLatentCodec(nn.Module):
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None, entropy_parameters: Optional[nn.Module] = None,
                  context_prediction: Optional[nn.Module] = None, anchor_parity: str = "even", forward_method: str = "twopass",
-                 fuse_head=False, **kwargs: Any):
+                 fuse_head=False, rdo_lambda: float = 0.0, **kwargs: Any):
         super().__init__()
+        # rdo_lambda > 0: each half's latents are quantised with rate-distortion optimisation before the half's y_hat is taken, so the
+        # non-anchors' context sees what the decoder will see (prepare); 0: the latent codec's own setting.  Precedence when both
+        # this codec and its latent codec "y" carry an rdo_lambda: this one, if > 0, REPLACES the inner codec's for both halves (the two
+        # are never combined); only when this one is 0 does the inner codec's own rdo_lambda apply
+        self.rdo_lambda = _check_rdo_lambda(rdo_lambda)
+        if fuse_head and self.rdo_lambda > 0:
+            raise RuntimeError("rdo_lambda > 0 together with fuse_head is not supported: RDOQ needs the parameter planes the fused head never writes")
         if anchor_parity not in ("even", "odd"):
             raise ValueError(f"anchor_parity {anchor_parity!r}")
         # fuse_head: the LAST layer of entropy_parameters - nn.Conv2d(c_in, 3*K*M, 1), models/ckbd_gmm.py:115-121 - runs inside the
@@ -277,10 +310,13 @@ class CheckerboardLatentCodec(nn.Module):
         body = self._head_parts()[0] if self.fuse_head else None
         for i in range(2):
             if self.fuse_head:  # (y, the features the head's last layer reads): the parameters are the encode kernel's business
+                if codec.rdo_lambda > 0:
+                    raise RuntimeError("rdo_lambda > 0 together with fuse_head is not supported")
                 prepared.append((y_[i], body(self.merge(self._ctx(y_hat_, i), side_params_[i]))))
             else:
                 params_i = self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_params_[i]))
-                prepared.append(codec.coder_inputs(y_[i], params_i))
+                # (rdo_lambda = 0: the latent codec's own entry point, with its own setting - today's path)
+                prepared.append(codec.coder_inputs_rdo(y_[i], params_i, self.rdo_lambda) if self.rdo_lambda > 0 else codec.coder_inputs(y_[i], params_i))
             y_hat_[i] = torch.round(prepared[i][0])  # what compress() of this half returns as y_hat
         return prepared, self.embed(y_hat_)
 

@@ -41,7 +41,12 @@ extern "C" {
 #define FGMM_ABI_VERSION 6 /* 6: + the parameter head (fgmm_head_*, fgmm_gmc_compress_head_batch); + fgmm_sink and the _to forms of the batched
                               compress calls; FGMM_WORKER_CPUS that cannot be honoured fails fgmm_ctx_create.  5: + fgmm_ctx_call_log; REMOVED (measured, lost, pruned): options tab_place /
                               tab_spin / copy_engine / dec_pair / dec_group, fgmm_rans_decode_tab2 + fgmm_tab_ref, fgmm_ctx_stat index 6.
-                              Added since without a bump (nothing existing changed): section 3b, the coded size without running the coder */
+                              Added since without a bump (nothing existing changed): section 3b, the coded size without running the coder; section 3c,
+                              rate-distortion optimised quantisation.  fgmm_abi_version() therefore does NOT tell a caller whether 3b / 3c are
+                              there: at compile time test FGMM_HAS_ESTIMATE / FGMM_HAS_RDOQ below, at run time look the symbol up
+                              (dlsym(handle, "fgmm_gmc_rdoq_batch")) */
+#define FGMM_HAS_ESTIMATE 1 /* section 3b: fgmm_gmc_estimate_batch, fgmm_symtab_bits[_hip], fgmm_rate_stream_bytes */
+#define FGMM_HAS_RDOQ 1     /* section 3c: fgmm_gmc_rdoq_batch */
 
 typedef enum {
   FGMM_OK = 0,
@@ -514,6 +519,46 @@ typedef struct {
   uint64_t bits_q, bytes_pred; /* out */
 } fgmm_rate_item;
 int fgmm_gmc_estimate_batch(fgmm_ctx *ctx, void *stream, fgmm_rate_item *items, int count, int mode, int clamp_scales);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3c. Rate-distortion optimised quantisation (RDOQ): spend the exact cost function of 3b to encode better.  For every latent of a
+ *    channel the compress call would code for y, keep round(y) or move ONE step to a neighbour, whichever minimises
+ *    (y - v)^2 + lambda * bits(v), bits being the coder's own cost of v under that latent's mixture.  A pure encoder-side choice:
+ *    y_rdo goes through the unchanged compress call, the bitstream is the reference's format, any reference decoder reads it;
+ *    lambda = 0 returns round(y).  The decision, exactly (restatable on a CPU; tests/rdoq_ref.py does):
+ *      rounding      v0 = rintf(y) (round half to even), as everywhere in the library
+ *      coded         the channels fgmm_gmc_compress_batch would code for y: any round(y) != 0.  The other channels are written as
+ *                    round(y) - zeros - and never reconsidered
+ *      candidates    v0 - 1, v0, v0 + 1 when y is finite and |v0| <= 2^20; only v0 otherwise (within the bound float(v0 +- 1) - 0.5f
+ *                    and float(v0) - 0.5f + 1.0f are the same binary32 numbers, so the four edges v0 - 1.5 .. v0 + 1.5 give all three
+ *                    entries; beyond it the encoder's own two roundings differ and the latent is left alone)
+ *      entry, cost   each candidate's table entry is what the encode-side kernel yields for that symbol (same Phi, clamp, softmax
+ *                    over K, bypass rule); cost_q is fgmm_symtab_bits' cost of that entry and symbol, a bypass candidate being
+ *                    priced by the symbol's own nibbles
+ *      objective     J(v) = d * d + lam_q * (double)cost_q(v) with d = (double)y - (double)v and lam_q = lambda * 2^-24: every
+ *                    operation one IEEE binary64 operation, no contraction
+ *      choice        start from v0; take v0 - 1 if its J is strictly smaller; then v0 + 1 if its J is strictly smaller than the best
+ *                    so far.  Ties keep the earlier candidate
+ *    Per item: y_rdo (integer-valued floats, +0.0 for zero, NaN / +-inf latents kept as they are; its range may not overlap
+ *    y's: FGMM_ERR_INVALID), n_changed (latents
+ *    whose symbol is not round(y)), bits_q_before / bits_q_after (uint64 sums of cost_q of v0 / of the chosen symbol over the channels
+ *    coded for y), chan_bits_q_after (per channel), abs_max and zero_bitmap OF y_rdo - what compressing y_rdo returns.  Sums are
+ *    integer, the same bits on every run.  lambda must be finite and >= 0 (else FGMM_ERR_INVALID); otherwise arguments are validated
+ *    as by the estimate call; an item with M * hw == 0 is a no-op with zero sums.  Returns with every output complete.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *y;          /* device [M*hw] */
+  fgmm_params params;
+  int32_t M, K;
+  int64_t hw;
+  float *y_rdo;            /* DEVICE float32[M*hw] out */
+  int64_t *zero_bitmap;    /* HOST int64[M] out, may be NULL */
+  uint64_t *chan_bits_q_after; /* HOST uint64[M] out, may be NULL */
+  int32_t abs_max, status; /* out */
+  int64_t n_changed;       /* out */
+  uint64_t bits_q_before, bits_q_after; /* out */
+} fgmm_rdoq_item;
+int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
