@@ -135,14 +135,6 @@ int fgmm_ctx::prof_end(int which, dev::Stream s) {
 
 namespace {
 bool mode_ok(int mode) { return mode >= 0 && mode <= 2; }
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// can a raw (n,K) table use the 16-B-per-lane symtab kernel?
-bool enc_vec4_ok(const EncDesc &d, bool f16) {
-  const uintptr_t pm = f16 ? 7 : 15;
-  auto al = [pm](const void *p) { return (reinterpret_cast<uintptr_t>(p) & pm) == 0; };
-  return d.stride_p == 1 && (d.hw & 3) == 0 && (d.stride_c & 3) == 0 && (d.stride_k & 3) == 0 && al(d.scales) && al(d.means) &&
-         al(d.weights) && (d.y ? aligned16(d.y) : aligned16(d.sym)) && aligned16(d.packed);
-}
 // stage an (n,K) host parameter triple on the device; returns device pointers + strides to use
 struct StagedRows {
   const float *s = nullptr, *m = nullptr, *w = nullptr;
@@ -950,7 +942,7 @@ int fgmm_build_symtab_hip(fgmm_ctx *ctx, void *stream, const int32_t *symbols, c
   dev::Stream s = (dev::Stream)stream;
   DEV_TRY(dev::copy_async(ctx->d_ws, hd, sizeof *hd, dev::kH2D, s));
   DEV_TRY(dev::memset_async(ctx->d_ws + 1024, 0, meta_bytes, s));
-  LAUNCH_TRY(launch_symtab(reinterpret_cast<const EncDesc *>(ctx->d_ws), 1, 1, n, n, false, mode, enc_vec4_ok(*hd, false) ? 4 : 1, false, false, s));
+  LAUNCH_TRY(launch_symtab(reinterpret_cast<const EncDesc *>(ctx->d_ws), 1, 1, n, n, false, mode, enc_vec4_ok(*hd, hd->packed, false) ? 4 : 1, false, false, s));
   DEV_TRY(dev::stream_sync(s));
   return FGMM_OK;
 }

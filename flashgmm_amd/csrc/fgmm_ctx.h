@@ -289,19 +289,26 @@ struct Arena {
   }
 };
 
-// ---- fgmm_estimate.cpp: what the estimate call (3b) and the RDOQ call (3c) share ------------------------------------------------
-int ensure_rate_table(fgmm_ctx *ctx); // the context's device copy of rate_log2_table(), uploaded on first use
-struct CensusOff {                    // workspace offsets of one item's census: per channel min | max | any non-zero, the compact list
-  size_t o_min, o_max, o_nz, o_list;
+// ---- the channel census of a latent (quant_stats_kernel + chan_compact_kernel) on the host side: ONE copy, in fgmm_encode.cpp, for the
+// compress call, the estimate call (3b) and the RDOQ call (3c) ---------------------------------------------------------------------
+struct CensusOff { // workspace offsets of one item's census: per channel min | max | any non-zero, the compact list
+  size_t o_min = 0, o_max = 0, o_nz = 0, o_list = 0;
 };
 CensusOff census_take(Arena &ar, int M);
+void census_bind(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o); // the descriptor's four census arrays, at `o` of the device workspace
 // the EncDesc of an item without a table: its latent, its census arrays at `o`, and (params non-null) its parameter planes
 void census_desc(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o, const float *y, const fgmm_params *params_or_null, int M, int64_t hw,
                  int clamp);
 // can every load of an item, and the store to `out` (may be null), be 4 positions wide?
-bool census_vec4_ok(const EncDesc &d, const void *out, bool f16);
-// from the census copied back to the host: abs_max as the compress call returns it, zero_bitmap (may be null); the coded channels' count
-int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap_or_null, int32_t *abs_max_out);
+bool enc_vec4_ok(const EncDesc &d, const void *out, bool f16);
+// from the census copied back to the host: abs_max as the compress call returns it, zero_bitmap (may be null), the latent's {min, max}
+// with NaN kept (may be null); returns the coded channels' count
+int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap_or_null, int32_t *abs_max_out,
+                     float *min_max_or_null = nullptr);
+// ---- fgmm_estimate.cpp: what the estimate call and the RDOQ call share besides -----------------------------------------------------
+int ensure_rate_table(fgmm_ctx *ctx); // the context's device copy of rate_log2_table(), uploaded on first use
+// one item of either call: K, sizes, tensors, the parameters' dtype (one per batch) and flags; FGMM_OK or the failure, already reported
+int check_latent_item(int i, int K, int M, int64_t hw, const float *y, const fgmm_params &params, int batch_dtype);
 
 struct DeviceGuard {
   int prev = -1;
@@ -425,7 +432,8 @@ struct EncItem {
   size_t bytes_len = 0;
   int status = FGMM_OK;
   // workspace offsets
-  size_t o_min = 0, o_max = 0, o_nz = 0, o_list = 0, o_meta = 0, o_packed = 0, meta_count = 0;
+  CensusOff census;
+  size_t o_meta = 0, o_packed = 0, meta_count = 0;
   // the table in segments of compact channels (EncDesc::packed_seg): offsets, channels per segment, segments, copy group of each
   size_t o_seg[kEncSegs] = {0, 0, 0, 0};
   int32_t cps = 0, n_seg = 0, seg_group[kEncSegs] = {0, 0, 0, 0};

@@ -12,16 +12,72 @@
 #include "fgmm_ctx.h"
 
 namespace fgmm {
-namespace {
 
-// can item use the 16-B-per-lane symtab kernel?
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool enc_vec4_ok(const EncDesc &d, bool f16) {
+// ---- the channel census (fgmm_ctx.h): its place in the workspace, in a descriptor, and what the host reads from it ------------------
+CensusOff census_take(Arena &ar, int M) {
+  CensusOff o;
+  o.o_min = ar.take(sizeof(float) * M, 16);
+  o.o_max = ar.take(sizeof(float) * M, 16);
+  o.o_nz = ar.take(sizeof(int32_t) * M, 16);
+  o.o_list = ar.take(sizeof(int32_t) * ((size_t)M + 1), 16);
+  return o;
+}
+
+void census_bind(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o) {
+  d.chan_min = reinterpret_cast<float *>(ctx->d_ws + o.o_min);
+  d.chan_max = reinterpret_cast<float *>(ctx->d_ws + o.o_max);
+  d.chan_nz = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_nz);
+  d.chan_list = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_list);
+}
+
+void census_desc(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o, const float *y, const fgmm_params *params, int M, int64_t hw, int clamp) {
+  memset(&d, 0, sizeof d);
+  d.y = y;
+  if (params) { // (quant_stats_kernel and chan_compact_kernel read nothing but y, hw and M)
+    d.scales = params->scales;
+    d.means = params->means;
+    d.weights = params->weights;
+    d.stride_k = params->stride_k;
+    d.stride_c = params->stride_c;
+    d.logits = (params->flags & FGMM_PARAMS_LOGITS) ? 1 : 0;
+  }
+  d.stride_p = 1;
+  d.hw = hw;
+  d.M = M;
+  d.clamp = clamp;
+  census_bind(d, ctx, o);
+  d.seg_b[0] = d.seg_b[1] = d.seg_b[2] = INT32_MAX; // (no table: `packed` and `meta` stay null, neither kernel touches them)
+}
+
+static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool enc_vec4_ok(const EncDesc &d, const void *out, bool f16) {
   const uintptr_t pm = f16 ? 7 : 15; // 4 parameters per load: 8 B (fp16) or 16 B (fp32)
   auto al = [pm](const void *p) { return (reinterpret_cast<uintptr_t>(p) & pm) == 0; };
   return d.stride_p == 1 && (d.hw & 3) == 0 && (d.stride_c & 3) == 0 && (d.stride_k & 3) == 0 && al(d.scales) && al(d.means) &&
-         al(d.weights) && (d.y ? aligned16(d.y) : aligned16(d.sym)) && aligned16(d.packed);
+         al(d.weights) && (d.y ? aligned16(d.y) : aligned16(d.sym)) && aligned16(out);
 }
+
+int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap, int32_t *abs_max_out, float *min_max) {
+  const float *mn = reinterpret_cast<const float *>(ctx->h_ws + o.o_min);
+  const float *mx = reinterpret_cast<const float *>(ctx->h_ws + o.o_max);
+  const int32_t *nz = reinterpret_cast<const int32_t *>(ctx->h_ws + o.o_nz);
+  float gmin = INFINITY, gmax = -INFINITY;
+  int n_nz = 0;
+  for (int c = 0; c < M; ++c) { // NaN is kept, as torch.min / torch.max keep it (quant_stats_kernel's census does too)
+    gmin = (mn[c] < gmin || mn[c] != mn[c]) ? mn[c] : gmin;
+    gmax = (mx[c] > gmax || mx[c] != mx[c]) ? mx[c] : gmax;
+    n_nz += nz[c] != 0;
+    if (zero_bitmap) zero_bitmap[c] = nz[c] != 0;
+  }
+  // max(torch.abs(y.max()).int(), torch.abs(y.min()).int()) + 1, floored at 1   (entropy_models.py:834-837)
+  int64_t am = ((int64_t)M * hw) ? std::max((int64_t)cvtt_i32(fabsf(gmax)), (int64_t)cvtt_i32(fabsf(gmin))) + 1 : 1;
+  if (am < 1) am = 1;
+  *abs_max_out = (int32_t)am;
+  if (min_max) min_max[0] = gmin, min_max[1] = gmax;
+  return n_nz;
+}
+
+namespace {
 
 // segmented tables: an encoder asks for a segment before it enters it and SLEEPS on the event of the copy that carries it
 struct SegWaitArg {
@@ -205,10 +261,7 @@ struct EncodeCall {
     o_descs = ar.take(sizeof(EncDesc) * (size_t)count);
     o_small = ar.take(0);
     for (auto &it : items) {
-      it.o_min = ar.take(sizeof(float) * it.M, 16);
-      it.o_max = ar.take(sizeof(float) * it.M, 16);
-      it.o_nz = ar.take(sizeof(int32_t) * it.M, 16);
-      it.o_list = ar.take(sizeof(int32_t) * ((size_t)it.M + 1), 16);
+      it.census = census_take(ar, it.M);
       it.meta_count = (size_t)it.M * (size_t)((it.hw + 255) / 256) * 4; // one slot per wave, sized for the 1-symbol-per-lane form
       it.o_meta = ar.take(sizeof(uint32_t) * it.meta_count, 16);
       M_max = std::max(M_max, it.M);
@@ -293,10 +346,8 @@ struct EncodeCall {
     d.xs = it.xs;
     d.meta_slots = (uint32_t)it.meta_count;
     d.yq = it.yq;
-    d.chan_min = reinterpret_cast<float *>(ctx->d_ws + it.o_min);
-    d.chan_max = reinterpret_cast<float *>(ctx->d_ws + it.o_max);
-    d.chan_nz = it.latent ? reinterpret_cast<int32_t *>(ctx->d_ws + it.o_nz) : nullptr;
-    d.chan_list = it.latent ? reinterpret_cast<int32_t *>(ctx->d_ws + it.o_list) : nullptr;
+    census_bind(d, ctx, it.census);
+    if (!it.latent) d.chan_nz = d.chan_list = nullptr; // the raw boundary: every row is coded, in order
     d.packed = reinterpret_cast<uint32_t *>(ctx->d_ws + it.o_packed);
     d.seg_b[0] = d.seg_b[1] = d.seg_b[2] = INT32_MAX;
     d.packed_seg[0] = d.packed;
@@ -317,7 +368,7 @@ struct EncodeCall {
     for (int i = 0; i < count; ++i) {
       fill_desc(i, hd[i]);
       const EncDesc &d = hd[i];
-      vec4 = vec4 && enc_vec4_ok(d, items[i].prm.dtype == FGMM_F16);
+      vec4 = vec4 && enc_vec4_ok(d, d.packed, items[i].prm.dtype == FGMM_F16);
       // 8 positions per lane for fp16 planes (one 16-byte load per plane: +4-5 % over 8-byte loads on ELIC-4K batches,
       // profiles/r05_symtab_fp16_vec8_ab.txt): everything 16-byte aligned, rows of 8
       vec8 = vec8 && items[i].prm.dtype == FGMM_F16 && (d.hw & 7) == 0 && (d.stride_c & 7) == 0 && (d.stride_k & 7) == 0 && aligned16(d.scales) &&
@@ -424,21 +475,11 @@ struct EncodeCall {
     for (size_t k = 0; k < it.meta_count; ++k) n_bypass += reinterpret_cast<const uint32_t *>(ctx->h_ws + it.o_meta)[k];
     const int32_t *syms_for_bypass = it.sym_host;
     if (it.latent) {
-      const float *mn = reinterpret_cast<const float *>(ctx->h_ws + it.o_min);
-      const float *mx = reinterpret_cast<const float *>(ctx->h_ws + it.o_max);
-      const int32_t *nz = reinterpret_cast<const int32_t *>(ctx->h_ws + it.o_nz);
-      float gmin = INFINITY, gmax = -INFINITY;
-      int n_nz = 0;
-      for (int c = 0; c < it.M; ++c) { // NaN is kept, as torch.min / torch.max keep it (quant_stats_kernel's census does too)
-        gmin = (mn[c] < gmin || mn[c] != mn[c]) ? mn[c] : gmin;
-        gmax = (mx[c] > gmax || mx[c] != mx[c]) ? mx[c] : gmax;
-        n_nz += nz[c] != 0;
-        if (it.zero_bitmap) it.zero_bitmap[c] = nz[c] != 0;
-      }
-      // max(torch.abs(y.max()).int(), torch.abs(y.min()).int()) + 1, floored at 1   (entropy_models.py:834-837)
-      int64_t am = (it.M * it.hw) ? std::max((int64_t)cvtt_i32(fabsf(gmax)), (int64_t)cvtt_i32(fabsf(gmin))) + 1 : 1;
-      if (am < 1) am = 1;
-      it.abs_max = (int32_t)am;
+      const int32_t *nz = reinterpret_cast<const int32_t *>(ctx->h_ws + it.census.o_nz);
+      float mm[2]; // the latent's min, max
+      const int n_nz = census_side_info(ctx, it.census, it.M, it.hw, it.zero_bitmap, &it.abs_max, mm);
+      const float gmin = mm[0], gmax = mm[1];
+      const int64_t am = it.abs_max;
       n = (int64_t)n_nz * it.hw;
       // a latent that is NaN, infinite or beyond int32 is the symbol INT32_MIN (torch's .int()), bypass-coded whatever abs_max is:
       // its two CDF abscissae are the same float (NaN, +-inf, or |v| >= 2^31 where floats are >= 128 apart: v - 0.5 + 1 == v - 0.5),

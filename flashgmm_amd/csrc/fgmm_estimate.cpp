@@ -1,8 +1,9 @@
 // fgmm_estimate.cpp — the coded size of a batch of latents without coding them (include/flashgmm_amd.h section 3b): what
 // fgmm_gmc_compress_batch would return, priced on the GPU.  The encode call's front half - quant_stats_kernel and
 // chan_compact_kernel, unchanged - then rate_kernel (fgmm_rate.hip) in place of symtab_kernel: no table is written, nothing but
-// the per-channel census and sums (a few KB) crosses PCIe, no host worker runs.  Also the building block over a finished table,
-// fgmm_symtab_bits_hip.  A file of its own: the host sources that build against the fake device reference no launcher of these.
+// the per-channel census and sums (a few KB) crosses PCIe, no host worker runs.  The census is laid out and read by the compress
+// call's own helpers (fgmm_encode.cpp).  Also the building block over a finished table, fgmm_symtab_bits_hip.  A file of its own: the
+// host sources that build against the fake device reference no launcher of these.
 #include "fgmm_ctx.h"
 
 using namespace fgmm;
@@ -22,61 +23,14 @@ int ensure_rate_table(fgmm_ctx *ctx) {
   return FGMM_OK;
 }
 
-CensusOff census_take(Arena &ar, int M) {
-  CensusOff o;
-  o.o_min = ar.take(sizeof(float) * M, 16);
-  o.o_max = ar.take(sizeof(float) * M, 16);
-  o.o_nz = ar.take(sizeof(int32_t) * M, 16);
-  o.o_list = ar.take(sizeof(int32_t) * ((size_t)M + 1), 16);
-  return o;
-}
-
-void census_desc(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o, const float *y, const fgmm_params *params, int M, int64_t hw, int clamp) {
-  memset(&d, 0, sizeof d);
-  d.y = y;
-  if (params) { // (quant_stats_kernel and chan_compact_kernel read nothing but y, hw and M)
-    d.scales = params->scales;
-    d.means = params->means;
-    d.weights = params->weights;
-    d.stride_k = params->stride_k;
-    d.stride_c = params->stride_c;
-    d.logits = (params->flags & FGMM_PARAMS_LOGITS) ? 1 : 0;
-  }
-  d.stride_p = 1;
-  d.hw = hw;
-  d.M = M;
-  d.clamp = clamp;
-  d.chan_min = reinterpret_cast<float *>(ctx->d_ws + o.o_min);
-  d.chan_max = reinterpret_cast<float *>(ctx->d_ws + o.o_max);
-  d.chan_nz = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_nz);
-  d.chan_list = reinterpret_cast<int32_t *>(ctx->d_ws + o.o_list);
-  d.seg_b[0] = d.seg_b[1] = d.seg_b[2] = INT32_MAX; // (no table: `packed` and `meta` stay null, neither kernel touches them)
-}
-
-bool census_vec4_ok(const EncDesc &d, const void *out, bool f16) {
-  const uintptr_t pm = f16 ? 7 : 15; // 4 parameters per load: 8 B (fp16) or 16 B (fp32)
-  auto al = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
-  return d.stride_p == 1 && (d.hw & 3) == 0 && (d.stride_c & 3) == 0 && (d.stride_k & 3) == 0 && al(d.scales, pm) && al(d.means, pm) &&
-         al(d.weights, pm) && al(d.y, 15) && al(out, 15);
-}
-
-int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap, int32_t *abs_max_out) {
-  const float *mn = reinterpret_cast<const float *>(ctx->h_ws + o.o_min);
-  const float *mx = reinterpret_cast<const float *>(ctx->h_ws + o.o_max);
-  const int32_t *nz = reinterpret_cast<const int32_t *>(ctx->h_ws + o.o_nz);
-  float gmin = INFINITY, gmax = -INFINITY;
-  int n_nz = 0;
-  for (int c = 0; c < M; ++c) { // NaN is kept, as torch.min / torch.max keep it
-    gmin = (mn[c] < gmin || mn[c] != mn[c]) ? mn[c] : gmin;
-    gmax = (mx[c] > gmax || mx[c] != mx[c]) ? mx[c] : gmax;
-    n_nz += nz[c] != 0;
-    if (zero_bitmap) zero_bitmap[c] = nz[c] != 0;
-  }
-  // max(torch.abs(y.max()).int(), torch.abs(y.min()).int()) + 1, floored at 1   (entropy_models.py:834-837)
-  int64_t am = ((int64_t)M * hw) ? std::max((int64_t)cvtt_i32(fabsf(gmax)), (int64_t)cvtt_i32(fabsf(gmin))) + 1 : 1;
-  if (am < 1) am = 1;
-  *abs_max_out = (int32_t)am;
-  return n_nz;
+int check_latent_item(int i, int K, int M, int64_t hw, const float *y, const fgmm_params &p, int batch_dtype) {
+  if (K != FGMM_K) return fail(FGMM_ERR_INVALID, "K = %d: the reference binds K = 4 only", K);
+  if (M < 0 || hw < 0 || ((int64_t)M * hw && (!y || !p.scales || !p.means || !p.weights)))
+    return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
+  if (p.dtype != batch_dtype || (p.dtype != FGMM_F32 && p.dtype != FGMM_F16))
+    return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32 or FGMM_F16 and the same for a whole batch", i);
+  if (p.flags & ~FGMM_PARAMS_LOGITS) return fail(FGMM_ERR_INVALID, "item %d: unknown fgmm_params.flags %d", i, p.flags);
+  return FGMM_OK;
 }
 } // namespace fgmm
 
@@ -124,7 +78,7 @@ int estimate_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rate_item *items, int
     r.chan_bits = reinterpret_cast<unsigned long long *>(ctx->d_ws + o.o_bits);
     r.chan_bypass = reinterpret_cast<unsigned long long *>(ctx->d_ws + o.o_byp);
     r.bits_map = (int64_t)it.M * it.hw ? it.bits_map : nullptr;
-    vec4 = vec4 && census_vec4_ok(d, r.bits_map, f16);
+    vec4 = vec4 && enc_vec4_ok(d, r.bits_map, f16);
   }
   const int vec = vec4 ? 4 : 1;
   for (int i = 0; i < count; ++i) linear = linear && items[i].hw % (64 * vec) == 0;
@@ -170,12 +124,7 @@ int fgmm_gmc_estimate_batch(fgmm_ctx *ctx, void *stream, fgmm_rate_item *items, 
   if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
   for (int i = 0; i < count; ++i) {
     const fgmm_rate_item &s = items[i];
-    if (s.K != FGMM_K) return fail(FGMM_ERR_INVALID, "K = %d: the reference binds K = 4 only", s.K);
-    if (s.M < 0 || s.hw < 0 || ((int64_t)s.M * s.hw && (!s.y || !s.params.scales || !s.params.means || !s.params.weights)))
-      return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
-    if (s.params.dtype != items[0].params.dtype || (s.params.dtype != FGMM_F32 && s.params.dtype != FGMM_F16))
-      return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32 or FGMM_F16 and the same for a whole batch", i);
-    if (s.params.flags & ~FGMM_PARAMS_LOGITS) return fail(FGMM_ERR_INVALID, "item %d: unknown fgmm_params.flags %d", i, s.params.flags);
+    if (int rc = check_latent_item(i, s.K, s.M, s.hw, s.y, s.params, items[0].params.dtype)) return rc;
   }
   if (count == 0) return FGMM_OK;
   std::lock_guard<std::mutex> lock(ctx->mu);

@@ -14,7 +14,7 @@
 
 #include <algorithm>
 
-#include "fgmm_dev.h"
+#include "fgmm_encframe.h"
 
 namespace fgmm {
 
@@ -109,10 +109,10 @@ __global__ __launch_bounds__(kBlock) void chan_compact_kernel(const EncDesc *__r
 // ---------------------------------------------------------------------------------------------------------
 // symtab_kernel — THE encode-side CDF kernel.  Algorithmic traffic 56 B/latent at K = 4:
 //   4 (y or symbol) + 3*4*4 (sigma, mu, pi planes) in, 4 out (start | range << 16).
-// grid = (tiles over hw, compact channel j, item): block j codes the j-th NON-ZERO channel (chan_list, built on the
-// device by chan_compact_kernel — entropy_models.py:844-845 channel compaction with no host round trip) and writes
-// row j of the table; blocks with j >= count leave after one scalar load.
-// VEC = 4: each lane owns 4 consecutive positions, every plane read is one 16-B load (1 KiB per wave-instr).
+// Placement, loads and the gathering of a position's mixture are the encode frame's (fgmm_encframe.h); its own: row `rank` of the
+// table - one piece or up to four segments - written with VEC-wide stores, and the wave's bypass count.
+// VEC = 4: each lane owns 4 consecutive positions, every plane read is one 16-B load (1 KiB per wave-instr).  VEC = 8: the default
+// for aligned fp16 planes; option "enc_vec" = 4 is the A/B.
 // ---------------------------------------------------------------------------------------------------------
 #ifndef FGMM_SYMTAB_WAVES
 #define FGMM_SYMTAB_WAVES 5 // min waves per SIMD the register allocator must leave room for (<= 96 VGPRs)
@@ -121,162 +121,39 @@ template <int MODE, int VEC, bool CLAMPED, typename PT, bool LINEAR>
 __global__ __launch_bounds__(kBlock, VEC == 8 ? 4 : FGMM_SYMTAB_WAVES) void symtab_kernel(const EncDesc *__restrict__ descs) { // (VEC = 8: 128 VGPRs, else it spills)
   const EncDesc &d = descs[blockIdx.z];
   const int64_t hw = d.hw;
-  const int n_nz = d.chan_list ? d.chan_list[d.M] : d.M; // wave-uniform scalar load
-  int rank;     // compact (coded) channel of this wave: wave-uniform in both forms, so all addressing stays scalar
-  int64_t p0;   // position of the lane's first symbol within the channel
-  int64_t slot; // where this wave leaves its bypass count
-  bool active;  // lanes past the end stay for the wave reduction below
-  if constexpr (LINEAR) {
-    // Every hw of the batch is a multiple of 64 * VEC (checked by the host): the coded symbols of an item are one
-    // linear range [0, n_nz * hw) and each WAVE takes 64 * VEC consecutive ones, never straddling a channel.  All
-    // waves are full whatever hw is (a 768-symbol Kodak plane fills only 3 of the 4 waves of a per-channel block).
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t w0 = ((int64_t)blockIdx.x * kBlock + wave * 64) * VEC;
-    if (w0 >= (int64_t)n_nz * hw) return;
-    rank = __builtin_amdgcn_readfirstlane((int)(w0 / hw));
-    p0 = (w0 - (int64_t)rank * hw) + (int64_t)(threadIdx.x & 63) * VEC;
-    slot = (int64_t)blockIdx.x * (kBlock / 64) + wave;
-    active = true;
-  } else {
-    // one block per (tile of kBlock * VEC positions, compact channel)
-    rank = blockIdx.y;
-    if (rank >= n_nz) return;
-    if ((int64_t)blockIdx.x * kBlock * VEC >= hw) return;
-    p0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * VEC;
-    const int64_t tiles = (hw + (int64_t)kBlock * VEC - 1) / ((int64_t)kBlock * VEC);
-    slot = ((int64_t)rank * tiles + blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
-    active = p0 < hw;
-  }
-  const int c = d.chan_list ? d.chan_list[rank] : rank;
+  int rank;
+  int64_t p0;
+  bool active;
+  if (!enc_place<VEC, LINEAR>(hw, enc_n_coded(d), rank, p0, active)) return;
+  const int c = enc_channel(d, rank);
+  // where this wave leaves its bypass count: one slot per wave of the grid
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t tiles = (hw + (int64_t)kBlock * VEC - 1) / ((int64_t)kBlock * VEC);
+  const int64_t slot = (LINEAR ? (int64_t)blockIdx.x : (int64_t)rank * tiles + blockIdx.x) * (kBlock / 64) + wave;
   // where the compact channel's entries go: the table is one piece, or up to four segments of compact channels (wave-uniform)
   const int seg = (rank >= d.seg_b[0]) + (rank >= d.seg_b[1]) + (rank >= d.seg_b[2]);
   uint32_t *const row_out = (seg ? d.packed_seg[seg] : d.packed) + (int64_t)(rank - seg * d.cps) * hw;
   int nbypass = 0;
-  if (!active) {
-  } else if constexpr (VEC == 8) {
-    // fp16 planes, 8 positions per lane: every plane read is ONE 16-byte load (the VEC = 4 form reads 8 bytes per lane and plane);
-    // the halves stay packed in registers (48 VGPRs for the twelve planes) and are widened as each position is evaluated.
-    // Measured against VEC = 4 on ELIC-4K batches (profiles/r05_symtab_fp16_vec8_ab.txt): 127.6 / 133.1 against 123.0 / 126.8 G
-    // symbols per second (2 / 4 images) - the kernel is bound by VALU issue (0.86 of the issue roof, bench.py's valu_frac) and
-    // this form issues fewer load and address instructions.  The default for aligned fp16 planes; option "enc_vec" = 4 is the A/B.
-    typedef PT pvec_t __attribute__((ext_vector_type(8)));
-    typedef float f4_t __attribute__((ext_vector_type(4)));
-    typedef int i4_t __attribute__((ext_vector_type(4)));
-    typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
-    const int64_t base = (int64_t)c * d.stride_c + p0;
-    float vq[8];
-    int vi[8];
-    if (d.sym) {
-      const i4_t t0 = ldg<i4_t>(d.sym + (int64_t)c * hw + p0), t1 = ldg<i4_t>(d.sym + (int64_t)c * hw + p0 + 4);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        vi[e] = e < 4 ? t0[e & 3] : t1[e & 3];
-        vq[e] = (float)vi[e];
-      }
-    } else {
-      const f4_t t0 = ldg<f4_t>(d.y + (int64_t)c * hw + p0), t1 = ldg<f4_t>(d.y + (int64_t)c * hw + p0 + 4);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        vq[e] = __builtin_rintf(e < 4 ? t0[e & 3] : t1[e & 3]);
-        vi[e] = (int)vq[e];
-      }
-    }
-    pvec_t rS[4], rM[4], rP[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      rS[k] = ldg<pvec_t>(static_cast<const PT *>(d.scales) + base + k * d.stride_k);
-      rM[k] = ldg<pvec_t>(static_cast<const PT *>(d.means) + base + k * d.stride_k);
-      rP[k] = ldg<pvec_t>(static_cast<const PT *>(d.weights) + base + k * d.stride_k);
-    }
-    u4_t out[2];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float mu[4], sg[4], pi[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sg[k] = (float)rS[k][e];
-        mu[k] = (float)rM[k][e];
-        pi[k] = (float)rP[k][e];
-      }
-      if (d.logits) softmax4(pi);
-      int bp;
-      out[e >> 2][e & 3] = sym_entry<MODE, CLAMPED>(vq[e], vi[e], mu, sg, pi, bp);
-      nbypass += __popcll(__ballot(bp));
-    }
-    stg<u4_t>(row_out + p0, out[0]);
-    stg<u4_t>(row_out + p0 + 4, out[1]);
-  } else if constexpr (VEC > 1) {
-    // planar, aligned (checked by the host): one VEC-wide load per plane per lane (16 B fp32 / 8 B fp16 at VEC = 4)
-    typedef float fvec_t __attribute__((ext_vector_type(VEC)));
-    typedef int ivec_t __attribute__((ext_vector_type(VEC)));
-    typedef uint32_t uvec_t __attribute__((ext_vector_type(VEC)));
-    const int64_t base = (int64_t)c * d.stride_c + p0;
+  if (active) {
     float vq[VEC];
     int vi[VEC];
-    if (d.sym) {
-      const ivec_t t = ldg<ivec_t>(d.sym + (int64_t)c * hw + p0);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        vi[e] = t[e];
-        vq[e] = (float)vi[e];
-      }
-    } else {
-      const fvec_t t = ldg<fvec_t>(d.y + (int64_t)c * hw + p0);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        vq[e] = __builtin_rintf(t[e]);
-        vi[e] = (int)vq[e];
-      }
-    }
-    float S[4][VEC], Mu[4][VEC], Pi[4][VEC];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      ldv<PT, VEC>(d.scales, base + k * d.stride_k, S[k]);
-      ldv<PT, VEC>(d.means, base + k * d.stride_k, Mu[k]);
-      ldv<PT, VEC>(d.weights, base + k * d.stride_k, Pi[k]);
-    }
-    uvec_t out;
+    enc_load_sym<VEC>(d, c, p0, vq, vi);
+    EncPlanes<PT, VEC> P;
+    P.load(d, c, p0);
+    uint32_t out[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       float mu[4], sg[4], pi[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sg[k] = S[k][e];
-        mu[k] = Mu[k][e];
-        pi[k] = Pi[k][e];
-      }
-      if (d.logits) softmax4(pi);
+      P.get(e, d.logits, mu, sg, pi);
       int bp;
       out[e] = sym_entry<MODE, CLAMPED>(vq[e], vi[e], mu, sg, pi, bp);
       nbypass += __popcll(__ballot(bp)); // the wave's count on the scalar unit: no lane-wise sum, no cross-lane reduction
+      if constexpr (VEC == 1) break; // (one position: no loop, see EncPlanes<PT, 1>)
     }
-    stg<uvec_t>(row_out + p0, out);
-  } else {
-    const int64_t base = (int64_t)c * d.stride_c + p0 * d.stride_p;
-    float vq;
-    int vi;
-    if (d.sym) {
-      vi = ldg<int32_t>(d.sym + (int64_t)c * hw + p0);
-      vq = (float)vi;
-    } else {
-      vq = __builtin_rintf(ldg<float>(d.y + (int64_t)c * hw + p0));
-      vi = (int)vq;
-    }
-    float mu[4], sg[4], pi[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sg[k] = ld1<PT>(d.scales, base + k * d.stride_k);
-      mu[k] = ld1<PT>(d.means, base + k * d.stride_k);
-      pi[k] = ld1<PT>(d.weights, base + k * d.stride_k);
-    }
-    if (d.logits) softmax4(pi);
-    int bp;
-    stg<uint32_t>(row_out + p0, sym_entry<MODE, CLAMPED>(vq, vi, mu, sg, pi, bp));
-    nbypass = __popcll(__ballot(bp));
+    enc_st<uint32_t, VEC>(row_out + p0, out);
   }
   // bypass census (the host sizes its output buffer from it): one plain store per wave that saw any, no atomics.  nbypass is
-  // the same on every active lane (ballots); lanes past the end of a channel are the wave's last ones, so lane 0 is active
-  // whenever any lane is
+  // the same on every active lane (ballots), and lane 0 is active whenever any lane is
   if ((threadIdx.x & 63) == 0 && nbypass)
     d.meta[slot] = (uint32_t)nbypass;
 }
@@ -529,42 +406,15 @@ int launch_quant_stats(const EncDesc *d_descs, int count, int M_max, void *strea
   return launch_err();
 }
 
-template <int VEC, bool CLAMPED, typename PT, bool LINEAR>
-static int launch_symtab_v(const EncDesc *d, int count, int M_max, int64_t hw_max, int64_t n_max, int mode, hipStream_t s) {
-  const int64_t per_block = (int64_t)kBlock * VEC;
-  const dim3 grid = LINEAR ? dim3((unsigned)((n_max + per_block - 1) / per_block), 1u, (unsigned)count)
-                           : dim3((unsigned)((hw_max + per_block - 1) / per_block), (unsigned)M_max, (unsigned)count);
-  switch (mode) {
-  case MODE_AS: hipLaunchKernelGGL((symtab_kernel<MODE_AS, VEC, CLAMPED, PT, LINEAR>), grid, dim3(kBlock), 0, s, d); break;
-  case MODE_LOGISTIC: hipLaunchKernelGGL((symtab_kernel<MODE_LOGISTIC, VEC, CLAMPED, PT, LINEAR>), grid, dim3(kBlock), 0, s, d); break;
-  default: hipLaunchKernelGGL((symtab_kernel<MODE_POLYA, VEC, CLAMPED, PT, LINEAR>), grid, dim3(kBlock), 0, s, d); break;
+struct SymtabLaunch {
+  const EncDesc *d;
+  template <int MODE, int VEC, bool CLAMPED, typename PT, bool LINEAR> void go(dim3 grid, hipStream_t s) const {
+    hipLaunchKernelGGL((symtab_kernel<MODE, VEC, CLAMPED, PT, LINEAR>), grid, dim3(kBlock), 0, s, d);
   }
-  return launch_err();
-}
-template <typename PT, bool LINEAR>
-static int launch_symtab_t(const EncDesc *d, int count, int M_max, int64_t hw_max, int64_t n_max, int mode, int vec, bool clamped,
-                           hipStream_t s) {
-  if constexpr (sizeof(PT) == 2) // (fp16 planes only: 16-byte loads per plane)
-    if (vec == 8) return clamped ? launch_symtab_v<8, true, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s)
-                                 : launch_symtab_v<8, false, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s);
-  if (vec >= 4) return clamped ? launch_symtab_v<4, true, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s)
-                               : launch_symtab_v<4, false, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s);
-  if (vec == 2) return clamped ? launch_symtab_v<2, true, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s)
-                               : launch_symtab_v<2, false, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s);
-  return clamped ? launch_symtab_v<1, true, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s)
-                 : launch_symtab_v<1, false, PT, LINEAR>(d, count, M_max, hw_max, n_max, mode, s);
-}
-
+};
 int launch_symtab(const EncDesc *d_descs, int count, int M_max, int64_t hw_max, int64_t n_max, bool linear, int mode, int vec,
                   bool clamped, bool f16, void *stream) {
-  if (count <= 0 || M_max <= 0 || hw_max <= 0) return 0;
-  if (linear && (n_max + kBlock - 1) / kBlock > 0x7FFFFFFFll) linear = false; // grid.x
-  hipStream_t s = (hipStream_t)stream;
-  if (linear)
-    return f16 ? launch_symtab_t<_Float16, true>(d_descs, count, M_max, hw_max, n_max, mode, vec, clamped, s)
-               : launch_symtab_t<float, true>(d_descs, count, M_max, hw_max, n_max, mode, vec, clamped, s);
-  return f16 ? launch_symtab_t<_Float16, false>(d_descs, count, M_max, hw_max, n_max, mode, vec, clamped, s)
-             : launch_symtab_t<float, false>(d_descs, count, M_max, hw_max, n_max, mode, vec, clamped, s);
+  return enc_launch<true>(SymtabLaunch{d_descs}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream);
 }
 
 int launch_cdf_pair(const int32_t *v, const float *scales, const float *means, const float *weights, int64_t n,

@@ -57,7 +57,7 @@ int rdoq_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int cou
     q.chan_before = reinterpret_cast<unsigned long long *>(ctx->d_ws + o.o_before);
     q.chan_after = reinterpret_cast<unsigned long long *>(ctx->d_ws + o.o_after);
     q.chan_changed = reinterpret_cast<unsigned long long *>(ctx->d_ws + o.o_changed);
-    vec4 = vec4 && census_vec4_ok(d, q.y_out, f16);
+    vec4 = vec4 && enc_vec4_ok(d, q.y_out, f16);
   }
   const int vec = vec4 ? 4 : 1;
   for (int i = 0; i < count; ++i) linear = linear && items[i].hw % (64 * vec) == 0;
@@ -108,16 +108,11 @@ int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int 
   if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
   for (int i = 0; i < count; ++i) {
     const fgmm_rdoq_item &s = items[i];
-    if (s.K != FGMM_K) return fail(FGMM_ERR_INVALID, "K = %d: the reference binds K = 4 only", s.K);
-    if (s.M < 0 || s.hw < 0 ||
-        ((int64_t)s.M * s.hw && (!s.y || !s.y_rdo || !s.params.scales || !s.params.means || !s.params.weights)))
-      return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
+    if (int rc = check_latent_item(i, s.K, s.M, s.hw, s.y, s.params, items[0].params.dtype)) return rc;
+    if ((int64_t)s.M * s.hw && !s.y_rdo) return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
     const uintptr_t y0 = reinterpret_cast<uintptr_t>(s.y), r0 = reinterpret_cast<uintptr_t>(s.y_rdo);
     const uintptr_t nb = sizeof(float) * (uintptr_t)s.M * (uintptr_t)s.hw; // (y_rdo is zeroed before the census reads y)
     if (nb && y0 < r0 + nb && r0 < y0 + nb) return fail(FGMM_ERR_INVALID, "item %d: y_rdo may not overlap y", i);
-    if (s.params.dtype != items[0].params.dtype || (s.params.dtype != FGMM_F32 && s.params.dtype != FGMM_F16))
-      return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32 or FGMM_F16 and the same for a whole batch", i);
-    if (s.params.flags & ~FGMM_PARAMS_LOGITS) return fail(FGMM_ERR_INVALID, "item %d: unknown fgmm_params.flags %d", i, s.params.flags);
   }
   if (count == 0) return FGMM_OK;
   std::lock_guard<std::mutex> lock(ctx->mu);
