@@ -21,6 +21,8 @@ FGMM_HEAD_BF16X6 = 1  # fgmm_head_create_ex flags
 FGMM_PARAMS_LOGITS = 1  # fgmm_params.flags: the weights planes hold logits, softmax over K runs in the kernels
 MODES = {"polya": 0, "as": 1, "logistic": 2}  # numbering of the reference CODE (rans_interface.cpp:224-232)
 
+FGMM_BUDGET_UNMET = 7  # fgmm_budget_result.status: not an error - no lambda up to lambda_max meets the group's byte budget
+FGMM_RDCURVE_MAX = 16  # lambdas per fgmm_gmc_rdcurve_batch call
 STATUS_NAMES = {1: "FGMM_ERR_INVALID", 2: "FGMM_ERR_NO_DEVICE", 3: "FGMM_ERR_HIP", 4: "FGMM_ERR_NOMEM",
                 5: "FGMM_ERR_STREAM", 6: "FGMM_ERR_UNSUPPORTED"}
 
@@ -62,6 +64,18 @@ class fgmm_rdoq_item(C.Structure):
     _fields_ = [("y", C.c_void_p), ("params", fgmm_params), ("M", C.c_int32), ("K", C.c_int32), ("hw", C.c_int64),
                 ("y_rdo", C.c_void_p), ("zero_bitmap", C.c_void_p), ("chan_bits_q_after", C.c_void_p), ("abs_max", C.c_int32),
                 ("status", C.c_int32), ("n_changed", C.c_int64), ("bits_q_before", C.c_uint64), ("bits_q_after", C.c_uint64)]
+
+
+class fgmm_rdcurve_item(C.Structure):
+    """one item of fgmm_gmc_rdcurve_batch (include/flashgmm_amd.h section 3d)"""
+    _fields_ = [("y", C.c_void_p), ("params", fgmm_params), ("M", C.c_int32), ("K", C.c_int32), ("hw", C.c_int64),
+                ("bits_q_before", C.c_uint64), ("bits_q_after", C.c_uint64 * FGMM_RDCURVE_MAX), ("n_changed", C.c_uint64 * FGMM_RDCURVE_MAX),
+                ("ddist_q", C.c_uint64 * FGMM_RDCURVE_MAX), ("n_symbols", C.c_int64), ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
+class fgmm_budget_result(C.Structure):
+    """one group's result of fgmm_gmc_rdoq_budget_batch (section 3d)"""
+    _fields_ = [("lambda_", C.c_double), ("bytes_pred", C.c_uint64), ("passes", C.c_int32), ("status", C.c_int32)]
 
 
 def _item_dtype(struct=fgmm_item):
@@ -147,6 +161,9 @@ SIGNATURES = {
     "fgmm_symtab_bits_hip": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p]),
     "fgmm_gmc_estimate_batch": (_i, [_p, _p, C.POINTER(fgmm_rate_item), _i, _i, _i]),
     "fgmm_gmc_rdoq_batch": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.c_double]),
+    "fgmm_gmc_rdcurve_batch": (_i, [_p, _p, C.POINTER(fgmm_rdcurve_item), _i, _i, _i, C.POINTER(C.c_double), _i]),
+    "fgmm_gmc_rdoq_budget_batch": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_uint64), C.c_double, _i,
+                                        C.POINTER(fgmm_budget_result)]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

@@ -5,19 +5,19 @@
 #   -march=x86-64-v3                          : host rANS code may use AVX2/BMI2, stays portable across hosts
 #   -Xarch_device -fno-slp-vectorize          : packed fp32 ops (v_pk_fma_f32 ...) issue at half rate on gfx950 and cost
 #                                               pairing moves: measured 1-6 % (symtab) / 12 % (cdftab count) slower with them
-# Sources: the kernels (*.hip; fgmm_encframe.h is the frame fgmm_kernels.hip, fgmm_rate.hip and fgmm_rdoq.hip share), the device layer over HIP (fgmm_device_hip.cpp), and the host side, which sees the device only
+# Sources: the kernels (*.hip; fgmm_encframe.h is the frame fgmm_kernels.hip, fgmm_rate.hip, fgmm_rdoq.hip and fgmm_rdcurve.hip share), the device layer over HIP (fgmm_device_hip.cpp), and the host side, which sees the device only
 # through fgmm_device.h (fgmm_capi / fgmm_encode / fgmm_decode / fgmm_decode_gpu / fgmm_rans: plain C++, also built without a GPU
 # toolchain against tests/fake/fake_device.cpp by scripts/tsan_host.sh); fgmm_rate_host.cpp (the coded size of a table, integer only) and
-# fgmm_estimate.cpp / fgmm_rdoq.cpp (the size estimate's and the RDOQ call's orchestration over fgmm_rate.hip / fgmm_rdoq.hip: not part of
-# the fake-device build).
+# fgmm_estimate.cpp / fgmm_rdoq.cpp / fgmm_rdcurve.cpp (the size estimate's, the RDOQ call's and the curve and budget calls' orchestration
+# over fgmm_rate.hip / fgmm_rdoq.hip / fgmm_rdcurve.hip: not part of the fake-device build).
 set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OUT=${OUT:-../libflashgmm_amd.so}
 COMMON="-O3 -fPIC -std=c++17 -Wall -Wextra -Wno-unused-parameter -ffp-contract=off -fno-fast-math"
 $HIPCC $COMMON --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-rdc -Xarch_device -fno-slp-vectorize \
-    -march=x86-64-v3 -shared -o $OUT fgmm_kernels.hip fgmm_tab.hip fgmm_head.hip fgmm_head16.hip fgmm_rate.hip fgmm_rdoq.hip fgmm_device_hip.cpp fgmm_rans.cpp fgmm_rate_host.cpp fgmm_capi.cpp \
-    fgmm_encode.cpp fgmm_decode.cpp fgmm_decode_gpu.cpp fgmm_estimate.cpp fgmm_rdoq.cpp -lpthread "$@"
+    -march=x86-64-v3 -shared -o $OUT fgmm_kernels.hip fgmm_tab.hip fgmm_head.hip fgmm_head16.hip fgmm_rate.hip fgmm_rdoq.hip fgmm_rdcurve.hip fgmm_device_hip.cpp fgmm_rans.cpp fgmm_rate_host.cpp fgmm_capi.cpp \
+    fgmm_encode.cpp fgmm_decode.cpp fgmm_decode_gpu.cpp fgmm_estimate.cpp fgmm_rdoq.cpp fgmm_rdcurve.cpp -lpthread "$@"
 echo "built $(realpath $OUT)"
 # The compiled Python boundary over the C ABI (fgmm_pybind.cpp -> flashgmm_amd/_native.*.so): plain C++ against the Python and pybind11
 # headers, linked to the library above through an $ORIGIN rpath.  Skipped (the ctypes binding, flashgmm_amd/_lib.py, binds the same

@@ -309,6 +309,9 @@ int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw,
 int ensure_rate_table(fgmm_ctx *ctx); // the context's device copy of rate_log2_table(), uploaded on first use
 // one item of either call: K, sizes, tensors, the parameters' dtype (one per batch) and flags; FGMM_OK or the failure, already reported
 int check_latent_item(int i, int K, int M, int64_t hw, const float *y, const fgmm_params &params, int batch_dtype);
+// ---- fgmm_rdoq.cpp: the RDOQ call with the context's lock held, for the budget call (fgmm_rdcurve.cpp) too --------------------------
+int rdoq_check_items(const fgmm_rdoq_item *items, int count); // the items of either call: FGMM_OK or the failure, already reported
+int rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride);
 
 struct DeviceGuard {
   int prev = -1;

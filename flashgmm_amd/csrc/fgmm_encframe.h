@@ -156,6 +156,57 @@ template <typename PT> struct EncPlanes<PT, 1> {
 };
 
 // ---------------------------------------------------------------------------------------------------------
+// The decision of include/flashgmm_amd.h section 3c, shared by rdoq_kernel (fgmm_rdoq.hip: one lambda, the symbol written) and
+// rdcurve_kernel (fgmm_rdcurve.hip: the same latent decided at up to 16 lambdas, nothing written): one text, so the two cannot drift.
+// rdoq_price: a latent of a coded channel -> vq = round(y) and the exact costs cm, c0, cp of vq - 1, vq, vq + 1.  false: the latent is
+// not finite or |vq| > 2^20 - it keeps round(y), and all three are rate_kernel's price of it.
+// rdoq_choose: -1 / 0 / +1, the step 3c takes at lam_q = lambda * 2^-24.
+// ---------------------------------------------------------------------------------------------------------
+constexpr float kRdoqMaxAbs = 0x1p20f;
+template <int MODE, bool CLAMPED>
+__device__ __forceinline__ bool rdoq_price(float y, const float (&mu)[4], const float (&sg)[4], const float (&pi)[4], const uint32_t *__restrict__ L,
+                                           float &vq, uint32_t &cm, uint32_t &c0, uint32_t &cp) {
+  vq = __builtin_rintf(y);
+  const int vi = (int)vq;
+  if (__builtin_expect(!(__builtin_fabsf(y) < INFINITY && __builtin_fabsf(vq) <= kRdoqMaxAbs), 0)) { // (false for NaN too)
+    int bp;
+    const uint32_t ent = sym_entry<MODE, CLAMPED>(vq, vi, mu, sg, pi, bp); // exactly rate_kernel's pricing
+    cm = c0 = cp = entry_cost(ent, vq, vi, true, L);
+    return false;
+  }
+  uint32_t q[4];
+  sym_edges4<MODE, CLAMPED>(vq, mu, sg, pi, q);
+  int bp;
+  cm = rate_cost_q(entry_from_edges(q[0], q[1], vi - 1, bp), vi - 1, L);
+  c0 = rate_cost_q(entry_from_edges(q[1], q[2], vi, bp), vi, L);
+  cp = rate_cost_q(entry_from_edges(q[2], q[3], vi + 1, bp), vi + 1, L);
+  return true;
+}
+// d0, d: the distances (double)y - (double)v of round(y) and of the choice, for a caller that goes on with them
+__device__ __forceinline__ int rdoq_choose(float y, float vq, uint32_t cm, uint32_t c0, uint32_t cp, double lam_q, double &d0, double &d) {
+  const float vm = vq - 1.0f, vp = vq + 1.0f;
+  const double yd = (double)y;
+  d0 = yd - (double)vq;
+  const double dm = yd - (double)vm, dp = yd - (double)vp;
+  const double j0 = d0 * d0 + lam_q * (double)c0;
+  const double jm = dm * dm + lam_q * (double)cm;
+  const double jp = dp * dp + lam_q * (double)cp;
+  int pick = 0;
+  double jb = j0;
+  d = d0;
+  if (jm < jb) {
+    pick = -1;
+    jb = jm;
+    d = dm;
+  }
+  if (jp < jb) {
+    pick = 1;
+    d = dp;
+  }
+  return pick;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // the launchers' ladder.  F::go<MODE, VEC, CLAMPED, PT, LINEAR>(grid, stream) does the kernel's hipLaunchKernelGGL with its own
 // arguments.  ALL_VEC: VEC = 2, and 8 for fp16 planes, exist too (symtab_kernel's A/B forms and its fp16 default); else vec >= 4 is 4
 // and anything below is 1.  M_max, hw_max, n_max: the largest M, hw and M * hw of the batch.

@@ -304,6 +304,18 @@ struct RdoqDesc {                   // item i of an rdoq_kernel launch, beside i
 int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, double lam_q, int count, int M_max, int64_t hw_max,
                 int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
 
+// ---- the rate-distortion curve and quantisation to a byte budget (fgmm_rdcurve.hip, fgmm_rdcurve.cpp; header section 3d) ---------
+constexpr int kRdCurveRow = 1 + 3 * FGMM_RDCURVE_MAX; // one row of sums: [0] bits_q_before, then 16 each of bits_q_after, n_changed, ddist_q
+struct RdCurveDesc {                // item i of an rdcurve_kernel launch, beside its EncDesc
+  unsigned long long *chan_acc;     // device [M][kRdCurveRow], zeroed by the host: the sums of channel c (all 0: not coded)
+  unsigned long long *sums;         // device [kRdCurveRow], zeroed by the host: the item's, folded from chan_acc by rdcurve_fold_kernel
+  int32_t n_lambda, pad_;           // 1 .. FGMM_RDCURVE_MAX; 0: the item takes no part in this launch
+  double lam_q[FGMM_RDCURVE_MAX];   // lambda_j * 2^-FGMM_RATE_Q - per item, so that one launch serves groups with grids of their own
+};
+// the addressing of launch_rdoq; rdcurve_kernel, then rdcurve_fold_kernel
+int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, int count, int M_max, int64_t hw_max, int64_t n_max,
+                   bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
+
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the
 // encoder asks it for storage of the stream's exact size once that is known and copies the stream there out of its scratch: the

@@ -1,0 +1,265 @@
+// fgmm_rdcurve.cpp — the rate-distortion curve of a batch of latents and their quantisation to a byte budget (include/flashgmm_amd.h
+// section 3d).  The size estimate's front half once per call (fgmm_estimate.cpp: quant_stats_kernel and chan_compact_kernel give the
+// channels the compress call would code for y), then one or more PASSES: rdcurve_kernel (fgmm_rdcurve.hip) at up to 16 lambdas per
+// item, the channels' sums folded to the items' on the device, a few KB back.  The budget call searches lambda on those passes by the
+// header's rule, every group on its own grid within one launch, and ends in the RDOQ call's own path (fgmm_rdoq.cpp: rdoq_run) at the
+// lambdas found.  A file of its own, as fgmm_rdoq.cpp: the host sources that build against the fake device reference no launcher of these.
+#include <algorithm>
+#include <cmath>
+
+#include "fgmm_ctx.h"
+
+using namespace fgmm;
+
+namespace {
+
+struct CurveIn { // what a pass reads of an item, whichever call it belongs to
+  const float *y;
+  const fgmm_params *params;
+  int32_t M;
+  int64_t hw;
+};
+
+struct Curve { // the front half of a call and the state its passes share
+  fgmm_ctx *ctx;
+  dev::Stream stream;
+  int count, mode, clamp;
+  int M_max = 0, vec = 1;
+  int64_t hw_max = 0, n_max = 0;
+  bool f16 = false, linear = true, census_back = false;
+  size_t o_descs = 0, o_cdescs = 0, o_census = 0, o_sums = 0, o_acc = 0, end = 0;
+  std::vector<CensusOff> census;
+  Curve(fgmm_ctx *ctx_, dev::Stream stream_, int count_, int mode_, int clamp_) : ctx(ctx_), stream(stream_), count(count_), mode(mode_), clamp(clamp_) {}
+  RdCurveDesc *hc = nullptr; // host copy of the curve descriptors: a pass sets n_lambda and lam_q of every item, then run()
+  const unsigned long long *sums(int i) const { return reinterpret_cast<const unsigned long long *>(ctx->h_ws + o_sums) + (size_t)i * kRdCurveRow; }
+
+  // workspace: [EncDesc x count][RdCurveDesc x count][census of every item][sums: count rows][device only: per item M rows]
+  int begin(const std::vector<CurveIn> &in) {
+    int rc;
+    if ((rc = ensure_rate_table(ctx))) return rc;
+    Arena ar;
+    o_descs = ar.take(sizeof(EncDesc) * (size_t)count);
+    o_cdescs = ar.take(sizeof(RdCurveDesc) * (size_t)count);
+    o_census = ar.take(0);
+    census.resize((size_t)count);
+    for (int i = 0; i < count; ++i) {
+      census[(size_t)i] = census_take(ar, in[(size_t)i].M);
+      M_max = std::max(M_max, in[(size_t)i].M);
+      hw_max = std::max(hw_max, in[(size_t)i].hw);
+      n_max = std::max(n_max, (int64_t)in[(size_t)i].M * in[(size_t)i].hw);
+    }
+    o_sums = ar.take(sizeof(unsigned long long) * kRdCurveRow * (size_t)count, 16);
+    o_acc = ar.take(0);
+    std::vector<size_t> o_item((size_t)count);
+    for (int i = 0; i < count; ++i) o_item[(size_t)i] = ar.take(sizeof(unsigned long long) * kRdCurveRow * (size_t)in[(size_t)i].M, 16);
+    end = ar.off;
+    if ((rc = ctx->ensure_device(end)) || (rc = ctx->ensure_host(o_acc)) || (rc = ctx->ensure_events(1))) return rc;
+    EncDesc *hd = reinterpret_cast<EncDesc *>(ctx->h_ws + o_descs);
+    hc = reinterpret_cast<RdCurveDesc *>(ctx->h_ws + o_cdescs);
+    f16 = in[0].params->dtype == FGMM_F16;
+    bool vec4 = true;
+    for (int i = 0; i < count; ++i) {
+      const CurveIn &it = in[(size_t)i];
+      census_desc(hd[i], ctx, census[(size_t)i], it.y, it.params, it.M, it.hw, clamp);
+      memset(&hc[i], 0, sizeof hc[i]);
+      hc[i].chan_acc = reinterpret_cast<unsigned long long *>(ctx->d_ws + o_item[(size_t)i]);
+      hc[i].sums = reinterpret_cast<unsigned long long *>(ctx->d_ws + o_sums) + (size_t)i * kRdCurveRow;
+      vec4 = vec4 && enc_vec4_ok(hd[i], nullptr, f16);
+    }
+    vec = vec4 ? 4 : 1;
+    for (int i = 0; i < count; ++i) linear = linear && in[(size_t)i].hw % (64 * vec) == 0;
+    // the census, once: every pass prices the channels it names
+    DEV_TRY(dev::copy_async(ctx->d_ws + o_descs, hd, sizeof(EncDesc) * (size_t)count, dev::kH2D, stream));
+    DEV_TRY(dev::memset_async(ctx->d_ws + o_census, 0, o_sums - o_census, stream));
+    LAUNCH_TRY(launch_quant_stats(reinterpret_cast<const EncDesc *>(ctx->d_ws + o_descs), count, M_max, stream));
+    return FGMM_OK;
+  }
+
+  // one pass with the descriptors as `hc` holds them; returns with the items' sums (and, after the first, the census) on the host
+  int run() {
+    DEV_TRY(dev::copy_async(ctx->d_ws + o_cdescs, hc, sizeof(RdCurveDesc) * (size_t)count, dev::kH2D, stream));
+    DEV_TRY(dev::memset_async(ctx->d_ws + o_sums, 0, end - o_sums, stream)); // the items' sums and the channels'
+    LAUNCH_TRY(launch_rdcurve(reinterpret_cast<const EncDesc *>(ctx->d_ws + o_descs), reinterpret_cast<const RdCurveDesc *>(ctx->d_ws + o_cdescs),
+                              ctx->d_rate_log2, count, M_max, hw_max, n_max, linear, mode, vec, clamp != 0, f16, stream));
+    const size_t from = census_back ? o_sums : o_census;
+    DEV_TRY(dev::copy_async(ctx->h_ws + from, ctx->d_ws + from, o_acc - from, dev::kD2H, stream));
+    census_back = true;
+    DEV_TRY(dev::event_record(ctx->events[0], stream));
+    DEV_TRY(dev::event_sync(ctx->events[0]));
+    return FGMM_OK;
+  }
+};
+
+bool lambda_ok(double v) { return v >= 0.0 && v < (double)INFINITY; } // (false for NaN)
+
+int curve_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdcurve_item *items, int count, int mode, int clamp, const double *lambdas, int n_lambda) {
+  std::vector<CurveIn> in((size_t)count);
+  for (int i = 0; i < count; ++i) in[(size_t)i] = CurveIn{items[i].y, &items[i].params, items[i].M, items[i].hw};
+  Curve cv(ctx, stream, count, mode, clamp);
+  int rc;
+  if ((rc = cv.begin(in))) return rc;
+  for (int i = 0; i < count; ++i) {
+    cv.hc[i].n_lambda = n_lambda;
+    for (int j = 0; j < n_lambda; ++j) cv.hc[i].lam_q[j] = lambdas[j] * 0x1p-24;
+  }
+  if ((rc = cv.run())) return rc;
+  for (int i = 0; i < count; ++i) {
+    fgmm_rdcurve_item &it = items[i];
+    const unsigned long long *s = cv.sums(i);
+    int32_t abs_max;
+    const int n_nz = census_side_info(ctx, cv.census[(size_t)i], it.M, it.hw, nullptr, &abs_max);
+    it.bits_q_before = s[0];
+    for (int j = 0; j < n_lambda; ++j) {
+      it.bits_q_after[j] = s[1 + j];
+      it.n_changed[j] = s[1 + FGMM_RDCURVE_MAX + j];
+      it.ddist_q[j] = s[1 + 2 * FGMM_RDCURVE_MAX + j];
+    }
+    it.n_symbols = (int64_t)n_nz * it.hw;
+    it.status = FGMM_OK;
+  }
+  return FGMM_OK;
+}
+
+struct Search { // one group's search (header section 3d)
+  double grid[FGMM_RDCURVE_MAX];
+  double lo = 0.0, hi = 0.0;
+  uint64_t f_hi = 0;
+  int passes = 0, status = FGMM_OK;
+  bool active = true;
+};
+
+int budget_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const int32_t *group, int n_groups,
+                 const uint64_t *budget, double lambda_max, int refine, fgmm_budget_result *results) {
+  std::vector<CurveIn> in((size_t)count);
+  for (int i = 0; i < count; ++i) in[(size_t)i] = CurveIn{items[i].y, &items[i].params, items[i].M, items[i].hw};
+  Curve cv(ctx, stream, count, mode, clamp);
+  int rc;
+  if ((rc = cv.begin(in))) return rc;
+  std::vector<Search> gs((size_t)n_groups);
+  for (Search &g : gs) { // round 0: 0, then lambda_max * 2^(j - 15)
+    g.grid[0] = 0.0;
+    for (int j = 1; j < FGMM_RDCURVE_MAX; ++j) g.grid[j] = lambda_max * ldexp(1.0, j - 15);
+  }
+  std::vector<uint64_t> f((size_t)n_groups * FGMM_RDCURVE_MAX);
+  for (int round = 0; round <= refine; ++round) {
+    bool any = false;
+    for (const Search &g : gs) any = any || g.active;
+    if (!any) break;
+    for (int i = 0; i < count; ++i) {
+      const Search &g = gs[(size_t)(group ? group[i] : i)];
+      cv.hc[i].n_lambda = g.active ? FGMM_RDCURVE_MAX : 0;
+      for (int j = 0; j < FGMM_RDCURVE_MAX; ++j) cv.hc[i].lam_q[j] = g.grid[j] * 0x1p-24;
+    }
+    if ((rc = cv.run())) return rc;
+    std::fill(f.begin(), f.end(), 0);
+    for (int i = 0; i < count; ++i) {
+      const int gi = group ? group[i] : i;
+      if (!gs[(size_t)gi].active) continue;
+      const unsigned long long *s = cv.sums(i);
+      for (int j = 0; j < FGMM_RDCURVE_MAX; ++j) f[(size_t)gi * FGMM_RDCURVE_MAX + j] += rate_stream_bytes(s[1 + j]);
+    }
+    for (int gi = 0; gi < n_groups; ++gi) {
+      Search &g = gs[(size_t)gi];
+      if (!g.active) continue;
+      const uint64_t *fg = &f[(size_t)gi * FGMM_RDCURVE_MAX];
+      g.passes++;
+      int k = 0;
+      while (k < FGMM_RDCURVE_MAX && fg[k] > budget[gi]) ++k; // the first feasible point of the grid
+      if (round == 0) {
+        if (k == FGMM_RDCURVE_MAX) { // no lambda up to lambda_max fits
+          g.hi = lambda_max, g.f_hi = fg[FGMM_RDCURVE_MAX - 1], g.status = FGMM_BUDGET_UNMET, g.active = false;
+          continue;
+        }
+        g.hi = g.grid[k], g.f_hi = fg[k];
+        if (k == 0) { // round(y) already fits
+          g.active = false;
+          continue;
+        }
+        g.lo = g.grid[k - 1];
+      } else {
+        if (fg[FGMM_RDCURVE_MAX - 1] > budget[gi]) { // hi, evaluated again, no longer fits: lo and hi stay
+          g.active = false;
+          continue;
+        }
+        if (k > 0) g.lo = g.grid[k - 1];
+        g.hi = g.grid[k], g.f_hi = fg[k];
+      }
+      if (round == refine || g.lo == g.hi) {
+        g.active = false;
+        continue;
+      }
+      for (int q = 1; q < FGMM_RDCURVE_MAX; ++q) g.grid[q - 1] = g.lo + (g.hi - g.lo) * (double)q / 16.0;
+      g.grid[FGMM_RDCURVE_MAX - 1] = g.hi;
+    }
+  }
+  // 3c at the lambdas found: the RDOQ call's own path, its second census included (the workspace of the passes is no longer needed)
+  std::vector<double> lam((size_t)count);
+  for (int i = 0; i < count; ++i) lam[(size_t)i] = gs[(size_t)(group ? group[i] : i)].hi;
+  if ((rc = rdoq_run(ctx, stream, items, count, mode, clamp, lam.data(), 1))) return rc;
+  for (int gi = 0; gi < n_groups; ++gi) {
+    const Search &g = gs[(size_t)gi];
+    results[gi].lambda = g.hi;
+    results[gi].bytes_pred = g.f_hi;
+    results[gi].passes = g.passes;
+    results[gi].status = g.status;
+  }
+  return FGMM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int fgmm_gmc_rdcurve_batch(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales, const double *lambdas,
+                           int n_lambda) {
+  if (n_lambda < 1 || n_lambda > FGMM_RDCURVE_MAX || !lambdas)
+    return fail(FGMM_ERR_INVALID, "n_lambda = %d: must lie in 1 .. %d", n_lambda, FGMM_RDCURVE_MAX);
+  for (int j = 0; j < n_lambda; ++j)
+    if (!lambda_ok(lambdas[j])) return fail(FGMM_ERR_INVALID, "lambda[%d] = %g: must be finite and >= 0", j, lambdas[j]);
+  if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
+  for (int i = 0; i < count; ++i) {
+    const fgmm_rdcurve_item &s = items[i];
+    if (int rc = check_latent_item(i, s.K, s.M, s.hw, s.y, s.params, items[0].params.dtype)) return rc;
+  }
+  if (count == 0) return FGMM_OK;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
+  const int rc = curve_batch(ctx, (dev::Stream)stream, items, count, mode, clamp_scales, lambdas, n_lambda);
+  if (rc != FGMM_OK) {
+    (void)dev::stream_sync((dev::Stream)stream); // (nothing of this call may still be writing the workspace the next one reuses)
+    for (int i = 0; i < count; ++i) items[i].status = rc;
+  }
+  return rc;
+}
+
+int fgmm_gmc_rdoq_budget_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, const int32_t *group,
+                               int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine, fgmm_budget_result *results) {
+  if (!(lambda_max > 0.0 && lambda_max < (double)INFINITY)) return fail(FGMM_ERR_INVALID, "lambda_max = %g: must be finite and > 0", lambda_max);
+  if (refine < 0 || refine > 8) return fail(FGMM_ERR_INVALID, "refine = %d: must lie in 0 .. 8", refine);
+  if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2 || n_groups < 0 || (n_groups && (!budget_bytes || !results)))
+    return fail(FGMM_ERR_INVALID, "bad argument");
+  if (!group && n_groups != count) return fail(FGMM_ERR_INVALID, "n_groups = %d: without group ids every item is its own group (%d)", n_groups, count);
+  if (group) {
+    std::vector<char> seen((size_t)n_groups, 0);
+    for (int i = 0; i < count; ++i) {
+      if (group[i] < 0 || group[i] >= n_groups) return fail(FGMM_ERR_INVALID, "item %d: group %d outside 0 .. %d", i, group[i], n_groups - 1);
+      seen[(size_t)group[i]] = 1;
+    }
+    for (int gi = 0; gi < n_groups; ++gi)
+      if (!seen[(size_t)gi]) return fail(FGMM_ERR_INVALID, "group %d is empty", gi);
+  }
+  if (int rc = rdoq_check_items(items, count)) return rc;
+  if (count == 0) return FGMM_OK;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
+  const int rc = budget_batch(ctx, (dev::Stream)stream, items, count, mode, clamp_scales, group, n_groups, budget_bytes, lambda_max, refine, results);
+  if (rc != FGMM_OK) {
+    (void)dev::stream_sync((dev::Stream)stream);
+    for (int i = 0; i < count; ++i) items[i].status = rc;
+  }
+  return rc;
+}
+
+} // extern "C"

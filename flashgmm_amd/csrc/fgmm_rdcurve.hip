@@ -1,0 +1,124 @@
+// fgmm_rdcurve.hip — a stretch of the rate-distortion curve of a latent in one pass (include/flashgmm_amd.h section 3d), for CDNA4 / gfx950
+// (MI355X).
+//
+//   rdcurve_kernel  (y, sigma, mu, pi, up to 16 lambdas) -> per channel and lambda what rdoq_kernel would sum at that lambda: the cost of
+//                   the chosen symbols, the latents moved, the distortion the moves add.  Nothing is written per latent
+//   rdcurve_fold_kernel  the channels' sums -> the item's
+//
+// The fourth kernel on the encode frame (fgmm_encframe.h).  Placement, loads and pricing are rdoq_kernel's (enc_place, enc_load_y,
+// EncPlanes, rdoq_price): 52 B in per latent, 0 out.  Once a latent is priced the lane keeps of it y, round(y) and three costs - five
+// registers - and the twelve plane registers are dead; the decision at one more lambda (rdoq_choose, the text rdoq_kernel runs) is a
+// few binary64 operations on those five and no memory traffic.  The lambdas are the item's (RdCurveDesc, read by scalar loads once per
+// wave and lambda: a budget search gives every group of items its own grid in one launch).
+//   Registers: sixteen sets of per-lane 64-bit sums do not fit beside the pricing (rdoq_kernel holds 106-112 VGPRs at VEC = 4 under
+// the same 4-waves-per-SIMD bound).  Each lambda is therefore reduced across the wave as it is evaluated (wave_sum64, the moves by
+// ballots) and the wave's three results are kept by ONE lane, lane j for lambda j: three accumulators per lane in all.  After the
+// loop lanes 0 .. n - 1 add their results into the channel's row with one 64-bit atomic each (integers: the same bits on every run).
+#include <hip/hip_runtime.h>
+
+#include "fgmm_encframe.h"
+
+namespace fgmm {
+
+#ifndef FGMM_RDCURVE_WAVES
+#define FGMM_RDCURVE_WAVES 4 // min waves per SIMD, as rdoq_kernel: the pricing is the same
+#endif
+template <int MODE, int VEC, bool CLAMPED, typename PT, bool LINEAR>
+__global__ __launch_bounds__(kBlock, FGMM_RDCURVE_WAVES) void rdcurve_kernel(const EncDesc *__restrict__ descs, const RdCurveDesc *__restrict__ cdescs,
+                                                                             const uint32_t *__restrict__ L) {
+  const RdCurveDesc &r = cdescs[blockIdx.z];
+  const int n = r.n_lambda; // (0: the item takes no part in this pass)
+  if (n <= 0) return;
+  const EncDesc &d = descs[blockIdx.z];
+  const int64_t hw = d.hw;
+  int rank;
+  int64_t p0;
+  bool active;
+  if (!enc_place<VEC, LINEAR>(hw, d.chan_list[d.M], rank, p0, active)) return;
+  const int c = d.chan_list[rank];
+  // the lane's priced latents.  A lane past the end of its channel holds latents that cost nothing and never move
+  float y[VEC], vq[VEC];
+  uint32_t cm[VEC], c0[VEC], cp[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) y[e] = vq[e] = 0.0f, cm[e] = c0[e] = cp[e] = 0u;
+  unsigned long long before = 0;
+  if (active) {
+    enc_load_y<VEC>(d, c, p0, y);
+    EncPlanes<PT, VEC> P;
+    P.load(d, c, p0);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float mu[4], sg[4], pi[4];
+      P.get(e, d.logits, mu, sg, pi);
+      if (!rdoq_price<MODE, CLAMPED>(y[e], mu, sg, pi, L, vq[e], cm[e], c0[e], cp[e])) y[e] = vq[e] = 0.0f; // keeps round(y) at every lambda: three
+      before += c0[e];                                                                                      // equal costs at distance 0, 1, 1
+      if constexpr (VEC == 1) break; // (one position: no loop, see EncPlanes<PT, 1>)
+    }
+  }
+  before = wave_sum64(before);
+  if (!before) return; // (every symbol costs something: 0 = a wave wholly past the end of its channel; wave-uniform)
+  const int lane = threadIdx.x & 63;
+  unsigned long long r_after = 0, r_dd = 0, r_changed = 0; // lane j: the wave's sums at lambda j
+  for (int j = 0; j < n; ++j) {
+    const double lam_q = r.lam_q[j]; // wave-uniform: a scalar load
+    unsigned long long after = 0, dd = 0;
+    int changed = 0; // the wave's, the same on every lane (ballots)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      double d0, dv;
+      const int pick = rdoq_choose(y[e], vq[e], cm[e], c0[e], cp[e], lam_q, d0, dv);
+      after += pick < 0 ? cm[e] : pick > 0 ? cp[e] : c0[e];
+      changed += __popcll(__ballot(pick != 0));
+      if (pick) { // what the move adds to the squared error, in units of 2^-32, rounded half to even: an integer, so the sum has no order
+        const double inc = dv * dv - d0 * d0;
+        dd += (unsigned long long)(long long)__builtin_rint(inc * 0x1p32);
+      }
+      if constexpr (VEC == 1) break;
+    }
+    after = wave_sum64(after);
+    if (changed) dd = wave_sum64(dd); // (wave-uniform)
+    if (lane == j) r_after = after, r_dd = dd, r_changed = (unsigned long long)changed;
+  }
+  unsigned long long *row = r.chan_acc + (int64_t)c * kRdCurveRow;
+  if (lane == 0) add64(row, before);
+  if (lane < n) {
+    add64(row + 1 + lane, r_after);
+    if (r_changed) {
+      add64(row + 1 + FGMM_RDCURVE_MAX + lane, r_changed);
+      add64(row + 1 + 2 * FGMM_RDCURVE_MAX + lane, r_dd);
+    }
+  }
+}
+
+// the item's sums from its channels': block = (item), thread t of slice s adds the channels s, s + 4 ... of column t
+__global__ __launch_bounds__(kBlock) void rdcurve_fold_kernel(const EncDesc *__restrict__ descs, const RdCurveDesc *__restrict__ cdescs) {
+  const RdCurveDesc &r = cdescs[blockIdx.x];
+  if (r.n_lambda <= 0) return;
+  const int M = descs[blockIdx.x].M;
+  const int t = threadIdx.x & 63, s = threadIdx.x >> 6;
+  if (t >= kRdCurveRow) return;
+  unsigned long long v = 0;
+  for (int c = s; c < M; c += kBlock / 64) v += r.chan_acc[(int64_t)c * kRdCurveRow + t];
+  if (v) add64(r.sums + t, v);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------------------------
+struct RdCurveLaunch {
+  const EncDesc *d;
+  const RdCurveDesc *r;
+  const uint32_t *L;
+  template <int MODE, int VEC, bool CLAMPED, typename PT, bool LINEAR> void go(dim3 grid, hipStream_t s) const {
+    hipLaunchKernelGGL((rdcurve_kernel<MODE, VEC, CLAMPED, PT, LINEAR>), grid, dim3(kBlock), 0, s, d, r, L);
+  }
+};
+int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, int count, int M_max, int64_t hw_max, int64_t n_max,
+                   bool linear, int mode, int vec, bool clamped, bool f16, void *stream) {
+  if (count <= 0 || M_max <= 0 || hw_max <= 0) return 0;
+  if (const int e = enc_launch<false>(RdCurveLaunch{d_descs, d_cdescs, d_log2}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream)) return e;
+  hipLaunchKernelGGL(rdcurve_fold_kernel, dim3((unsigned)count), dim3(kBlock), 0, (hipStream_t)stream, d_descs, d_cdescs);
+  return (int)hipGetLastError();
+}
+
+} // namespace fgmm

@@ -14,7 +14,11 @@ struct RdoqOff { // workspace offsets of one item: the census of y, the census o
   size_t o_before, o_after, o_changed;
 };
 
-int rdoq_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, double lambda) {
+} // namespace
+
+// lambdas[i * lambda_stride] is item i's lambda (stride 0: one for the call, fgmm_gmc_rdoq_batch; 1: the budget call of section 3d, whose
+// groups end at lambdas of their own): consecutive items of one lambda share a launch of rdoq_kernel, everything else is once per call
+int fgmm::rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride) {
   int rc;
   if ((rc = ensure_rate_table(ctx))) return rc;
   // ---- workspace: [EncDesc x count (y)][EncDesc x count (y_rdo)][RdoqDesc x count][small: per item the arrays of RdoqOff] ----------
@@ -71,7 +75,11 @@ int rdoq_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int cou
   const EncDesc *dd2 = reinterpret_cast<const EncDesc *>(ctx->d_ws + o_descs2);
   const RdoqDesc *dq = reinterpret_cast<const RdoqDesc *>(ctx->d_ws + o_qdescs);
   LAUNCH_TRY(launch_quant_stats(dd, count, M_max, stream));
-  LAUNCH_TRY(launch_rdoq(dd, dq, ctx->d_rate_log2, lambda * 0x1p-24, count, M_max, hw_max, n_max, linear, mode, vec, clamp != 0, f16, stream));
+  for (int i0 = 0, i1; i0 < count; i0 = i1) {
+    const double lambda = lambdas[(size_t)i0 * lambda_stride];
+    for (i1 = i0 + 1; i1 < count && lambdas[(size_t)i1 * lambda_stride] == lambda;) ++i1;
+    LAUNCH_TRY(launch_rdoq(dd + i0, dq + i0, ctx->d_rate_log2, lambda * 0x1p-24, i1 - i0, M_max, hw_max, n_max, linear, mode, vec, clamp != 0, f16, stream));
+  }
   LAUNCH_TRY(launch_quant_stats(dd2, count, M_max, stream));
   if (small_bytes) DEV_TRY(dev::copy_async(ctx->h_ws + o_small, ctx->d_ws + o_small, small_bytes, dev::kD2H, stream));
   DEV_TRY(dev::event_record(ctx->events[0], stream));
@@ -99,13 +107,7 @@ int rdoq_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int cou
   return FGMM_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda) {
-  if (!(lambda >= 0.0 && lambda < (double)INFINITY)) return fail(FGMM_ERR_INVALID, "lambda = %g: must be finite and >= 0", lambda);
-  if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
+int fgmm::rdoq_check_items(const fgmm_rdoq_item *items, int count) {
   for (int i = 0; i < count; ++i) {
     const fgmm_rdoq_item &s = items[i];
     if (int rc = check_latent_item(i, s.K, s.M, s.hw, s.y, s.params, items[0].params.dtype)) return rc;
@@ -114,11 +116,20 @@ int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int 
     const uintptr_t nb = sizeof(float) * (uintptr_t)s.M * (uintptr_t)s.hw; // (y_rdo is zeroed before the census reads y)
     if (nb && y0 < r0 + nb && r0 < y0 + nb) return fail(FGMM_ERR_INVALID, "item %d: y_rdo may not overlap y", i);
   }
+  return FGMM_OK;
+}
+
+extern "C" {
+
+int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda) {
+  if (!(lambda >= 0.0 && lambda < (double)INFINITY)) return fail(FGMM_ERR_INVALID, "lambda = %g: must be finite and >= 0", lambda);
+  if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
+  if (int rc = rdoq_check_items(items, count)) return rc;
   if (count == 0) return FGMM_OK;
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
-  const int rc = rdoq_batch(ctx, (dev::Stream)stream, items, count, mode, clamp_scales, lambda);
+  const int rc = rdoq_run(ctx, (dev::Stream)stream, items, count, mode, clamp_scales, &lambda, 0);
   if (rc != FGMM_OK) {
     (void)dev::stream_sync((dev::Stream)stream); // (nothing of this call may still be writing the workspace the next one reuses)
     for (int i = 0; i < count; ++i) items[i].status = rc;

@@ -21,44 +21,22 @@
 
 namespace fgmm {
 
-constexpr float kRdoqMaxAbs = 0x1p20f;
-
-// one latent of a coded channel -> the chosen symbol as a float (+0.0 for zero); cb / ca: cost of round(y) / of the choice
+// one latent of a coded channel -> the chosen symbol as a float (+0.0 for zero); cb / ca: cost of round(y) / of the choice.  The pricing and
+// the choice are the frame's (fgmm_encframe.h: rdoq_price, rdoq_choose), shared with rdcurve_kernel
 template <int MODE, bool CLAMPED>
 __device__ __forceinline__ float rdoq_one(float y, const float (&mu)[4], const float (&sg)[4], const float (&pi)[4], double lam_q,
                                           const uint32_t *__restrict__ L, uint32_t &cb, uint32_t &ca) {
-  const float vq = __builtin_rintf(y);
-  const int vi = (int)vq;
-  if (__builtin_expect(!(__builtin_fabsf(y) < INFINITY && __builtin_fabsf(vq) <= kRdoqMaxAbs), 0)) { // (false for NaN too)
-    int bp;
-    const uint32_t ent = sym_entry<MODE, CLAMPED>(vq, vi, mu, sg, pi, bp); // exactly rate_kernel's pricing
-    cb = ca = entry_cost(ent, vq, vi, true, L);
+  float vq;
+  uint32_t cm, c0, cp;
+  if (!rdoq_price<MODE, CLAMPED>(y, mu, sg, pi, L, vq, cm, c0, cp)) {
+    cb = ca = c0;
     return vq + 0.0f;
   }
-  uint32_t q[4];
-  sym_edges4<MODE, CLAMPED>(vq, mu, sg, pi, q);
-  int bp;
-  const uint32_t cm = rate_cost_q(entry_from_edges(q[0], q[1], vi - 1, bp), vi - 1, L);
-  const uint32_t c0 = rate_cost_q(entry_from_edges(q[1], q[2], vi, bp), vi, L);
-  const uint32_t cp = rate_cost_q(entry_from_edges(q[2], q[3], vi + 1, bp), vi + 1, L);
-  const float vm = vq - 1.0f, vp = vq + 1.0f;
-  const double yd = (double)y;
-  const double d0 = yd - (double)vq, dm = yd - (double)vm, dp = yd - (double)vp;
-  const double j0 = d0 * d0 + lam_q * (double)c0;
-  const double jm = dm * dm + lam_q * (double)cm;
-  const double jp = dp * dp + lam_q * (double)cp;
-  float v = vq;
-  double jb = j0;
-  cb = ca = c0;
-  if (jm < jb) {
-    v = vm;
-    jb = jm;
-    ca = cm;
-  }
-  if (jp < jb) {
-    v = vp;
-    ca = cp;
-  }
+  double d0, d;
+  const int pick = rdoq_choose(y, vq, cm, c0, cp, lam_q, d0, d);
+  cb = c0;
+  ca = pick < 0 ? cm : pick > 0 ? cp : c0;
+  const float v = pick < 0 ? vq - 1.0f : pick > 0 ? vq + 1.0f : vq;
   return v + 0.0f; // (-0.0 -> +0.0)
 }
 

@@ -27,7 +27,7 @@ from torch import Tensor
 
 from . import _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "BudgetQuantized", "RdCurve"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -170,6 +170,69 @@ class RdoQuantized:
 
     def __repr__(self) -> str:
         return f"RdoQuantized(n_changed={self.n_changed}, bits_before={self.bits_before:.3f}, bits_after={self.bits_after:.3f}, abs_max={self.abs_max})"
+
+
+# what a budget search adds to an RdoQuantized: None on the result of quantize_rdo (the slots of RdoQuantized itself stay what they are)
+RdoQuantized.lam = RdoQuantized.bytes_pred = RdoQuantized.budget_met = RdoQuantized.passes = None
+
+
+class BudgetQuantized(RdoQuantized):
+    """The ``RdoQuantized`` of a latent quantised to a byte budget (``GaussianMixtureConditional.quantize_to_budget`` /
+    ``quantize_to_budget_batch``; include/flashgmm_amd.h section 3d), with what the search found for the latent's GROUP:
+
+    ``lam``          the lambda found - every other field is ``quantize_rdo``'s at this lambda, bit for bit
+    ``bytes_pred``   predicted bytes of the group's bitstreams at ``lam`` (the sum over its items)
+    ``budget_met``   False: no lambda up to ``lambda_max`` meets the budget; the result is the one at ``lambda_max``
+    ``passes``       passes of the curve kernel the group took part in
+
+    The budget is on predicted bytes: a real stream may be 4 bytes longer where ``RateEstimate.nbytes`` may be; a channel the
+    quantisation empties is no longer coded at all, so on that account the real size can only be smaller."""
+
+    __slots__ = ("lam", "bytes_pred", "budget_met", "passes")
+
+    def __init__(self, y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after=None, lam=None, bytes_pred=None,
+                 budget_met=None, passes=None):
+        super().__init__(y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after)
+        self.lam, self.bytes_pred, self.budget_met, self.passes = lam, bytes_pred, budget_met, passes
+
+    def __repr__(self) -> str:
+        return (f"BudgetQuantized(lam={self.lam!r}, bytes_pred={self.bytes_pred}, budget_met={self.budget_met}, passes={self.passes}, "
+                f"n_changed={self.n_changed}, bits_after={self.bits_after:.3f})")
+
+
+class RdCurve:
+    """A stretch of the rate-distortion curve of one latent (``GaussianMixtureConditional.rd_curve`` / ``rd_curve_batch``;
+    include/flashgmm_amd.h section 3d): what ``quantize_rdo`` would report at each of ``lambdas``, from one pass per 16 of them.
+
+    ``lambdas``        the lambdas, as given (any order, repeats allowed)
+    ``bits_q_before``  exact cost of ``round(y)``, units of 2^-24 bit
+    ``bits_q_after``   per lambda: exact cost of the chosen symbols;  ``bits_after`` in bits, ``nbytes`` the predicted stream length
+    ``n_changed``      per lambda: latents whose symbol is not ``round(y)``
+    ``ddist_q``        per lambda: squared error the moves add over ``round(y)``, units of 2^-32;  ``distortion_added`` as floats
+    ``n_symbols``      symbols coded (coded channels x h x w)"""
+
+    __slots__ = ("lambdas", "bits_q_before", "bits_q_after", "n_changed", "ddist_q", "n_symbols")
+
+    def __init__(self, lambdas, bits_q_before, bits_q_after, n_changed, ddist_q, n_symbols=0):
+        self.lambdas, self.bits_q_before = tuple(float(v) for v in lambdas), int(bits_q_before)
+        self.bits_q_after, self.n_changed, self.ddist_q = tuple(map(int, bits_q_after)), tuple(map(int, n_changed)), tuple(map(int, ddist_q))
+        self.n_symbols = int(n_symbols)
+
+    @property
+    def bits_after(self):
+        return tuple(b / float(1 << _lib.FGMM_RATE_Q) for b in self.bits_q_after)
+
+    @property
+    def nbytes(self):
+        f = _lib.lib().fgmm_rate_stream_bytes
+        return tuple(int(f(b)) for b in self.bits_q_after)
+
+    @property
+    def distortion_added(self):
+        return tuple(d / float(1 << 32) for d in self.ddist_q)
+
+    def __repr__(self) -> str:
+        return f"RdCurve(lambdas={self.lambdas}, nbytes={self.nbytes}, n_changed={self.n_changed})"
 
 
 def _take_ckpts_many(device: int, ptrs, counts):
@@ -782,6 +845,133 @@ class GaussianMixtureConditional(nn.Module):
                      per_channel: bool = False) -> RdoQuantized:
         """-> the ``RdoQuantized`` of one latent (``quantize_rdo_batch``)"""
         return self.quantize_rdo_batch([y], [scales], [means], [weights], lam, weights_are_logits=weights_are_logits, per_channel=per_channel)[0]
+
+    def _latent_items(self, struct, ys, scales, means, weights, flags: int):
+        """the items of a call that takes latents (sequences, or stacked tensors taken apart) as a ctypes array of ``struct`` with the
+        input fields set -> (array, N, keep, device, shapes)"""
+        if isinstance(ys, Tensor):
+            if ys.dim() != 4 or scales.dim() != 4 or not (ys.shape[0] == scales.shape[0] == means.shape[0] == weights.shape[0]):
+                raise RuntimeError("stacked inputs must be [N, M, h, w] / [N, K*M, h, w] tensors of one N")
+            ys, scales, means, weights = ([t[i:i + 1] for i in range(t.shape[0])] for t in (ys, scales, means, weights))
+        N = len(ys)
+        arr = (struct * N)()
+        keep, shapes, dev = [], [], None
+        for i in range(N):
+            yp, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
+            dev = dev or d
+            if d != dev:
+                raise RuntimeError("all items of a batch must be on one device")
+            it = arr[i]
+            it.y = yp
+            it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
+            it.M, it.K, it.hw = M, self.K, hw
+            shapes.append((1, M) + tuple(ys[i].shape[2:]))
+        return arr, N, keep, dev, shapes
+
+    def rd_curve_batch(self, ys, scales, means, weights, lambdas, *, weights_are_logits: bool = False) -> List[RdCurve]:
+        """What ``quantize_rdo_batch`` would report at every lambda of ``lambdas`` - the cost after, the latents moved, the distortion
+        added - WITHOUT quantising: one kernel prices each latent once and decides it at up to 16 lambdas (include/flashgmm_amd.h
+        section 3d); more are served in chunks of 16.  Inputs as ``quantize_rdo_batch`` takes them; ``lambdas`` finite, >= 0, in any
+        order.  -> one ``RdCurve`` per item."""
+        if self.K != _lib.FGMM_K:
+            raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
+        lambdas = [float(v) for v in lambdas]
+        if not lambdas or not all(0.0 <= v < float("inf") for v in lambdas):
+            raise ValueError(f"lambdas = {lambdas!r}: at least one, each finite and >= 0")
+        arr, N, keep, dev, _ = self._latent_items(_lib.fgmm_rdcurve_item, ys, scales, means, weights, _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0)
+        if N == 0:
+            return []
+        di = dev.index if dev.index is not None else -1
+        nat = _lib.native()
+        cols = [([], [], []) for _ in range(N)]
+        for at in range(0, len(lambdas), _lib.FGMM_RDCURVE_MAX):
+            chunk = lambdas[at:at + _lib.FGMM_RDCURVE_MAX]
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if nat is not None:
+                nat.rdcurve_items(_lib.ctx_addr(di), stream, C.addressof(arr), N, self._mode(), int(self.clamp_scales), chunk)
+            else:
+                rc = _lib.lib().fgmm_gmc_rdcurve_batch(_lib.ctx(di), stream, arr, N, self._mode(), int(self.clamp_scales),
+                                                       (C.c_double * len(chunk))(*chunk), len(chunk))
+                _lib.check(rc, "GaussianMixtureConditional.rd_curve")
+            for it, col in zip(arr, cols):
+                for dst, src in zip(col, (it.bits_q_after, it.n_changed, it.ddist_q)):
+                    dst += src[:len(chunk)]
+        return [RdCurve(lambdas, it.bits_q_before, *col, it.n_symbols) for it, col in zip(arr, cols)]
+
+    def rd_curve(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lambdas, *, weights_are_logits: bool = False) -> RdCurve:
+        """-> the ``RdCurve`` of one latent (``rd_curve_batch``)"""
+        return self.rd_curve_batch([y], [scales], [means], [weights], lambdas, weights_are_logits=weights_are_logits)[0]
+
+    def quantize_to_budget_batch(self, ys, scales, means, weights, budget_bytes, *, groups=None, lambda_max: float = 16.0, refine: int = 2,
+                                 weights_are_logits: bool = False, per_channel: bool = False) -> List[BudgetQuantized]:
+        """Rate-distortion optimised quantisation TO A BYTE BUDGET: lambda is searched on the rate-distortion curve by the fixed rule of
+        include/flashgmm_amd.h section 3d - a 16-point grid 0, lambda_max * 2^-14 .. lambda_max, then ``refine`` (0..8) rounds of 16
+        points between the last infeasible and the first feasible one, each round one pass of the curve kernel - then ``quantize_rdo_batch``'s
+        result at the lambda found.  ``groups``: one group id per item, 0 .. n_groups - 1 - the items of a group share one lambda and
+        one budget on the sum of their bytes (None: every item its own group).  ``budget_bytes``: an int for all groups, or one per
+        group.  -> one ``BudgetQuantized`` per item (an ``RdoQuantized`` that carries ``lam``, ``bytes_pred``, ``budget_met``, ``passes``
+        of its group).  The budget is on PREDICTED bytes: a real stream may be 4 bytes longer where ``estimate_bits`` may be off;
+        a channel the quantisation empties is no longer coded, so on that account the real size can only be smaller."""
+        if self.K != _lib.FGMM_K:
+            raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
+        lambda_max, refine = float(lambda_max), int(refine)
+        if not (0.0 < lambda_max < float("inf")):
+            raise ValueError(f"lambda_max = {lambda_max!r}: must be finite and > 0")
+        if not 0 <= refine <= 8:
+            raise ValueError(f"refine = {refine!r}: must lie in 0 .. 8")
+        arr, N, keep, dev, shapes = self._latent_items(_lib.fgmm_rdoq_item, ys, scales, means, weights, _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0)
+        if groups is not None:
+            groups = [int(g) for g in groups]
+            if len(groups) != N:
+                raise ValueError(f"groups: one id per item ({N}), got {len(groups)}")
+            n_groups = max(groups, default=-1) + 1
+            if min(groups, default=0) < 0 or set(groups) != set(range(n_groups)):
+                raise ValueError("groups: ids must be 0 .. n_groups - 1 with no group empty")
+        else:
+            n_groups = N
+        if isinstance(budget_bytes, (list, tuple)):
+            budgets = [int(b) for b in budget_bytes]
+            if len(budgets) != n_groups:
+                raise ValueError(f"budget_bytes: one per group ({n_groups}), got {len(budgets)}")
+        else:
+            budgets = [int(budget_bytes)] * n_groups
+        if any(b < 0 for b in budgets):
+            raise ValueError("budget_bytes must be >= 0")
+        if N == 0:
+            return []
+        outs, bitmaps, chans = [], [], []
+        for it, shape in zip(arr, shapes):
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+            zb = torch.empty(shape[1], dtype=torch.int64)
+            cb = torch.empty(shape[1], dtype=torch.int64) if per_channel else None
+            it.y_rdo, it.zero_bitmap = out.data_ptr(), zb.data_ptr()
+            if cb is not None:
+                it.chan_bits_q_after = cb.data_ptr()
+            outs.append(out), bitmaps.append(zb), chans.append(cb)
+        di = dev.index if dev.index is not None else -1
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat = _lib.native()
+        if nat is not None:
+            res = nat.rdoq_budget_items(_lib.ctx_addr(di), stream, C.addressof(arr), N, self._mode(), int(self.clamp_scales), groups, budgets, lambda_max, refine)
+        else:
+            out_res = (_lib.fgmm_budget_result * n_groups)()
+            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch(_lib.ctx(di), stream, arr, N, self._mode(), int(self.clamp_scales),
+                                                       (C.c_int32 * N)(*groups) if groups is not None else None, n_groups,
+                                                       (C.c_uint64 * n_groups)(*budgets), lambda_max, refine, out_res)
+            _lib.check(rc, "GaussianMixtureConditional.quantize_to_budget")
+            res = [(r.lambda_, r.bytes_pred, r.passes, r.status) for r in out_res]
+        got = []
+        for i, it in enumerate(arr):
+            lam, nbytes, passes, status = res[groups[i] if groups is not None else i]
+            got.append(BudgetQuantized(outs[i], it.n_changed, it.bits_q_before, it.bits_q_after, it.abs_max, bitmaps[i], chans[i], float(lam), int(nbytes),
+                                       status != _lib.FGMM_BUDGET_UNMET, int(passes)))
+        return got
+
+    def quantize_to_budget(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, budget_bytes: int, *, lambda_max: float = 16.0,
+                           refine: int = 2, weights_are_logits: bool = False, per_channel: bool = False) -> BudgetQuantized:
+        """-> the ``BudgetQuantized`` of one latent (``quantize_to_budget_batch``)"""
+        return self.quantize_to_budget_batch([y], [scales], [means], [weights], budget_bytes, lambda_max=lambda_max, refine=refine,
+                                             weights_are_logits=weights_are_logits, per_channel=per_channel)[0]
 
     def compress(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, weights_are_logits: bool = False):
         """-> ((bytes, abs_max, zero_bitmap), y_quantized)     (entropy_models.py:833-867)"""

@@ -44,16 +44,32 @@ def _check_rdo_lambda(lam) -> float:
     return lam
 
 
+def _check_target_bytes(n) -> Optional[int]:
+    if n is None:
+        return None
+    if int(n) != n or int(n) < 0:
+        raise ValueError(f"target_bytes = {n!r}: must be an integer >= 0")
+    return int(n)
+
+
 class GaussianMixtureConditionalLatentCodec(nn.Module):
     def __init__(self, K: int = 4, gaussian_mixture_conditional: Optional[GaussianMixtureConditional] = None,
                  entropy_parameters: Optional[nn.Module] = None, quantizer: str = "noise",
                  chunks: Tuple[str, ...] = ("scales", "means", "weights"), mode=None, param_dtype: torch.dtype = torch.float32,
-                 fuse_softmax: bool = False, checkpoint_stride: int = 0, rdo_lambda: float = 0.0, **kwargs: Any):
+                 fuse_softmax: bool = False, checkpoint_stride: int = 0, rdo_lambda: float = 0.0, target_bytes: Optional[int] = None,
+                 **kwargs: Any):
         super().__init__()
         # rdo_lambda > 0: rate-distortion optimised quantisation (GaussianMixtureConditional.quantize_rdo) - what is coded is, per latent,
         # round(.) or one of its two neighbours, whichever minimises (y - v)^2 + rdo_lambda * bits(v).  An encoder-side choice: the
         # decoder needs no switch.  0: plain rounding, no extra launch
         self.rdo_lambda = _check_rdo_lambda(rdo_lambda)
+        # target_bytes: quantisation to a byte budget (GaussianMixtureConditional.quantize_to_budget) - the lambda of the above is
+        # searched so that the PREDICTED length of the bitstream is at most this many bytes (a real stream may be 4 bytes longer, see
+        # RateEstimate.nbytes; if no lambda up to the search's lambda_max fits, the result at lambda_max is coded).  Either a lambda or
+        # a budget, not both
+        self.target_bytes = _check_target_bytes(target_bytes)
+        if self.target_bytes is not None and self.rdo_lambda > 0:
+            raise ValueError("target_bytes together with rdo_lambda > 0: give either the lambda or the budget that determines it")
         if param_dtype not in (torch.float32, torch.float16):
             raise ValueError("param_dtype must be torch.float32 or torch.float16")
         self.param_dtype = param_dtype  # float16: BASELINE configs[4], "fp16 (mu, sigma, pi) with fp32 CDF accumulate"
@@ -121,8 +137,26 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
     def coder_inputs(self, y: Tensor, ctx_params: Tensor):
         """What ``compress`` hands the entropy model: ``(y_to_code, scales, means, weights)``.  ``round(y_to_code)`` is
         the ``y_hat`` that ``compress`` returns (:127-149) — known before any coding happens.  With the codec's ``rdo_lambda`` > 0
-        ``y_to_code`` is the RDOQ result of what would be rounded."""
+        ``y_to_code`` is the RDOQ result of what would be rounded; with its ``target_bytes`` set, the RDOQ result at the lambda that
+        budget determines."""
+        if self.target_bytes is not None:
+            return self.coder_inputs_budget(y, ctx_params, self.target_bytes)
         return self.coder_inputs_rdo(y, ctx_params, self.rdo_lambda)
+
+    def coder_inputs_budget(self, y: Tensor, ctx_params: Tensor, budget_bytes: int):
+        """``coder_inputs`` with what would be rounded quantised to ``budget_bytes`` of predicted bitstream
+        (``GaussianMixtureConditional.quantize_to_budget``, its default search)"""
+        budget = _check_target_bytes(budget_bytes)
+        if budget is None:
+            raise ValueError("budget_bytes must be given")
+        scales_hat, means_hat, weights = self._params(ctx_params)
+        y_code = y
+        if self.quantizer != "noise":
+            weighted_sum, means_hat = self._recentre(means_hat, weights)
+            y_code = y - weighted_sum
+        planes = self._planes(scales_hat, means_hat, weights)
+        q = self.gaussian_mixture_conditional.quantize_to_budget(y_code, *planes, budget, weights_are_logits=self.fuse_softmax)
+        return (q.y, *planes)
 
     def coder_inputs_rdo(self, y: Tensor, ctx_params: Tensor, rdo_lambda: float):
         """``coder_inputs`` with a given ``rdo_lambda`` in place of the codec's own (0: plain rounding, no extra launch)"""
@@ -239,6 +273,9 @@ class CheckerboardLatentCodec(nn.Module):
         # non-anchors' context sees what the decoder will see (prepare); 0: the latent codec's own setting.  Precedence when both
         # this codec and its latent codec "y" carry an rdo_lambda: this one, if > 0, REPLACES the inner codec's for both halves (the two
         # are never combined); only when this one is 0 does the inner codec's own rdo_lambda apply
+        # (No byte budget here: the non-anchor half's parameters depend on the anchor half's y_hat, so ONE lambda for both halves that
+        # meets a budget on their sum needs the context network inside the search loop - a search over whole compress passes, not over
+        # the curve of section 3d.  A latent codec "y" built with target_bytes still budgets each half on its own.)
         self.rdo_lambda = _check_rdo_lambda(rdo_lambda)
         if fuse_head and self.rdo_lambda > 0:
             raise RuntimeError("rdo_lambda > 0 together with fuse_head is not supported: RDOQ needs the parameter planes the fused head never writes")

@@ -47,6 +47,8 @@ extern "C" {
                               (dlsym(handle, "fgmm_gmc_rdoq_batch")) */
 #define FGMM_HAS_ESTIMATE 1 /* section 3b: fgmm_gmc_estimate_batch, fgmm_symtab_bits[_hip], fgmm_rate_stream_bytes */
 #define FGMM_HAS_RDOQ 1     /* section 3c: fgmm_gmc_rdoq_batch */
+#define FGMM_HAS_RDCURVE 1  /* section 3d: fgmm_gmc_rdcurve_batch, fgmm_gmc_rdoq_budget_batch */
+#define FGMM_RDCURVE_MAX 16 /* lambdas per fgmm_gmc_rdcurve_batch call */
 
 typedef enum {
   FGMM_OK = 0,
@@ -55,7 +57,9 @@ typedef enum {
   FGMM_ERR_HIP = 3,         /* a HIP call failed; fgmm_last_error() has the text */
   FGMM_ERR_NOMEM = 4,
   FGMM_ERR_STREAM = 5,      /* bitstream shorter than the symbols it is asked to yield (corrupt input) */
-  FGMM_ERR_UNSUPPORTED = 6  /* outside the built envelope (e.g. max_bs_value > FGMM_MAX_BS) */
+  FGMM_ERR_UNSUPPORTED = 6, /* outside the built envelope (e.g. max_bs_value > FGMM_MAX_BS) */
+  FGMM_BUDGET_UNMET = 7     /* NOT an error, never a return value: fgmm_budget_result.status of a group whose byte budget no lambda up to
+                               lambda_max meets (section 3d) */
 } fgmm_status;
 
 /* Phi approximation, numbered as the reference CODE numbers APPROX_MODE (the README swaps 1 and 2). */
@@ -559,6 +563,76 @@ typedef struct {
   uint64_t bits_q_before, bits_q_after; /* out */
 } fgmm_rdoq_item;
 int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3d. The rate-distortion curve, and quantisation to a BYTE BUDGET: what turns 3c into rate control.  A caller with a byte target does
+ *    not know lambda; one kernel pass prices every latent once and evaluates 3c's decision at up to FGMM_RDCURVE_MAX lambdas, so a
+ *    stretch of the curve costs one pass over y and the planes instead of one fgmm_gmc_rdoq_batch call per lambda tried.
+ *
+ *    THE CURVE.  Everything about one latent is 3c's: rounding, the channels coded (those of y), the candidates and the
+ *    |v0| <= 2^20 / non-finite rule, the entries, cost_q, J(v) in binary64 with lam_q = lambda * 2^-24, the strict-less choice in
+ *    the order v0, v0 - 1, v0 + 1.  At lambda_j the curve is the sum, over the latents of the channels coded for y, of what 3c
+ *    decides at lambda_j.  Per item:
+ *      bits_q_before     uint64 sum of cost_q(v0), once
+ *      bits_q_after[j]   uint64 sum of cost_q of the choice - fgmm_gmc_rdoq_batch's bits_q_after at lambda_j
+ *      n_changed[j]      latents whose choice is not v0 - its n_changed
+ *      ddist_q[j]        the distortion the moves add over round(y), as an integer so that it has no order: a moved latent
+ *                        contributes llrint(inc * 2^32) (round half to even) with inc = d * d - d0 * d0, d and d0 the binary64
+ *                        distances of 3c to the choice and to v0: two binary64 multiplies and one subtract, no contraction.  Never
+ *                        negative (v0 is the nearest integer and the rounding of the squares is monotone).  An unmoved latent
+ *                        contributes 0.  The uint64 sum, in units of 2^-32 of a squared quantisation step
+ *      n_symbols         symbols coded for y (coded channels * hw)
+ *    At lambda_j = 0 the three are bits_q_before, 0 and 0.  Entries j >= n_lambda are left untouched.  n_lambda must lie in
+ *    1 .. FGMM_RDCURVE_MAX and every lambda_j be finite and >= 0 (else FGMM_ERR_INVALID); they may come in any order and repeat.
+ *    Items are validated as by the estimate call; an item with M * hw == 0 has zero sums.  All outputs HOST, integer, the same bits on
+ *    every run.
+ *
+ *    THE BUDGET SEARCH - fixed here, restated by tests/rdcurve_ref.py.  A GROUP is a set of items that share one lambda (group ==
+ *    NULL: every item its own group, n_groups == count).  f(lambda) = sum over the group's items of
+ *    fgmm_rate_stream_bytes(bits_q_after of the item at lambda) - an item with M * hw == 0 counts 8 bytes.  f is non-increasing in
+ *    exact arithmetic, but J is rounded, so the search does not rely on that at the last ulp: it takes the FIRST FEASIBLE POINT OF
+ *    EACH GRID, which needs no monotonicity.  Every host operation below is one binary64 operation.
+ *      round 0     the grid lambda_0 = 0, lambda_j = lambda_max * 2^(j - 15) for j = 1 .. 15 (the last point is lambda_max itself).
+ *                  j* = the first j with f(lambda_j) <= budget.  None: the result is lambda_max with status FGMM_BUDGET_UNMET
+ *                  (not an error: y_rdo at lambda_max is still returned).  j* = 0: the result is lambda = 0, round(y) already
+ *                  fits.  Otherwise lo = lambda_{j* - 1}, hi = lambda_{j*}
+ *      refinement  `refine` rounds (0 .. 8).  A round whose lo == hi does not run: the search stops.  Its grid is
+ *                  lo + (hi - lo) * (double)k / 16.0 for k = 1 .. 15 (subtract, multiply, divide, add), and hi itself as the 16th
+ *                  point, taken as given, not recomputed.  hi is thereby evaluated again: if it is no longer feasible, through
+ *                  any cause, lo and hi stay what they were and the search stops.  Otherwise the first feasible point k* becomes
+ *                  hi, and lo the point before it (the old lo for k* = 1)
+ *      result      lambda* = hi; then 3c at lambda* - every item of the group gets exactly fgmm_gmc_rdoq_batch's outputs at
+ *                  lambda* - with lambda*, bytes_pred = f(lambda*) and the number of curve passes the group took part in
+ *                  (1 + the refinement rounds run)
+ *    lambda_max must be finite and > 0, refine in 0 .. 8, group ids in 0 .. n_groups - 1 and no group empty (else FGMM_ERR_INVALID).
+ *    The front half (census, descriptors) is taken once per call; a pass launches only rdcurve_kernel over the items whose group
+ *    is still searching, every group on its own grid, and reads back a few KB of sums.
+ *    Caveats.  The budget is on bytes_pred: 3b says when a real stream is 4 bytes longer.  A channel that RDOQ empties is no longer
+ *    coded at all, so the real size can only be smaller than f(lambda*) on that account.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *y;          /* device [M*hw] */
+  fgmm_params params;
+  int32_t M, K;
+  int64_t hw;
+  uint64_t bits_q_before;                    /* out */
+  uint64_t bits_q_after[FGMM_RDCURVE_MAX];   /* out */
+  uint64_t n_changed[FGMM_RDCURVE_MAX];      /* out */
+  uint64_t ddist_q[FGMM_RDCURVE_MAX];        /* out */
+  int64_t n_symbols;                         /* out */
+  int32_t status, pad_;                      /* out */
+} fgmm_rdcurve_item;
+int fgmm_gmc_rdcurve_batch(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales,
+                           const double *lambdas, int n_lambda);
+typedef struct {
+  double lambda;           /* lambda* of the group */
+  uint64_t bytes_pred;     /* f(lambda*) */
+  int32_t passes;          /* curve passes the group took part in */
+  int32_t status;          /* FGMM_OK, or FGMM_BUDGET_UNMET */
+} fgmm_budget_result;
+int fgmm_gmc_rdoq_budget_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales,
+                               const int32_t *group_or_null, int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine,
+                               fgmm_budget_result *results /* per group */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
