@@ -89,6 +89,8 @@ def _item_dtype(struct=fgmm_item):
         if typ is fgmm_params:
             for pn, pt in fgmm_params._fields_:
                 names.append(pn); formats.append(kinds[pt]); offsets.append(base + getattr(fgmm_params, pn).offset)
+        elif issubclass(typ, C.Array):
+            names.append(name); formats.append((kinds[typ._type_], (typ._length_,))); offsets.append(base)
         else:
             names.append(name); formats.append(kinds[typ]); offsets.append(base)
     return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": C.sizeof(struct)})
@@ -97,6 +99,7 @@ def _item_dtype(struct=fgmm_item):
 ITEM_DTYPE = _item_dtype()
 RATE_ITEM_DTYPE = _item_dtype(fgmm_rate_item)
 RDOQ_ITEM_DTYPE = _item_dtype(fgmm_rdoq_item)
+RDCURVE_ITEM_DTYPE = _item_dtype(fgmm_rdcurve_item)
 FGMM_RATE_Q = 24  # unit of the size estimate's costs: 2^-24 bit
 
 SINK_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)  # fgmm_sink.alloc(user, item, nbytes) -> address

@@ -9,7 +9,8 @@
 # through fgmm_device.h (fgmm_capi / fgmm_encode / fgmm_decode / fgmm_decode_gpu / fgmm_rans: plain C++, also built without a GPU
 # toolchain against tests/fake/fake_device.cpp by scripts/tsan_host.sh); fgmm_rate_host.cpp (the coded size of a table, integer only) and
 # fgmm_estimate.cpp / fgmm_rdoq.cpp / fgmm_rdcurve.cpp (the size estimate's, the RDOQ call's and the curve and budget calls' orchestration
-# over fgmm_rate.hip / fgmm_rdoq.hip / fgmm_rdcurve.hip: not part of the fake-device build).
+# over fgmm_rate.hip / fgmm_rdoq.hip / fgmm_rdcurve.hip, all on the one frame fgmm_estimate.cpp holds - validation, the entry points' shell,
+# the census front half: not part of the fake-device build).
 set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}

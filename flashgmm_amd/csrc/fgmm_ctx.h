@@ -305,13 +305,6 @@ bool enc_vec4_ok(const EncDesc &d, const void *out, bool f16);
 // with NaN kept (may be null); returns the coded channels' count
 int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap_or_null, int32_t *abs_max_out,
                      float *min_max_or_null = nullptr);
-// ---- fgmm_estimate.cpp: what the estimate call and the RDOQ call share besides -----------------------------------------------------
-int ensure_rate_table(fgmm_ctx *ctx); // the context's device copy of rate_log2_table(), uploaded on first use
-// one item of either call: K, sizes, tensors, the parameters' dtype (one per batch) and flags; FGMM_OK or the failure, already reported
-int check_latent_item(int i, int K, int M, int64_t hw, const float *y, const fgmm_params &params, int batch_dtype);
-// ---- fgmm_rdoq.cpp: the RDOQ call with the context's lock held, for the budget call (fgmm_rdcurve.cpp) too --------------------------
-int rdoq_check_items(const fgmm_rdoq_item *items, int count); // the items of either call: FGMM_OK or the failure, already reported
-int rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride);
 
 struct DeviceGuard {
   int prev = -1;
@@ -502,6 +495,66 @@ int decode_batch(fgmm_ctx *ctx, dev::Stream stream, std::vector<DecItem> &items,
 // checkpointed bitstreams decoded ON THE GPU (segdec_kernel); `redo`: items whose segments did not all verify
 int decode_batch_gpu(fgmm_ctx *ctx, dev::Stream stream, std::vector<DecItem> &items, const std::vector<int> &which, int mode, std::vector<int> &redo);
 bool gpu_decodable(const DecItem &it, int64_t n);
+
+// ---- fgmm_estimate.cpp: the one frame of the pricing calls - estimate (3b), RDOQ (3c), curve and budget (3d); not in the fake-device build
+struct LatentIn { // the fields fgmm_rate_item, fgmm_rdoq_item and fgmm_rdcurve_item begin with
+  const float *y;
+  const fgmm_params *params;
+  int32_t M, K;
+  int64_t hw;
+};
+template <class Item> std::vector<LatentIn> latent_in(const Item *items, int count) {
+  std::vector<LatentIn> in((size_t)std::max(count, 0));
+  for (int i = 0; i < count; ++i) in[(size_t)i] = LatentIn{items[i].y, &items[i].params, items[i].M, items[i].K, items[i].hw};
+  return in;
+}
+int ensure_rate_table(fgmm_ctx *ctx); // the context's device copy of rate_log2_table(), uploaded on first use
+// every item of a batch: K, sizes, tensors, the parameters' dtype (one per batch) and flags; FGMM_OK or the failure, already reported
+int check_latent_items(const std::vector<LatentIn> &in);
+// the shell of an entry point whose arguments have been checked: the context's lock and device around `body(stream)`; a failure drains
+// the stream (nothing of this call may still be writing the workspace the next one reuses) and becomes every item's status
+template <class Item, class Body> int latent_call(fgmm_ctx *ctx, void *stream, Item *items, int count, Body body) {
+  if (count == 0) return FGMM_OK;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
+  const int rc = body((dev::Stream)stream);
+  if (rc != FGMM_OK) {
+    (void)dev::stream_sync((dev::Stream)stream);
+    for (int i = 0; i < count; ++i) items[i].status = rc;
+  }
+  return rc;
+}
+template <class T> T *ws(char *base, size_t off) { return reinterpret_cast<T *>(base + off); } // typed view of h_ws / d_ws at `off`
+struct LatentNeeds {           // what a call asks of the frame's workspace
+  size_t desc_bytes;           // its descriptors, per item: they precede the small region and are uploaded with the EncDesc arrays
+  size_t back_item, back_chan; // its sums that come back with the census: uint64 words per item + per channel of the item
+  size_t dev_chan;             // uint64 words per channel that stay on the device
+  bool census2;                // a second census, of each item's `out` (RDOQ: y_rdo)
+};
+// The front half.  Workspace: [EncDesc x count (x 2 with census2)][the call's descriptors][small: every item's census | every item's
+// sums][device only].  layout(), then the caller fills its descriptors and `out`, then start(): the one upload, the small region and
+// the outputs zeroed, the census of y.  finish() after the call's own kernel: the second census, the small region from `from` back, the wait.
+struct LatentFrame {
+  fgmm_ctx *ctx;
+  dev::Stream stream;
+  std::vector<LatentIn> in;
+  int count, clamp, M_max = 0, vec = 1;
+  int64_t hw_max = 0, n_max = 0;
+  bool f16 = false, linear = true, census2 = false;
+  size_t o_descs = 0, o_call = 0, o_small = 0, o_sums = 0, o_dev = 0, end = 0;
+  std::vector<CensusOff> census, census_out;
+  std::vector<size_t> o_back, o_acc; // per item: its sums (back_item + back_chan * M words), its device-only words
+  std::vector<float *> out;          // per item, null or [M * hw]: what the call's kernel writes in part - tested by enc_vec4_ok, zeroed by start()
+  LatentFrame(fgmm_ctx *c, dev::Stream s, std::vector<LatentIn> items, int clamp_) : ctx(c), stream(s), in(std::move(items)), count((int)in.size()), clamp(clamp_) {}
+  const EncDesc *dd(bool of_out = false) const { return ws<const EncDesc>(ctx->d_ws, o_descs) + (of_out ? count : 0); }
+  int layout(const LatentNeeds &n);
+  int start();
+  int finish(size_t from);
+};
+// ---- fgmm_rdoq.cpp: the RDOQ call with the context's lock held, for the budget call (fgmm_rdcurve.cpp) too --------------------------
+int rdoq_check_items(const fgmm_rdoq_item *items, int count); // check_latent_items, then what is RDOQ's own: y_rdo null or over y
+int rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride);
 
 constexpr size_t kCounterBytes = kTabCounters * sizeof(unsigned long long); // per launch unit, see DecDesc::counters
 

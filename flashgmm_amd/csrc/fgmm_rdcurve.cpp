@@ -1,5 +1,5 @@
 // fgmm_rdcurve.cpp — the rate-distortion curve of a batch of latents and their quantisation to a byte budget (include/flashgmm_amd.h
-// section 3d).  The size estimate's front half once per call (fgmm_estimate.cpp: quant_stats_kernel and chan_compact_kernel give the
+// section 3d).  The frame of fgmm_estimate.cpp once per call (LatentFrame: quant_stats_kernel and chan_compact_kernel give the
 // channels the compress call would code for y), then one or more PASSES: rdcurve_kernel (fgmm_rdcurve.hip) at up to 16 lambdas per
 // item, the channels' sums folded to the items' on the device, a few KB back.  The budget call searches lambda on those passes by the
 // header's rule, every group on its own grid within one launch, and ends in the RDOQ call's own path (fgmm_rdoq.cpp: rdoq_run) at the
@@ -13,99 +13,49 @@ using namespace fgmm;
 
 namespace {
 
-struct CurveIn { // what a pass reads of an item, whichever call it belongs to
-  const float *y;
-  const fgmm_params *params;
-  int32_t M;
-  int64_t hw;
-};
+struct Curve : LatentFrame { // the passes of a call, on the frame: a pass sets n_lambda and lam_q of every item in `hc`, then run()
+  using LatentFrame::LatentFrame;
+  RdCurveDesc *hc = nullptr; // host copy of the curve descriptors
+  bool census_back = false;
+  const uint64_t *sums(int i) const { return ws<const uint64_t>(ctx->h_ws, o_back[(size_t)i]); }
 
-struct Curve { // the front half of a call and the state its passes share
-  fgmm_ctx *ctx;
-  dev::Stream stream;
-  int count, mode, clamp;
-  int M_max = 0, vec = 1;
-  int64_t hw_max = 0, n_max = 0;
-  bool f16 = false, linear = true, census_back = false;
-  size_t o_descs = 0, o_cdescs = 0, o_census = 0, o_sums = 0, o_acc = 0, end = 0;
-  std::vector<CensusOff> census;
-  Curve(fgmm_ctx *ctx_, dev::Stream stream_, int count_, int mode_, int clamp_) : ctx(ctx_), stream(stream_), count(count_), mode(mode_), clamp(clamp_) {}
-  RdCurveDesc *hc = nullptr; // host copy of the curve descriptors: a pass sets n_lambda and lam_q of every item, then run()
-  const unsigned long long *sums(int i) const { return reinterpret_cast<const unsigned long long *>(ctx->h_ws + o_sums) + (size_t)i * kRdCurveRow; }
-
-  // workspace: [EncDesc x count][RdCurveDesc x count][census of every item][sums: count rows][device only: per item M rows]
-  int begin(const std::vector<CurveIn> &in) {
-    int rc;
-    if ((rc = ensure_rate_table(ctx))) return rc;
-    Arena ar;
-    o_descs = ar.take(sizeof(EncDesc) * (size_t)count);
-    o_cdescs = ar.take(sizeof(RdCurveDesc) * (size_t)count);
-    o_census = ar.take(0);
-    census.resize((size_t)count);
+  int begin() { // the census, once: every pass prices the channels it names
+    if (int rc = layout({sizeof(RdCurveDesc), kRdCurveRow, 0, kRdCurveRow, false})) return rc; // the item's row of sums | on the device, a row per channel
+    hc = ws<RdCurveDesc>(ctx->h_ws, o_call);
     for (int i = 0; i < count; ++i) {
-      census[(size_t)i] = census_take(ar, in[(size_t)i].M);
-      M_max = std::max(M_max, in[(size_t)i].M);
-      hw_max = std::max(hw_max, in[(size_t)i].hw);
-      n_max = std::max(n_max, (int64_t)in[(size_t)i].M * in[(size_t)i].hw);
-    }
-    o_sums = ar.take(sizeof(unsigned long long) * kRdCurveRow * (size_t)count, 16);
-    o_acc = ar.take(0);
-    std::vector<size_t> o_item((size_t)count);
-    for (int i = 0; i < count; ++i) o_item[(size_t)i] = ar.take(sizeof(unsigned long long) * kRdCurveRow * (size_t)in[(size_t)i].M, 16);
-    end = ar.off;
-    if ((rc = ctx->ensure_device(end)) || (rc = ctx->ensure_host(o_acc)) || (rc = ctx->ensure_events(1))) return rc;
-    EncDesc *hd = reinterpret_cast<EncDesc *>(ctx->h_ws + o_descs);
-    hc = reinterpret_cast<RdCurveDesc *>(ctx->h_ws + o_cdescs);
-    f16 = in[0].params->dtype == FGMM_F16;
-    bool vec4 = true;
-    for (int i = 0; i < count; ++i) {
-      const CurveIn &it = in[(size_t)i];
-      census_desc(hd[i], ctx, census[(size_t)i], it.y, it.params, it.M, it.hw, clamp);
       memset(&hc[i], 0, sizeof hc[i]);
-      hc[i].chan_acc = reinterpret_cast<unsigned long long *>(ctx->d_ws + o_item[(size_t)i]);
-      hc[i].sums = reinterpret_cast<unsigned long long *>(ctx->d_ws + o_sums) + (size_t)i * kRdCurveRow;
-      vec4 = vec4 && enc_vec4_ok(hd[i], nullptr, f16);
+      hc[i].chan_acc = ws<unsigned long long>(ctx->d_ws, o_acc[(size_t)i]);
+      hc[i].sums = ws<unsigned long long>(ctx->d_ws, o_back[(size_t)i]);
     }
-    vec = vec4 ? 4 : 1;
-    for (int i = 0; i < count; ++i) linear = linear && in[(size_t)i].hw % (64 * vec) == 0;
-    // the census, once: every pass prices the channels it names
-    DEV_TRY(dev::copy_async(ctx->d_ws + o_descs, hd, sizeof(EncDesc) * (size_t)count, dev::kH2D, stream));
-    DEV_TRY(dev::memset_async(ctx->d_ws + o_census, 0, o_sums - o_census, stream));
-    LAUNCH_TRY(launch_quant_stats(reinterpret_cast<const EncDesc *>(ctx->d_ws + o_descs), count, M_max, stream));
-    return FGMM_OK;
+    return start();
   }
 
-  // one pass with the descriptors as `hc` holds them; returns with the items' sums (and, after the first, the census) on the host
-  int run() {
-    DEV_TRY(dev::copy_async(ctx->d_ws + o_cdescs, hc, sizeof(RdCurveDesc) * (size_t)count, dev::kH2D, stream));
+  // one pass: only the curve descriptors go up again; back come the items' sums and, after the first pass alone, the census
+  int run(int mode) {
+    DEV_TRY(dev::copy_async(ctx->d_ws + o_call, hc, sizeof(RdCurveDesc) * (size_t)count, dev::kH2D, stream));
     DEV_TRY(dev::memset_async(ctx->d_ws + o_sums, 0, end - o_sums, stream)); // the items' sums and the channels'
-    LAUNCH_TRY(launch_rdcurve(reinterpret_cast<const EncDesc *>(ctx->d_ws + o_descs), reinterpret_cast<const RdCurveDesc *>(ctx->d_ws + o_cdescs),
-                              ctx->d_rate_log2, count, M_max, hw_max, n_max, linear, mode, vec, clamp != 0, f16, stream));
-    const size_t from = census_back ? o_sums : o_census;
-    DEV_TRY(dev::copy_async(ctx->h_ws + from, ctx->d_ws + from, o_acc - from, dev::kD2H, stream));
+    LAUNCH_TRY(launch_rdcurve(dd(), ws<const RdCurveDesc>(ctx->d_ws, o_call), ctx->d_rate_log2, count, M_max, hw_max, n_max, linear, mode, vec,
+                              clamp != 0, f16, stream));
+    const size_t from = census_back ? o_sums : o_small;
     census_back = true;
-    DEV_TRY(dev::event_record(ctx->events[0], stream));
-    DEV_TRY(dev::event_sync(ctx->events[0]));
-    return FGMM_OK;
+    return finish(from);
   }
 };
 
 bool lambda_ok(double v) { return v >= 0.0 && v < (double)INFINITY; } // (false for NaN)
 
 int curve_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdcurve_item *items, int count, int mode, int clamp, const double *lambdas, int n_lambda) {
-  std::vector<CurveIn> in((size_t)count);
-  for (int i = 0; i < count; ++i) in[(size_t)i] = CurveIn{items[i].y, &items[i].params, items[i].M, items[i].hw};
-  Curve cv(ctx, stream, count, mode, clamp);
+  Curve cv(ctx, stream, latent_in(items, count), clamp);
   int rc;
-  if ((rc = cv.begin(in))) return rc;
+  if ((rc = cv.begin())) return rc;
   for (int i = 0; i < count; ++i) {
     cv.hc[i].n_lambda = n_lambda;
     for (int j = 0; j < n_lambda; ++j) cv.hc[i].lam_q[j] = lambdas[j] * 0x1p-24;
   }
-  if ((rc = cv.run())) return rc;
+  if ((rc = cv.run(mode))) return rc;
   for (int i = 0; i < count; ++i) {
     fgmm_rdcurve_item &it = items[i];
-    const unsigned long long *s = cv.sums(i);
+    const uint64_t *s = cv.sums(i);
     int32_t abs_max;
     const int n_nz = census_side_info(ctx, cv.census[(size_t)i], it.M, it.hw, nullptr, &abs_max);
     it.bits_q_before = s[0];
@@ -130,11 +80,9 @@ struct Search { // one group's search (header section 3d)
 
 int budget_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const int32_t *group, int n_groups,
                  const uint64_t *budget, double lambda_max, int refine, fgmm_budget_result *results) {
-  std::vector<CurveIn> in((size_t)count);
-  for (int i = 0; i < count; ++i) in[(size_t)i] = CurveIn{items[i].y, &items[i].params, items[i].M, items[i].hw};
-  Curve cv(ctx, stream, count, mode, clamp);
+  Curve cv(ctx, stream, latent_in(items, count), clamp);
   int rc;
-  if ((rc = cv.begin(in))) return rc;
+  if ((rc = cv.begin())) return rc;
   std::vector<Search> gs((size_t)n_groups);
   for (Search &g : gs) { // round 0: 0, then lambda_max * 2^(j - 15)
     g.grid[0] = 0.0;
@@ -150,12 +98,12 @@ int budget_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int c
       cv.hc[i].n_lambda = g.active ? FGMM_RDCURVE_MAX : 0;
       for (int j = 0; j < FGMM_RDCURVE_MAX; ++j) cv.hc[i].lam_q[j] = g.grid[j] * 0x1p-24;
     }
-    if ((rc = cv.run())) return rc;
+    if ((rc = cv.run(mode))) return rc;
     std::fill(f.begin(), f.end(), 0);
     for (int i = 0; i < count; ++i) {
       const int gi = group ? group[i] : i;
       if (!gs[(size_t)gi].active) continue;
-      const unsigned long long *s = cv.sums(i);
+      const uint64_t *s = cv.sums(i);
       for (int j = 0; j < FGMM_RDCURVE_MAX; ++j) f[(size_t)gi * FGMM_RDCURVE_MAX + j] += rate_stream_bytes(s[1 + j]);
     }
     for (int gi = 0; gi < n_groups; ++gi) {
@@ -217,20 +165,8 @@ int fgmm_gmc_rdcurve_batch(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items
   for (int j = 0; j < n_lambda; ++j)
     if (!lambda_ok(lambdas[j])) return fail(FGMM_ERR_INVALID, "lambda[%d] = %g: must be finite and >= 0", j, lambdas[j]);
   if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
-  for (int i = 0; i < count; ++i) {
-    const fgmm_rdcurve_item &s = items[i];
-    if (int rc = check_latent_item(i, s.K, s.M, s.hw, s.y, s.params, items[0].params.dtype)) return rc;
-  }
-  if (count == 0) return FGMM_OK;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
-  const int rc = curve_batch(ctx, (dev::Stream)stream, items, count, mode, clamp_scales, lambdas, n_lambda);
-  if (rc != FGMM_OK) {
-    (void)dev::stream_sync((dev::Stream)stream); // (nothing of this call may still be writing the workspace the next one reuses)
-    for (int i = 0; i < count; ++i) items[i].status = rc;
-  }
-  return rc;
+  if (int rc = check_latent_items(latent_in(items, count))) return rc;
+  return latent_call(ctx, stream, items, count, [&](dev::Stream s) { return curve_batch(ctx, s, items, count, mode, clamp_scales, lambdas, n_lambda); });
 }
 
 int fgmm_gmc_rdoq_budget_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, const int32_t *group,
@@ -250,16 +186,9 @@ int fgmm_gmc_rdoq_budget_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *item
       if (!seen[(size_t)gi]) return fail(FGMM_ERR_INVALID, "group %d is empty", gi);
   }
   if (int rc = rdoq_check_items(items, count)) return rc;
-  if (count == 0) return FGMM_OK;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
-  const int rc = budget_batch(ctx, (dev::Stream)stream, items, count, mode, clamp_scales, group, n_groups, budget_bytes, lambda_max, refine, results);
-  if (rc != FGMM_OK) {
-    (void)dev::stream_sync((dev::Stream)stream);
-    for (int i = 0; i < count; ++i) items[i].status = rc;
-  }
-  return rc;
+  return latent_call(ctx, stream, items, count, [&](dev::Stream s) {
+    return budget_batch(ctx, s, items, count, mode, clamp_scales, group, n_groups, budget_bytes, lambda_max, refine, results);
+  });
 }
 
 } // extern "C"

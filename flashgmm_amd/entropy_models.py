@@ -235,6 +235,42 @@ class RdCurve:
         return f"RdCurve(lambdas={self.lambdas}, nbytes={self.nbytes}, n_changed={self.n_changed})"
 
 
+class _LatentItems:
+    """The items of one call that prices latents, built by ``GaussianMixtureConditional._latent_items`` from either input form:
+    ``arr`` the ``struct[N]`` ctypes passes, ``items`` the same memory as a numpy record array (filled and read column by column),
+    ``keep`` the input tensors whose storage the items name; for the outputs' shapes ``shape``, the ``(1, M, h, w)`` of every item
+    of a stacked batch, or ``ys``, the latents of a sequence."""
+
+    DTYPES = {_lib.fgmm_rate_item: _lib.RATE_ITEM_DTYPE, _lib.fgmm_rdoq_item: _lib.RDOQ_ITEM_DTYPE, _lib.fgmm_rdcurve_item: _lib.RDCURVE_ITEM_DTYPE}
+    __slots__ = ("arr", "items", "N", "keep", "dev", "shape", "ys")
+
+    def __init__(self, struct, N, keep, dev=None, shape=None, ys=None):
+        self.arr = (struct * N)()
+        self.items, self.N = np.frombuffer(self.arr, self.DTYPES[struct]), N
+        self.keep, self.dev, self.shape, self.ys = keep, dev, shape, ys
+
+    @property
+    def di(self) -> int:
+        return self.dev.index if self.dev.index is not None else -1
+
+    def stream(self) -> int:
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def output(self, field: str, dtype, per_latent: bool = False):
+        """allocates the output ``field`` of every item - per latent ``[1, M, h, w]`` on the device, else per channel ``[M]`` on the
+        host; ONE ``[N, ...]`` tensor for stacked input, one per item for sequences - and writes the addresses -> the items' tensors
+        (the caller holds them across the call)"""
+        device = self.dev if per_latent else None
+        if self.shape is not None:
+            t = torch.empty((self.N,) + (self.shape if per_latent else self.shape[1:2]), dtype=dtype, device=device)
+            self.items[field] = np.uint64(t.data_ptr()) + np.arange(self.N, dtype=np.uint64) * np.uint64(t.stride(0) * t.element_size())
+            return t.unbind(0)
+        ts = [torch.empty((1, M) + tuple(y.shape[2:]) if per_latent else (M,), dtype=dtype, device=device)
+              for M, y in zip(self.items["M"].tolist(), self.ys)]
+        self.items[field] = [t.data_ptr() for t in ts]
+        return ts
+
+
 def _take_ckpts_many(device: int, ptrs, counts):
     """the library-allocated fgmm_ckpt arrays of a batch -> [(ndarray view, its address)], the arrays released: ONE array for the
     batch and one native call instead of a copy and a free per bitstream"""
@@ -416,49 +452,8 @@ class GaussianMixtureConditional(nn.Module):
             keep.append(yc)
         return yp, s.data_ptr(), m.data_ptr(), w.data_ptr(), M, hw, sk, sc, s.device, s.dtype
 
-    def _stacked_items(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, flags: int = 0, dtype=None):
-        """``fgmm_item[N]`` (as a numpy record array) for N items given as ONE tensor each: y ``[N, M, h, w]``,
-        parameters ``[N, K*M, h, w]``.  One validation and one set of strides for the whole batch; the item
-        pointers are the batch-dimension offsets."""
-        if not scales.is_cuda:
-            raise RuntimeError(
-                "flashgmm_amd runs the GMM entropy-coding path on the GPU only: tensors must be on a HIP device "
-                "(there is deliberately no CPU fallback)")
-        if scales.dim() != 4 or means.shape != scales.shape or weights.shape != scales.shape:
-            raise RuntimeError("stacked entropy parameters must be three [N, K*M, h, w] tensors of one shape")
-        if not (scales.dtype == means.dtype == weights.dtype) or scales.dtype not in _PARAM_DTYPES:
-            raise RuntimeError("scales, means and weights must share one dtype, float32 or float16")
-        N, KM, h, w = scales.shape
-        hw = h * w
-        st = scales.stride()
-        if (hw > 1 and not (st[3] == 1 and st[2] == w)) or means.stride() != st or weights.stride() != st:
-            scales, means, weights = scales.contiguous(), means.contiguous(), weights.contiguous()
-            st = scales.stride()
-        M = KM // self.K
-        sc = st[1] if KM > 1 else hw
-        esz = scales.element_size()
-        items = np.zeros(N, _lib.ITEM_DTYPE if dtype is None else dtype)  # (fgmm_item[], or fgmm_rate_item[]: the same input fields)
-        step = np.arange(N, dtype=np.uint64) * np.uint64(st[0] * esz)
-        items["scales"] = np.uint64(scales.data_ptr()) + step
-        items["means"] = np.uint64(means.data_ptr()) + step
-        items["weights"] = np.uint64(weights.data_ptr()) + step
-        items["stride_k"], items["stride_c"] = M * sc, sc
-        items["dtype"] = _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32
-        items["flags"] = flags
-        items["M"], items["K"], items["hw"] = M, self.K, hw
-        keep = [scales, means, weights]
-        if y is not None:
-            if y.dim() != 4 or tuple(y.shape) != (N, M, h, w):
-                raise RuntimeError(f"y must be [{N}, {M}, {h}, {w}] matching the parameters; got {tuple(y.shape)}")
-            if y.dtype != torch.float32 or y.device != scales.device:
-                raise RuntimeError("y must be float32 on the parameters' device")
-            y = y.contiguous()
-            items["y"] = np.uint64(y.data_ptr()) + np.arange(N, dtype=np.uint64) * np.uint64(M * hw * 4)
-            keep.append(y)
-        return items, keep, N, M, h, w, scales.device
-
     def _stacked_view(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor):
-        """validation of stacked inputs for the compiled boundary -> (y, scales, means, weights, N, M, h, w, item stride, stride_c)"""
+        """THE validation of stacked inputs -> (y, scales, means, weights, N, M, h, w, item stride, stride_c)"""
         if not scales.is_cuda:
             raise RuntimeError(
                 "flashgmm_amd runs the GMM entropy-coding path on the GPU only: tensors must be on a HIP device "
@@ -480,6 +475,30 @@ class GaussianMixtureConditional(nn.Module):
                 raise RuntimeError("y must be float32 on the parameters' device")
             y = y.contiguous()
         return y, scales, means, weights, N, M, h, w, st[0], (st[1] if KM > 1 else h * w)
+
+    def _stacked_fill(self, items, y, scales, means, weights, N, M, h, w, s_item, sc, flags: int = 0):
+        """the input fields of N items (a numpy record array over ``fgmm_item[]`` or an item type that begins alike) from what
+        ``_stacked_view`` returns: one set of strides for the whole batch; the item pointers are the batch-dimension offsets"""
+        rng = np.arange(N, dtype=np.uint64)
+        step = rng * np.uint64(s_item * scales.element_size())
+        items["scales"] = np.uint64(scales.data_ptr()) + step
+        items["means"] = np.uint64(means.data_ptr()) + step
+        items["weights"] = np.uint64(weights.data_ptr()) + step
+        items["stride_k"], items["stride_c"] = M * sc, sc
+        items["dtype"] = _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32
+        items["flags"] = flags
+        items["M"], items["K"], items["hw"] = M, self.K, h * w
+        if y is not None:
+            items["y"] = np.uint64(y.data_ptr()) + rng * np.uint64(M * h * w * 4)
+
+    def _stacked_items(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, flags: int = 0):
+        """``fgmm_item[N]`` (as a numpy record array) for N items given as ONE tensor each: y ``[N, M, h, w]``, parameters
+        ``[N, K*M, h, w]``: ``_stacked_view``, then ``_stacked_fill``"""
+        view = self._stacked_view(y, scales, means, weights)
+        y, scales, means, weights, N, M, h, w = view[:8]
+        items = np.zeros(N, _lib.ITEM_DTYPE)
+        self._stacked_fill(items, *view, flags)
+        return items, [scales, means, weights] + ([y] if y is not None else []), N, M, h, w, scales.device
 
     def _compress_stacked(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, flags: int = 0):
         nat = _lib.native()
@@ -703,56 +722,15 @@ class GaussianMixtureConditional(nn.Module):
         -> one ``RateEstimate`` per item; ``per_channel`` / ``per_latent`` add the per-channel sums and the per-latent map."""
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
-        flags = _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0
-        if isinstance(ys, Tensor):
-            items, keep, N, M, h, w, dev = self._stacked_items(ys, scales, means, weights, flags, _lib.RATE_ITEM_DTYPE)
-            if N == 0:
-                return []
-            rng = np.arange(N, dtype=np.uint64)
-            zb = torch.empty((N, M), dtype=torch.int64)
-            items["zero_bitmap"] = np.uint64(zb.data_ptr()) + rng * np.uint64(M * 8)
-            bitmaps = zb.unbind(0)
-            chans = maps = [None] * N
-            if per_channel:
-                cb = torch.empty((N, M), dtype=torch.int64)
-                items["chan_bits_q"] = np.uint64(cb.data_ptr()) + rng * np.uint64(M * 8)
-                chans = cb.unbind(0)
-            if per_latent:
-                lm = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
-                items["bits_map"] = np.uint64(lm.data_ptr()) + rng * np.uint64(M * h * w * 4)
-                maps = lm.unbind(0)
-            ptr = C.cast(items.ctypes.data, C.POINTER(_lib.fgmm_rate_item))
-        else:
-            N = len(ys)
-            if N == 0:
-                return []
-            arr = (_lib.fgmm_rate_item * N)()
-            keep, bitmaps, chans, maps, dev = [], [], [], [], None
-            for i in range(N):
-                yp, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
-                dev = dev or d
-                if d != dev:
-                    raise RuntimeError("all items of a batch must be on one device")
-                it = arr[i]
-                it.y = yp
-                it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
-                it.M, it.K, it.hw = M, self.K, hw
-                zb = torch.empty(M, dtype=torch.int64)
-                it.zero_bitmap = zb.data_ptr()
-                bitmaps.append(zb)
-                cb = torch.empty(M, dtype=torch.int64) if per_channel else None
-                if cb is not None:
-                    it.chan_bits_q = cb.data_ptr()
-                chans.append(cb)
-                lm = torch.empty((1, M) + tuple(ys[i].shape[2:]), dtype=torch.float32, device=d) if per_latent else None
-                if lm is not None:
-                    it.bits_map = lm.data_ptr()
-                maps.append(lm)
-            items = np.frombuffer(arr, dtype=_lib.RATE_ITEM_DTYPE)
-            ptr = arr
-        di = dev.index if dev.index is not None else -1
-        rc = _lib.lib().fgmm_gmc_estimate_batch(_lib.ctx(di), torch.cuda.current_stream(dev).cuda_stream, ptr, N, self._mode(), int(self.clamp_scales))
+        L = self._latent_items(_lib.fgmm_rate_item, ys, scales, means, weights, weights_are_logits)
+        if L.N == 0:
+            return []
+        bitmaps = L.output("zero_bitmap", torch.int64)
+        chans = L.output("chan_bits_q", torch.int64) if per_channel else [None] * L.N
+        maps = L.output("bits_map", torch.float32, per_latent=True) if per_latent else [None] * L.N
+        rc = _lib.lib().fgmm_gmc_estimate_batch(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales))
         _lib.check(rc, "GaussianMixtureConditional.estimate_bits")
+        items = L.items
         cols = zip(items["bits_q"].tolist(), items["bytes_pred"].tolist(), items["n_symbols"].tolist(), items["n_bypass"].tolist(),
                    items["abs_max"].tolist(), bitmaps, chans, maps)
         return [RateEstimate(*c) for c in cols]
@@ -790,53 +768,14 @@ class GaussianMixtureConditional(nn.Module):
                                                      _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32, flags, self._mode(),
                                                      int(self.clamp_scales), lam, out.data_ptr(), zb.data_ptr(), cb.data_ptr() if per_channel else 0)
             return [RdoQuantized(*c) for c in zip(out.unbind(0), ch, before, after, am, zb.unbind(0), cb.unbind(0) if per_channel else [None] * N)]
-        if isinstance(ys, Tensor):
-            items, keep, N, M, h, w, dev = self._stacked_items(ys, scales, means, weights, flags, _lib.RDOQ_ITEM_DTYPE)
-            if N == 0:
-                return []
-            rng = np.arange(N, dtype=np.uint64)
-            out = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
-            items["y_rdo"] = np.uint64(out.data_ptr()) + rng * np.uint64(M * h * w * 4)
-            outs = out.unbind(0)
-            zb = torch.empty((N, M), dtype=torch.int64)
-            items["zero_bitmap"] = np.uint64(zb.data_ptr()) + rng * np.uint64(M * 8)
-            bitmaps = zb.unbind(0)
-            chans = [None] * N
-            if per_channel:
-                cb = torch.empty((N, M), dtype=torch.int64)
-                items["chan_bits_q_after"] = np.uint64(cb.data_ptr()) + rng * np.uint64(M * 8)
-                chans = cb.unbind(0)
-            ptr = C.cast(items.ctypes.data, C.POINTER(_lib.fgmm_rdoq_item))
-        else:
-            N = len(ys)
-            if N == 0:
-                return []
-            arr = (_lib.fgmm_rdoq_item * N)()
-            keep, outs, bitmaps, chans, dev = [], [], [], [], None
-            for i in range(N):
-                yp, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
-                dev = dev or d
-                if d != dev:
-                    raise RuntimeError("all items of a batch must be on one device")
-                it = arr[i]
-                it.y = yp
-                it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
-                it.M, it.K, it.hw = M, self.K, hw
-                out = torch.empty((1, M) + tuple(ys[i].shape[2:]), dtype=torch.float32, device=d)
-                it.y_rdo = out.data_ptr()
-                outs.append(out)
-                zb = torch.empty(M, dtype=torch.int64)
-                it.zero_bitmap = zb.data_ptr()
-                bitmaps.append(zb)
-                cb = torch.empty(M, dtype=torch.int64) if per_channel else None
-                if cb is not None:
-                    it.chan_bits_q_after = cb.data_ptr()
-                chans.append(cb)
-            items = np.frombuffer(arr, dtype=_lib.RDOQ_ITEM_DTYPE)
-            ptr = arr
-        di = dev.index if dev.index is not None else -1
-        rc = _lib.lib().fgmm_gmc_rdoq_batch(_lib.ctx(di), torch.cuda.current_stream(dev).cuda_stream, ptr, N, self._mode(), int(self.clamp_scales), lam)
+        L = self._latent_items(_lib.fgmm_rdoq_item, ys, scales, means, weights, weights_are_logits)
+        if L.N == 0:
+            return []
+        outs, bitmaps = L.output("y_rdo", torch.float32, per_latent=True), L.output("zero_bitmap", torch.int64)
+        chans = L.output("chan_bits_q_after", torch.int64) if per_channel else [None] * L.N
+        rc = _lib.lib().fgmm_gmc_rdoq_batch(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales), lam)
         _lib.check(rc, "GaussianMixtureConditional.quantize_rdo")
+        items = L.items
         cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
                    bitmaps, chans)
         return [RdoQuantized(*c) for c in cols]
@@ -846,27 +785,29 @@ class GaussianMixtureConditional(nn.Module):
         """-> the ``RdoQuantized`` of one latent (``quantize_rdo_batch``)"""
         return self.quantize_rdo_batch([y], [scales], [means], [weights], lam, weights_are_logits=weights_are_logits, per_channel=per_channel)[0]
 
-    def _latent_items(self, struct, ys, scales, means, weights, flags: int):
-        """the items of a call that takes latents (sequences, or stacked tensors taken apart) as a ctypes array of ``struct`` with the
-        input fields set -> (array, N, keep, device, shapes)"""
+    def _latent_items(self, struct, ys, scales, means, weights, logits: bool) -> _LatentItems:
+        """THE item builder of the calls that price latents (estimate, RDOQ, curve, budget): ``struct[N]`` with the input fields
+        set - stacked tensors column by column (``_stacked_view``, ``_stacked_fill``: one validation, the pointers batch-dimension
+        offsets), sequences through ``_item_ints`` item by item"""
+        flags = _lib.FGMM_PARAMS_LOGITS if logits else 0
         if isinstance(ys, Tensor):
-            if ys.dim() != 4 or scales.dim() != 4 or not (ys.shape[0] == scales.shape[0] == means.shape[0] == weights.shape[0]):
-                raise RuntimeError("stacked inputs must be [N, M, h, w] / [N, K*M, h, w] tensors of one N")
-            ys, scales, means, weights = ([t[i:i + 1] for i in range(t.shape[0])] for t in (ys, scales, means, weights))
-        N = len(ys)
-        arr = (struct * N)()
-        keep, shapes, dev = [], [], None
-        for i in range(N):
+            view = self._stacked_view(ys, scales, means, weights)
+            N, M, h, w = view[4:8]
+            L = _LatentItems(struct, N, list(view[:4]), view[1].device, shape=(1, M, h, w))
+            self._stacked_fill(L.items, *view, flags)
+            return L
+        L = _LatentItems(struct, len(ys), [], ys=ys)
+        keep, dev = L.keep, None
+        for i, it in enumerate(L.arr):
             yp, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
             dev = dev or d
             if d != dev:
                 raise RuntimeError("all items of a batch must be on one device")
-            it = arr[i]
             it.y = yp
             it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
             it.M, it.K, it.hw = M, self.K, hw
-            shapes.append((1, M) + tuple(ys[i].shape[2:]))
-        return arr, N, keep, dev, shapes
+        L.dev = dev
+        return L
 
     def rd_curve_batch(self, ys, scales, means, weights, lambdas, *, weights_are_logits: bool = False) -> List[RdCurve]:
         """What ``quantize_rdo_batch`` would report at every lambda of ``lambdas`` - the cost after, the latents moved, the distortion
@@ -878,25 +819,24 @@ class GaussianMixtureConditional(nn.Module):
         lambdas = [float(v) for v in lambdas]
         if not lambdas or not all(0.0 <= v < float("inf") for v in lambdas):
             raise ValueError(f"lambdas = {lambdas!r}: at least one, each finite and >= 0")
-        arr, N, keep, dev, _ = self._latent_items(_lib.fgmm_rdcurve_item, ys, scales, means, weights, _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0)
-        if N == 0:
+        L = self._latent_items(_lib.fgmm_rdcurve_item, ys, scales, means, weights, weights_are_logits)
+        if L.N == 0:
             return []
-        di = dev.index if dev.index is not None else -1
-        nat = _lib.native()
-        cols = [([], [], []) for _ in range(N)]
+        nat, items = _lib.native(), L.items
+        names = ("bits_q_after", "n_changed", "ddist_q")
+        cols = [[] for _ in names]
         for at in range(0, len(lambdas), _lib.FGMM_RDCURVE_MAX):
             chunk = lambdas[at:at + _lib.FGMM_RDCURVE_MAX]
-            stream = torch.cuda.current_stream(dev).cuda_stream
             if nat is not None:
-                nat.rdcurve_items(_lib.ctx_addr(di), stream, C.addressof(arr), N, self._mode(), int(self.clamp_scales), chunk)
+                nat.rdcurve_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), chunk)
             else:
-                rc = _lib.lib().fgmm_gmc_rdcurve_batch(_lib.ctx(di), stream, arr, N, self._mode(), int(self.clamp_scales),
+                rc = _lib.lib().fgmm_gmc_rdcurve_batch(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales),
                                                        (C.c_double * len(chunk))(*chunk), len(chunk))
                 _lib.check(rc, "GaussianMixtureConditional.rd_curve")
-            for it, col in zip(arr, cols):
-                for dst, src in zip(col, (it.bits_q_after, it.n_changed, it.ddist_q)):
-                    dst += src[:len(chunk)]
-        return [RdCurve(lambdas, it.bits_q_before, *col, it.n_symbols) for it, col in zip(arr, cols)]
+            for col, name in zip(cols, names):
+                col.append(items[name][:, :len(chunk)].copy())
+        cols = [np.concatenate(col, axis=1).tolist() for col in cols]
+        return [RdCurve(lambdas, *c) for c in zip(items["bits_q_before"].tolist(), *cols, items["n_symbols"].tolist())]
 
     def rd_curve(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lambdas, *, weights_are_logits: bool = False) -> RdCurve:
         """-> the ``RdCurve`` of one latent (``rd_curve_batch``)"""
@@ -919,7 +859,8 @@ class GaussianMixtureConditional(nn.Module):
             raise ValueError(f"lambda_max = {lambda_max!r}: must be finite and > 0")
         if not 0 <= refine <= 8:
             raise ValueError(f"refine = {refine!r}: must lie in 0 .. 8")
-        arr, N, keep, dev, shapes = self._latent_items(_lib.fgmm_rdoq_item, ys, scales, means, weights, _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0)
+        L = self._latent_items(_lib.fgmm_rdoq_item, ys, scales, means, weights, weights_are_logits)
+        N, items = L.N, L.items
         if groups is not None:
             groups = [int(g) for g in groups]
             if len(groups) != N:
@@ -939,32 +880,25 @@ class GaussianMixtureConditional(nn.Module):
             raise ValueError("budget_bytes must be >= 0")
         if N == 0:
             return []
-        outs, bitmaps, chans = [], [], []
-        for it, shape in zip(arr, shapes):
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-            zb = torch.empty(shape[1], dtype=torch.int64)
-            cb = torch.empty(shape[1], dtype=torch.int64) if per_channel else None
-            it.y_rdo, it.zero_bitmap = out.data_ptr(), zb.data_ptr()
-            if cb is not None:
-                it.chan_bits_q_after = cb.data_ptr()
-            outs.append(out), bitmaps.append(zb), chans.append(cb)
-        di = dev.index if dev.index is not None else -1
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        outs, bitmaps = L.output("y_rdo", torch.float32, per_latent=True), L.output("zero_bitmap", torch.int64)
+        chans = L.output("chan_bits_q_after", torch.int64) if per_channel else [None] * N
         nat = _lib.native()
         if nat is not None:
-            res = nat.rdoq_budget_items(_lib.ctx_addr(di), stream, C.addressof(arr), N, self._mode(), int(self.clamp_scales), groups, budgets, lambda_max, refine)
+            res = nat.rdoq_budget_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), N, self._mode(), int(self.clamp_scales), groups, budgets,
+                                        lambda_max, refine)
         else:
             out_res = (_lib.fgmm_budget_result * n_groups)()
-            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch(_lib.ctx(di), stream, arr, N, self._mode(), int(self.clamp_scales),
+            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch(_lib.ctx(L.di), L.stream(), L.arr, N, self._mode(), int(self.clamp_scales),
                                                        (C.c_int32 * N)(*groups) if groups is not None else None, n_groups,
                                                        (C.c_uint64 * n_groups)(*budgets), lambda_max, refine, out_res)
             _lib.check(rc, "GaussianMixtureConditional.quantize_to_budget")
             res = [(r.lambda_, r.bytes_pred, r.passes, r.status) for r in out_res]
         got = []
-        for i, it in enumerate(arr):
+        cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
+                   bitmaps, chans)
+        for i, c in enumerate(cols):
             lam, nbytes, passes, status = res[groups[i] if groups is not None else i]
-            got.append(BudgetQuantized(outs[i], it.n_changed, it.bits_q_before, it.bits_q_after, it.abs_max, bitmaps[i], chans[i], float(lam), int(nbytes),
-                                       status != _lib.FGMM_BUDGET_UNMET, int(passes)))
+            got.append(BudgetQuantized(*c, float(lam), int(nbytes), status != _lib.FGMM_BUDGET_UNMET, int(passes)))
         return got
 
     def quantize_to_budget(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, budget_bytes: int, *, lambda_max: float = 16.0,
