@@ -23,6 +23,7 @@ MODES = {"polya": 0, "as": 1, "logistic": 2}  # numbering of the reference CODE 
 
 FGMM_BUDGET_UNMET = 7  # fgmm_budget_result.status: not an error - no lambda up to lambda_max meets the group's byte budget
 FGMM_RDCURVE_MAX = 16  # lambdas per fgmm_gmc_rdcurve_batch call
+FGMM_RDO_W_MAX = 256.0  # largest factor of a weighted call's chan_w / pos_w (section 3e)
 STATUS_NAMES = {1: "FGMM_ERR_INVALID", 2: "FGMM_ERR_NO_DEVICE", 3: "FGMM_ERR_HIP", 4: "FGMM_ERR_NOMEM",
                 5: "FGMM_ERR_STREAM", 6: "FGMM_ERR_UNSUPPORTED"}
 
@@ -76,6 +77,11 @@ class fgmm_rdcurve_item(C.Structure):
 class fgmm_budget_result(C.Structure):
     """one group's result of fgmm_gmc_rdoq_budget_batch (section 3d)"""
     _fields_ = [("lambda_", C.c_double), ("bytes_pred", C.c_uint64), ("passes", C.c_int32), ("status", C.c_int32)]
+
+
+class fgmm_rdo_weights(C.Structure):
+    """one item's factors of the weighted calls (section 3e): device float32 ``chan_w[M]`` / ``pos_w[hw]``, either may be null"""
+    _fields_ = [("chan_w", C.c_void_p), ("pos_w", C.c_void_p)]
 
 
 def _item_dtype(struct=fgmm_item):
@@ -167,6 +173,10 @@ SIGNATURES = {
     "fgmm_gmc_rdcurve_batch": (_i, [_p, _p, C.POINTER(fgmm_rdcurve_item), _i, _i, _i, C.POINTER(C.c_double), _i]),
     "fgmm_gmc_rdoq_budget_batch": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_uint64), C.c_double, _i,
                                         C.POINTER(fgmm_budget_result)]),
+    "fgmm_gmc_rdoq_batch_w": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.c_double, C.POINTER(fgmm_rdo_weights)]),
+    "fgmm_gmc_rdcurve_batch_w": (_i, [_p, _p, C.POINTER(fgmm_rdcurve_item), _i, _i, _i, C.POINTER(C.c_double), _i, C.POINTER(fgmm_rdo_weights)]),
+    "fgmm_gmc_rdoq_budget_batch_w": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_uint64), C.c_double, _i,
+                                          C.POINTER(fgmm_budget_result), C.POINTER(fgmm_rdo_weights)]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

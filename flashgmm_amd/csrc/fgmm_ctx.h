@@ -535,6 +535,9 @@ struct LatentNeeds {           // what a call asks of the frame's workspace
 // The front half.  Workspace: [EncDesc x count (x 2 with census2)][the call's descriptors][small: every item's census | every item's
 // sums][device only].  layout(), then the caller fills its descriptors and `out`, then start(): the one upload, the small region and
 // the outputs zeroed, the census of y.  finish() after the call's own kernel: the second census, the small region from `from` back, the wait.
+// With `w` set before layout() and some factor array in it (section 3e): an RdoWDesc per item after the call's descriptors and a word
+// per item at the head of the small region; start() lets pos_w take part in the load-width decision and runs the domain check beside
+// the census, the first finish() that reads the small region whole reports a factor outside the domain (FGMM_ERR_INVALID, item named).
 struct LatentFrame {
   fgmm_ctx *ctx;
   dev::Stream stream;
@@ -546,6 +549,11 @@ struct LatentFrame {
   std::vector<CensusOff> census, census_out;
   std::vector<size_t> o_back, o_acc; // per item: its sums (back_item + back_chan * M words), its device-only words
   std::vector<float *> out;          // per item, null or [M * hw]: what the call's kernel writes in part - tested by enc_vec4_ok, zeroed by start()
+  const fgmm_rdo_weights *w = nullptr; // [count] or null: the items' factors (section 3e)
+  bool weighted = false, w_check = true, w_checked = false; // some array is given | start() checks the domain | a finish() has looked
+  size_t o_wdesc = 0, o_wbad = 0;
+  const float *chan_w(int i) const { return weighted ? w[i].chan_w : nullptr; }
+  const float *pos_w(int i) const { return weighted ? w[i].pos_w : nullptr; }
   LatentFrame(fgmm_ctx *c, dev::Stream s, std::vector<LatentIn> items, int clamp_) : ctx(c), stream(s), in(std::move(items)), count((int)in.size()), clamp(clamp_) {}
   const EncDesc *dd(bool of_out = false) const { return ws<const EncDesc>(ctx->d_ws, o_descs) + (of_out ? count : 0); }
   int layout(const LatentNeeds &n);
@@ -554,7 +562,9 @@ struct LatentFrame {
 };
 // ---- fgmm_rdoq.cpp: the RDOQ call with the context's lock held, for the budget call (fgmm_rdcurve.cpp) too --------------------------
 int rdoq_check_items(const fgmm_rdoq_item *items, int count); // check_latent_items, then what is RDOQ's own: y_rdo null or over y
-int rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride);
+// w: the items' factors or null; w_check false: the caller's frame has checked their domain in this call already
+int rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride,
+             const fgmm_rdo_weights *w = nullptr, bool w_check = true);
 
 constexpr size_t kCounterBytes = kTabCounters * sizeof(unsigned long long); // per launch unit, see DecDesc::counters
 

@@ -156,7 +156,7 @@ template <typename PT> struct EncPlanes<PT, 1> {
 };
 
 // ---------------------------------------------------------------------------------------------------------
-// The decision of include/flashgmm_amd.h section 3c, shared by rdoq_kernel (fgmm_rdoq.hip: one lambda, the symbol written) and
+// The decision of include/flashgmm_amd.h sections 3c and 3e, shared by rdoq_kernel (fgmm_rdoq.hip: one lambda, the symbol written) and
 // rdcurve_kernel (fgmm_rdcurve.hip: the same latent decided at up to 16 lambdas, nothing written): one text, so the two cannot drift.
 // rdoq_price: a latent of a coded channel -> vq = round(y) and the exact costs cm, c0, cp of vq - 1, vq, vq + 1.  false: the latent is
 // not finite or |vq| > 2^20 - it keeps round(y), and all three are rate_kernel's price of it.
@@ -182,15 +182,17 @@ __device__ __forceinline__ bool rdoq_price(float y, const float (&mu)[4], const 
   cp = rate_cost_q(entry_from_edges(q[2], q[3], vi + 1, bp), vi + 1, L);
   return true;
 }
-// d0, d: the distances (double)y - (double)v of round(y) and of the choice, for a caller that goes on with them
-__device__ __forceinline__ int rdoq_choose(float y, float vq, uint32_t cm, uint32_t c0, uint32_t cp, double lam_q, double &d0, double &d) {
+// d0, d: the distances (double)y - (double)v of round(y) and of the choice, for a caller that goes on with them.  wt: the latent's
+// factor of section 3e, chan_w[c] * pos_w[p] as ONE binary64 product; 1.0 (a constant in the unweighted instantiations: the multiply
+// folds away, and would change no bit if it stayed) gives 3c
+__device__ __forceinline__ int rdoq_choose(float y, float vq, uint32_t cm, uint32_t c0, uint32_t cp, double lam_q, double wt, double &d0, double &d) {
   const float vm = vq - 1.0f, vp = vq + 1.0f;
   const double yd = (double)y;
   d0 = yd - (double)vq;
   const double dm = yd - (double)vm, dp = yd - (double)vp;
-  const double j0 = d0 * d0 + lam_q * (double)c0;
-  const double jm = dm * dm + lam_q * (double)cm;
-  const double jp = dp * dp + lam_q * (double)cp;
+  const double j0 = wt * (d0 * d0) + lam_q * (double)c0;
+  const double jm = wt * (dm * dm) + lam_q * (double)cm;
+  const double jp = wt * (dp * dp) + lam_q * (double)cp;
   int pick = 0;
   double jb = j0;
   d = d0;
@@ -204,6 +206,25 @@ __device__ __forceinline__ int rdoq_choose(float y, float vq, uint32_t cm, uint3
     d = dp;
   }
   return pick;
+}
+// The factors of section 3e as the weighted instantiations read them.  chan_w[c] is wave-uniform: a scalar load.  pos_w: the lane's VEC
+// positions from p0, one VEC-wide load in POSITION index (no stride_p).  Every coded channel of an item reads the same hw floats again,
+// so these are ordinary cached loads, not the frame's non-temporal ldg.  A null array: every factor 1
+__device__ __forceinline__ float rdo_chan_w(const float *__restrict__ chan_w, int c) { return chan_w ? ((const FGMM_GLOBAL float *)chan_w)[c] : 1.0f; }
+template <int VEC> __device__ __forceinline__ void rdo_pos_w(const float *__restrict__ pos_w, int64_t p0, float (&w)[VEC]) {
+  static_assert(VEC == 1 || VEC == 4, "rdoq_kernel and rdcurve_kernel run 1 or 4 positions per lane");
+  if (pos_w) { // (wave-uniform)
+    if constexpr (VEC == 1) {
+      w[0] = ((const FGMM_GLOBAL float *)pos_w)[p0];
+    } else {
+      const float4_t t = *(const FGMM_GLOBAL float4_t *)(pos_w + p0);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) w[e] = t[e];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) w[e] = 1.0f;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -46,7 +46,10 @@ int LatentFrame::layout(const LatentNeeds &n) {
   Arena ar;
   o_descs = ar.take(sizeof(EncDesc) * (size_t)count * (census2 ? 2 : 1));
   o_call = ar.take(n.desc_bytes * (size_t)count);
+  for (int i = 0; w && i < count; ++i) weighted = weighted || w[i].chan_w || w[i].pos_w;
+  if (weighted) o_wdesc = ar.take(sizeof(RdoWDesc) * (size_t)count);
   o_small = ar.take(0);
+  if (weighted) o_wbad = ar.take(sizeof(uint32_t) * (size_t)count);
   census.resize((size_t)count), census_out.resize((size_t)count), o_back.resize((size_t)count), o_acc.resize((size_t)count);
   out.assign((size_t)count, nullptr);
   for (int i = 0; i < count; ++i) {
@@ -78,6 +81,10 @@ int LatentFrame::start() {
     const LatentIn &it = in[(size_t)i];
     if (census2) census_desc(hd[count + i], ctx, census_out[(size_t)i], out[(size_t)i], nullptr, it.M, it.hw, clamp);
     vec4 = vec4 && enc_vec4_ok(hd[i], out[(size_t)i], f16);
+    if (weighted) { // pos_w is read VEC positions wide as the planes are (hw % 4 is enc_vec4_ok's)
+      ws<RdoWDesc>(ctx->h_ws, o_wdesc)[i] = RdoWDesc{w[i].chan_w, w[i].pos_w};
+      vec4 = vec4 && (reinterpret_cast<uintptr_t>(w[i].pos_w) & 15) == 0;
+    }
   }
   vec = vec4 ? 4 : 1;
   for (const LatentIn &it : in) linear = linear && it.hw % (64 * vec) == 0;
@@ -88,6 +95,8 @@ int LatentFrame::start() {
     if (out[(size_t)i] && n) DEV_TRY(dev::memset_async(out[(size_t)i], 0, sizeof(float) * n, stream));
   }
   LAUNCH_TRY(launch_quant_stats(dd(), count, M_max, stream));
+  if (weighted && w_check)
+    LAUNCH_TRY(launch_rdo_weights_check(dd(), ws<const RdoWDesc>(ctx->d_ws, o_wdesc), ws<uint32_t>(ctx->d_ws, o_wbad), count, M_max, hw_max, stream));
   return FGMM_OK;
 }
 
@@ -96,6 +105,12 @@ int LatentFrame::finish(size_t from) {
   if (o_dev > from) DEV_TRY(dev::copy_async(ctx->h_ws + from, ctx->d_ws + from, o_dev - from, dev::kD2H, stream));
   DEV_TRY(dev::event_record(ctx->events[0], stream));
   DEV_TRY(dev::event_sync(ctx->events[0]));
+  if (weighted && w_check && !w_checked && from <= o_wbad) {
+    w_checked = true;
+    for (int i = 0; i < count; ++i)
+      if (ws<const uint32_t>(ctx->h_ws, o_wbad)[i])
+        return fail(FGMM_ERR_INVALID, "item %d: a factor of chan_w / pos_w is not finite or lies outside [0, %g]", i, (double)FGMM_RDO_W_MAX);
+  }
   return FGMM_OK;
 }
 } // namespace fgmm

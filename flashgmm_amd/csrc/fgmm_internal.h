@@ -299,10 +299,20 @@ struct RdoqDesc {                   // item i of an rdoq_kernel launch, beside i
   unsigned long long *chan_before;  // device [M], zeroed by the host: sum of cost_q(round(y)) over channel c (0: not coded)
   unsigned long long *chan_after;   // device [M], zeroed by the host: sum of cost_q(chosen symbol)
   unsigned long long *chan_changed; // device [M], zeroed by the host: latents whose symbol is not round(y)
+  double lam_q;                     // the item's lambda * 2^-FGMM_RATE_Q (the objective is in units of one squared quantisation step): per item, so
+                                    // that ONE launch serves a budget call whose groups end at lambdas of their own
+  const float *chan_w, *pos_w;      // section 3e: device [M] / [hw] factors of the distortion, either may be null (every factor 1); read by the
+                                    // weighted instantiation only
 };
-// the addressing of launch_rate; lam_q = lambda * 2^-FGMM_RATE_Q (the objective is in units of one squared quantisation step)
-int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, double lam_q, int count, int M_max, int64_t hw_max,
+// the addressing of launch_rate.  weighted: some item of the batch carries factors (section 3e) - the instantiation that reads them
+int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, bool weighted, int count, int M_max, int64_t hw_max,
                 int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
+// section 3e's domain check, in the frame's front half beside quant_stats_kernel: item i's word bad[i] (zeroed by the host) becomes
+// non-zero when a factor of either array is not finite or lies outside [0, FGMM_RDO_W_MAX]
+struct RdoWDesc {
+  const float *chan_w, *pos_w; // device [M] / [hw] or null
+};
+int launch_rdo_weights_check(const EncDesc *d_descs, const RdoWDesc *d_wdescs, uint32_t *bad, int count, int M_max, int64_t hw_max, void *stream);
 
 // ---- the rate-distortion curve and quantisation to a byte budget (fgmm_rdcurve.hip, fgmm_rdcurve.cpp; header section 3d) ---------
 constexpr int kRdCurveRow = 1 + 3 * FGMM_RDCURVE_MAX; // one row of sums: [0] bits_q_before, then 16 each of bits_q_after, n_changed, ddist_q
@@ -311,9 +321,10 @@ struct RdCurveDesc {                // item i of an rdcurve_kernel launch, besid
   unsigned long long *sums;         // device [kRdCurveRow], zeroed by the host: the item's, folded from chan_acc by rdcurve_fold_kernel
   int32_t n_lambda, pad_;           // 1 .. FGMM_RDCURVE_MAX; 0: the item takes no part in this launch
   double lam_q[FGMM_RDCURVE_MAX];   // lambda_j * 2^-FGMM_RATE_Q - per item, so that one launch serves groups with grids of their own
+  const float *chan_w, *pos_w;      // section 3e, as RdoqDesc's
 };
 // the addressing of launch_rdoq; rdcurve_kernel, then rdcurve_fold_kernel
-int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, int count, int M_max, int64_t hw_max, int64_t n_max,
+int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, bool weighted, int count, int M_max, int64_t hw_max, int64_t n_max,
                    bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
 
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------

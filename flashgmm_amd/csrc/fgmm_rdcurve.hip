@@ -23,7 +23,9 @@ namespace fgmm {
 #ifndef FGMM_RDCURVE_WAVES
 #define FGMM_RDCURVE_WAVES 4 // min waves per SIMD, as rdoq_kernel: the pricing is the same
 #endif
-template <int MODE, int VEC, bool CLAMPED, typename PT, bool LINEAR>
+// WEIGHTED: section 3e, as rdoq_kernel's.  The lane keeps the FLOAT factor of each of its positions (VEC registers, not 2 * VEC) and the
+// channel's in a scalar; their binary64 product is formed inside the lambda loop - exact, so where it is formed changes no bit
+template <int MODE, int VEC, bool CLAMPED, typename PT, bool LINEAR, bool WEIGHTED>
 __global__ __launch_bounds__(kBlock, FGMM_RDCURVE_WAVES) void rdcurve_kernel(const EncDesc *__restrict__ descs, const RdCurveDesc *__restrict__ cdescs,
                                                                              const uint32_t *__restrict__ L) {
   const RdCurveDesc &r = cdescs[blockIdx.z];
@@ -42,7 +44,14 @@ __global__ __launch_bounds__(kBlock, FGMM_RDCURVE_WAVES) void rdcurve_kernel(con
 #pragma unroll
   for (int e = 0; e < VEC; ++e) y[e] = vq[e] = 0.0f, cm[e] = c0[e] = cp[e] = 0u;
   unsigned long long before = 0;
+  float cw = 1.0f, pw[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) pw[e] = 1.0f;
   if (active) {
+    if constexpr (WEIGHTED) {
+      cw = rdo_chan_w(r.chan_w, c);
+      rdo_pos_w<VEC>(r.pos_w, p0, pw);
+    }
     enc_load_y<VEC>(d, c, p0, y);
     EncPlanes<PT, VEC> P;
     P.load(d, c, p0);
@@ -65,13 +74,14 @@ __global__ __launch_bounds__(kBlock, FGMM_RDCURVE_WAVES) void rdcurve_kernel(con
     int changed = 0; // the wave's, the same on every lane (ballots)
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      double d0, dv;
-      const int pick = rdoq_choose(y[e], vq[e], cm[e], c0[e], cp[e], lam_q, d0, dv);
+      double d0, dv, wt = 1.0;
+      if constexpr (WEIGHTED) wt = (double)cw * (double)pw[e];
+      const int pick = rdoq_choose(y[e], vq[e], cm[e], c0[e], cp[e], lam_q, wt, d0, dv);
       after += pick < 0 ? cm[e] : pick > 0 ? cp[e] : c0[e];
       changed += __popcll(__ballot(pick != 0));
-      if (pick) { // what the move adds to the squared error, in units of 2^-32, rounded half to even: an integer, so the sum has no order
+      if (pick) { // what the move adds to the (weighted) squared error, in units of 2^-32, rounded half to even: an integer, so the sum has no order
         const double inc = dv * dv - d0 * d0;
-        dd += (unsigned long long)(long long)__builtin_rint(inc * 0x1p32);
+        dd += (unsigned long long)(long long)__builtin_rint((wt * inc) * 0x1p32);
       }
       if constexpr (VEC == 1) break;
     }
@@ -109,14 +119,18 @@ struct RdCurveLaunch {
   const EncDesc *d;
   const RdCurveDesc *r;
   const uint32_t *L;
+  bool weighted;
   template <int MODE, int VEC, bool CLAMPED, typename PT, bool LINEAR> void go(dim3 grid, hipStream_t s) const {
-    hipLaunchKernelGGL((rdcurve_kernel<MODE, VEC, CLAMPED, PT, LINEAR>), grid, dim3(kBlock), 0, s, d, r, L);
+    if (weighted)
+      hipLaunchKernelGGL((rdcurve_kernel<MODE, VEC, CLAMPED, PT, LINEAR, true>), grid, dim3(kBlock), 0, s, d, r, L);
+    else
+      hipLaunchKernelGGL((rdcurve_kernel<MODE, VEC, CLAMPED, PT, LINEAR, false>), grid, dim3(kBlock), 0, s, d, r, L);
   }
 };
-int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, int count, int M_max, int64_t hw_max, int64_t n_max,
+int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, bool weighted, int count, int M_max, int64_t hw_max, int64_t n_max,
                    bool linear, int mode, int vec, bool clamped, bool f16, void *stream) {
   if (count <= 0 || M_max <= 0 || hw_max <= 0) return 0;
-  if (const int e = enc_launch<false>(RdCurveLaunch{d_descs, d_cdescs, d_log2}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream)) return e;
+  if (const int e = enc_launch<false>(RdCurveLaunch{d_descs, d_cdescs, d_log2, weighted}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream)) return e;
   hipLaunchKernelGGL(rdcurve_fold_kernel, dim3((unsigned)count), dim3(kBlock), 0, (hipStream_t)stream, d_descs, d_cdescs);
   return (int)hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// fgmm_rdoq.cpp — rate-distortion optimised quantisation of a batch of latents (include/flashgmm_amd.h section 3c).  On the frame of
+// fgmm_rdoq.cpp — rate-distortion optimised quantisation of a batch of latents (include/flashgmm_amd.h sections 3c and 3e).  On the frame of
 // fgmm_estimate.cpp (quant_stats_kernel and chan_compact_kernel give the channels the compress call would code for y): rdoq_kernel
 // (fgmm_rdoq.hip) in place of rate_kernel, then the frame's second census, over y_rdo: its abs_max and zero_bitmap are what a compress
 // call of y_rdo will return.  Nothing but the per-channel census and sums crosses PCIe.  A file of its own, as fgmm_estimate.cpp: the
@@ -8,9 +8,11 @@
 using namespace fgmm;
 
 // lambdas[i * lambda_stride] is item i's lambda (stride 0: one for the call, fgmm_gmc_rdoq_batch; 1: the budget call of section 3d, whose
-// groups end at lambdas of their own): consecutive items of one lambda share a launch of rdoq_kernel, everything else is once per call
-int fgmm::rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride) {
+// groups end at lambdas of their own): it travels in the item's RdoqDesc, so either way rdoq_kernel is launched once
+int fgmm::rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride,
+                   const fgmm_rdo_weights *w, bool w_check) {
   LatentFrame fr(ctx, stream, latent_in(items, count), clamp);
+  fr.w = w, fr.w_check = w_check;
   int rc;
   if ((rc = fr.layout({sizeof(RdoqDesc), 0, 3, 0, true}))) return rc; // per channel: bits before | bits after | latents changed
   RdoqDesc *hq = ws<RdoqDesc>(ctx->h_ws, fr.o_call);
@@ -19,15 +21,12 @@ int fgmm::rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int
     hq[i].chan_before = ws<unsigned long long>(ctx->d_ws, fr.o_back[(size_t)i]);
     hq[i].chan_after = hq[i].chan_before + items[i].M;
     hq[i].chan_changed = hq[i].chan_after + items[i].M;
+    hq[i].lam_q = lambdas[(size_t)i * lambda_stride] * 0x1p-24;
+    hq[i].chan_w = fr.chan_w(i), hq[i].pos_w = fr.pos_w(i);
   }
   if ((rc = fr.start())) return rc;
-  const RdoqDesc *dq = ws<const RdoqDesc>(ctx->d_ws, fr.o_call);
-  for (int i0 = 0, i1; i0 < count; i0 = i1) {
-    const double lambda = lambdas[(size_t)i0 * lambda_stride];
-    for (i1 = i0 + 1; i1 < count && lambdas[(size_t)i1 * lambda_stride] == lambda;) ++i1;
-    LAUNCH_TRY(launch_rdoq(fr.dd() + i0, dq + i0, ctx->d_rate_log2, lambda * 0x1p-24, i1 - i0, fr.M_max, fr.hw_max, fr.n_max, fr.linear, mode, fr.vec,
-                           clamp != 0, fr.f16, stream));
-  }
+  LAUNCH_TRY(launch_rdoq(fr.dd(), ws<const RdoqDesc>(ctx->d_ws, fr.o_call), ctx->d_rate_log2, fr.weighted, count, fr.M_max, fr.hw_max, fr.n_max, fr.linear,
+                         mode, fr.vec, clamp != 0, fr.f16, stream));
   if ((rc = fr.finish(fr.o_small))) return rc; // (with the census of y_rdo)
   // ---- per item, on the host: the census of y_rdo as the compress call will read it (fgmm_encode.cpp side_info), the sums ------
   for (int i = 0; i < count; ++i) {
@@ -63,11 +62,15 @@ int fgmm::rdoq_check_items(const fgmm_rdoq_item *items, int count) {
 
 extern "C" {
 
-int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda) {
+int fgmm_gmc_rdoq_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda,
+                          const fgmm_rdo_weights *w) {
   if (!(lambda >= 0.0 && lambda < (double)INFINITY)) return fail(FGMM_ERR_INVALID, "lambda = %g: must be finite and >= 0", lambda);
   if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
   if (int rc = rdoq_check_items(items, count)) return rc;
-  return latent_call(ctx, stream, items, count, [&](dev::Stream s) { return rdoq_run(ctx, s, items, count, mode, clamp_scales, &lambda, 0); });
+  return latent_call(ctx, stream, items, count, [&](dev::Stream s) { return rdoq_run(ctx, s, items, count, mode, clamp_scales, &lambda, 0, w); });
+}
+int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda) {
+  return fgmm_gmc_rdoq_batch_w(ctx, stream, items, count, mode, clamp_scales, lambda, nullptr);
 }
 
 } // extern "C"

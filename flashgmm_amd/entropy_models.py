@@ -208,7 +208,9 @@ class RdCurve:
     ``bits_q_before``  exact cost of ``round(y)``, units of 2^-24 bit
     ``bits_q_after``   per lambda: exact cost of the chosen symbols;  ``bits_after`` in bits, ``nbytes`` the predicted stream length
     ``n_changed``      per lambda: latents whose symbol is not ``round(y)``
-    ``ddist_q``        per lambda: squared error the moves add over ``round(y)``, units of 2^-32;  ``distortion_added`` as floats
+    ``ddist_q``        per lambda: squared error the moves add over ``round(y)``, units of 2^-32;  ``distortion_added`` as floats.
+                       WEIGHTED - each latent's share times ``channel_weights[c] * position_weights[p]`` - when the call was given
+                       weights (section 3e)
     ``n_symbols``      symbols coded (coded channels x h x w)"""
 
     __slots__ = ("lambdas", "bits_q_before", "bits_q_after", "n_changed", "ddist_q", "n_symbols")
@@ -269,6 +271,73 @@ class _LatentItems:
               for M, y in zip(self.items["M"].tolist(), self.ys)]
         self.items[field] = [t.data_ptr() for t in ts]
         return ts
+
+
+def _rdo_weight_lists(ys, channel_weights, position_weights):
+    """THE validation of the factors of a weighted call (include/flashgmm_amd.h section 3e), before anything native runs -> None (no
+    factors at all), or per item ``(chan_w or None, pos_w or None)``: contiguous float32 tensors ``[M]`` / ``[h * w]`` on the
+    latents' device.  ``channel_weights``: one ``[M]`` tensor for the batch, or a sequence of one (or None) per item;
+    ``position_weights``: per item ``[h, w]`` or ``[1, 1, h, w]`` (or None), ``[N, 1, h, w]`` for stacked latents.  The factors'
+    VALUES (finite, 0 .. 256) are checked on the device by the call itself."""
+    if channel_weights is None and position_weights is None:
+        return None
+    stacked = isinstance(ys, Tensor)
+    N = ys.shape[0] if stacked else len(ys)
+    lat = [ys[i:i + 1] for i in range(N)] if stacked else list(ys)
+
+    def one(t, what, i, shapes):
+        if t is None:
+            return None
+        if not isinstance(t, Tensor):
+            raise TypeError(f"{what}[{i}]: a float32 tensor or None, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}[{i}]: must be float32, got {t.dtype}")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{what}[{i}]: shape {tuple(t.shape)}, expected {' or '.join(str(s) for s in shapes)}")
+        if t.device != lat[i].device:
+            raise ValueError(f"{what}[{i}]: on {t.device}, the latents are on {lat[i].device}")
+        return t.contiguous().view(-1)
+
+    def per_item(arg, what, shared_ok):
+        if arg is None:
+            return [None] * N
+        if isinstance(arg, Tensor):
+            if shared_ok:
+                return [arg] * N
+            if stacked:
+                if arg.dim() != 4 or arg.shape[0] != N:
+                    raise ValueError(f"{what}: shape {tuple(arg.shape)}, expected [{N}, 1, h, w] for stacked latents")
+                return [arg[i:i + 1] for i in range(N)]
+            raise ValueError(f"{what}: a sequence of one tensor (or None) per item for a sequence of latents")
+        arg = list(arg)
+        if len(arg) != N:
+            raise ValueError(f"{what}: one per item ({N}), got {len(arg)}")
+        return arg
+
+    cws = per_item(channel_weights, "channel_weights", True)
+    pws = per_item(position_weights, "position_weights", False)
+    out = []
+    for i, y in enumerate(lat):
+        if y.dim() != 4:
+            raise ValueError(f"latent {i}: expected 4 dimensions, got {tuple(y.shape)}")
+        M, h, w = y.shape[1:]
+        out.append((one(cws[i], "channel_weights", i, [(M,)]), one(pws[i], "position_weights", i, [(h, w), (1, 1, h, w)])))
+    return out
+
+
+def _one_item(t):
+    """the single calls' ``position_weights`` as the batch calls take it"""
+    return None if t is None else [t]
+
+
+def _rdo_weights_array(lists):
+    """per item ``(chan_w, pos_w)`` tensors -> the ``fgmm_rdo_weights[N]`` ctypes passes (None: no factors, the unweighted call)"""
+    if lists is None or all(c is None and p is None for c, p in lists):
+        return None
+    arr = (_lib.fgmm_rdo_weights * len(lists))()
+    for a, (c, p) in zip(arr, lists):
+        a.chan_w, a.pos_w = (c.data_ptr() if c is not None else None), (p.data_ptr() if p is not None else None)
+    return arr
 
 
 def _take_ckpts_many(device: int, ptrs, counts):
@@ -742,21 +811,28 @@ class GaussianMixtureConditional(nn.Module):
                                         per_latent=per_latent)[0]
 
     def quantize_rdo_batch(self, ys, scales, means, weights, lam: float, *, weights_are_logits: bool = False,
-                           per_channel: bool = False) -> List[RdoQuantized]:
+                           per_channel: bool = False, channel_weights=None, position_weights=None) -> List[RdoQuantized]:
         """Rate-distortion optimised quantisation: per latent of a channel ``compress_batch`` would code, ``round(y)`` or one of its
         two neighbours, whichever minimises ``(y - v)**2 + lam * bits(v)`` - ``bits`` the coder's own exact cost of ``v`` under that
         latent's mixture (the rule, exactly: include/flashgmm_amd.h section 3c).  One kernel; nothing is coded.  Inputs as
         ``compress_batch`` takes them - sequences of ``[1, M, h, w]`` / ``[1, K*M, h, w]`` tensors, or stacked; ``lam`` finite, >= 0
         (0 returns ``round(y)``).  -> one ``RdoQuantized`` per item; ``compress(result.y, ...)`` then codes it through the unchanged
-        encode path."""
+        encode path.
+
+        ``channel_weights`` / ``position_weights`` (section 3e) weight the squared error of the latent at channel ``c``, position ``p``
+        by ``channel_weights[c] * position_weights[p]``: float32 tensors on the latents' device, every factor finite and in
+        ``[0, 256]``.  ``channel_weights``: ``[M]`` shared by the batch, or a sequence of one (or None) per item.
+        ``position_weights``: ``[h, w]`` or ``[1, 1, h, w]`` per item, or ``[N, 1, h, w]`` for stacked input.  None, or arrays of
+        ones: exactly the unweighted result."""
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
         lam = float(lam)
         if not (0.0 <= lam < float("inf")):
             raise ValueError(f"lam = {lam!r}: must be finite and >= 0")
+        wl = _rdo_weight_lists(ys, channel_weights, position_weights)
         flags = _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0
         nat = _lib.native()
-        if isinstance(ys, Tensor) and nat is not None and scales.dim() == 4 and scales.shape[0] > 0:  # the compiled boundary: items built in C++
+        if wl is None and isinstance(ys, Tensor) and nat is not None and scales.dim() == 4 and scales.shape[0] > 0:  # the compiled boundary: items built in C++
             y, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(ys, scales, means, weights)
             dev = scales.device
             out = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
@@ -773,17 +849,23 @@ class GaussianMixtureConditional(nn.Module):
             return []
         outs, bitmaps = L.output("y_rdo", torch.float32, per_latent=True), L.output("zero_bitmap", torch.int64)
         chans = L.output("chan_bits_q_after", torch.int64) if per_channel else [None] * L.N
-        rc = _lib.lib().fgmm_gmc_rdoq_batch(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales), lam)
-        _lib.check(rc, "GaussianMixtureConditional.quantize_rdo")
+        warr = _rdo_weights_array(wl)
+        if nat is not None:
+            nat.rdoq_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), lam,
+                           C.addressof(warr) if warr is not None else 0)
+        else:
+            rc = _lib.lib().fgmm_gmc_rdoq_batch_w(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales), lam, warr)
+            _lib.check(rc, "GaussianMixtureConditional.quantize_rdo")
         items = L.items
         cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
                    bitmaps, chans)
         return [RdoQuantized(*c) for c in cols]
 
     def quantize_rdo(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lam: float, *, weights_are_logits: bool = False,
-                     per_channel: bool = False) -> RdoQuantized:
+                     per_channel: bool = False, channel_weights=None, position_weights=None) -> RdoQuantized:
         """-> the ``RdoQuantized`` of one latent (``quantize_rdo_batch``)"""
-        return self.quantize_rdo_batch([y], [scales], [means], [weights], lam, weights_are_logits=weights_are_logits, per_channel=per_channel)[0]
+        return self.quantize_rdo_batch([y], [scales], [means], [weights], lam, weights_are_logits=weights_are_logits, per_channel=per_channel,
+                                       channel_weights=channel_weights, position_weights=_one_item(position_weights))[0]
 
     def _latent_items(self, struct, ys, scales, means, weights, logits: bool) -> _LatentItems:
         """THE item builder of the calls that price latents (estimate, RDOQ, curve, budget): ``struct[N]`` with the input fields
@@ -809,41 +891,48 @@ class GaussianMixtureConditional(nn.Module):
         L.dev = dev
         return L
 
-    def rd_curve_batch(self, ys, scales, means, weights, lambdas, *, weights_are_logits: bool = False) -> List[RdCurve]:
+    def rd_curve_batch(self, ys, scales, means, weights, lambdas, *, weights_are_logits: bool = False, channel_weights=None,
+                       position_weights=None) -> List[RdCurve]:
         """What ``quantize_rdo_batch`` would report at every lambda of ``lambdas`` - the cost after, the latents moved, the distortion
         added - WITHOUT quantising: one kernel prices each latent once and decides it at up to 16 lambdas (include/flashgmm_amd.h
         section 3d); more are served in chunks of 16.  Inputs as ``quantize_rdo_batch`` takes them; ``lambdas`` finite, >= 0, in any
-        order.  -> one ``RdCurve`` per item."""
+        order.  ``channel_weights`` / ``position_weights``: as ``quantize_rdo_batch`` takes them - the curve is then the weighted
+        call's, ``ddist_q`` the weighted added distortion.  -> one ``RdCurve`` per item."""
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
         lambdas = [float(v) for v in lambdas]
         if not lambdas or not all(0.0 <= v < float("inf") for v in lambdas):
             raise ValueError(f"lambdas = {lambdas!r}: at least one, each finite and >= 0")
+        wl = _rdo_weight_lists(ys, channel_weights, position_weights)
         L = self._latent_items(_lib.fgmm_rdcurve_item, ys, scales, means, weights, weights_are_logits)
         if L.N == 0:
             return []
-        nat, items = _lib.native(), L.items
+        nat, items, warr = _lib.native(), L.items, _rdo_weights_array(wl)
         names = ("bits_q_after", "n_changed", "ddist_q")
         cols = [[] for _ in names]
         for at in range(0, len(lambdas), _lib.FGMM_RDCURVE_MAX):
             chunk = lambdas[at:at + _lib.FGMM_RDCURVE_MAX]
             if nat is not None:
-                nat.rdcurve_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), chunk)
+                nat.rdcurve_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), chunk,
+                                  C.addressof(warr) if warr is not None else 0)
             else:
-                rc = _lib.lib().fgmm_gmc_rdcurve_batch(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales),
-                                                       (C.c_double * len(chunk))(*chunk), len(chunk))
+                rc = _lib.lib().fgmm_gmc_rdcurve_batch_w(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales),
+                                                         (C.c_double * len(chunk))(*chunk), len(chunk), warr)
                 _lib.check(rc, "GaussianMixtureConditional.rd_curve")
             for col, name in zip(cols, names):
                 col.append(items[name][:, :len(chunk)].copy())
         cols = [np.concatenate(col, axis=1).tolist() for col in cols]
         return [RdCurve(lambdas, *c) for c in zip(items["bits_q_before"].tolist(), *cols, items["n_symbols"].tolist())]
 
-    def rd_curve(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lambdas, *, weights_are_logits: bool = False) -> RdCurve:
+    def rd_curve(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lambdas, *, weights_are_logits: bool = False,
+                 channel_weights=None, position_weights=None) -> RdCurve:
         """-> the ``RdCurve`` of one latent (``rd_curve_batch``)"""
-        return self.rd_curve_batch([y], [scales], [means], [weights], lambdas, weights_are_logits=weights_are_logits)[0]
+        return self.rd_curve_batch([y], [scales], [means], [weights], lambdas, weights_are_logits=weights_are_logits,
+                                   channel_weights=channel_weights, position_weights=_one_item(position_weights))[0]
 
     def quantize_to_budget_batch(self, ys, scales, means, weights, budget_bytes, *, groups=None, lambda_max: float = 16.0, refine: int = 2,
-                                 weights_are_logits: bool = False, per_channel: bool = False) -> List[BudgetQuantized]:
+                                 weights_are_logits: bool = False, per_channel: bool = False, channel_weights=None,
+                                 position_weights=None) -> List[BudgetQuantized]:
         """Rate-distortion optimised quantisation TO A BYTE BUDGET: lambda is searched on the rate-distortion curve by the fixed rule of
         include/flashgmm_amd.h section 3d - a 16-point grid 0, lambda_max * 2^-14 .. lambda_max, then ``refine`` (0..8) rounds of 16
         points between the last infeasible and the first feasible one, each round one pass of the curve kernel - then ``quantize_rdo_batch``'s
@@ -851,7 +940,9 @@ class GaussianMixtureConditional(nn.Module):
         one budget on the sum of their bytes (None: every item its own group).  ``budget_bytes``: an int for all groups, or one per
         group.  -> one ``BudgetQuantized`` per item (an ``RdoQuantized`` that carries ``lam``, ``bytes_pred``, ``budget_met``, ``passes``
         of its group).  The budget is on PREDICTED bytes: a real stream may be 4 bytes longer where ``estimate_bits`` may be off;
-        a channel the quantisation empties is no longer coded, so on that account the real size can only be smaller."""
+        a channel the quantisation empties is no longer coded, so on that account the real size can only be smaller.
+        ``channel_weights`` / ``position_weights``: as ``quantize_rdo_batch`` takes them - the search is the same, the decisions it
+        sums and the final quantisation are the weighted ones."""
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
         lambda_max, refine = float(lambda_max), int(refine)
@@ -859,8 +950,9 @@ class GaussianMixtureConditional(nn.Module):
             raise ValueError(f"lambda_max = {lambda_max!r}: must be finite and > 0")
         if not 0 <= refine <= 8:
             raise ValueError(f"refine = {refine!r}: must lie in 0 .. 8")
+        wl = _rdo_weight_lists(ys, channel_weights, position_weights)
         L = self._latent_items(_lib.fgmm_rdoq_item, ys, scales, means, weights, weights_are_logits)
-        N, items = L.N, L.items
+        N, items, warr = L.N, L.items, _rdo_weights_array(wl)
         if groups is not None:
             groups = [int(g) for g in groups]
             if len(groups) != N:
@@ -885,12 +977,12 @@ class GaussianMixtureConditional(nn.Module):
         nat = _lib.native()
         if nat is not None:
             res = nat.rdoq_budget_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), N, self._mode(), int(self.clamp_scales), groups, budgets,
-                                        lambda_max, refine)
+                                        lambda_max, refine, C.addressof(warr) if warr is not None else 0)
         else:
             out_res = (_lib.fgmm_budget_result * n_groups)()
-            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch(_lib.ctx(L.di), L.stream(), L.arr, N, self._mode(), int(self.clamp_scales),
-                                                       (C.c_int32 * N)(*groups) if groups is not None else None, n_groups,
-                                                       (C.c_uint64 * n_groups)(*budgets), lambda_max, refine, out_res)
+            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch_w(_lib.ctx(L.di), L.stream(), L.arr, N, self._mode(), int(self.clamp_scales),
+                                                         (C.c_int32 * N)(*groups) if groups is not None else None, n_groups,
+                                                         (C.c_uint64 * n_groups)(*budgets), lambda_max, refine, out_res, warr)
             _lib.check(rc, "GaussianMixtureConditional.quantize_to_budget")
             res = [(r.lambda_, r.bytes_pred, r.passes, r.status) for r in out_res]
         got = []
@@ -902,10 +994,12 @@ class GaussianMixtureConditional(nn.Module):
         return got
 
     def quantize_to_budget(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, budget_bytes: int, *, lambda_max: float = 16.0,
-                           refine: int = 2, weights_are_logits: bool = False, per_channel: bool = False) -> BudgetQuantized:
+                           refine: int = 2, weights_are_logits: bool = False, per_channel: bool = False, channel_weights=None,
+                           position_weights=None) -> BudgetQuantized:
         """-> the ``BudgetQuantized`` of one latent (``quantize_to_budget_batch``)"""
         return self.quantize_to_budget_batch([y], [scales], [means], [weights], budget_bytes, lambda_max=lambda_max, refine=refine,
-                                             weights_are_logits=weights_are_logits, per_channel=per_channel)[0]
+                                             weights_are_logits=weights_are_logits, per_channel=per_channel, channel_weights=channel_weights,
+                                             position_weights=_one_item(position_weights))[0]
 
     def compress(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, weights_are_logits: bool = False):
         """-> ((bytes, abs_max, zero_bitmap), y_quantized)     (entropy_models.py:833-867)"""

@@ -57,8 +57,17 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
                  entropy_parameters: Optional[nn.Module] = None, quantizer: str = "noise",
                  chunks: Tuple[str, ...] = ("scales", "means", "weights"), mode=None, param_dtype: torch.dtype = torch.float32,
                  fuse_softmax: bool = False, checkpoint_stride: int = 0, rdo_lambda: float = 0.0, target_bytes: Optional[int] = None,
-                 **kwargs: Any):
+                 rdo_channel_weights: Optional[Tensor] = None, **kwargs: Any):
         super().__init__()
+        # rdo_channel_weights: a float32 [M] buffer of per-channel factors of the squared error in the two quantisations below
+        # (include/flashgmm_amd.h section 3e: the latent-domain proxy for what a step in that channel costs the image), every factor in
+        # [0, 256].  With rdo_lambda == 0 and no target_bytes it does nothing and costs no launch
+        if rdo_channel_weights is not None:
+            rdo_channel_weights = torch.as_tensor(rdo_channel_weights)
+            if rdo_channel_weights.dtype != torch.float32 or rdo_channel_weights.dim() != 1:
+                raise ValueError("rdo_channel_weights must be a float32 tensor of shape [M]")
+            rdo_channel_weights = rdo_channel_weights.detach().clone()
+        self.register_buffer("rdo_channel_weights", rdo_channel_weights)
         # rdo_lambda > 0: rate-distortion optimised quantisation (GaussianMixtureConditional.quantize_rdo) - what is coded is, per latent,
         # round(.) or one of its two neighbours, whichever minimises (y - v)^2 + rdo_lambda * bits(v).  An encoder-side choice: the
         # decoder needs no switch.  0: plain rounding, no extra launch
@@ -128,24 +137,26 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         weighted_sum = torch.sum(me * we, dim=1)
         return weighted_sum, (me - weighted_sum.unsqueeze(1)).reshape(B, KM, H, W)
 
-    def _rdo(self, y_code: Tensor, planes, lam: float):
+    def _rdo(self, y_code: Tensor, planes, lam: float, position_weights: Optional[Tensor] = None):
         """(y_to_code, planes) with y_to_code replaced by its rate-distortion optimised quantisation (integer-valued: the encode path
         then rounds it to itself)"""
-        q = self.gaussian_mixture_conditional.quantize_rdo(y_code, *planes, lam, weights_are_logits=self.fuse_softmax)
+        q = self.gaussian_mixture_conditional.quantize_rdo(y_code, *planes, lam, weights_are_logits=self.fuse_softmax,
+                                                           channel_weights=self.rdo_channel_weights, position_weights=position_weights)
         return (q.y, *planes)
 
-    def coder_inputs(self, y: Tensor, ctx_params: Tensor):
+    def coder_inputs(self, y: Tensor, ctx_params: Tensor, position_weights: Optional[Tensor] = None):
         """What ``compress`` hands the entropy model: ``(y_to_code, scales, means, weights)``.  ``round(y_to_code)`` is
         the ``y_hat`` that ``compress`` returns (:127-149) — known before any coding happens.  With the codec's ``rdo_lambda`` > 0
         ``y_to_code`` is the RDOQ result of what would be rounded; with its ``target_bytes`` set, the RDOQ result at the lambda that
         budget determines."""
         if self.target_bytes is not None:
-            return self.coder_inputs_budget(y, ctx_params, self.target_bytes)
-        return self.coder_inputs_rdo(y, ctx_params, self.rdo_lambda)
+            return self.coder_inputs_budget(y, ctx_params, self.target_bytes, position_weights)
+        return self.coder_inputs_rdo(y, ctx_params, self.rdo_lambda, position_weights)
 
-    def coder_inputs_budget(self, y: Tensor, ctx_params: Tensor, budget_bytes: int):
+    def coder_inputs_budget(self, y: Tensor, ctx_params: Tensor, budget_bytes: int, position_weights: Optional[Tensor] = None):
         """``coder_inputs`` with what would be rounded quantised to ``budget_bytes`` of predicted bitstream
-        (``GaussianMixtureConditional.quantize_to_budget``, its default search)"""
+        (``GaussianMixtureConditional.quantize_to_budget``, its default search).  ``position_weights`` (``[h, w]`` or ``[1, 1, h, w]``)
+        and the codec's ``rdo_channel_weights`` weight the squared error (section 3e)"""
         budget = _check_target_bytes(budget_bytes)
         if budget is None:
             raise ValueError("budget_bytes must be given")
@@ -155,20 +166,22 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
             weighted_sum, means_hat = self._recentre(means_hat, weights)
             y_code = y - weighted_sum
         planes = self._planes(scales_hat, means_hat, weights)
-        q = self.gaussian_mixture_conditional.quantize_to_budget(y_code, *planes, budget, weights_are_logits=self.fuse_softmax)
+        q = self.gaussian_mixture_conditional.quantize_to_budget(y_code, *planes, budget, weights_are_logits=self.fuse_softmax,
+                                                                 channel_weights=self.rdo_channel_weights, position_weights=position_weights)
         return (q.y, *planes)
 
-    def coder_inputs_rdo(self, y: Tensor, ctx_params: Tensor, rdo_lambda: float):
-        """``coder_inputs`` with a given ``rdo_lambda`` in place of the codec's own (0: plain rounding, no extra launch)"""
+    def coder_inputs_rdo(self, y: Tensor, ctx_params: Tensor, rdo_lambda: float, position_weights: Optional[Tensor] = None):
+        """``coder_inputs`` with a given ``rdo_lambda`` in place of the codec's own (0: plain rounding, no extra launch - weights then do
+        nothing).  ``position_weights``: as ``coder_inputs_budget`` takes it"""
         lam = _check_rdo_lambda(rdo_lambda)
         scales_hat, means_hat, weights = self._params(ctx_params)
         if self.quantizer == "noise":
             planes = self._planes(scales_hat, means_hat, weights)
-            return self._rdo(y, planes, lam) if lam > 0 else (y, *planes)
+            return self._rdo(y, planes, lam, position_weights) if lam > 0 else (y, *planes)
         weighted_sum, means_rel = self._recentre(means_hat, weights)
         d = y - weighted_sum
         if lam > 0:
-            return self._rdo(d, self._planes(scales_hat, means_rel, weights), lam)
+            return self._rdo(d, self._planes(scales_hat, means_rel, weights), lam, position_weights)
         # quantize_ste (compressai/ops/ops.py:66-80) is (round(d) - d) + d: the value of round(d), but +0.0 where
         # round(d) is -0.0 — kept, so that the returned y_hat has the reference's bits
         return ((torch.round(d) - d) + d, *self._planes(scales_hat, means_rel, weights))
@@ -303,6 +316,8 @@ class CheckerboardLatentCodec(nn.Module):
         self.context_prediction = context_prediction or nn.Identity()
         self.latent_codec = nn.ModuleDict(latent_codec if latent_codec is not None
                                           else {"y": GaussianMixtureConditionalLatentCodec()})
+        if self.fuse_head and getattr(self.latent_codec["y"], "rdo_channel_weights", None) is not None:
+            raise RuntimeError("rdo_channel_weights together with fuse_head is not supported: RDOQ needs the parameter planes the fused head never writes")
 
     def __getitem__(self, key: str) -> nn.Module:
         return self.latent_codec[key]
@@ -332,14 +347,26 @@ class CheckerboardLatentCodec(nn.Module):
         y_ctx_i = self.unembed(self.context_prediction(self.embed(y_hat_)))[i]
         return torch.zeros_like(y_ctx_i) if i == 0 else y_ctx_i  # _mask(., "all") for the anchors
 
-    def prepare(self, y: Tensor, side_params: Tensor):
+    def prepare(self, y: Tensor, side_params: Tensor, importance: Optional[Tensor] = None):
         """Everything of ``compress`` that is not coding: -> (coder inputs of the two halves, y_hat).  The reconstruction
         a half's parameters depend on is ``round(.)`` of data the encoder holds (checkerboard.py:282-288), so the coder
-        inputs of BOTH halves — and ``y_hat`` — exist before a single symbol is coded."""
+        inputs of BOTH halves — and ``y_hat`` — exist before a single symbol is coded.  ``importance``: a float32 ``[1, 1, h, w]``
+        map of per-position factors of the squared error in the halves' rate-distortion optimised quantisation (section 3e: region
+        of interest, perceptual masking), every factor in [0, 256]; it is split as the latent is and half i's part handed to half i.
+        Where no half is quantised that way (no rdo_lambda, no target_bytes) it does nothing and costs no launch."""
         n, c, h, w = y.shape
         if n != 1:
             raise RuntimeError("batch size 1 (as the reference's coder path, checkerboard.py:307)")
         codec = self.latent_codec["y"]
+        if importance is not None:
+            if self.fuse_head:
+                raise RuntimeError("importance together with fuse_head is not supported: RDOQ needs the parameter planes the fused head never writes")
+            if not isinstance(importance, Tensor) or importance.dtype != torch.float32:
+                raise TypeError("importance must be a float32 tensor")
+            if tuple(importance.shape) != (1, 1, h, w):
+                raise ValueError(f"importance: shape {tuple(importance.shape)}, expected {(1, 1, h, w)}")
+        rdo_runs = self.rdo_lambda > 0 or getattr(codec, "rdo_lambda", 0.0) > 0 or getattr(codec, "target_bytes", None) is not None
+        imp_ = self.unembed(importance) if importance is not None and rdo_runs else (None, None)
         y_hat_ = side_params.new_zeros((2, n, c, h, w // 2))
         side_params_ = self.unembed(side_params)
         y_ = self.unembed(y)
@@ -353,7 +380,8 @@ class CheckerboardLatentCodec(nn.Module):
             else:
                 params_i = self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_params_[i]))
                 # (rdo_lambda = 0: the latent codec's own entry point, with its own setting - today's path)
-                prepared.append(codec.coder_inputs_rdo(y_[i], params_i, self.rdo_lambda) if self.rdo_lambda > 0 else codec.coder_inputs(y_[i], params_i))
+                prepared.append(codec.coder_inputs_rdo(y_[i], params_i, self.rdo_lambda, imp_[i]) if self.rdo_lambda > 0
+                                else codec.coder_inputs(y_[i], params_i, imp_[i]) if imp_[i] is not None else codec.coder_inputs(y_[i], params_i))
             y_hat_[i] = torch.round(prepared[i][0])  # what compress() of this half returns as y_hat
         return prepared, self.embed(y_hat_)
 
@@ -361,8 +389,8 @@ class CheckerboardLatentCodec(nn.Module):
         """the two halves' coding results (``codec.compress_many``) -> the codec's result"""
         return {"strings": [o["strings"][0] for o in outs], "shape": y_hat.shape[1:], "y_hat": y_hat}
 
-    def compress(self, y: Tensor, side_params: Tensor) -> Dict[str, Any]:
-        prepared, y_hat = self.prepare(y, side_params)
+    def compress(self, y: Tensor, side_params: Tensor, importance: Optional[Tensor] = None) -> Dict[str, Any]:
+        prepared, y_hat = self.prepare(y, side_params, importance)
         if self.fuse_head:
             return self.finish(self.latent_codec["y"].compress_many_head(prepared, self._head_parts()[1]), y_hat)
         return self.finish(self.latent_codec["y"].compress_many(prepared), y_hat)

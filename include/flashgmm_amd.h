@@ -49,6 +49,8 @@ extern "C" {
 #define FGMM_HAS_RDOQ 1     /* section 3c: fgmm_gmc_rdoq_batch */
 #define FGMM_HAS_RDCURVE 1  /* section 3d: fgmm_gmc_rdcurve_batch, fgmm_gmc_rdoq_budget_batch */
 #define FGMM_RDCURVE_MAX 16 /* lambdas per fgmm_gmc_rdcurve_batch call */
+#define FGMM_HAS_RDO_WEIGHTS 1 /* section 3e: fgmm_gmc_rdoq_batch_w, fgmm_gmc_rdcurve_batch_w, fgmm_gmc_rdoq_budget_batch_w (added without a bump, as 3b - 3d) */
+#define FGMM_RDO_W_MAX 256.0f  /* largest factor of a weighted call's chan_w / pos_w */
 
 typedef enum {
   FGMM_OK = 0,
@@ -633,6 +635,44 @@ typedef struct {
 int fgmm_gmc_rdoq_budget_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales,
                                const int32_t *group_or_null, int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine,
                                fgmm_budget_result *results /* per group */);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3e. WEIGHTED distortion for 3c and 3d: a per-channel gain (the synthesis transform does not treat channels alike) and a spatial
+ *    importance map (region of interest, perceptual masking), applied where the decision is made.  An item may carry two optional
+ *    factor arrays, both DEVICE float32: chan_w[M] and pos_w[hw] (fgmm_rdo_weights; a NULL array means every factor is 1).  The
+ *    rule, exactly (restatable on a CPU; tests/rdo_weights_ref.py does), for the latent at channel c, position p:
+ *      weight        wt = (double)chan_w[c] * (double)pos_w[p]: ONE binary64 multiply.  It is exact - two 24-bit significands fit 53
+ *                    bits - so the order of evaluation cannot matter
+ *      objective     J(v) = wt * (d * d) + lam_q * (double)cost_q(v): three multiplies and one add, each a single IEEE binary64
+ *                    operation, no contraction.  d, lam_q, the candidates, the |v0| <= 2^20 / non-finite rule, the strict-less
+ *                    choice in the order v0, v0 - 1, v0 + 1 and the channels coded are 3c's, unchanged
+ *      the curve     ddist_q[j] is the WEIGHTED added distortion: a moved latent contributes llrint((wt * inc) * 2^32) (round half
+ *                    to even) with inc = d * d - d0 * d0 as in 3d.  bits_q_after and n_changed sum the weighted decisions
+ *      the budget    the search of 3d - grids, first feasible point, refine - is untouched; the decisions it sums are the weighted
+ *                    ones, in the curve passes and in the final 3c step alike
+ *    With wt == 1.0 both expressions are the unweighted ones bit for bit: the _w calls with w == NULL, with {NULL, NULL} entries, or
+ *    with arrays of ones return exactly what fgmm_gmc_rdoq_batch / fgmm_gmc_rdcurve_batch / fgmm_gmc_rdoq_budget_batch return -
+ *    which ARE the _w forms with w == NULL.
+ *    Domain.  Every factor must be finite and lie in [0, FGMM_RDO_W_MAX] (256); -0.0 counts as 0.  wt is then <= 2^16 and, a move
+ *    being one step (|inc| <= 2), a latent's contribution to ddist_q at most 2^49.  The uint64 sum wraps only when the true sum of
+ *    wt * inc over an item's moved latents reaches 2^32 squared steps: not below 2^15 moved latents of the largest weight, and never
+ *    with wt <= 1 and fewer than 2^31 moved latents.  A zero weight is legal: that latent takes the cheapest of its three
+ *    candidates, ties to the earlier.  A factor outside the domain - anywhere in either array, whether its channel is coded or
+ *    not - fails the call with FGMM_ERR_INVALID, fgmm_last_error() naming the item; every item's status is the error and y_rdo is
+ *    unspecified.  The check runs on the device beside the census and costs no extra synchronisation.
+ *    w is an array of `count` entries (entry i belongs to item i) or NULL; everything else is validated as by the unweighted call.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *chan_w;     /* device float32 [M]  or NULL */
+  const float *pos_w;      /* device float32 [hw] or NULL */
+} fgmm_rdo_weights;
+int fgmm_gmc_rdoq_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda,
+                          const fgmm_rdo_weights *w /* [count] or NULL */);
+int fgmm_gmc_rdcurve_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales,
+                             const double *lambdas, int n_lambda, const fgmm_rdo_weights *w /* [count] or NULL */);
+int fgmm_gmc_rdoq_budget_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales,
+                                 const int32_t *group_or_null, int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine,
+                                 fgmm_budget_result *results /* per group */, const fgmm_rdo_weights *w /* [count] or NULL */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other

@@ -8,10 +8,13 @@ HIP events on the launch's stream around each call, after warm-up, all in one ru
   budget_call     ``quantize_to_budget_batch`` at refine = 2, every stream its own group, the budget half way between the predicted bytes
                   at lambda = 0 and at lambda = 16: census + three rdcurve_kernel passes + the RDOQ path at the lambdas found
   rdoq_x48        48 ``quantize_rdo_batch`` calls: the same 3 x 16 evaluations done the only way possible without the curve
+  *_w             the first three with the weighted distortion of header section 3e: a shared ``channel_weights`` [M] cycling 0.25, 1, 4 and
+                  a ``position_weights`` [N, 1, h, w] cycling 0.5, 1, 2, 1 (the weighted instantiations of the two kernels, the domain
+                  check beside the census); the budgets are those of the unweighted rows
 
 The kernels alone (rdcurve_kernel against rdoq_kernel): run this script under
 ``rocprofv3 --kernel-trace --stats -- python scripts/rd_budget_time.py --reps 20`` and read the kernel rows.
-Prints one JSON object; profiles/rd_budget.md records a run."""
+``--no-x48`` leaves the 48-call row out.  Prints one JSON object; profiles/rd_budget.md and profiles/rdo_weights.md record runs."""
 import argparse
 import json
 import os
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", default="polya")
+    ap.add_argument("--no-x48", action="store_true")
     a = ap.parse_args()
     import bench
     from flashgmm_amd import GaussianMixtureConditional
@@ -46,9 +50,19 @@ def main():
     out["curve16_call"] = timed(lambda: gmc.rd_curve_batch(y, s, m, w, lams), a.reps, a.warmup)
     out["rdoq_call"] = timed(lambda: gmc.quantize_rdo_batch(y, s, m, w, 0.1), a.reps, a.warmup)
     out["budget_call"] = timed(lambda: gmc.quantize_to_budget_batch(y, s, m, w, budgets, refine=2), a.reps, a.warmup)
-    out["rdoq_x48"] = timed(lambda: [gmc.quantize_rdo_batch(y, s, m, w, 0.01 * (k + 1)) for k in range(48)], max(a.reps // 6, 3), 1)
+    N, M, h, wd = y.shape
+    kw = {"channel_weights": torch.tensor([(0.25, 1.0, 4.0)[c % 3] for c in range(M)], device=dev),
+          "position_weights": torch.tensor([(0.5, 1.0, 2.0, 1.0)[p % 4] for p in range(h * wd)], device=dev).view(1, 1, h, wd).repeat(N, 1, 1, 1)}
+    out["curve16_call_w"] = timed(lambda: gmc.rd_curve_batch(y, s, m, w, lams, **kw), a.reps, a.warmup)
+    out["rdoq_call_w"] = timed(lambda: gmc.quantize_rdo_batch(y, s, m, w, 0.1, **kw), a.reps, a.warmup)
+    out["budget_call_w"] = timed(lambda: gmc.quantize_to_budget_batch(y, s, m, w, budgets, refine=2, **kw), a.reps, a.warmup)
+    out["weighted_to_unweighted"] = {k: round(out[k + "_w"]["median_ms"] / out[k]["median_ms"], 3) for k in ("curve16_call", "rdoq_call", "budget_call")}
+    rows = ["curve16_call", "budget_call"]
+    if not a.no_x48:
+        out["rdoq_x48"] = timed(lambda: [gmc.quantize_rdo_batch(y, s, m, w, 0.01 * (k + 1)) for k in range(48)], max(a.reps // 6, 3), 1)
+        rows.append("rdoq_x48")
     r = out["rdoq_call"]["median_ms"]
-    out["ratios_to_rdoq_call"] = {k: round(out[k]["median_ms"] / r, 3) for k in ("curve16_call", "budget_call", "rdoq_x48")}
+    out["ratios_to_rdoq_call"] = {k: round(out[k]["median_ms"] / r, 3) for k in rows}
     q = gmc.quantize_to_budget_batch(y, s, m, w, budgets, refine=2)
     out["budget"] = {"bytes_at_0": sum(r.nbytes[0] for r in c), "bytes_at_16": sum(r.nbytes[1] for r in c), "budget": sum(budgets),
                      "bytes_pred": sum(r.bytes_pred for r in q), "met": sum(r.budget_met for r in q), "passes": sorted({r.passes for r in q}),
