@@ -84,6 +84,16 @@ class fgmm_rdo_weights(C.Structure):
     _fields_ = [("chan_w", C.c_void_p), ("pos_w", C.c_void_p)]
 
 
+class fgmm_rdo_skip(C.Structure):
+    """one item's outputs of channel skipping (section 3f): host int64 ``skipped[M]`` (may be null), the counts, the added distortion"""
+    _fields_ = [("skipped", C.c_void_p), ("n_skipped", C.c_int64), ("n_eligible", C.c_int64), ("ddist_q", C.c_uint64)]
+
+
+class fgmm_rdcurve_skip(C.Structure):
+    """one item's outputs of channel skipping on the curve (section 3f)"""
+    _fields_ = [("n_skipped", C.c_uint64 * FGMM_RDCURVE_MAX), ("n_eligible", C.c_int64)]
+
+
 def _item_dtype(struct=fgmm_item):
     """numpy view of ``fgmm_item[]`` (offsets taken from the ctypes declaration): lets a batch be filled column by
     column instead of field by field."""
@@ -177,6 +187,11 @@ SIGNATURES = {
     "fgmm_gmc_rdcurve_batch_w": (_i, [_p, _p, C.POINTER(fgmm_rdcurve_item), _i, _i, _i, C.POINTER(C.c_double), _i, C.POINTER(fgmm_rdo_weights)]),
     "fgmm_gmc_rdoq_budget_batch_w": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_uint64), C.c_double, _i,
                                           C.POINTER(fgmm_budget_result), C.POINTER(fgmm_rdo_weights)]),
+    "fgmm_gmc_rdoq_batch_s": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.c_double, C.POINTER(fgmm_rdo_weights), C.POINTER(fgmm_rdo_skip)]),
+    "fgmm_gmc_rdcurve_batch_s": (_i, [_p, _p, C.POINTER(fgmm_rdcurve_item), _i, _i, _i, C.POINTER(C.c_double), _i, C.POINTER(fgmm_rdo_weights),
+                                      C.POINTER(fgmm_rdcurve_skip)]),
+    "fgmm_gmc_rdoq_budget_batch_s": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_uint64), C.c_double, _i,
+                                          C.POINTER(fgmm_budget_result), C.POINTER(fgmm_rdo_weights), C.POINTER(fgmm_rdo_skip)]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

@@ -562,9 +562,10 @@ struct LatentFrame {
 };
 // ---- fgmm_rdoq.cpp: the RDOQ call with the context's lock held, for the budget call (fgmm_rdcurve.cpp) too --------------------------
 int rdoq_check_items(const fgmm_rdoq_item *items, int count); // check_latent_items, then what is RDOQ's own: y_rdo null or over y
-// w: the items' factors or null; w_check false: the caller's frame has checked their domain in this call already
+// w: the items' factors or null; w_check false: the caller's frame has checked their domain in this call already; sk: the items' section-3f
+// outputs, or null: no channel is skipped
 int rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride,
-             const fgmm_rdo_weights *w = nullptr, bool w_check = true);
+             const fgmm_rdo_weights *w = nullptr, bool w_check = true, fgmm_rdo_skip *sk = nullptr);
 
 constexpr size_t kCounterBytes = kTabCounters * sizeof(unsigned long long); // per launch unit, see DecDesc::counters
 

@@ -228,6 +228,23 @@ template <int VEC> __device__ __forceinline__ void rdo_pos_w(const float *__rest
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Section 3f: the channel decision, ONE text for rdoq_skip_kernel and rdcurve_fold_kernel's skip form - every wave that asks about a
+// channel runs the same binary64 sequence on the same integers.  rdo_skip_dz: a latent's term of Dz, in units of 2^-16
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool rdo_skip_rule(bool inelig, unsigned long long A, unsigned long long nzA, unsigned long long Dk, unsigned long long Dz,
+                                              double lam_q) {
+  if (inelig) return false;
+  const double jk = (double)Dk * 0x1p-32 + lam_q * (double)A;
+  const double jz = (double)Dz * 0x1p-16;
+  return nzA == 0 || jz < jk;
+}
+__device__ __forceinline__ unsigned long long rdo_skip_dz(float y, float vq, double wt) { // (vq != 0, |vq| <= FGMM_SKIP_VMAX, y finite)
+  const double dz = (double)y, d0 = (double)y - (double)vq;
+  const double incz = dz * dz - d0 * d0;
+  return (unsigned long long)(long long)__builtin_rint((wt * incz) * 0x1p16);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // the launchers' ladder.  F::go<MODE, VEC, CLAMPED, PT, LINEAR>(grid, stream) does the kernel's hipLaunchKernelGGL with its own
 // arguments.  ALL_VEC: VEC = 2, and 8 for fp16 planes, exist too (symtab_kernel's A/B forms and its fp16 default); else vec >= 4 is 4
 // and anything below is 1.  M_max, hw_max, n_max: the largest M, hw and M * hw of the batch.

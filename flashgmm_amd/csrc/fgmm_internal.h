@@ -303,9 +303,16 @@ struct RdoqDesc {                   // item i of an rdoq_kernel launch, beside i
                                     // that ONE launch serves a budget call whose groups end at lambdas of their own
   const float *chan_w, *pos_w;      // section 3e: device [M] / [hw] factors of the distortion, either may be null (every factor 1); read by the
                                     // weighted instantiation only
+  // section 3f, read by the SKIP instantiation and rdoq_skip_kernel only (appended: the fields above keep their offsets)
+  unsigned long long *chan_skip;    // device [kRdoSkipWords][M], zeroed by the host: rdoq_kernel's sums of channel c (kRdoSkipDk .. kRdoSkipInelig),
+                                    // then what rdoq_skip_kernel decides (kRdoSkipAfter .. kRdoSkipFlag) - words no decision reads
+  unsigned long long *item_sums;    // device [kRdoSkipItem], zeroed by the host: bits after | latents changed | ddist_q | channels skipped | eligible
 };
-// the addressing of launch_rate.  weighted: some item of the batch carries factors (section 3e) - the instantiation that reads them
-int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, bool weighted, int count, int M_max, int64_t hw_max,
+enum { kRdoSkipDk = 0, kRdoSkipDz, kRdoSkipNz0, kRdoSkipNzA, kRdoSkipInelig, kRdoSkipAfter, kRdoSkipChanged, kRdoSkipDd, kRdoSkipFlag, kRdoSkipWords };
+constexpr int kRdoSkipItem = 6; // (five used; an even count keeps the channel arrays behind them 16-byte aligned)
+// the addressing of launch_rate.  weighted: some item of the batch carries factors (section 3e) - the instantiation that reads them.
+// skip: section 3f - the instantiation that also sums what the channel decision needs, then rdoq_skip_kernel on the same stream
+int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, bool weighted, bool skip, int count, int M_max, int64_t hw_max,
                 int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
 // section 3e's domain check, in the frame's front half beside quant_stats_kernel: item i's word bad[i] (zeroed by the host) becomes
 // non-zero when a factor of either array is not finite or lies outside [0, FGMM_RDO_W_MAX]
@@ -323,8 +330,12 @@ struct RdCurveDesc {                // item i of an rdcurve_kernel launch, besid
   double lam_q[FGMM_RDCURVE_MAX];   // lambda_j * 2^-FGMM_RATE_Q - per item, so that one launch serves groups with grids of their own
   const float *chan_w, *pos_w;      // section 3e, as RdoqDesc's
 };
-// the addressing of launch_rdoq; rdcurve_kernel, then rdcurve_fold_kernel
-int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, bool weighted, int count, int M_max, int64_t hw_max, int64_t n_max,
+// section 3f: the skip form's rows are wider.  A channel's: + 16 of nzA (latents whose choice is not 0, per lambda), then Dz, nz0, inelig.
+// The item's: + 16 of n_skipped, then n_eligible
+constexpr int kRdCurveRowS = kRdCurveRow + FGMM_RDCURVE_MAX + 3;
+constexpr int kRdCurveSumsS = kRdCurveRow + FGMM_RDCURVE_MAX + 1;
+// the addressing of launch_rdoq; rdcurve_kernel, then rdcurve_fold_kernel.  skip: both in their section-3f forms, on rows of kRdCurveRowS / kRdCurveSumsS words
+int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, bool weighted, bool skip, int count, int M_max, int64_t hw_max, int64_t n_max,
                    bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
 
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------

@@ -278,30 +278,32 @@ py::tuple rdoq_stacked(uintptr_t ctx_, uintptr_t stream, uintptr_t y, uintptr_t 
 
 // GaussianMixtureConditional.rd_curve / quantize_to_budget (header section 3d): the items arrive as the address of an fgmm_rdcurve_item[] /
 // fgmm_rdoq_item[] the caller has built (flashgmm_amd/_lib.py mirrors both); the results are written through it.  The native call
-// runs with the GIL released.  `weights`: 0, or the address of an fgmm_rdo_weights[count] (section 3e) - the _w forms are called either way
+// runs with the GIL released.  `weights`: 0, or the address of an fgmm_rdo_weights[count] (section 3e); `skip`: 0, or the address of an
+// fgmm_rdcurve_skip[count] / fgmm_rdo_skip[count] (section 3f) - the _s forms are called either way
 void rdcurve_items(uintptr_t ctx_, uintptr_t stream, uintptr_t items, int count, int mode, int clamp_scales, const std::vector<double> &lambdas,
-                   uintptr_t weights) {
+                   uintptr_t weights, uintptr_t skip) {
   int rc;
   {
     py::gil_scoped_release nogil;
-    rc = fgmm_gmc_rdcurve_batch_w(ptr<fgmm_ctx>(ctx_), ptr<void>(stream), ptr<fgmm_rdcurve_item>(items), count, mode, clamp_scales, lambdas.data(),
-                                  (int)lambdas.size(), ptr<const fgmm_rdo_weights>(weights));
+    rc = fgmm_gmc_rdcurve_batch_s(ptr<fgmm_ctx>(ctx_), ptr<void>(stream), ptr<fgmm_rdcurve_item>(items), count, mode, clamp_scales, lambdas.data(),
+                                  (int)lambdas.size(), ptr<const fgmm_rdo_weights>(weights), ptr<fgmm_rdcurve_skip>(skip));
   }
   if (rc) raise("GaussianMixtureConditional.rd_curve", rc);
 }
-// GaussianMixtureConditional.quantize_rdo with factors (fgmm_gmc_rdoq_batch_w): items and weights by address, as above
-void rdoq_items(uintptr_t ctx_, uintptr_t stream, uintptr_t items, int count, int mode, int clamp_scales, double lambda, uintptr_t weights) {
+// GaussianMixtureConditional.quantize_rdo with factors or channel skipping (fgmm_gmc_rdoq_batch_s): items, weights and skip by address, as above
+void rdoq_items(uintptr_t ctx_, uintptr_t stream, uintptr_t items, int count, int mode, int clamp_scales, double lambda, uintptr_t weights,
+                uintptr_t skip) {
   int rc;
   {
     py::gil_scoped_release nogil;
-    rc = fgmm_gmc_rdoq_batch_w(ptr<fgmm_ctx>(ctx_), ptr<void>(stream), ptr<fgmm_rdoq_item>(items), count, mode, clamp_scales, lambda,
-                               ptr<const fgmm_rdo_weights>(weights));
+    rc = fgmm_gmc_rdoq_batch_s(ptr<fgmm_ctx>(ctx_), ptr<void>(stream), ptr<fgmm_rdoq_item>(items), count, mode, clamp_scales, lambda,
+                               ptr<const fgmm_rdo_weights>(weights), ptr<fgmm_rdo_skip>(skip));
   }
   if (rc) raise("GaussianMixtureConditional.quantize_rdo", rc);
 }
 //   -> per group (lambda, bytes_pred, passes, status)
 py::list rdoq_budget_items(uintptr_t ctx_, uintptr_t stream, uintptr_t items, int count, int mode, int clamp_scales, const py::object &groups,
-                           const std::vector<uint64_t> &budgets, double lambda_max, int refine, uintptr_t weights) {
+                           const std::vector<uint64_t> &budgets, double lambda_max, int refine, uintptr_t weights, uintptr_t skip) {
   std::vector<int32_t> group;
   const bool grouped = !groups.is_none();
   if (grouped) group = groups.cast<std::vector<int32_t>>();
@@ -309,9 +311,9 @@ py::list rdoq_budget_items(uintptr_t ctx_, uintptr_t stream, uintptr_t items, in
   int rc;
   {
     py::gil_scoped_release nogil;
-    rc = fgmm_gmc_rdoq_budget_batch_w(ptr<fgmm_ctx>(ctx_), ptr<void>(stream), ptr<fgmm_rdoq_item>(items), count, mode, clamp_scales,
+    rc = fgmm_gmc_rdoq_budget_batch_s(ptr<fgmm_ctx>(ctx_), ptr<void>(stream), ptr<fgmm_rdoq_item>(items), count, mode, clamp_scales,
                                       grouped ? group.data() : nullptr, (int)budgets.size(), budgets.data(), lambda_max, refine, res.data(),
-                                      ptr<const fgmm_rdo_weights>(weights));
+                                      ptr<const fgmm_rdo_weights>(weights), ptr<fgmm_rdo_skip>(skip));
   }
   if (rc) raise("GaussianMixtureConditional.quantize_to_budget", rc);
   py::list out;
@@ -405,10 +407,10 @@ PYBIND11_MODULE(_native, m) {
         "ckpt_stride"_a, "yq"_a, "zero_bitmap"_a, "bytes_cls"_a = py::none());
   m.def("rdoq_stacked", &rdoq_stacked, "ctx"_a, "stream"_a, "y"_a, "scales"_a, "means"_a, "weights"_a, "N"_a, "M"_a, "hw"_a, "item_stride"_a, "stride_k"_a,
         "stride_c"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "lambda"_a, "y_rdo"_a, "zero_bitmap"_a, "chan_after"_a = 0);
-  m.def("rdcurve_items", &rdcurve_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "lambdas"_a, "weights"_a = 0);
-  m.def("rdoq_items", &rdoq_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "lambda"_a, "weights"_a = 0);
+  m.def("rdcurve_items", &rdcurve_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "lambdas"_a, "weights"_a = 0, "skip"_a = 0);
+  m.def("rdoq_items", &rdoq_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "lambda"_a, "weights"_a = 0, "skip"_a = 0);
   m.def("rdoq_budget_items", &rdoq_budget_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "groups"_a, "budgets"_a, "lambda_max"_a,
-        "refine"_a, "weights"_a = 0);
+        "refine"_a, "weights"_a = 0, "skip"_a = 0);
   m.def("compress_items", &compress_items, "ctx"_a, "stream"_a, "items"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "ckpt_stride"_a, "bytes_cls"_a = py::none());
   m.def("decompress_items", &decompress_items, "ctx"_a, "stream"_a, "strings"_a, "abs_maxes"_a, "items"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a,
         "ckpt_cls"_a = py::none());

@@ -1,5 +1,5 @@
 // fgmm_rdcurve.cpp — the rate-distortion curve of a batch of latents and their quantisation to a byte budget (include/flashgmm_amd.h
-// sections 3d and 3e).  The frame of fgmm_estimate.cpp once per call (LatentFrame: quant_stats_kernel and chan_compact_kernel give the
+// sections 3d, 3e and 3f).  The frame of fgmm_estimate.cpp once per call (LatentFrame: quant_stats_kernel and chan_compact_kernel give the
 // channels the compress call would code for y), then one or more PASSES: rdcurve_kernel (fgmm_rdcurve.hip) at up to 16 lambdas per
 // item, the channels' sums folded to the items' on the device, a few KB back.  The budget call searches lambda on those passes by the
 // header's rule, every group on its own grid within one launch, and ends in the RDOQ call's own path (fgmm_rdoq.cpp: rdoq_run) at the
@@ -17,10 +17,12 @@ struct Curve : LatentFrame { // the passes of a call, on the frame: a pass sets 
   using LatentFrame::LatentFrame;
   RdCurveDesc *hc = nullptr; // host copy of the curve descriptors
   bool census_back = false;
+  bool skip = false; // section 3f: the kernels' skip forms, on their wider rows
   const uint64_t *sums(int i) const { return ws<const uint64_t>(ctx->h_ws, o_back[(size_t)i]); }
 
   int begin() { // the census, once: every pass prices the channels it names
-    if (int rc = layout({sizeof(RdCurveDesc), kRdCurveRow, 0, kRdCurveRow, false})) return rc; // the item's row of sums | on the device, a row per channel
+    // the item's row of sums | on the device, a row per channel
+    if (int rc = layout({sizeof(RdCurveDesc), (size_t)(skip ? kRdCurveSumsS : kRdCurveRow), 0, (size_t)(skip ? kRdCurveRowS : kRdCurveRow), false})) return rc;
     hc = ws<RdCurveDesc>(ctx->h_ws, o_call);
     for (int i = 0; i < count; ++i) {
       memset(&hc[i], 0, sizeof hc[i]);
@@ -35,7 +37,7 @@ struct Curve : LatentFrame { // the passes of a call, on the frame: a pass sets 
   int run(int mode) {
     DEV_TRY(dev::copy_async(ctx->d_ws + o_call, hc, sizeof(RdCurveDesc) * (size_t)count, dev::kH2D, stream));
     DEV_TRY(dev::memset_async(ctx->d_ws + o_sums, 0, end - o_sums, stream)); // the items' sums and the channels'
-    LAUNCH_TRY(launch_rdcurve(dd(), ws<const RdCurveDesc>(ctx->d_ws, o_call), ctx->d_rate_log2, weighted, count, M_max, hw_max, n_max, linear, mode,
+    LAUNCH_TRY(launch_rdcurve(dd(), ws<const RdCurveDesc>(ctx->d_ws, o_call), ctx->d_rate_log2, weighted, skip, count, M_max, hw_max, n_max, linear, mode,
                               vec, clamp != 0, f16, stream));
     const size_t from = census_back ? o_sums : o_small;
     census_back = true;
@@ -46,9 +48,9 @@ struct Curve : LatentFrame { // the passes of a call, on the frame: a pass sets 
 bool lambda_ok(double v) { return v >= 0.0 && v < (double)INFINITY; } // (false for NaN)
 
 int curve_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdcurve_item *items, int count, int mode, int clamp, const double *lambdas, int n_lambda,
-                const fgmm_rdo_weights *w) {
+                const fgmm_rdo_weights *w, fgmm_rdcurve_skip *sk) {
   Curve cv(ctx, stream, latent_in(items, count), clamp);
-  cv.w = w;
+  cv.w = w, cv.skip = sk != nullptr;
   int rc;
   if ((rc = cv.begin())) return rc;
   for (int i = 0; i < count; ++i) {
@@ -66,7 +68,9 @@ int curve_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdcurve_item *items, int
       it.bits_q_after[j] = s[1 + j];
       it.n_changed[j] = s[1 + FGMM_RDCURVE_MAX + j];
       it.ddist_q[j] = s[1 + 2 * FGMM_RDCURVE_MAX + j];
+      if (sk) sk[i].n_skipped[j] = s[kRdCurveRow + j];
     }
+    if (sk) sk[i].n_eligible = (int64_t)s[kRdCurveRow + FGMM_RDCURVE_MAX];
     it.n_symbols = (int64_t)n_nz * it.hw;
     it.status = FGMM_OK;
   }
@@ -82,9 +86,9 @@ struct Search { // one group's search (header section 3d)
 };
 
 int budget_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const int32_t *group, int n_groups,
-                 const uint64_t *budget, double lambda_max, int refine, fgmm_budget_result *results, const fgmm_rdo_weights *w) {
+                 const uint64_t *budget, double lambda_max, int refine, fgmm_budget_result *results, const fgmm_rdo_weights *w, fgmm_rdo_skip *sk) {
   Curve cv(ctx, stream, latent_in(items, count), clamp);
-  cv.w = w;
+  cv.w = w, cv.skip = sk != nullptr;
   int rc;
   if ((rc = cv.begin())) return rc;
   std::vector<Search> gs((size_t)n_groups);
@@ -147,7 +151,7 @@ int budget_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int c
   // 3c at the lambdas found: the RDOQ call's own path, its second census included (the workspace of the passes is no longer needed)
   std::vector<double> lam((size_t)count);
   for (int i = 0; i < count; ++i) lam[(size_t)i] = gs[(size_t)(group ? group[i] : i)].hi;
-  if ((rc = rdoq_run(ctx, stream, items, count, mode, clamp, lam.data(), 1, w, false))) return rc; // (the factors' domain: checked by the first pass)
+  if ((rc = rdoq_run(ctx, stream, items, count, mode, clamp, lam.data(), 1, w, false, sk))) return rc; // (the factors' domain: checked by the first pass)
   for (int gi = 0; gi < n_groups; ++gi) {
     const Search &g = gs[(size_t)gi];
     results[gi].lambda = g.hi;
@@ -162,24 +166,28 @@ int budget_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int c
 
 extern "C" {
 
-int fgmm_gmc_rdcurve_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales, const double *lambdas,
-                             int n_lambda, const fgmm_rdo_weights *w) {
+int fgmm_gmc_rdcurve_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales, const double *lambdas,
+                             int n_lambda, const fgmm_rdo_weights *w, fgmm_rdcurve_skip *skip) {
   if (n_lambda < 1 || n_lambda > FGMM_RDCURVE_MAX || !lambdas)
     return fail(FGMM_ERR_INVALID, "n_lambda = %d: must lie in 1 .. %d", n_lambda, FGMM_RDCURVE_MAX);
   for (int j = 0; j < n_lambda; ++j)
     if (!lambda_ok(lambdas[j])) return fail(FGMM_ERR_INVALID, "lambda[%d] = %g: must be finite and >= 0", j, lambdas[j]);
   if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2) return fail(FGMM_ERR_INVALID, "bad argument");
   if (int rc = check_latent_items(latent_in(items, count))) return rc;
-  return latent_call(ctx, stream, items, count, [&](dev::Stream s) { return curve_batch(ctx, s, items, count, mode, clamp_scales, lambdas, n_lambda, w); });
+  return latent_call(ctx, stream, items, count, [&](dev::Stream s) { return curve_batch(ctx, s, items, count, mode, clamp_scales, lambdas, n_lambda, w, skip); });
+}
+int fgmm_gmc_rdcurve_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales, const double *lambdas,
+                             int n_lambda, const fgmm_rdo_weights *w) {
+  return fgmm_gmc_rdcurve_batch_s(ctx, stream, items, count, mode, clamp_scales, lambdas, n_lambda, w, nullptr);
 }
 int fgmm_gmc_rdcurve_batch(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales, const double *lambdas,
                            int n_lambda) {
   return fgmm_gmc_rdcurve_batch_w(ctx, stream, items, count, mode, clamp_scales, lambdas, n_lambda, nullptr);
 }
 
-int fgmm_gmc_rdoq_budget_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, const int32_t *group,
+int fgmm_gmc_rdoq_budget_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, const int32_t *group,
                                  int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine, fgmm_budget_result *results,
-                                 const fgmm_rdo_weights *w) {
+                                 const fgmm_rdo_weights *w, fgmm_rdo_skip *skip) {
   if (!(lambda_max > 0.0 && lambda_max < (double)INFINITY)) return fail(FGMM_ERR_INVALID, "lambda_max = %g: must be finite and > 0", lambda_max);
   if (refine < 0 || refine > 8) return fail(FGMM_ERR_INVALID, "refine = %d: must lie in 0 .. 8", refine);
   if (!ctx || count < 0 || (count && !items) || mode < 0 || mode > 2 || n_groups < 0 || (n_groups && (!budget_bytes || !results)))
@@ -196,8 +204,13 @@ int fgmm_gmc_rdoq_budget_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *it
   }
   if (int rc = rdoq_check_items(items, count)) return rc;
   return latent_call(ctx, stream, items, count, [&](dev::Stream s) {
-    return budget_batch(ctx, s, items, count, mode, clamp_scales, group, n_groups, budget_bytes, lambda_max, refine, results, w);
+    return budget_batch(ctx, s, items, count, mode, clamp_scales, group, n_groups, budget_bytes, lambda_max, refine, results, w, skip);
   });
+}
+int fgmm_gmc_rdoq_budget_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, const int32_t *group,
+                                 int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine, fgmm_budget_result *results,
+                                 const fgmm_rdo_weights *w) {
+  return fgmm_gmc_rdoq_budget_batch_s(ctx, stream, items, count, mode, clamp_scales, group, n_groups, budget_bytes, lambda_max, refine, results, w, nullptr);
 }
 int fgmm_gmc_rdoq_budget_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, const int32_t *group,
                                int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine, fgmm_budget_result *results) {

@@ -27,7 +27,7 @@ from torch import Tensor
 
 from . import _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "BudgetQuantized", "RdCurve"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -174,9 +174,27 @@ class RdoQuantized:
 
 # what a budget search adds to an RdoQuantized: None on the result of quantize_rdo (the slots of RdoQuantized itself stay what they are)
 RdoQuantized.lam = RdoQuantized.bytes_pred = RdoQuantized.budget_met = RdoQuantized.passes = None
+# what channel skipping adds (section 3f): None where it was not asked for
+RdoQuantized.n_skipped = RdoQuantized.n_eligible = RdoQuantized.skipped = RdoQuantized.ddist_q = None
 
 
-class BudgetQuantized(RdoQuantized):
+class RdoSkipQuantized(RdoQuantized):
+    """The ``RdoQuantized`` of a call with ``channel_skip=True`` (include/flashgmm_amd.h section 3f): after the per-latent decisions,
+    a coded channel is dropped whole - its plane of ``y`` zero, nothing of it in the stream - where that lowers distortion + lam * bits.
+    The inherited sums are those after the channel decisions; ``estimate_bits(result.y, ...)`` returns exactly ``bits_q_after``.
+
+    ``n_skipped``    channels skipped;  ``n_eligible``  coded channels that may be (every latent finite, ``|round(y)| <= 15``)
+    ``skipped``      bool ``[M]`` CPU tensor (``per_channel=True``; else None)
+    ``ddist_q``      the (weighted) squared error ``y`` adds over ``round(input)``, units of 2^-32"""
+
+    __slots__ = ("n_skipped", "n_eligible", "skipped", "ddist_q")
+
+    def __init__(self, y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after=None, skip=None):
+        super().__init__(y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after)
+        self.n_skipped, self.n_eligible, self.skipped, self.ddist_q = skip if skip is not None else (None, None, None, None)
+
+
+class BudgetQuantized(RdoSkipQuantized):
     """The ``RdoQuantized`` of a latent quantised to a byte budget (``GaussianMixtureConditional.quantize_to_budget`` /
     ``quantize_to_budget_batch``; include/flashgmm_amd.h section 3d), with what the search found for the latent's GROUP:
 
@@ -186,13 +204,15 @@ class BudgetQuantized(RdoQuantized):
     ``passes``       passes of the curve kernel the group took part in
 
     The budget is on predicted bytes: a real stream may be 4 bytes longer where ``RateEstimate.nbytes`` may be; a channel the
-    quantisation empties is no longer coded at all, so on that account the real size can only be smaller."""
+    quantisation empties is no longer coded at all, so on that account the real size can only be smaller - unless the search ran
+    with ``channel_skip=True``, where such a channel counts nothing (``n_skipped``, ``n_eligible``, ``skipped``, ``ddist_q``: as
+    ``RdoSkipQuantized``'s; None otherwise)."""
 
     __slots__ = ("lam", "bytes_pred", "budget_met", "passes")
 
     def __init__(self, y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after=None, lam=None, bytes_pred=None,
-                 budget_met=None, passes=None):
-        super().__init__(y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after)
+                 budget_met=None, passes=None, skip=None):
+        super().__init__(y, n_changed, bits_q_before, bits_q_after, abs_max, zero_bitmap, channel_bits_q_after, skip)
         self.lam, self.bytes_pred, self.budget_met, self.passes = lam, bytes_pred, budget_met, passes
 
     def __repr__(self) -> str:
@@ -211,11 +231,16 @@ class RdCurve:
     ``ddist_q``        per lambda: squared error the moves add over ``round(y)``, units of 2^-32;  ``distortion_added`` as floats.
                        WEIGHTED - each latent's share times ``channel_weights[c] * position_weights[p]`` - when the call was given
                        weights (section 3e)
-    ``n_symbols``      symbols coded (coded channels x h x w)"""
+    ``n_symbols``      symbols coded (coded channels x h x w)
+    ``n_skipped``      per lambda: channels skipped (``channel_skip=True``, section 3f - the three sums above are then those after the
+                       channel decisions); None otherwise
+    ``n_eligible``     coded channels that may be skipped, as ``RdoSkipQuantized.n_eligible`` (``channel_skip=True``; else None)"""
 
-    __slots__ = ("lambdas", "bits_q_before", "bits_q_after", "n_changed", "ddist_q", "n_symbols")
+    __slots__ = ("lambdas", "bits_q_before", "bits_q_after", "n_changed", "ddist_q", "n_symbols", "n_skipped", "n_eligible")
 
-    def __init__(self, lambdas, bits_q_before, bits_q_after, n_changed, ddist_q, n_symbols=0):
+    def __init__(self, lambdas, bits_q_before, bits_q_after, n_changed, ddist_q, n_symbols=0, n_skipped=None, n_eligible=None):
+        self.n_skipped = None if n_skipped is None else tuple(map(int, n_skipped))
+        self.n_eligible = None if n_eligible is None else int(n_eligible)
         self.lambdas, self.bits_q_before = tuple(float(v) for v in lambdas), int(bits_q_before)
         self.bits_q_after, self.n_changed, self.ddist_q = tuple(map(int, bits_q_after)), tuple(map(int, n_changed)), tuple(map(int, ddist_q))
         self.n_symbols = int(n_symbols)
@@ -338,6 +363,22 @@ def _rdo_weights_array(lists):
     for a, (c, p) in zip(arr, lists):
         a.chan_w, a.pos_w = (c.data_ptr() if c is not None else None), (p.data_ptr() if p is not None else None)
     return arr
+
+
+def _rdo_skip_array(L, per_channel):
+    """the ``fgmm_rdo_skip[N]`` of a call with channel skipping (section 3f) and, ``per_channel``, the items' host int64 ``[M]`` flags"""
+    arr = (_lib.fgmm_rdo_skip * L.N)()
+    flags = [None] * L.N
+    if per_channel:
+        flags = [torch.empty((int(M),), dtype=torch.int64) for M in L.items["M"].tolist()]
+        for a, t in zip(arr, flags):
+            a.skipped = t.data_ptr()
+    return arr, flags
+
+
+def _rdo_skip_cols(arr, flags):
+    """-> per item ``(n_skipped, n_eligible, skipped bool [M] or None, ddist_q)``"""
+    return [(int(a.n_skipped), int(a.n_eligible), None if t is None else t != 0, int(a.ddist_q)) for a, t in zip(arr, flags)]
 
 
 def _take_ckpts_many(device: int, ptrs, counts):
@@ -811,7 +852,7 @@ class GaussianMixtureConditional(nn.Module):
                                         per_latent=per_latent)[0]
 
     def quantize_rdo_batch(self, ys, scales, means, weights, lam: float, *, weights_are_logits: bool = False,
-                           per_channel: bool = False, channel_weights=None, position_weights=None) -> List[RdoQuantized]:
+                           per_channel: bool = False, channel_weights=None, position_weights=None, channel_skip: bool = False) -> List[RdoQuantized]:
         """Rate-distortion optimised quantisation: per latent of a channel ``compress_batch`` would code, ``round(y)`` or one of its
         two neighbours, whichever minimises ``(y - v)**2 + lam * bits(v)`` - ``bits`` the coder's own exact cost of ``v`` under that
         latent's mixture (the rule, exactly: include/flashgmm_amd.h section 3c).  One kernel; nothing is coded.  Inputs as
@@ -823,7 +864,10 @@ class GaussianMixtureConditional(nn.Module):
         by ``channel_weights[c] * position_weights[p]``: float32 tensors on the latents' device, every factor finite and in
         ``[0, 256]``.  ``channel_weights``: ``[M]`` shared by the batch, or a sequence of one (or None) per item.
         ``position_weights``: ``[h, w]`` or ``[1, 1, h, w]`` per item, or ``[N, 1, h, w]`` for stacked input.  None, or arrays of
-        ones: exactly the unweighted result."""
+        ones: exactly the unweighted result.
+
+        ``channel_skip`` (section 3f): after the per-latent decisions a coded channel is dropped whole where that lowers the
+        objective; -> ``RdoSkipQuantized``.  False changes nothing."""
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
         lam = float(lam)
@@ -832,7 +876,7 @@ class GaussianMixtureConditional(nn.Module):
         wl = _rdo_weight_lists(ys, channel_weights, position_weights)
         flags = _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0
         nat = _lib.native()
-        if wl is None and isinstance(ys, Tensor) and nat is not None and scales.dim() == 4 and scales.shape[0] > 0:  # the compiled boundary: items built in C++
+        if wl is None and not channel_skip and isinstance(ys, Tensor) and nat is not None and scales.dim() == 4 and scales.shape[0] > 0:  # the compiled boundary: items built in C++
             y, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(ys, scales, means, weights)
             dev = scales.device
             out = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
@@ -850,22 +894,25 @@ class GaussianMixtureConditional(nn.Module):
         outs, bitmaps = L.output("y_rdo", torch.float32, per_latent=True), L.output("zero_bitmap", torch.int64)
         chans = L.output("chan_bits_q_after", torch.int64) if per_channel else [None] * L.N
         warr = _rdo_weights_array(wl)
+        sarr, sflags = _rdo_skip_array(L, per_channel) if channel_skip else (None, None)
         if nat is not None:
             nat.rdoq_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), lam,
-                           C.addressof(warr) if warr is not None else 0)
+                           C.addressof(warr) if warr is not None else 0, C.addressof(sarr) if sarr is not None else 0)
         else:
-            rc = _lib.lib().fgmm_gmc_rdoq_batch_w(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales), lam, warr)
+            rc = _lib.lib().fgmm_gmc_rdoq_batch_s(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales), lam, warr, sarr)
             _lib.check(rc, "GaussianMixtureConditional.quantize_rdo")
         items = L.items
         cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
                    bitmaps, chans)
+        if channel_skip:
+            return [RdoSkipQuantized(*c, sk) for c, sk in zip(cols, _rdo_skip_cols(sarr, sflags))]
         return [RdoQuantized(*c) for c in cols]
 
     def quantize_rdo(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lam: float, *, weights_are_logits: bool = False,
-                     per_channel: bool = False, channel_weights=None, position_weights=None) -> RdoQuantized:
+                     per_channel: bool = False, channel_weights=None, position_weights=None, channel_skip: bool = False) -> RdoQuantized:
         """-> the ``RdoQuantized`` of one latent (``quantize_rdo_batch``)"""
         return self.quantize_rdo_batch([y], [scales], [means], [weights], lam, weights_are_logits=weights_are_logits, per_channel=per_channel,
-                                       channel_weights=channel_weights, position_weights=_one_item(position_weights))[0]
+                                       channel_weights=channel_weights, position_weights=_one_item(position_weights), channel_skip=channel_skip)[0]
 
     def _latent_items(self, struct, ys, scales, means, weights, logits: bool) -> _LatentItems:
         """THE item builder of the calls that price latents (estimate, RDOQ, curve, budget): ``struct[N]`` with the input fields
@@ -892,12 +939,13 @@ class GaussianMixtureConditional(nn.Module):
         return L
 
     def rd_curve_batch(self, ys, scales, means, weights, lambdas, *, weights_are_logits: bool = False, channel_weights=None,
-                       position_weights=None) -> List[RdCurve]:
+                       position_weights=None, channel_skip: bool = False) -> List[RdCurve]:
         """What ``quantize_rdo_batch`` would report at every lambda of ``lambdas`` - the cost after, the latents moved, the distortion
         added - WITHOUT quantising: one kernel prices each latent once and decides it at up to 16 lambdas (include/flashgmm_amd.h
         section 3d); more are served in chunks of 16.  Inputs as ``quantize_rdo_batch`` takes them; ``lambdas`` finite, >= 0, in any
         order.  ``channel_weights`` / ``position_weights``: as ``quantize_rdo_batch`` takes them - the curve is then the weighted
-        call's, ``ddist_q`` the weighted added distortion.  -> one ``RdCurve`` per item."""
+        call's, ``ddist_q`` the weighted added distortion.  ``channel_skip``: what ``quantize_rdo_batch(channel_skip=True)`` would
+        report, with ``n_skipped`` per lambda (section 3f).  -> one ``RdCurve`` per item."""
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
         lambdas = [float(v) for v in lambdas]
@@ -910,29 +958,35 @@ class GaussianMixtureConditional(nn.Module):
         nat, items, warr = _lib.native(), L.items, _rdo_weights_array(wl)
         names = ("bits_q_after", "n_changed", "ddist_q")
         cols = [[] for _ in names]
+        sarr = (_lib.fgmm_rdcurve_skip * L.N)() if channel_skip else None
+        n_skipped = [[] for _ in range(L.N)]
         for at in range(0, len(lambdas), _lib.FGMM_RDCURVE_MAX):
             chunk = lambdas[at:at + _lib.FGMM_RDCURVE_MAX]
             if nat is not None:
                 nat.rdcurve_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), chunk,
-                                  C.addressof(warr) if warr is not None else 0)
+                                  C.addressof(warr) if warr is not None else 0, C.addressof(sarr) if sarr is not None else 0)
             else:
-                rc = _lib.lib().fgmm_gmc_rdcurve_batch_w(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales),
-                                                         (C.c_double * len(chunk))(*chunk), len(chunk), warr)
+                rc = _lib.lib().fgmm_gmc_rdcurve_batch_s(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales),
+                                                         (C.c_double * len(chunk))(*chunk), len(chunk), warr, sarr)
                 _lib.check(rc, "GaussianMixtureConditional.rd_curve")
+            for i in range(L.N if channel_skip else 0):
+                n_skipped[i].extend(sarr[i].n_skipped[:len(chunk)])
             for col, name in zip(cols, names):
                 col.append(items[name][:, :len(chunk)].copy())
         cols = [np.concatenate(col, axis=1).tolist() for col in cols]
-        return [RdCurve(lambdas, *c) for c in zip(items["bits_q_before"].tolist(), *cols, items["n_symbols"].tolist())]
+        return [RdCurve(lambdas, *c) for c in zip(items["bits_q_before"].tolist(), *cols, items["n_symbols"].tolist(),
+                                                  n_skipped if channel_skip else [None] * L.N,
+                                                  [a.n_eligible for a in sarr] if channel_skip else [None] * L.N)]
 
     def rd_curve(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, lambdas, *, weights_are_logits: bool = False,
-                 channel_weights=None, position_weights=None) -> RdCurve:
+                 channel_weights=None, position_weights=None, channel_skip: bool = False) -> RdCurve:
         """-> the ``RdCurve`` of one latent (``rd_curve_batch``)"""
         return self.rd_curve_batch([y], [scales], [means], [weights], lambdas, weights_are_logits=weights_are_logits,
-                                   channel_weights=channel_weights, position_weights=_one_item(position_weights))[0]
+                                   channel_weights=channel_weights, position_weights=_one_item(position_weights), channel_skip=channel_skip)[0]
 
     def quantize_to_budget_batch(self, ys, scales, means, weights, budget_bytes, *, groups=None, lambda_max: float = 16.0, refine: int = 2,
                                  weights_are_logits: bool = False, per_channel: bool = False, channel_weights=None,
-                                 position_weights=None) -> List[BudgetQuantized]:
+                                 position_weights=None, channel_skip: bool = False) -> List[BudgetQuantized]:
         """Rate-distortion optimised quantisation TO A BYTE BUDGET: lambda is searched on the rate-distortion curve by the fixed rule of
         include/flashgmm_amd.h section 3d - a 16-point grid 0, lambda_max * 2^-14 .. lambda_max, then ``refine`` (0..8) rounds of 16
         points between the last infeasible and the first feasible one, each round one pass of the curve kernel - then ``quantize_rdo_batch``'s
@@ -942,7 +996,8 @@ class GaussianMixtureConditional(nn.Module):
         of its group).  The budget is on PREDICTED bytes: a real stream may be 4 bytes longer where ``estimate_bits`` may be off;
         a channel the quantisation empties is no longer coded, so on that account the real size can only be smaller.
         ``channel_weights`` / ``position_weights``: as ``quantize_rdo_batch`` takes them - the search is the same, the decisions it
-        sums and the final quantisation are the weighted ones."""
+        sums and the final quantisation are the weighted ones.  ``channel_skip`` (section 3f): the search runs over the curve after
+        the channel decisions and ends in ``quantize_rdo_batch(channel_skip=True)``; an emptied channel then counts nothing."""
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the coder is bound for K = 4 only (as the reference's)")
         lambda_max, refine = float(lambda_max), int(refine)
@@ -975,31 +1030,33 @@ class GaussianMixtureConditional(nn.Module):
         outs, bitmaps = L.output("y_rdo", torch.float32, per_latent=True), L.output("zero_bitmap", torch.int64)
         chans = L.output("chan_bits_q_after", torch.int64) if per_channel else [None] * N
         nat = _lib.native()
+        sarr, sflags = _rdo_skip_array(L, per_channel) if channel_skip else (None, None)
         if nat is not None:
             res = nat.rdoq_budget_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), N, self._mode(), int(self.clamp_scales), groups, budgets,
-                                        lambda_max, refine, C.addressof(warr) if warr is not None else 0)
+                                        lambda_max, refine, C.addressof(warr) if warr is not None else 0, C.addressof(sarr) if sarr is not None else 0)
         else:
             out_res = (_lib.fgmm_budget_result * n_groups)()
-            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch_w(_lib.ctx(L.di), L.stream(), L.arr, N, self._mode(), int(self.clamp_scales),
+            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch_s(_lib.ctx(L.di), L.stream(), L.arr, N, self._mode(), int(self.clamp_scales),
                                                          (C.c_int32 * N)(*groups) if groups is not None else None, n_groups,
-                                                         (C.c_uint64 * n_groups)(*budgets), lambda_max, refine, out_res, warr)
+                                                         (C.c_uint64 * n_groups)(*budgets), lambda_max, refine, out_res, warr, sarr)
             _lib.check(rc, "GaussianMixtureConditional.quantize_to_budget")
             res = [(r.lambda_, r.bytes_pred, r.passes, r.status) for r in out_res]
         got = []
         cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
                    bitmaps, chans)
+        skips = _rdo_skip_cols(sarr, sflags) if channel_skip else [None] * N
         for i, c in enumerate(cols):
             lam, nbytes, passes, status = res[groups[i] if groups is not None else i]
-            got.append(BudgetQuantized(*c, float(lam), int(nbytes), status != _lib.FGMM_BUDGET_UNMET, int(passes)))
+            got.append(BudgetQuantized(*c, float(lam), int(nbytes), status != _lib.FGMM_BUDGET_UNMET, int(passes), skips[i]))
         return got
 
     def quantize_to_budget(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, budget_bytes: int, *, lambda_max: float = 16.0,
                            refine: int = 2, weights_are_logits: bool = False, per_channel: bool = False, channel_weights=None,
-                           position_weights=None) -> BudgetQuantized:
+                           position_weights=None, channel_skip: bool = False) -> BudgetQuantized:
         """-> the ``BudgetQuantized`` of one latent (``quantize_to_budget_batch``)"""
         return self.quantize_to_budget_batch([y], [scales], [means], [weights], budget_bytes, lambda_max=lambda_max, refine=refine,
                                              weights_are_logits=weights_are_logits, per_channel=per_channel, channel_weights=channel_weights,
-                                             position_weights=_one_item(position_weights))[0]
+                                             position_weights=_one_item(position_weights), channel_skip=channel_skip)[0]
 
     def compress(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, weights_are_logits: bool = False):
         """-> ((bytes, abs_max, zero_bitmap), y_quantized)     (entropy_models.py:833-867)"""

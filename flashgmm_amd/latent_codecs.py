@@ -57,8 +57,11 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
                  entropy_parameters: Optional[nn.Module] = None, quantizer: str = "noise",
                  chunks: Tuple[str, ...] = ("scales", "means", "weights"), mode=None, param_dtype: torch.dtype = torch.float32,
                  fuse_softmax: bool = False, checkpoint_stride: int = 0, rdo_lambda: float = 0.0, target_bytes: Optional[int] = None,
-                 rdo_channel_weights: Optional[Tensor] = None, **kwargs: Any):
+                 rdo_channel_weights: Optional[Tensor] = None, rdo_channel_skip: bool = False, **kwargs: Any):
         super().__init__()
+        # rdo_channel_skip: the two quantisations below may also drop a coded channel whole where that lowers distortion + lambda * bits
+        # (include/flashgmm_amd.h section 3f).  It has an effect only together with rdo_lambda > 0 or target_bytes
+        self.rdo_channel_skip = bool(rdo_channel_skip)
         # rdo_channel_weights: a float32 [M] buffer of per-channel factors of the squared error in the two quantisations below
         # (include/flashgmm_amd.h section 3e: the latent-domain proxy for what a step in that channel costs the image), every factor in
         # [0, 256].  With rdo_lambda == 0 and no target_bytes it does nothing and costs no launch
@@ -137,11 +140,12 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         weighted_sum = torch.sum(me * we, dim=1)
         return weighted_sum, (me - weighted_sum.unsqueeze(1)).reshape(B, KM, H, W)
 
-    def _rdo(self, y_code: Tensor, planes, lam: float, position_weights: Optional[Tensor] = None):
+    def _rdo(self, y_code: Tensor, planes, lam: float, position_weights: Optional[Tensor] = None, channel_skip: Optional[bool] = None):
         """(y_to_code, planes) with y_to_code replaced by its rate-distortion optimised quantisation (integer-valued: the encode path
         then rounds it to itself)"""
         q = self.gaussian_mixture_conditional.quantize_rdo(y_code, *planes, lam, weights_are_logits=self.fuse_softmax,
-                                                           channel_weights=self.rdo_channel_weights, position_weights=position_weights)
+                                                           channel_weights=self.rdo_channel_weights, position_weights=position_weights,
+                                                           channel_skip=self.rdo_channel_skip if channel_skip is None else bool(channel_skip))
         return (q.y, *planes)
 
     def coder_inputs(self, y: Tensor, ctx_params: Tensor, position_weights: Optional[Tensor] = None):
@@ -167,21 +171,24 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
             y_code = y - weighted_sum
         planes = self._planes(scales_hat, means_hat, weights)
         q = self.gaussian_mixture_conditional.quantize_to_budget(y_code, *planes, budget, weights_are_logits=self.fuse_softmax,
-                                                                 channel_weights=self.rdo_channel_weights, position_weights=position_weights)
+                                                                 channel_weights=self.rdo_channel_weights, position_weights=position_weights,
+                                                                 channel_skip=self.rdo_channel_skip)
         return (q.y, *planes)
 
-    def coder_inputs_rdo(self, y: Tensor, ctx_params: Tensor, rdo_lambda: float, position_weights: Optional[Tensor] = None):
+    def coder_inputs_rdo(self, y: Tensor, ctx_params: Tensor, rdo_lambda: float, position_weights: Optional[Tensor] = None,
+                         channel_skip: Optional[bool] = None):
         """``coder_inputs`` with a given ``rdo_lambda`` in place of the codec's own (0: plain rounding, no extra launch - weights then do
-        nothing).  ``position_weights``: as ``coder_inputs_budget`` takes it"""
+        nothing).  ``position_weights``: as ``coder_inputs_budget`` takes it.  ``channel_skip``: in place of the codec's own
+        ``rdo_channel_skip`` (None: the codec's)"""
         lam = _check_rdo_lambda(rdo_lambda)
         scales_hat, means_hat, weights = self._params(ctx_params)
         if self.quantizer == "noise":
             planes = self._planes(scales_hat, means_hat, weights)
-            return self._rdo(y, planes, lam, position_weights) if lam > 0 else (y, *planes)
+            return self._rdo(y, planes, lam, position_weights, channel_skip) if lam > 0 else (y, *planes)
         weighted_sum, means_rel = self._recentre(means_hat, weights)
         d = y - weighted_sum
         if lam > 0:
-            return self._rdo(d, self._planes(scales_hat, means_rel, weights), lam, position_weights)
+            return self._rdo(d, self._planes(scales_hat, means_rel, weights), lam, position_weights, channel_skip)
         # quantize_ste (compressai/ops/ops.py:66-80) is (round(d) - d) + d: the value of round(d), but +0.0 where
         # round(d) is -0.0 — kept, so that the returned y_hat has the reference's bits
         return ((torch.round(d) - d) + d, *self._planes(scales_hat, means_rel, weights))
@@ -280,8 +287,11 @@ class CheckerboardLatentCodec(nn.Module):
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None, entropy_parameters: Optional[nn.Module] = None,
                  context_prediction: Optional[nn.Module] = None, anchor_parity: str = "even", forward_method: str = "twopass",
-                 fuse_head=False, rdo_lambda: float = 0.0, **kwargs: Any):
+                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, **kwargs: Any):
         super().__init__()
+        # rdo_channel_skip: channel skipping (section 3f) in the halves' quantisation at THIS codec's rdo_lambda - with rdo_lambda > 0 it
+        # replaces the inner codec's setting, as the lambda does; with rdo_lambda == 0 the inner codec's own settings apply
+        self.rdo_channel_skip = bool(rdo_channel_skip)
         # rdo_lambda > 0: each half's latents are quantised with rate-distortion optimisation before the half's y_hat is taken, so the
         # non-anchors' context sees what the decoder will see (prepare); 0: the latent codec's own setting.  Precedence when both
         # this codec and its latent codec "y" carry an rdo_lambda: this one, if > 0, REPLACES the inner codec's for both halves (the two
@@ -380,7 +390,7 @@ class CheckerboardLatentCodec(nn.Module):
             else:
                 params_i = self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_params_[i]))
                 # (rdo_lambda = 0: the latent codec's own entry point, with its own setting - today's path)
-                prepared.append(codec.coder_inputs_rdo(y_[i], params_i, self.rdo_lambda, imp_[i]) if self.rdo_lambda > 0
+                prepared.append(codec.coder_inputs_rdo(y_[i], params_i, self.rdo_lambda, imp_[i], self.rdo_channel_skip) if self.rdo_lambda > 0
                                 else codec.coder_inputs(y_[i], params_i, imp_[i]) if imp_[i] is not None else codec.coder_inputs(y_[i], params_i))
             y_hat_[i] = torch.round(prepared[i][0])  # what compress() of this half returns as y_hat
         return prepared, self.embed(y_hat_)

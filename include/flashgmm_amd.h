@@ -49,6 +49,7 @@ extern "C" {
 #define FGMM_HAS_RDOQ 1     /* section 3c: fgmm_gmc_rdoq_batch */
 #define FGMM_HAS_RDCURVE 1  /* section 3d: fgmm_gmc_rdcurve_batch, fgmm_gmc_rdoq_budget_batch */
 #define FGMM_RDCURVE_MAX 16 /* lambdas per fgmm_gmc_rdcurve_batch call */
+#define FGMM_HAS_RDO_SKIP 1    /* section 3f: fgmm_gmc_rdoq_batch_s, fgmm_gmc_rdcurve_batch_s, fgmm_gmc_rdoq_budget_batch_s (added without a bump, as 3b - 3e) */
 #define FGMM_HAS_RDO_WEIGHTS 1 /* section 3e: fgmm_gmc_rdoq_batch_w, fgmm_gmc_rdcurve_batch_w, fgmm_gmc_rdoq_budget_batch_w (added without a bump, as 3b - 3d) */
 #define FGMM_RDO_W_MAX 256.0f  /* largest factor of a weighted call's chan_w / pos_w */
 
@@ -610,7 +611,8 @@ int fgmm_gmc_rdoq_batch(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int 
  *    The front half (census, descriptors) is taken once per call; a pass launches only rdcurve_kernel over the items whose group
  *    is still searching, every group on its own grid, and reads back a few KB of sums.
  *    Caveats.  The budget is on bytes_pred: 3b says when a real stream is 4 bytes longer.  A channel that RDOQ empties is no longer
- *    coded at all, so the real size can only be smaller than f(lambda*) on that account.
+ *    coded at all, so the real size can only be smaller than f(lambda*) on that account.  With channel skipping on (section 3f) this
+ *    second caveat no longer applies: an emptied channel is a skipped one and counts nothing in f.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
   const float *y;          /* device [M*hw] */
@@ -673,6 +675,57 @@ int fgmm_gmc_rdcurve_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *ite
 int fgmm_gmc_rdoq_budget_batch_w(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales,
                                  const int32_t *group_or_null, int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine,
                                  fgmm_budget_result *results /* per group */, const fgmm_rdo_weights *w /* [count] or NULL */);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3f. CHANNEL SKIPPING for 3c - 3e: the format's second lever.  A channel whose symbols are all zero is not coded at all - one bit
+ *    of zero_bitmap, nothing in the stream - and no sequence of one-step decisions finds that trade, because it pays only when the
+ *    whole channel goes.  The _s calls decide it per channel, after the per-latent decisions; the decode side is untouched.
+ *    Everything about a single latent is 3c / 3e's, unchanged.  The rule, exactly (restatable on a CPU; tests/rdo_skip_ref.py does),
+ *    per channel c that the compress call would code for y, at a given lambda:
+ *      inelig(c)   some latent of the channel is not finite, or has |v0| > FGMM_SKIP_VMAX (15), or the item's hw > 2^24.  Such a
+ *                  channel is never skipped
+ *      nz0(c)      latents with v0 != 0 (at least 1: the channel is coded)
+ *      A(c)        the uint64 sum of cost_q of the 3c / 3e choices - chan_bits_q_after as the _w call returns it
+ *      nzA(c)      latents whose choice is not 0
+ *      Dk(c)       the uint64 sum over moved latents of llrint((wt * inc) * 2^32) - 3d / 3e's ddist_q term, per channel
+ *      Dz(c)       the uint64 sum, over latents with v0 != 0, of llrint((wt * incz) * 2^16) (round half to even) with
+ *                  incz = dz * dz - d0 * d0, dz = (double)y, d0 = (double)y - (double)v0: two multiplies and one subtract, no
+ *                  contraction; wt is 3e's exact product, 1.0 without weights.  The unit is 2^-16 on purpose: with |v0| <= 15,
+ *                  wt <= 2^16 and hw <= 2^24 the sum cannot wrap.  incz >= 0, because |y| >= 0.5 >= |d0| whenever v0 != 0
+ *      Jk, Jz      Jk = (double)Dk * 2^-32 + lam_q * (double)A and Jz = (double)Dz * 2^-16: each uint64 -> binary64 conversion one
+ *                  round-to-nearest-even conversion, each remaining operation one IEEE binary64 operation
+ *      skip(c)     !inelig(c) && (nzA(c) == 0 || Jz < Jk).  Strict, so lambda = 0 still returns round(y); the first clause makes
+ *                  "emptied by RDOQ" and "skipped" the same state
+ *    A skipped channel: its plane of y_rdo is +0.0; it contributes 0 to bits_q_after and chan_bits_q_after[c], nz0(c) to n_changed,
+ *    Dz(c) << 16 to the distortion sum (3e's wrap caveat applies there and nowhere else).  abs_max and zero_bitmap are those of the
+ *    final y_rdo; bits_q_before is unchanged.  Consequence: for finite y the estimate call (3b) on y_rdo returns exactly
+ *    bits_q_after and the same zero_bitmap.
+ *    The calls take the _w arguments plus an array of `count` side structures of OUTPUTS, or NULL; with NULL they return exactly
+ *    what the _w forms return - which ARE the _s forms with NULL.  With skipping on, the curve's bits_q_after[j], n_changed[j] and
+ *    ddist_q[j] are the sums after the channel decisions at lambda_j; the budget search is 3d's, untouched, over that f, and its
+ *    last step is the skip-form RDOQ at lambda*.  n_eligible counts the coded channels that are not inelig; `skipped` (HOST
+ *    int64[M], may be NULL) is 1 for a skipped channel, else 0.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FGMM_SKIP_VMAX 15
+typedef struct {
+  int64_t *skipped;        /* HOST int64[M] out, or NULL */
+  int64_t n_skipped;       /* out: channels skipped */
+  int64_t n_eligible;      /* out: coded channels that may be skipped */
+  uint64_t ddist_q;        /* out: the weighted added distortion of y_rdo over round(y), units of 2^-32 */
+} fgmm_rdo_skip;
+typedef struct {
+  uint64_t n_skipped[FGMM_RDCURVE_MAX]; /* out: channels skipped at lambda_j */
+  int64_t n_eligible;                   /* out */
+} fgmm_rdcurve_skip;
+int fgmm_gmc_rdoq_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales, double lambda,
+                          const fgmm_rdo_weights *w /* [count] or NULL */, fgmm_rdo_skip *skip /* [count] or NULL */);
+int fgmm_gmc_rdcurve_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdcurve_item *items, int count, int mode, int clamp_scales,
+                             const double *lambdas, int n_lambda, const fgmm_rdo_weights *w /* [count] or NULL */,
+                             fgmm_rdcurve_skip *skip /* [count] or NULL */);
+int fgmm_gmc_rdoq_budget_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *items, int count, int mode, int clamp_scales,
+                                 const int32_t *group_or_null, int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine,
+                                 fgmm_budget_result *results /* per group */, const fgmm_rdo_weights *w /* [count] or NULL */,
+                                 fgmm_rdo_skip *skip /* [count] or NULL */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
