@@ -770,7 +770,13 @@ int fgmm_decstream_decode(fgmm_decstream *d, const int32_t *indexes, int64_t n, 
  * CheckerboardLatentCodec.unembed / embed (compressai/latent_codecs/checkerboard.py:333-377): split a [planes, h, w]
  * device tensor into its two checkerboard halves [2, planes, h, w/2] (half 0 = anchors) and back.  planes = n * c;
  * w must be even; elem_bytes 4 (float32 / int32) or 2 (float16); anchor_odd = 0 for anchor_parity "even" (anchors at
- * (even row, even column) and (odd row, odd column)), 1 for "odd".  Pure data movement: any bit pattern is preserved. */
+ * (even row, even column) and (odd row, odd column)), 1 for "odd".  Pure data movement: any bit pattern is preserved.
+ * STREAM-ORDERED, unlike the calls of sections 2 and 3: the one kernel is enqueued on `stream` (NULL = default stream), behind
+ * whatever the caller enqueued there before, and the call returns WITHOUT waiting for it.  `dst` is complete for work enqueued on
+ * `stream` afterwards, and for another stream or the host only once they have waited for `stream` (an event recorded on it after
+ * the call, or a synchronisation); `src` must stay valid and unchanged until then.  No workspace of the context is used, and the
+ * context is not locked: calls from several threads on several streams run concurrently.  A refused call (odd w, a full tensor
+ * that is not aligned to a pair of elements, a halves tensor not aligned to an element) launches nothing and writes nothing. */
 int fgmm_ckbd_unembed(fgmm_ctx *ctx, void *stream, const void *src, void *dst, int64_t planes, int64_t h, int64_t w,
                       int elem_bytes, int anchor_odd);
 int fgmm_ckbd_embed(fgmm_ctx *ctx, void *stream, const void *src, void *dst, int64_t planes, int64_t h, int64_t w,

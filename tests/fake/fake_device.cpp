@@ -230,6 +230,12 @@ const char *error_string(int e) { return e == kErrUnsupported ? "fake device: ke
 
 } // namespace dev
 
+// test-only hook (tests/fake/stress_main.cpp): a nap of `us` microseconds in the stream's queue - a producer that is still running when
+// the call that consumes its output is made
+extern "C" void fgmm_fake_delay(void *stream, int us) {
+  S(stream)->push([us] { std::this_thread::sleep_for(std::chrono::microseconds(us)); });
+}
+
 // ================================================================================================================ the "kernels"
 namespace {
 

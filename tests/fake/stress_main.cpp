@@ -7,6 +7,11 @@
 // tables, scatter rounds, checkpointed streams decoded in host segments / handed to the "GPU" and partly handed back, a tiny staging
 // budget that forces overflow re-runs, an LDS budget that sends items to the generic kernels) and random worker counts; now and then a
 // truncated bitstream, which must be refused, and a corrupted one, which must decode to what the oracle's decoder makes of it.
+// About every other round runs on a CALLER'S STREAM (include/flashgmm_amd.h, section 2) instead of the default one, with the producer
+// of the call's inputs still PENDING on that stream: the "device" inputs hold a decoy (another item's values of the same shape) and
+// the true values arrive by async copies queued on the caller's stream behind a nap, immediately before the call.  Outputs are
+// poisoned before every call.  The checks are the same ones: work the library puts on another stream than the caller's, or reads
+// through the default stream too early, reads the decoy and fails them (or is a race for ThreadSanitizer).
 //   stress_main [seconds] [seed]
 #include <atomic>
 #include <thread>
@@ -24,6 +29,9 @@
 #include <vector>
 
 #include "../../include/flashgmm_amd.h"
+#include "../../flashgmm_amd/csrc/fgmm_device.h"
+
+extern "C" void fgmm_fake_delay(void *stream, int us); // fake_device.cpp: a nap in the stream's queue
 
 extern "C" int fgo_encode_gmm(int mode, int64_t n, const int32_t *symbols, const float *scales, const float *means, const float *weights, int64_t sn, int64_t sk,
                               uint8_t **out, size_t *out_len, int64_t *n_bypass_out);
@@ -55,6 +63,7 @@ struct Item {
   int64_t hw;
   std::vector<float> y, sg, mu, pi, yq, yhat; // planes [K, M, hw]
   std::vector<int64_t> zb;
+  std::vector<float> dy, dsg, dmu, dpi; // a caller's-stream round: the "device" inputs the call is given (decoy first, then y, sg, mu, pi)
 };
 
 // torch.clamp(s, 0.11, 256): NaN stays NaN (fminf / fmaxf would turn it into 0.11)
@@ -63,7 +72,7 @@ static float clamp_sigma(float s) {
   return (s > 256.0f) ? 256.0f : s;
 }
 
-static void make_item(Item &it, int M, int64_t hw, double zero_frac) {
+static void make_item(Item &it, int M, int64_t hw, double zero_frac, bool finite_only = false) {
   it.M = M, it.hw = hw;
   const size_t n = (size_t)M * (size_t)hw;
   it.y.resize(n), it.yq.assign(n, -7.f), it.yhat.assign(n, -9.f), it.zb.assign((size_t)M, -1);
@@ -85,7 +94,7 @@ static void make_item(Item &it, int M, int64_t hw, double zero_frac) {
   }
   // one item in three: what the clamped kernels' fast evaluation hands back to the IEEE one - a NaN sigma (the clamp keeps it:
   // Sigma4::set's `tame`) and a mean more than 2^11 from the latent (mix4_clamped2's compare) - in a few latents each
-  if (n > 0 && rnd() % 3 == 0)
+  if (n > 0 && !finite_only && rnd() % 3 == 0)
     for (int r = 0; r < 1 + (int)(n / 64); ++r) {
       it.sg[(size_t)(rnd() % 4) * n + (size_t)(rnd() % n)] = NAN;
       it.mu[(size_t)(rnd() % 4) * n + (size_t)(rnd() % n)] = (float)((rnd() % 2 ? 1.0 : -1.0) * (2040.0 + 40.0 * uni() + (rnd() % 4 ? 0.0 : 1e6 * uni())));
@@ -195,6 +204,8 @@ int main(int argc, char **argv) {
     CHECK(sched_setaffinity(0, sizeof one, &one) == 0, "setaffinity");
   }
   CHECK(fgmm_ctx_create(0, 4, &ctx) == FGMM_OK, "ctx");
+  fgmm::dev::Stream caller = nullptr; // the driver's own stream: the caller's stream of about every other round
+  CHECK(fgmm::dev::stream_create(&caller, false) == 0, "caller's stream");
   if (const char *want = getenv("FGMM_STRESS_EXPECT_WORKER_CPUS")) { // (tests/test_fake_device_cpu.py: FGMM_WORKER_CPUS is honoured)
     char got[4096];
     CHECK(fgmm_ctx_worker_cpus(ctx, got, sizeof got) == FGMM_OK && !strcmp(got, want), "worker CPUs '%s', expected '%s'", got, want);
@@ -235,7 +246,7 @@ int main(int argc, char **argv) {
     printf("worker CPUs: '%s' (%d threads checked)\n", got, seen);
   }
   const auto t_end = std::chrono::steady_clock::now() + std::chrono::duration<double>(budget);
-  long rounds = 0, refused = 0, streams = 0, symbols = 0, corrupted_same = 0, corrupted_refused = 0;
+  long rounds = 0, on_callers = 0, refused = 0, streams = 0, symbols = 0, corrupted_same = 0, corrupted_refused = 0;
   static const int kThreads[] = {1, 2, 3, 5, 8, 16};
   while (std::chrono::steady_clock::now() < t_end) {
     // The first three rounds of every run are LARGE bitstreams under the AUTOMATIC piece plan (pieces = 0), which the random
@@ -267,8 +278,10 @@ int main(int argc, char **argv) {
     const int mode = (int)(rnd() % 3), clamp = 1;
     const int32_t stride = !big && rnd() % 2 ? (int32_t)(256 << (rnd() % 3)) : 0; // checkpointed streams
     const int count = big ? (rounds == 2 ? 2 : 1) : mixed_segs ? (int)pick(5, 12) : (int)pick(1, 12);
-    std::vector<Item> its((size_t)count);
+    std::vector<Item> its((size_t)count), decoys;
     std::vector<fgmm_item> fi((size_t)count);
+    const bool on_stream = rnd() % 2 == 0;
+    void *const cs = on_stream ? caller : nullptr; // what the calls of this round are given as `stream`
     for (int i = 0; i < count; ++i) {
       static const int Ms[] = {1, 3, 8, 9, 17, 24};
       static const int64_t HWs[] = {1, 7, 64, 96, 192, 384};
@@ -283,6 +296,13 @@ int main(int argc, char **argv) {
       memset(&f, 0, sizeof f);
       f.y = it.y.data();
       f.params.scales = it.sg.data(), f.params.means = it.mu.data(), f.params.weights = it.pi.data();
+      if (on_stream) {
+        decoys.emplace_back();
+        make_item(decoys.back(), it.M, it.hw, 0.15, true);
+        it.dy = decoys.back().y, it.dsg = decoys.back().sg, it.dmu = decoys.back().mu, it.dpi = decoys.back().pi;
+        f.y = it.dy.data();
+        f.params.scales = it.dsg.data(), f.params.means = it.dmu.data(), f.params.weights = it.dpi.data();
+      }
       f.params.stride_k = (int64_t)it.M * it.hw, f.params.stride_c = it.hw, f.params.dtype = FGMM_F32;
       f.M = it.M, f.K = 4, f.hw = it.hw;
       f.yq_out = it.yq.data();
@@ -290,7 +310,7 @@ int main(int argc, char **argv) {
       f.ckpt_stride = stride;
     }
     if (getenv("FGMM_STRESS_VERBOSE")) {
-      fprintf(stderr, "[round %ld] threads %d mode %d stride %d count %d:", rounds, fgmm_ctx_threads(ctx), mode, stride, count);
+      fprintf(stderr, "[round %ld] threads %d mode %d stride %d count %d%s:", rounds, fgmm_ctx_threads(ctx), mode, stride, count, on_stream ? " caller's stream" : "");
       for (int i = 0; i < count; ++i) fprintf(stderr, " %dx%lld", its[(size_t)i].M, (long long)its[(size_t)i].hw);
       for (const char *nm : {"pieces", "dec_first", "ef_rows", "ef_min", "enc_ways", "enc_segs", "scatter_rounds", "ckpt_decode", "gpu_decode", "stage_max_mb", "tab_cap_e", "spin_lat"}) {
         int64_t v = 0;
@@ -302,6 +322,28 @@ int main(int argc, char **argv) {
     // One round in three through a SINK (fgmm_sink): the bitstreams go into storage handed out by the caller, of their exact size (a
     // malloc each: the sanitizer sees a byte too many), asked for once per item on the calling thread; now and then the sink
     // refuses an item first - the call must fail with FGMM_ERR_NOMEM and return no buffer - and the call is made again.
+    // Before every call: the outputs poisoned; on a caller's stream the inputs back to the decoy, then - queued on that stream behind a
+    // nap - the copies that bring the true values (for a decode: the parameter planes only).  The call follows at once.
+    auto arm = [&](bool compress) {
+      for (Item &it : its) std::fill(compress ? it.yq.begin() : it.yhat.begin(), compress ? it.yq.end() : it.yhat.end(), compress ? -7.f : -9.f);
+      if (!on_stream) return;
+      struct Plane {
+        std::vector<float> *d;
+        const std::vector<float> *decoy, *truth;
+      };
+      std::vector<Plane> planes;
+      for (size_t i = 0; i < its.size(); ++i) {
+        Item &it = its[i];
+        if (it.y.empty()) continue;
+        if (compress) planes.push_back(Plane{&it.dy, &decoys[i].y, &it.y});
+        planes.push_back(Plane{&it.dsg, &decoys[i].sg, &it.sg});
+        planes.push_back(Plane{&it.dmu, &decoys[i].mu, &it.mu});
+        planes.push_back(Plane{&it.dpi, &decoys[i].pi, &it.pi});
+      }
+      for (Plane &p : planes) memcpy(p.d->data(), p.decoy->data(), sizeof(float) * p.d->size());
+      fgmm_fake_delay(caller, 300);
+      for (Plane &p : planes) CHECK(fgmm::dev::copy_async(p.d->data(), p.truth->data(), sizeof(float) * p.d->size(), fgmm::dev::kH2D, caller) == 0, "producer copy");
+    };
     Sunk sunk;
     const bool to_sink = rnd() % 3 == 0;
     if (to_sink) {
@@ -309,16 +351,19 @@ int main(int argc, char **argv) {
       const fgmm_sink sink{&Sunk::alloc, &sunk};
       if (rnd() % 4 == 0) {
         sunk.refuse = (int)(rnd() % (uint64_t)count);
-        CHECK(fgmm_gmc_compress_batch_to(ctx, nullptr, fi.data(), count, mode, clamp, &sink) == FGMM_ERR_NOMEM, "a sink that refuses item %d: the call went through", sunk.refuse);
+        arm(true);
+        CHECK(fgmm_gmc_compress_batch_to(ctx, cs, fi.data(), count, mode, clamp, &sink) == FGMM_ERR_NOMEM, "a sink that refuses item %d: the call went through", sunk.refuse);
         for (int i = 0; i < count; ++i) CHECK(!fi[(size_t)i].bytes && !fi[(size_t)i].ckpt, "a failed call returned a buffer (item %d)", i);
         sunk.reset(count);
       }
-      CHECK(fgmm_gmc_compress_batch_to(ctx, nullptr, fi.data(), count, mode, clamp, &sink) == FGMM_OK, "compress_batch_to (count %d)", count);
+      arm(true);
+      CHECK(fgmm_gmc_compress_batch_to(ctx, cs, fi.data(), count, mode, clamp, &sink) == FGMM_OK, "compress_batch_to (count %d)", count);
       for (int i = 0; i < count; ++i)
         CHECK(sunk.calls[(size_t)i].load() == 1 && fi[(size_t)i].bytes == sunk.slot[(size_t)i] && fi[(size_t)i].bytes_len == sunk.len[(size_t)i],
               "sink: item %d asked %d times / bytes not where the sink said", i, sunk.calls[(size_t)i].load());
     } else {
-      CHECK(fgmm_gmc_compress_batch(ctx, nullptr, fi.data(), count, mode, clamp) == FGMM_OK, "compress_batch (count %d)", count);
+      arm(true);
+      CHECK(fgmm_gmc_compress_batch(ctx, cs, fi.data(), count, mode, clamp) == FGMM_OK, "compress_batch (count %d)", count);
     }
     // ---- every bitstream against the oracle's encoder
     for (int i = 0; i < count; ++i) {
@@ -346,7 +391,8 @@ int main(int argc, char **argv) {
     }
     // ---- decode: y_hat == y_q
     for (int i = 0; i < count; ++i) fi[(size_t)i].yq_out = its[(size_t)i].yhat.data();
-    CHECK(fgmm_gmc_decompress_batch(ctx, nullptr, fi.data(), count, mode, clamp) == FGMM_OK, "decompress_batch (count %d)", count);
+    arm(false);
+    CHECK(fgmm_gmc_decompress_batch(ctx, cs, fi.data(), count, mode, clamp) == FGMM_OK, "decompress_batch (count %d)", count);
     for (int i = 0; i < count; ++i) CHECK(its[(size_t)i].yhat == its[(size_t)i].yq, "y_hat != y_q, item %d of %d", i, count);
     // ---- a truncated bitstream must be refused (and must not take the call down with it)
     if (rnd() % 3 == 0) {
@@ -358,7 +404,8 @@ int main(int argc, char **argv) {
         const fgmm_item keep = fi[(size_t)victim];
         fi[(size_t)victim].bytes_len = 16;
         if (rnd() % 2) fi[(size_t)victim].ckpt = nullptr, fi[(size_t)victim].n_ckpt = 0; // (with and without its notes)
-        CHECK(fgmm_gmc_decompress_batch(ctx, nullptr, fi.data(), count, mode, clamp) != FGMM_OK, "a truncated bitstream decoded");
+        arm(false);
+        CHECK(fgmm_gmc_decompress_batch(ctx, cs, fi.data(), count, mode, clamp) != FGMM_OK, "a truncated bitstream decoded");
         fi[(size_t)victim] = keep;
         ++refused;
       }
@@ -380,8 +427,8 @@ int main(int argc, char **argv) {
         for (size_t k = (size_t)pick(0, (int64_t)keep.bytes_len - 1); k < keep.bytes_len; k += (size_t)pick(1, 9)) b8[k] = (uint8_t)rnd();
         fi[(size_t)victim].bytes = b8;
         if (rnd() % 2) fi[(size_t)victim].ckpt = nullptr, fi[(size_t)victim].n_ckpt = 0;
-        std::fill(it.yhat.begin(), it.yhat.end(), -9.f);
-        const int rc = fgmm_gmc_decompress_batch(ctx, nullptr, fi.data(), count, mode, clamp);
+        arm(false);
+        const int rc = fgmm_gmc_decompress_batch(ctx, cs, fi.data(), count, mode, clamp);
         if (rc == FGMM_OK) {
           std::vector<int32_t> sym, dec;
           std::vector<float> s, m, w;
@@ -439,10 +486,11 @@ int main(int argc, char **argv) {
       if (!to_sink) fgmm_free(f.bytes); // (a sink's storage is the caller's: released with `sunk`)
       fgmm_free(f.ckpt);
     }
-    ++rounds;
+    ++rounds, on_callers += on_stream;
   }
   fgmm_ctx_destroy(ctx);
-  printf("stress on the fake device: %ld batches, %ld bitstreams == oracle, %ld symbols, %ld truncated batches refused, %ld corrupted bitstreams == oracle's decoder (%ld ran off the end: refused)\n", rounds, streams, symbols, refused,
+  CHECK(fgmm::dev::stream_destroy(caller) == 0, "caller's stream");
+  printf("stress on the fake device: %ld batches (%ld on a caller's stream), %ld bitstreams == oracle, %ld symbols, %ld truncated batches refused, %ld corrupted bitstreams == oracle's decoder (%ld ran off the end: refused)\n", rounds, on_callers, streams, symbols, refused,
          corrupted_same, corrupted_refused);
   return 0;
 }

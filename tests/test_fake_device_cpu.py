@@ -1,9 +1,11 @@
 """The product's host pipeline on the FAKE device (tests/fake/fake_device.cpp: device memory = host memory, every stream an in-order
 queue on its own thread, the kernels restated from the oracle): randomized batches through the C ABI, every bitstream against the
-oracle's encoder, every decode against round(y), truncated bitstreams refused - the same driver scripts/tsan_host.sh runs under
+oracle's encoder, every decode against round(y), truncated bitstreams refused, about every other batch on a caller's stream with the
+producer of its inputs still pending - the same driver scripts/tsan_host.sh runs under
 ThreadSanitizer and AddressSanitizer + UBSan.  Here: an un-instrumented build, a few seconds, so that the CPU suite covers the
 concurrent pipeline (planner, staging, task queue, event waits, overflow re-runs, GPU-segment hand-back) without a GPU."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -29,6 +31,9 @@ def test_host_pipeline_on_the_fake_device(stress_binary, seed):
     r = subprocess.run([stress_binary, "4", str(seed)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "bitstreams == oracle" in r.stdout and " 0 batches" not in r.stdout, r.stdout
+    # about every other batch runs on a caller's stream with its producer still pending (stress_main.cpp): both seeds have some
+    on_callers = re.search(r"\((\d+) on a caller's stream\)", r.stdout)
+    assert on_callers and int(on_callers.group(1)) > 0, r.stdout
 
 
 def test_host_sources_do_not_include_the_gpu_runtime():

@@ -1326,7 +1326,13 @@ def test_checkerboard_split_merge_equals_reference_slicing(parity, dtype):
     from flashgmm_amd.ops import ckbd_embed, ckbd_unembed
 
     g = torch.Generator().manual_seed(5)
-    for shape in [(1, 6, 8, 12), (1, 3, 7, 10), (2, 5, 1, 2), (1, 192, 32, 48), (1, 1, 33, 258), (1, 4, 0, 6)]:
+    # launch_ckbd's forms (fgmm_kernels.hip): WIDE (V pairs per lane: V = 2 for 4-byte, 4 for 2-byte elements) when w/2 is a multiple of V,
+    # both tensors are 16-byte aligned and so is the second half; inside the kernel an odd h takes the row parity from row % h.
+    #   (1, 4, 7, 8), (2, 2, 5, 16)     wide with odd h, for both element sizes
+    #   (1, 1, 3, 4), (1, 3, 1, 8)      w/2 a multiple of V (the first for 4-byte, the second for 2-byte elements too) but the second half
+    #                                   starts 24 bytes in: narrow by the third condition
+    for shape in [(1, 6, 8, 12), (1, 3, 7, 10), (2, 5, 1, 2), (1, 192, 32, 48), (1, 1, 33, 258), (1, 4, 0, 6),
+                  (1, 4, 7, 8), (2, 2, 5, 16), (1, 1, 3, 4), (1, 3, 1, 8)]:
         y = (torch.randn(shape, generator=g) * 50).to(dtype).to("cuda")
         want = _ref_unembed(y, parity)
         got = ckbd_unembed(y, parity)
@@ -1337,6 +1343,40 @@ def test_checkerboard_split_merge_equals_reference_slicing(parity, dtype):
     bits = torch.tensor([0x80000000, 0x7FC12345, 0x7F800000, 0xFF800001], dtype=torch.int64).to(torch.int32)
     y = bits.view(torch.float32).reshape(1, 1, 2, 2).cuda()
     assert torch.equal(ckbd_embed(ckbd_unembed(y, parity), parity).view(torch.int32), y.view(torch.int32))
+    # tensors that are dense views INTO their storage, on a shape that is otherwise wide
+    shape = (1, 6, 8, 12)
+    y = (torch.randn(shape, generator=g) * 50).to(dtype).to("cuda")
+    want = _ref_unembed(y, parity)
+
+    def view_at(t, nbytes, fill=0):
+        """the values of t in a dense view that starts nbytes into a fresh storage -> (view, storage)"""
+        off = nbytes // t.element_size()
+        buf = torch.full((t.numel() + off,), fill, dtype=t.dtype, device=t.device)
+        v = buf[off:].view(t.shape)
+        v.copy_(t)
+        assert v.is_contiguous() and v.data_ptr() % 16 == nbytes % 16
+        return v, buf
+
+    # 8 bytes in: pair-aligned but not 16-byte aligned -> the narrow form, the same result (the full tensor, then the halves)
+    assert torch.equal(ckbd_unembed(view_at(y, 8)[0], parity), want)
+    assert torch.equal(ckbd_embed(view_at(want, 8)[0], parity), y)
+    # one element in: the full tensor is not pair-aligned -> refused (fgmm_capi.cpp), and the destination is not written
+    y1, _ = view_at(y, y.element_size())
+    with pytest.raises(RuntimeError):
+        ckbd_unembed(y1, parity)
+    L, ctx, odd = _lib.lib(), _lib.ctx(0), int(parity == "odd")
+    poison = torch.full_like(want, 77)
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError):
+        _lib.check(L.fgmm_ckbd_unembed(ctx, None, y1.data_ptr(), poison.data_ptr(), 6, 8, 12, y.element_size(), odd))
+    torch.cuda.synchronize()
+    assert torch.equal(poison, torch.full_like(want, 77))
+    full1, storage = view_at(torch.full_like(y, 77), y.element_size(), fill=77)
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError):
+        _lib.check(L.fgmm_ckbd_embed(ctx, None, want.data_ptr(), full1.data_ptr(), 6, 8, 12, y.element_size(), odd))
+    torch.cuda.synchronize()
+    assert torch.equal(storage, torch.full_like(storage, 77))
     with pytest.raises(RuntimeError):
         ckbd_unembed(torch.zeros(1, 2, 4, 5, device="cuda"), parity)  # odd width
     with pytest.raises(RuntimeError):
