@@ -1161,7 +1161,10 @@ def test_gpu_segment_decoder_equals_the_table_path_in_every_variant(oracle, mode
     """segdec_kernel (checkpointed bitstreams decoded ON the GPU, edges across the lanes, count + ballot for the reference's
     bisection) against the table path and the oracle: fp32 / fp16 planes, sigma clamped or not, weights as logits,
     windows beyond 64 edges (several passes per symbol), bypass-coded symbols (the synthetic latents have ~0.2 % of them), dead channels, tiny items (one segment,
-    fewer than 64 latents), and parameters the kernel must hand back (decreasing rows, NaN sigma)."""
+    fewer than 64 latents), and parameters the kernel must hand back (decreasing rows, NaN sigma).  The latents here are noise: which
+    window lengths, batch sizes and segment residues occur is chance.  The structural cases - 63 | 64 edges, the 2048-edge budget,
+    short last segments, escapes at segment and batch boundaries, both launch shapes - are placed on purpose and checked against
+    the oracle in tests/test_gpu_segdec_edges.py."""
     rng = np.random.default_rng(91)
     _lib.set_option(0, "gpu_decode", 1)  # (small items: by default they would be the host workers')
     cases = []
