@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("FGMM_LIB") or os.path.join(HERE, "libflashgmm_amd.so"
 FGMM_OK = 0
 FGMM_HOST, FGMM_DEVICE = 0, 1
 FGMM_K = 4
-FGMM_F32, FGMM_F16 = 0, 1
+FGMM_F32, FGMM_F16, FGMM_BF16 = 0, 1, 2
 FGMM_HEAD_BF16X6 = 1  # fgmm_head_create_ex flags
 FGMM_PARAMS_LOGITS = 1  # fgmm_params.flags: the weights planes hold logits, softmax over K runs in the kernels
 MODES = {"polya": 0, "as": 1, "logistic": 2}  # numbering of the reference CODE (rans_interface.cpp:224-232)

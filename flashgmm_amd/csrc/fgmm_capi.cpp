@@ -529,8 +529,8 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
     } else {
       if (s.M < 0 || s.hw < 0 || (s.M * s.hw && (!s.y || !s.params.scales || !s.params.means || !s.params.weights)))
         return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
-      if (s.params.dtype != items[0].params.dtype || (s.params.dtype != FGMM_F32 && s.params.dtype != FGMM_F16))
-        return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32 or FGMM_F16 and the same for a whole batch", i);
+      if (s.params.dtype != items[0].params.dtype || (s.params.dtype != FGMM_F32 && !planes_two_byte(s.params.dtype)))
+        return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32, FGMM_F16 or FGMM_BF16 and the same for a whole batch", i);
       if (s.params.flags & ~FGMM_PARAMS_LOGITS) return fail(FGMM_ERR_INVALID, "item %d: unknown fgmm_params.flags %d", i, s.params.flags);
       e.prm = s.params;
     }
@@ -719,8 +719,8 @@ int fgmm_gmc_decompress_batch(fgmm_ctx *ctx, void *stream, fgmm_item *items, int
     if (s.M < 0 || s.hw < 0 || !s.bytes || (s.M && !s.zero_bitmap) ||
         (s.M * s.hw && (!s.yq_out || !s.params.scales || !s.params.means || !s.params.weights)))
       return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
-    if (s.params.dtype != items[0].params.dtype || (s.params.dtype != FGMM_F32 && s.params.dtype != FGMM_F16))
-      return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32 or FGMM_F16 and the same for a whole batch", i);
+    if (s.params.dtype != items[0].params.dtype || (s.params.dtype != FGMM_F32 && !planes_two_byte(s.params.dtype)))
+      return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32, FGMM_F16 or FGMM_BF16 and the same for a whole batch", i);
     if (s.params.flags & ~FGMM_PARAMS_LOGITS) return fail(FGMM_ERR_INVALID, "item %d: unknown fgmm_params.flags %d", i, s.params.flags);
     DecItem &d = v[i];
     d.enc = s.bytes;

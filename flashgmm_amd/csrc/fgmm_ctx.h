@@ -300,7 +300,7 @@ void census_bind(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o); // the de
 void census_desc(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o, const float *y, const fgmm_params *params_or_null, int M, int64_t hw,
                  int clamp);
 // can every load of an item, and the store to `out` (may be null), be 4 positions wide?
-bool enc_vec4_ok(const EncDesc &d, const void *out, bool f16);
+bool enc_vec4_ok(const EncDesc &d, const void *out, bool two_byte); // two_byte: float16 or bfloat16 planes
 // from the census copied back to the host: abs_max as the compress call returns it, zero_bitmap (may be null), the latent's {min, max}
 // with NaN kept (may be null); returns the coded channels' count
 int census_side_info(const fgmm_ctx *ctx, const CensusOff &o, int M, int64_t hw, int64_t *zero_bitmap_or_null, int32_t *abs_max_out,
@@ -544,7 +544,8 @@ struct LatentFrame {
   std::vector<LatentIn> in;
   int count, clamp, M_max = 0, vec = 1;
   int64_t hw_max = 0, n_max = 0;
-  bool f16 = false, linear = true, census2 = false;
+  int planes = FGMM_F32; // the fgmm_dtype of the batch's parameter planes
+  bool linear = true, census2 = false;
   size_t o_descs = 0, o_call = 0, o_small = 0, o_sums = 0, o_dev = 0, end = 0;
   std::vector<CensusOff> census, census_out;
   std::vector<size_t> o_back, o_acc; // per item: its sums (back_item + back_chan * M words), its device-only words

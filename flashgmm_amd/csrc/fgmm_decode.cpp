@@ -59,6 +59,7 @@ struct DecodeCall {
   dev::Stream stream;
   std::vector<DecItem> &items;
   const int mode, count;
+  int kmode = 0; // `mode` as the launchers take it: with the plane type (fgmm_internal.h, kPlanesBf16)
   Trace tr;
   // ---- configuration of the call
   int cap_e = kTabCapE, np = 1, decoders = 1;
@@ -111,6 +112,7 @@ struct DecodeCall {
         }
     clamped = items[0].clamp != 0;
     f16 = items[0].prm.dtype == FGMM_F16;
+    kmode = mode_with_planes(mode, items[0].prm.dtype);
     // Segments pay when a call has fewer bitstreams than workers (one image, ELIC's stages of a few images); a call with a bitstream
     // per worker or more keeps them all busy piece by piece and would only pay the segments' bookkeeping: the notes are ignored there
     const bool use_ckpt = ctx->opt.ckpt_decode == 1 || (ctx->opt.ckpt_decode == 0 && count < std::max(ctx->decoders()->size(), 1));
@@ -402,7 +404,7 @@ struct DecodeCall {
       tl_max = std::max(tl_max, (int)items[p.item].tl);
     }
     const DecDesc *dd = reinterpret_cast<const DecDesc *>(ctx->d_ws + o_descs);
-    LAUNCH_TRY(launch_tab(dd + unit_desc0[(size_t)u], (int)un.parts.size(), (int)blocks_max, tl_max, cap_e, mode, clamped, f16, stream));
+    LAUNCH_TRY(launch_tab(dd + unit_desc0[(size_t)u], (int)un.parts.size(), (int)blocks_max, tl_max, cap_e, kmode, clamped, f16, stream));
     return FGMM_OK;
   }
   int launch_next() {
@@ -527,7 +529,7 @@ struct DecodeCall {
     d.blk_off = reinterpret_cast<unsigned long long *>(d_g + g_boff);
     DEV_TRY(dev::memset_async(d_g + g_used, 0, 64, stream));
     DEV_TRY(dev::copy_async(d_g + g_desc, &d, sizeof d, dev::kH2D, stream));
-    LAUNCH_TRY(launch_cdftab_count(reinterpret_cast<const DecDesc *>(d_g + g_desc), 1, it.n_ch, it.hw, mode, clamped, f16, stream));
+    LAUNCH_TRY(launch_cdftab_count(reinterpret_cast<const DecDesc *>(d_g + g_desc), 1, it.n_ch, it.hw, kmode, clamped, f16, stream));
     unsigned long long used4[4] = {0, 0, 0, 0};
     DEV_TRY(dev::copy_async(used4, d_g + g_used, sizeof used4, dev::kD2H, stream));
     DEV_TRY(dev::stream_sync(stream));
@@ -540,7 +542,7 @@ struct DecodeCall {
     if ((rc = temp.alloc(pool_bytes + 256, &d_pool)) || (rc = ctx->chunk_alloc(hdr_bytes + pool_bytes + 256, &h_range))) return rc;
     d.pool = reinterpret_cast<uint8_t *>(d_pool);
     DEV_TRY(dev::copy_async(d_g + g_desc, &d, sizeof d, dev::kH2D, stream));
-    LAUNCH_TRY(launch_cdftab_fill(reinterpret_cast<const DecDesc *>(d_g + g_desc), 1, it.n_ch, it.hw, mode, clamped, f16, stream));
+    LAUNCH_TRY(launch_cdftab_fill(reinterpret_cast<const DecDesc *>(d_g + g_desc), 1, it.n_ch, it.hw, kmode, clamped, f16, stream));
     DEV_TRY(dev::copy_async(h_range, d_g + g_hdr, hdr_bytes, dev::kD2H, stream));
     if (pool_bytes) DEV_TRY(dev::copy_async(h_range + hdr_bytes, d_pool, pool_bytes, dev::kD2H, stream));
     memset(h_range + hdr_bytes + pool_bytes, 0, 256);

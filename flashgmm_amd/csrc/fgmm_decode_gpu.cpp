@@ -121,7 +121,7 @@ int decode_batch_gpu(fgmm_ctx *ctx, dev::Stream stream, std::vector<DecItem> &it
   DEV_TRY(dev::copy_async(ctx->d_ws, ctx->h_ws, upload_bytes, dev::kH2D, stream));
   LAUNCH_TRY(launch_segzero(reinterpret_cast<const SegDesc *>(ctx->d_ws + o_descs), count, max_dead, stream));
   if ((rc = ctx->prof_begin(3, stream))) return rc;
-  LAUNCH_TRY(launch_segdec(reinterpret_cast<const SegDesc *>(ctx->d_ws + o_descs), reinterpret_cast<const SegRef *>(ctx->d_ws + o_segs), n_segs, mode,
+  LAUNCH_TRY(launch_segdec(reinterpret_cast<const SegDesc *>(ctx->d_ws + o_descs), reinterpret_cast<const SegRef *>(ctx->d_ws + o_segs), n_segs, mode_with_planes(mode, items[which[0]].prm.dtype),
                            clamped, f16, stream));
   if ((rc = ctx->prof_end(3, stream))) return rc;
   DEV_TRY(dev::copy_async(ctx->h_ws + o_status, ctx->d_ws + o_status, sizeof(uint32_t) * (size_t)n_segs, dev::kD2H, stream));

@@ -28,7 +28,8 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // parameter planes are float32, or float16 converted on load (BASELINE configs[4]: "fp16 (mu,sigma,pi) with fp32 CDF
-// accumulate"): every value is widened exactly, then the fp32 path runs unchanged
+// accumulate"), or bfloat16 (its 16 bits become the upper half of the binary32 pattern: one shift or mask, NaN payloads, infinities,
+// signed zeros and subnormals kept): every value is widened exactly, then the fp32 path runs unchanged
 // Descriptor pointers are generic (they come out of a struct in memory): cast to the global address space so that the
 // accesses are global_load / global_store (a flat_load also takes a slot of the LDS queue and is waited for out of order).
 #define FGMM_GLOBAL __attribute__((address_space(1)))
@@ -45,6 +46,7 @@ template <typename T> __device__ __forceinline__ T ldg(const void *p) {
 }
 template <typename T> __device__ __forceinline__ void stg(void *p, T v) { *(FGMM_GLOBAL T *)p = v; }
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bfloat4_t __attribute__((ext_vector_type(4)));
 typedef float float4_t __attribute__((ext_vector_type(4)));
 template <typename PT> __device__ __forceinline__ float ld1(const void *base, int64_t idx) {
   return (float)ldg<PT>(static_cast<const PT *>(base) + idx);
@@ -56,6 +58,10 @@ template <> __device__ __forceinline__ void ld4<float>(const void *base, int64_t
 }
 template <> __device__ __forceinline__ void ld4<_Float16>(const void *base, int64_t idx, float (&out)[4]) {
   const half4_t v = ldg<half4_t>(static_cast<const _Float16 *>(base) + idx); // 8 B / lane
+  out[0] = (float)v[0]; out[1] = (float)v[1]; out[2] = (float)v[2]; out[3] = (float)v[3];
+}
+template <> __device__ __forceinline__ void ld4<__bf16>(const void *base, int64_t idx, float (&out)[4]) {
+  const bfloat4_t v = ldg<bfloat4_t>(static_cast<const __bf16 *>(base) + idx); // 8 B / lane
   out[0] = (float)v[0]; out[1] = (float)v[1]; out[2] = (float)v[2]; out[3] = (float)v[3];
 }
 

@@ -92,8 +92,8 @@ template <int VEC> __device__ __forceinline__ void enc_load_sym(const EncDesc &d
 }
 
 // The twelve parameter planes of VEC positions of channel c: planar and aligned (checked by the host), one VEC-wide load per plane per
-// lane - 16 B fp32 / 8 B fp16 at VEC = 4, widened to float as they arrive.
-// VEC = 8 (fp16 planes only): every plane read is ONE 16-byte load and the halves stay packed in registers (48 VGPRs for the twelve
+// lane - 16 B fp32 / 8 B fp16 or bf16 at VEC = 4, widened to float as they arrive.
+// VEC = 8 (two-byte planes only, fp16 and bf16 alike): every plane read is ONE 16-byte load and the halves stay packed in registers (48 VGPRs for the twelve
 // planes), widened as each position is evaluated.  Measured against VEC = 4 on ELIC-4K batches (profiles/r05_symtab_fp16_vec8_ab.txt):
 // 127.6 / 133.1 against 123.0 / 126.8 G symbols per second (2 / 4 images) - symtab_kernel is bound by VALU issue (0.86 of the issue
 // roof, bench.py's valu_frac) and this form issues fewer load and address instructions.
@@ -246,7 +246,7 @@ __device__ __forceinline__ unsigned long long rdo_skip_dz(float y, float vq, dou
 
 // ---------------------------------------------------------------------------------------------------------
 // the launchers' ladder.  F::go<MODE, VEC, CLAMPED, PT, LINEAR>(grid, stream) does the kernel's hipLaunchKernelGGL with its own
-// arguments.  ALL_VEC: VEC = 2, and 8 for fp16 planes, exist too (symtab_kernel's A/B forms and its fp16 default); else vec >= 4 is 4
+// arguments.  ALL_VEC: VEC = 2, and 8 for two-byte planes, exist too (symtab_kernel's A/B forms and its fp16 / bf16 default); else vec >= 4 is 4
 // and anything below is 1.  M_max, hw_max, n_max: the largest M, hw and M * hw of the batch.
 // ---------------------------------------------------------------------------------------------------------
 template <int VEC, bool CLAMPED, typename PT, bool LINEAR, typename F> static int enc_launch_m(const F &f, dim3 grid, int mode, hipStream_t s) {
@@ -266,20 +266,25 @@ static int enc_launch_v(const F &f, int count, int M_max, int64_t hw_max, int64_
 }
 template <bool ALL_VEC, typename PT, bool LINEAR, typename F>
 static int enc_launch_t(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, int mode, int vec, bool clamped, hipStream_t s) {
-  if constexpr (ALL_VEC && sizeof(PT) == 2) // (fp16 planes only: 16-byte loads per plane)
+  if constexpr (ALL_VEC && sizeof(PT) == 2) // (two-byte planes only: 16-byte loads per plane)
     if (vec == 8) return enc_launch_v<8, PT, LINEAR>(f, count, M_max, hw_max, n_max, mode, clamped, s);
   if (vec >= 4) return enc_launch_v<4, PT, LINEAR>(f, count, M_max, hw_max, n_max, mode, clamped, s);
   if constexpr (ALL_VEC)
     if (vec == 2) return enc_launch_v<2, PT, LINEAR>(f, count, M_max, hw_max, n_max, mode, clamped, s);
   return enc_launch_v<1, PT, LINEAR>(f, count, M_max, hw_max, n_max, mode, clamped, s);
 }
+// planes: the fgmm_dtype of the parameter planes
 template <bool ALL_VEC, typename F>
-static int enc_launch(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16,
+static int enc_launch(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, bool linear, int mode, int vec, bool clamped, int planes,
                       void *stream) {
   if (count <= 0 || M_max <= 0 || hw_max <= 0) return 0;
   if (linear && (n_max + kBlock - 1) / kBlock > 0x7FFFFFFFll) linear = false; // grid.x
   if (count > 65535 || (!linear && M_max > 65535)) return (int)hipErrorInvalidValue; // grid.z; grid.y is M_max on the tiled grid only
   hipStream_t s = (hipStream_t)stream;
+  if (planes == FGMM_BF16)
+    return linear ? enc_launch_t<ALL_VEC, __bf16, true>(f, count, M_max, hw_max, n_max, mode, vec, clamped, s)
+                  : enc_launch_t<ALL_VEC, __bf16, false>(f, count, M_max, hw_max, n_max, mode, vec, clamped, s);
+  const bool f16 = planes == FGMM_F16;
   if (linear)
     return f16 ? enc_launch_t<ALL_VEC, _Float16, true>(f, count, M_max, hw_max, n_max, mode, vec, clamped, s)
                : enc_launch_t<ALL_VEC, float, true>(f, count, M_max, hw_max, n_max, mode, vec, clamped, s);

@@ -50,8 +50,8 @@ void census_desc(EncDesc &d, const fgmm_ctx *ctx, const CensusOff &o, const floa
 }
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool enc_vec4_ok(const EncDesc &d, const void *out, bool f16) {
-  const uintptr_t pm = f16 ? 7 : 15; // 4 parameters per load: 8 B (fp16) or 16 B (fp32)
+bool enc_vec4_ok(const EncDesc &d, const void *out, bool two_byte) {
+  const uintptr_t pm = two_byte ? 7 : 15; // 4 parameters per load: 8 B (fp16, bf16) or 16 B (fp32)
   auto al = [pm](const void *p) { return (reinterpret_cast<uintptr_t>(p) & pm) == 0; };
   return d.stride_p == 1 && (d.hw & 3) == 0 && (d.stride_c & 3) == 0 && (d.stride_k & 3) == 0 && al(d.scales) && al(d.means) &&
          al(d.weights) && (d.y ? aligned16(d.y) : aligned16(d.sym)) && aligned16(out);
@@ -368,10 +368,10 @@ struct EncodeCall {
     for (int i = 0; i < count; ++i) {
       fill_desc(i, hd[i]);
       const EncDesc &d = hd[i];
-      vec4 = vec4 && enc_vec4_ok(d, d.packed, items[i].prm.dtype == FGMM_F16);
-      // 8 positions per lane for fp16 planes (one 16-byte load per plane: +4-5 % over 8-byte loads on ELIC-4K batches,
+      vec4 = vec4 && enc_vec4_ok(d, d.packed, planes_two_byte(items[i].prm.dtype));
+      // 8 positions per lane for two-byte planes, fp16 and bf16 alike (one 16-byte load per plane: +4-5 % over 8-byte loads on ELIC-4K batches,
       // profiles/r05_symtab_fp16_vec8_ab.txt): everything 16-byte aligned, rows of 8
-      vec8 = vec8 && items[i].prm.dtype == FGMM_F16 && (d.hw & 7) == 0 && (d.stride_c & 7) == 0 && (d.stride_k & 7) == 0 && aligned16(d.scales) &&
+      vec8 = vec8 && planes_two_byte(items[i].prm.dtype) && (d.hw & 7) == 0 && (d.stride_c & 7) == 0 && (d.stride_k & 7) == 0 && aligned16(d.scales) &&
              aligned16(d.means) && aligned16(d.weights);
       any_y = any_y || items[i].latent;
     }
@@ -404,7 +404,7 @@ struct EncodeCall {
       n_max = std::max(n_max, (int64_t)it.M * it.hw);
       linear = linear && it.hw % (64 * vec) == 0;
     }
-    LAUNCH_TRY(launch_symtab(dd, count, M_max, hw_max, n_max, linear, mode, vec, items[0].clamp != 0, items[0].prm.dtype == FGMM_F16, stream));
+    LAUNCH_TRY(launch_symtab(dd, count, M_max, hw_max, n_max, linear, mode_with_planes(mode, items[0].prm.dtype), vec, items[0].clamp != 0, items[0].prm.dtype == FGMM_F16, stream));
     return ctx->prof_end(0, stream);
   }
 

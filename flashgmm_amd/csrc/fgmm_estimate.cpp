@@ -32,8 +32,8 @@ int check_latent_items(const std::vector<LatentIn> &in) {
     if (s.K != FGMM_K) return fail(FGMM_ERR_INVALID, "K = %d: the reference binds K = 4 only", s.K);
     if (s.M < 0 || s.hw < 0 || ((int64_t)s.M * s.hw && (!s.y || !p.scales || !p.means || !p.weights)))
       return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
-    if (p.dtype != in[0].params->dtype || (p.dtype != FGMM_F32 && p.dtype != FGMM_F16))
-      return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32 or FGMM_F16 and the same for a whole batch", i);
+    if (p.dtype != in[0].params->dtype || (p.dtype != FGMM_F32 && !planes_two_byte(p.dtype)))
+      return fail(FGMM_ERR_INVALID, "item %d: parameter dtype must be FGMM_F32, FGMM_F16 or FGMM_BF16 and the same for a whole batch", i);
     if (p.flags & ~FGMM_PARAMS_LOGITS) return fail(FGMM_ERR_INVALID, "item %d: unknown fgmm_params.flags %d", i, p.flags);
   }
   return FGMM_OK;
@@ -66,7 +66,7 @@ int LatentFrame::layout(const LatentNeeds &n) {
   for (int i = 0; i < count; ++i) o_acc[(size_t)i] = ar.take(sizeof(uint64_t) * n.dev_chan * (size_t)in[(size_t)i].M, 16);
   end = ar.off;
   if ((rc = ctx->ensure_device(end)) || (rc = ctx->ensure_host(o_dev)) || (rc = ctx->ensure_events(1))) return rc;
-  f16 = in[0].params->dtype == FGMM_F16;
+  planes = in[0].params->dtype;
   for (int i = 0; i < count; ++i) {
     const LatentIn &it = in[(size_t)i];
     census_desc(ws<EncDesc>(ctx->h_ws, o_descs)[i], ctx, census[(size_t)i], it.y, it.params, it.M, it.hw, clamp);
@@ -80,7 +80,7 @@ int LatentFrame::start() {
   for (int i = 0; i < count; ++i) {
     const LatentIn &it = in[(size_t)i];
     if (census2) census_desc(hd[count + i], ctx, census_out[(size_t)i], out[(size_t)i], nullptr, it.M, it.hw, clamp);
-    vec4 = vec4 && enc_vec4_ok(hd[i], out[(size_t)i], f16);
+    vec4 = vec4 && enc_vec4_ok(hd[i], out[(size_t)i], planes_two_byte(planes));
     if (weighted) { // pos_w is read VEC positions wide as the planes are (hw % 4 is enc_vec4_ok's)
       ws<RdoWDesc>(ctx->h_ws, o_wdesc)[i] = RdoWDesc{w[i].chan_w, w[i].pos_w};
       vec4 = vec4 && (reinterpret_cast<uintptr_t>(w[i].pos_w) & 15) == 0;
@@ -129,7 +129,7 @@ int estimate_batch(fgmm_ctx *ctx, dev::Stream stream, fgmm_rate_item *items, int
   }
   if ((rc = fr.start())) return rc;
   LAUNCH_TRY(launch_rate(fr.dd(), ws<const RateDesc>(ctx->d_ws, fr.o_call), ctx->d_rate_log2, count, fr.M_max, fr.hw_max, fr.n_max, fr.linear, mode,
-                         fr.vec, clamp != 0, fr.f16, stream));
+                         fr.vec, clamp != 0, fr.planes, stream));
   if ((rc = fr.finish(fr.o_small))) return rc;
   // ---- per item, on the host: the census as the compress call reads it (fgmm_encode.cpp side_info), the sums --------------------
   for (int i = 0; i < count; ++i) {

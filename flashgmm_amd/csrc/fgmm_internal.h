@@ -20,7 +20,7 @@ struct EncDesc {
   // inputs (device)
   const float *y;        // [M*hw] latents, rounded by the kernel;   null when `sym` is given
   const int32_t *sym;    // raw-boundary form: symbols given, [hw] with M == 1
-  const void *scales, *means, *weights; // float32 or float16 planes (the launcher picks the kernel)
+  const void *scales, *means, *weights; // float32, float16 or bfloat16 planes (the launcher picks the kernel)
   int64_t stride_k, stride_c, stride_p; // elements
   int64_t hw;
   int32_t M;
@@ -48,7 +48,7 @@ struct EncDesc {
 };
 
 struct DecDesc {
-  const void *scales, *means, *weights; // float32 or float16 planes
+  const void *scales, *means, *weights; // float32, float16 or bfloat16 planes
   int64_t stride_k, stride_c, stride_p;
   int64_t hw;
   int64_t n;                     // latents = n_ch * hw
@@ -129,7 +129,7 @@ int launch_head_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_
 
 // ---- GPU-side decode of CHECKPOINTED bitstreams (segdec_kernel): one wave per segment ---------------------------
 struct SegDesc {
-  const void *scales, *means, *weights; // float32 or float16 planes
+  const void *scales, *means, *weights; // float32, float16 or bfloat16 planes
   int64_t stride_k, stride_c, stride_p;
   int64_t hw;
   int64_t n;                     // coded latents = n_ch * hw
@@ -222,6 +222,15 @@ FGMM_HD static inline int tab_tl(int32_t max_bs, int cap_e) { // 0: the item doe
 }
 
 // ---- kernel launchers (fgmm_kernels.hip); stream is a hipStream_t; all return hipError_t as int ----------
+// The plane type of a launch.  launch_symtab, launch_tab, launch_cdftab*, launch_segdec carry it in two arguments: `f16` says IEEE
+// float16 as it always did, and bfloat16 planes are announced by kPlanesBf16 in the `mode` argument, whose low byte (kModeMask) is the
+// fgmm_mode.  The CPU stand-in for the device (tests/fake) defines these launchers too and has NO bfloat16 form: it is only ever
+// handed float32 and float16 planes, so the bits above kModeMask are zero there.  The launchers of fgmm_rate.hip, fgmm_rdoq.hip and
+// fgmm_rdcurve.hip take the fgmm_dtype itself (`planes`).
+constexpr int kModeMask = 0xFF, kPlanesBf16 = 0x100;
+static inline bool planes_two_byte(int dtype) { return dtype == FGMM_F16 || dtype == FGMM_BF16; }
+static inline int mode_with_planes(int mode, int dtype) { return dtype == FGMM_BF16 ? (mode | kPlanesBf16) : mode; }
+static inline int planes_of(int mode, bool f16) { return (mode & kPlanesBf16) ? FGMM_BF16 : (f16 ? FGMM_F16 : FGMM_F32); }
 int launch_quant_stats(const EncDesc *d_descs, int count, int M_max, void *stream);
 // M_max, hw_max, n_max: the largest M, hw and M * hw of the batch.  linear: every hw is a multiple of 64 * vec, waves
 // take consecutive coded symbols across channels (all waves full); else one block per (tile, channel).
@@ -288,7 +297,7 @@ struct RateDesc {                  // item i of a rate_kernel launch, beside its
 };
 // the arithmetic of launch_symtab ending in a reduction instead of a table: vec = 4 (everything 16-byte aligned) or 1
 int launch_rate(const EncDesc *d_descs, const RateDesc *d_rdescs, const uint32_t *d_log2, int count, int M_max, int64_t hw_max,
-                int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
+                int64_t n_max, bool linear, int mode, int vec, bool clamped, int planes, void *stream);
 // table -> cost: bits_q / n_bypass (device, single words) are ADDED to
 int launch_symtab_bits(const uint32_t *packed, const int32_t *symbols_or_null, int64_t n, const uint32_t *d_log2, uint32_t *cost_q_or_null,
                        unsigned long long *bits_q, unsigned long long *n_bypass, void *stream);
@@ -313,7 +322,7 @@ constexpr int kRdoSkipItem = 6; // (five used; an even count keeps the channel a
 // the addressing of launch_rate.  weighted: some item of the batch carries factors (section 3e) - the instantiation that reads them.
 // skip: section 3f - the instantiation that also sums what the channel decision needs, then rdoq_skip_kernel on the same stream
 int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, bool weighted, bool skip, int count, int M_max, int64_t hw_max,
-                int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
+                int64_t n_max, bool linear, int mode, int vec, bool clamped, int planes, void *stream);
 // section 3e's domain check, in the frame's front half beside quant_stats_kernel: item i's word bad[i] (zeroed by the host) becomes
 // non-zero when a factor of either array is not finite or lies outside [0, FGMM_RDO_W_MAX]
 struct RdoWDesc {
@@ -336,7 +345,7 @@ constexpr int kRdCurveRowS = kRdCurveRow + FGMM_RDCURVE_MAX + 3;
 constexpr int kRdCurveSumsS = kRdCurveRow + FGMM_RDCURVE_MAX + 1;
 // the addressing of launch_rdoq; rdcurve_kernel, then rdcurve_fold_kernel.  skip: both in their section-3f forms, on rows of kRdCurveRowS / kRdCurveSumsS words
 int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, bool weighted, bool skip, int count, int M_max, int64_t hw_max, int64_t n_max,
-                   bool linear, int mode, int vec, bool clamped, bool f16, void *stream);
+                   bool linear, int mode, int vec, bool clamped, int planes, void *stream);
 
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the

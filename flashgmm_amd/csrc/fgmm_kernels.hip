@@ -414,7 +414,7 @@ struct SymtabLaunch {
 };
 int launch_symtab(const EncDesc *d_descs, int count, int M_max, int64_t hw_max, int64_t n_max, bool linear, int mode, int vec,
                   bool clamped, bool f16, void *stream) {
-  return enc_launch<true>(SymtabLaunch{d_descs}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream);
+  return enc_launch<true>(SymtabLaunch{d_descs}, count, M_max, hw_max, n_max, linear, mode & kModeMask, vec, clamped, planes_of(mode, f16), stream);
 }
 
 int launch_cdf_pair(const int32_t *v, const float *scales, const float *means, const float *weights, int64_t n,

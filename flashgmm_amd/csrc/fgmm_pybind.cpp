@@ -50,7 +50,7 @@ struct Stacked {
 };
 
 void fill_items(std::vector<fgmm_item> &it, const Stacked &s) {
-  const size_t esz = s.dtype == FGMM_F16 ? 2 : 4;
+  const size_t esz = s.dtype == FGMM_F32 ? 4 : 2; // FGMM_F16 and FGMM_BF16: two-byte planes
   for (int i = 0; i < s.N; ++i) {
     fgmm_item &f = it[(size_t)i];
     std::memset(&f, 0, sizeof f);

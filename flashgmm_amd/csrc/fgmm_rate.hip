@@ -98,8 +98,8 @@ struct RateLaunch {
   }
 };
 int launch_rate(const EncDesc *d_descs, const RateDesc *d_rdescs, const uint32_t *d_log2, int count, int M_max, int64_t hw_max,
-                int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream) {
-  return enc_launch<false>(RateLaunch{d_descs, d_rdescs, d_log2}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream);
+                int64_t n_max, bool linear, int mode, int vec, bool clamped, int planes, void *stream) {
+  return enc_launch<false>(RateLaunch{d_descs, d_rdescs, d_log2}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, planes, stream);
 }
 
 int launch_symtab_bits(const uint32_t *packed, const int32_t *symbols_or_null, int64_t n, const uint32_t *d_log2, uint32_t *cost_q_or_null,

@@ -38,7 +38,7 @@ struct Curve : LatentFrame { // the passes of a call, on the frame: a pass sets 
     DEV_TRY(dev::copy_async(ctx->d_ws + o_call, hc, sizeof(RdCurveDesc) * (size_t)count, dev::kH2D, stream));
     DEV_TRY(dev::memset_async(ctx->d_ws + o_sums, 0, end - o_sums, stream)); // the items' sums and the channels'
     LAUNCH_TRY(launch_rdcurve(dd(), ws<const RdCurveDesc>(ctx->d_ws, o_call), ctx->d_rate_log2, weighted, skip, count, M_max, hw_max, n_max, linear, mode,
-                              vec, clamp != 0, f16, stream));
+                              vec, clamp != 0, planes, stream));
     const size_t from = census_back ? o_sums : o_small;
     census_back = true;
     return finish(from);

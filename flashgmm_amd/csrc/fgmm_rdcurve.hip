@@ -212,9 +212,9 @@ struct RdCurveLaunch {
   }
 };
 int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, bool weighted, bool skip, int count, int M_max, int64_t hw_max, int64_t n_max,
-                   bool linear, int mode, int vec, bool clamped, bool f16, void *stream) {
+                   bool linear, int mode, int vec, bool clamped, int planes, void *stream) {
   if (count <= 0 || M_max <= 0 || hw_max <= 0) return 0;
-  if (const int e = enc_launch<false>(RdCurveLaunch{d_descs, d_cdescs, d_log2, weighted, skip}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream)) return e;
+  if (const int e = enc_launch<false>(RdCurveLaunch{d_descs, d_cdescs, d_log2, weighted, skip}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, planes, stream)) return e;
   if (skip)
     hipLaunchKernelGGL(rdcurve_fold_skip_kernel, dim3((unsigned)count), dim3(kBlock), 0, (hipStream_t)stream, d_descs, d_cdescs);
   else

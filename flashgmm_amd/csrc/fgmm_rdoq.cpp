@@ -32,7 +32,7 @@ int fgmm::rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int
   }
   if ((rc = fr.start())) return rc;
   LAUNCH_TRY(launch_rdoq(fr.dd(), ws<const RdoqDesc>(ctx->d_ws, fr.o_call), ctx->d_rate_log2, fr.weighted, sk != nullptr, count, fr.M_max, fr.hw_max, fr.n_max, fr.linear,
-                         mode, fr.vec, clamp != 0, fr.f16, stream));
+                         mode, fr.vec, clamp != 0, fr.planes, stream));
   if ((rc = fr.finish(fr.o_small))) return rc; // (with the census of y_rdo)
   // ---- per item, on the host: the census of y_rdo as the compress call will read it (fgmm_encode.cpp side_info), the sums ------
   for (int i = 0; i < count; ++i) {

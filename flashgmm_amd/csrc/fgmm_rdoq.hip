@@ -201,10 +201,10 @@ struct RdoqSkipLaunch { // rdoq_kernel's grid: the ladder's choice of VEC and of
   }
 };
 int launch_rdoq(const EncDesc *d_descs, const RdoqDesc *d_qdescs, const uint32_t *d_log2, bool weighted, bool skip, int count, int M_max, int64_t hw_max,
-                int64_t n_max, bool linear, int mode, int vec, bool clamped, bool f16, void *stream) {
-  if (const int e = enc_launch<false>(RdoqLaunch{d_descs, d_qdescs, d_log2, weighted, skip}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream))
+                int64_t n_max, bool linear, int mode, int vec, bool clamped, int planes, void *stream) {
+  if (const int e = enc_launch<false>(RdoqLaunch{d_descs, d_qdescs, d_log2, weighted, skip}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, planes, stream))
     return e;
-  return skip ? enc_launch<false>(RdoqSkipLaunch{d_descs, d_qdescs}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, f16, stream) : 0;
+  return skip ? enc_launch<false>(RdoqSkipLaunch{d_descs, d_qdescs}, count, M_max, hw_max, n_max, linear, mode, vec, clamped, planes, stream) : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -1267,6 +1267,9 @@ int launch_segdec(const SegDesc *d_descs, const SegRef *d_segs, int64_t n_segs, 
   if (n_segs <= 0) return 0;
   if (n_segs > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
+  const bool bf16 = (mode & kPlanesBf16) != 0; // (fgmm_internal.h: the plane type of a launch)
+  mode &= kModeMask;
+  if (bf16) return clamped ? launch_segdec_c<true, __bf16>(d_descs, d_segs, n_segs, mode, s) : launch_segdec_c<false, __bf16>(d_descs, d_segs, n_segs, mode, s);
   if (f16) return clamped ? launch_segdec_c<true, _Float16>(d_descs, d_segs, n_segs, mode, s) : launch_segdec_c<false, _Float16>(d_descs, d_segs, n_segs, mode, s);
   return clamped ? launch_segdec_c<true, float>(d_descs, d_segs, n_segs, mode, s) : launch_segdec_c<false, float>(d_descs, d_segs, n_segs, mode, s);
 }
@@ -1293,6 +1296,10 @@ static int launch_cdftab_pass(const DecDesc *d_descs, int count, int n_ch_max, i
                               int pass, void *stream) {
   if (count <= 0 || n_ch_max <= 0 || hw_max <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  const bool bf16 = (mode & kPlanesBf16) != 0;
+  mode &= kModeMask;
+  if (bf16) return clamped ? launch_cdftab_c<true, __bf16>(d_descs, count, n_ch_max, hw_max, mode, pass, s)
+                           : launch_cdftab_c<false, __bf16>(d_descs, count, n_ch_max, hw_max, mode, pass, s);
   if (f16) return clamped ? launch_cdftab_c<true, _Float16>(d_descs, count, n_ch_max, hw_max, mode, pass, s)
                           : launch_cdftab_c<false, _Float16>(d_descs, count, n_ch_max, hw_max, mode, pass, s);
   return clamped ? launch_cdftab_c<true, float>(d_descs, count, n_ch_max, hw_max, mode, pass, s)
@@ -1327,6 +1334,10 @@ int launch_tab(const DecDesc *d_descs, int count, int blocks_max, int tl_max, in
   if (count <= 0 || blocks_max <= 0) return 0;
   if (tl_max < 1 || tl_max > kTabMaxTl || cap_e < 32 || cap_e > 32768 || (cap_e & 31) || tab_smem_bytes(tl_max, cap_e) > 160 * 1024) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
+  const bool bf16 = (mode & kPlanesBf16) != 0;
+  mode &= kModeMask;
+  if (bf16) return clamped ? launch_tab_c<true, __bf16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s)
+                           : launch_tab_c<false, __bf16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s);
   if (f16) return clamped ? launch_tab_c<true, _Float16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s)
                           : launch_tab_c<false, _Float16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s);
   return clamped ? launch_tab_c<true, float>(d_descs, count, blocks_max, tl_max, cap_e, mode, s)

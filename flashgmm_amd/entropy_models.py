@@ -408,7 +408,7 @@ def _plane_view(t: Tensor, K: int) -> Tuple[Tensor, int, int]:
     if len(shape) != 4 or shape[0] != 1:
         raise RuntimeError("entropy parameters must be [1, K*M, h, w] (the reference squeezes batch 1 too, entropy_models.py:841)")
     if t.dtype not in _PARAM_DTYPES:
-        raise RuntimeError(f"entropy parameters must be float32 or float16, got {t.dtype}")
+        raise RuntimeError(f"entropy parameters must be float32, float16 or bfloat16, got {t.dtype}")
     hw = shape[2] * shape[3]
     st = t.stride()
     if hw > 1 and not (st[3] == 1 and st[2] == shape[3]):
@@ -418,7 +418,16 @@ def _plane_view(t: Tensor, K: int) -> Tuple[Tensor, int, int]:
     return t, (shape[1] // K) * sc, sc
 
 
-_PARAM_DTYPES = (torch.float32, torch.float16)
+_PARAM_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+_ABI_DTYPE = {torch.float32: _lib.FGMM_F32, torch.float16: _lib.FGMM_F16, torch.bfloat16: _lib.FGMM_BF16}
+
+
+def _abi_dtype(dt: torch.dtype) -> int:
+    """the fgmm_dtype of parameter planes of torch dtype `dt` (include/flashgmm_amd.h section 2)"""
+    try:
+        return _ABI_DTYPE[dt]
+    except KeyError:
+        raise RuntimeError(f"entropy parameters must be float32, float16 or bfloat16, got {dt}") from None
 
 
 class ParameterHead:
@@ -522,7 +531,7 @@ class GaussianMixtureConditional(nn.Module):
         """one item of the sequence form as an ``fgmm_item`` (the ctypes binding) -> (item, M, hw, device)"""
         yp, sp, mp, wp, M, hw, sk, sc, dev, dt = self._item_ints(y, scales, means, weights, keep)
         it = _lib.fgmm_item()
-        it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
+        it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _abi_dtype(dt), flags)
         it.M, it.K, it.hw = M, self.K, hw
         if y is not None:
             it.y = yp
@@ -571,7 +580,7 @@ class GaussianMixtureConditional(nn.Module):
         if scales.dim() != 4 or means.shape != scales.shape or weights.shape != scales.shape:
             raise RuntimeError("stacked entropy parameters must be three [N, K*M, h, w] tensors of one shape")
         if not (scales.dtype == means.dtype == weights.dtype) or scales.dtype not in _PARAM_DTYPES:
-            raise RuntimeError("scales, means and weights must share one dtype, float32 or float16")
+            raise RuntimeError("scales, means and weights must share one dtype, float32, float16 or bfloat16")
         N, KM, h, w = scales.shape
         st = scales.stride()
         if (h * w > 1 and not (st[3] == 1 and st[2] == w)) or means.stride() != st or weights.stride() != st:
@@ -595,7 +604,7 @@ class GaussianMixtureConditional(nn.Module):
         items["means"] = np.uint64(means.data_ptr()) + step
         items["weights"] = np.uint64(weights.data_ptr()) + step
         items["stride_k"], items["stride_c"] = M * sc, sc
-        items["dtype"] = _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32
+        items["dtype"] = _abi_dtype(scales.dtype)
         items["flags"] = flags
         items["M"], items["K"], items["hw"] = M, self.K, h * w
         if y is not None:
@@ -620,7 +629,7 @@ class GaussianMixtureConditional(nn.Module):
             zb = torch.empty((N, M), dtype=torch.int64)
             strings, amax = nat.compress_stacked(
                 _lib.ctx_addr(di), torch.cuda.current_stream(dev).cuda_stream, y.data_ptr(), scales.data_ptr(), means.data_ptr(), weights.data_ptr(),
-                N, M, h * w, s_item, M * sc, sc, _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32, flags, self._mode(),
+                N, M, h * w, s_item, M * sc, sc, _abi_dtype(scales.dtype), flags, self._mode(),
                 int(self.clamp_scales), self.checkpoint_stride, yq.data_ptr(), zb.data_ptr(), CheckpointedBytes if self.checkpoint_stride else None)
             return CompressedBatch(strings, amax, zb, yq)
         items, keep, N, M, h, w, dev = self._stacked_items(y, scales, means, weights, flags)
@@ -663,7 +672,7 @@ class GaussianMixtureConditional(nn.Module):
             y_hat = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
             nat.decompress_stacked(_lib.ctx_addr(dev.index if dev.index is not None else -1), torch.cuda.current_stream(dev).cuda_stream, strings, abs_maxes,
                                    zb.data_ptr(), zb.stride(0) if N > 1 else M, scales.data_ptr(), means.data_ptr(), weights.data_ptr(), N, M, h * w, s_item,
-                                   M * sc, sc, _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32, flags, self._mode(), int(self.clamp_scales),
+                                   M * sc, sc, _abi_dtype(scales.dtype), flags, self._mode(), int(self.clamp_scales),
                                    y_hat.data_ptr(), CheckpointedBytes)  # (the out-of-band notes of the bitstreams that carry them: read off the objects)
             return y_hat if stacked_output else list(y_hat.unbind(0))
         items, keep, N, M, h, w, dev = self._stacked_items(None, scales, means, weights, flags)
@@ -741,7 +750,7 @@ class GaussianMixtureConditional(nn.Module):
                 at += M
             di = dev.index if dev.index is not None else -1
             strings, amax = nat.compress_items(_lib.ctx_addr(di), torch.cuda.current_stream(dev).cuda_stream, [tuple(t) for t in tuples],
-                                               _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags, self._mode(), int(self.clamp_scales),
+                                               _abi_dtype(dt), flags, self._mode(), int(self.clamp_scales),
                                                self.checkpoint_stride, CheckpointedBytes if self.checkpoint_stride else None)
             bitmaps = zb_all.split(ms)
             return [((strings[i], amax[i], bitmaps[i]), outs[i].view_as(ys[i])) for i in range(n_items)]
@@ -885,7 +894,7 @@ class GaussianMixtureConditional(nn.Module):
             di = dev.index if dev.index is not None else -1
             ch, before, after, am = nat.rdoq_stacked(_lib.ctx_addr(di), torch.cuda.current_stream(dev).cuda_stream, y.data_ptr(), scales.data_ptr(),
                                                      means.data_ptr(), weights.data_ptr(), N, M, h * w, s_item, M * sc, sc,
-                                                     _lib.FGMM_F16 if scales.dtype == torch.float16 else _lib.FGMM_F32, flags, self._mode(),
+                                                     _abi_dtype(scales.dtype), flags, self._mode(),
                                                      int(self.clamp_scales), lam, out.data_ptr(), zb.data_ptr(), cb.data_ptr() if per_channel else 0)
             return [RdoQuantized(*c) for c in zip(out.unbind(0), ch, before, after, am, zb.unbind(0), cb.unbind(0) if per_channel else [None] * N)]
         L = self._latent_items(_lib.fgmm_rdoq_item, ys, scales, means, weights, weights_are_logits)
@@ -933,7 +942,7 @@ class GaussianMixtureConditional(nn.Module):
             if d != dev:
                 raise RuntimeError("all items of a batch must be on one device")
             it.y = yp
-            it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags)
+            it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _abi_dtype(dt), flags)
             it.M, it.K, it.hw = M, self.K, hw
         L.dev = dev
         return L
@@ -1100,7 +1109,7 @@ class GaussianMixtureConditional(nn.Module):
                 tuples.append((sp, mp, wp, M, hw, sk, sc, y_hat.data_ptr(), zb.data_ptr()))
             data = strings if isinstance(strings, list) and all(isinstance(s_, bytes) for s_ in strings) else [s_ if isinstance(s_, bytes) else bytes(s_) for s_ in strings]
             nat.decompress_items(_lib.ctx_addr(dev.index if dev.index is not None else -1), torch.cuda.current_stream(dev).cuda_stream, data,
-                                 [int(a) for a in abs_maxes], tuples, _lib.FGMM_F16 if dt == torch.float16 else _lib.FGMM_F32, flags, self._mode(),
+                                 [int(a) for a in abs_maxes], tuples, _abi_dtype(dt), flags, self._mode(),
                                  int(self.clamp_scales), CheckpointedBytes)
             return outs
         items = (_lib.fgmm_item * n_items)()

@@ -82,9 +82,10 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         self.target_bytes = _check_target_bytes(target_bytes)
         if self.target_bytes is not None and self.rdo_lambda > 0:
             raise ValueError("target_bytes together with rdo_lambda > 0: give either the lambda or the budget that determines it")
-        if param_dtype not in (torch.float32, torch.float16):
-            raise ValueError("param_dtype must be torch.float32 or torch.float16")
-        self.param_dtype = param_dtype  # float16: BASELINE configs[4], "fp16 (mu, sigma, pi) with fp32 CDF accumulate"
+        if param_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("param_dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        # float16: BASELINE configs[4], "fp16 (mu, sigma, pi) with fp32 CDF accumulate"; bfloat16: the same bytes with float32's range
+        self.param_dtype = param_dtype
         # fuse_softmax: the softmax over K (:198-202) runs inside the HIP kernels, on the head's logits in place — the pi
         # plane (16 B / latent written, 16 read back) never exists.  One fixed fp32 sequence on both sides of the codec:
         # streams are self-consistent on any device; they are NOT the streams of the un-fused path (torch.softmax's pi
@@ -123,10 +124,15 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         return scales_hat, means_hat, (weights if self.fuse_softmax else self._reshape_gmm_weight(weights))
 
     def _planes(self, scales: Tensor, means: Tensor, weights: Tensor):
-        """the planes as the entropy model gets them: float32 as they are, or float16 copies — weights rounded TOWARD ZERO,
-        because the algorithm needs sum_k pi_k <= 1 after widening (tests/synth.py to_float16_planes does it for the synthetic workloads)"""
+        """the planes as the entropy model gets them: float32 as they are, or float16 / bfloat16 copies — weights rounded TOWARD ZERO,
+        because the algorithm needs sum_k pi_k <= 1 after widening (tests/synth.py to_float16_planes does it for the synthetic workloads);
+        scales and means rounded to nearest"""
         if self.param_dtype == torch.float32:
             return scales, means, weights
+        if self.param_dtype == torch.bfloat16:
+            # toward zero = the low 16 bits of the binary32 pattern cleared; the conversion of what is left is exact
+            wz = (weights.contiguous().view(torch.int32) & -65536).view(torch.float32)
+            return scales.to(torch.bfloat16), means.to(torch.bfloat16), wz.to(torch.bfloat16)
         w16 = weights.to(torch.float16)
         over = w16.to(torch.float32) > weights
         w16 = torch.where(over, torch.nextafter(w16, torch.zeros_like(w16)), w16)

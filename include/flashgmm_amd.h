@@ -51,6 +51,7 @@ extern "C" {
 #define FGMM_RDCURVE_MAX 16 /* lambdas per fgmm_gmc_rdcurve_batch call */
 #define FGMM_HAS_RDO_SKIP 1    /* section 3f: fgmm_gmc_rdoq_batch_s, fgmm_gmc_rdcurve_batch_s, fgmm_gmc_rdoq_budget_batch_s (added without a bump, as 3b - 3e) */
 #define FGMM_HAS_RDO_WEIGHTS 1 /* section 3e: fgmm_gmc_rdoq_batch_w, fgmm_gmc_rdcurve_batch_w, fgmm_gmc_rdoq_budget_batch_w (added without a bump, as 3b - 3d) */
+#define FGMM_HAS_BF16 1        /* section 2: FGMM_BF16 parameter planes in every call that takes planes (added without a bump, as 3b - 3f) */
 #define FGMM_RDO_W_MAX 256.0f  /* largest factor of a weighted call's chan_w / pos_w */
 
 typedef enum {
@@ -215,15 +216,29 @@ int fgmm_decode_with_indexes_gmm(fgmm_ctx *ctx, const uint8_t *encoded, size_t e
  *    the library orders its own work after it and returns with all outputs complete.
  * ---------------------------------------------------------------------------------------------------------- */
 
-typedef enum { FGMM_F32 = 0, FGMM_F16 = 1 } fgmm_dtype;
+typedef enum { FGMM_F32 = 0, FGMM_F16 = 1, FGMM_BF16 = 2 } fgmm_dtype;
 
 typedef struct {
-  const void *scales, *means, *weights;  /* device; float32 or IEEE float16 planes, see dtype */
+  const void *scales, *means, *weights;  /* device; float32, IEEE float16 or bfloat16 planes, see dtype */
   int64_t stride_k, stride_c;            /* elements */
   int32_t dtype;                         /* fgmm_dtype.  FGMM_F16 (BASELINE configs[4]): each value is widened to
                                             float32 exactly on load, then the float32 path runs unchanged — the result
                                             is that of the reference fed the widened values (the reference itself
-                                            rejects half tensors: accessor<float,2>, rans_interface.cpp:478-480) */
+                                            rejects half tensors: accessor<float,2>, rans_interface.cpp:478-480).
+                                            FGMM_BF16 (FGMM_HAS_BF16): a bfloat16 value is widened exactly to binary32 — its 16 bits
+                                            become the upper half and the lower half is zero; NaN payloads, infinities, signed zeros
+                                            and subnormals are kept — and the float32 path then runs unchanged.  The result of EVERY
+                                            call is that of the same call on float32 planes holding the widened values: bitstream
+                                            bytes, abs_max, zero bitmap, y_q / y_hat, checkpoint notes, and every sum, flag, count,
+                                            curve point, lambda and y_rdo of sections 3b - 3f.
+                                            One dtype per batch.  y, yq_out, y_hat, chan_w, pos_w and the parameter head (fgmm_head_*,
+                                            fuse_head) stay float32 whatever the planes are, and so does the raw (n, 4) boundary of
+                                            section 1.
+                                            PRECONDITION of both two-byte forms: AFTER widening, sum_k pi_k must not exceed 1, or the
+                                            reference's algorithm desynchronises (tests: test_fp16_parameter_planes).  bfloat16 has 8
+                                            significant bits, and weights rounded to nearest violate this often: pass logits
+                                            (FGMM_PARAMS_LOGITS — the softmax runs in binary32 in the kernel) or weights rounded
+                                            TOWARD ZERO */
   int32_t flags;                         /* FGMM_PARAMS_LOGITS: `weights` holds the parameter head's LOGITS; the kernels compute
                                             pi = softmax over K themselves (the pi plane is never
                                             written and read back), with one fixed binary32 sequence shared by the encode- and
@@ -504,7 +519,7 @@ int fgmm_symtab_bits_hip(fgmm_ctx *ctx, void *stream, const uint32_t *packed, co
 
 /* The fused form at the entropy-model level: what fgmm_gmc_compress_batch WOULD return for these items, priced by one kernel that
  * does the encode-side CDF kernel's arithmetic on the same inputs (same addressing, same Phi, same softmax over K with
- * FGMM_PARAMS_LOGITS, float32 or float16 planes) and ends in a reduction instead of a table: no table, no table traffic over
+ * FGMM_PARAMS_LOGITS, float32, float16 or bfloat16 planes) and ends in a reduction instead of a table: no table, no table traffic over
  * PCIe, no host coder.  Per item:
  *   abs_max, zero_bitmap   as fgmm_gmc_compress_batch returns them
  *   n_symbols              symbols it would code (coded channels * hw);  n_bypass: those that take the bypass escape
@@ -769,7 +784,7 @@ int fgmm_decstream_decode(fgmm_decstream *d, const int32_t *indexes, int64_t n, 
 /* ---- section 5: the callers either side of the path ---------------------------------
  * CheckerboardLatentCodec.unembed / embed (compressai/latent_codecs/checkerboard.py:333-377): split a [planes, h, w]
  * device tensor into its two checkerboard halves [2, planes, h, w/2] (half 0 = anchors) and back.  planes = n * c;
- * w must be even; elem_bytes 4 (float32 / int32) or 2 (float16); anchor_odd = 0 for anchor_parity "even" (anchors at
+ * w must be even; elem_bytes 4 (float32 / int32) or 2 (float16 / bfloat16); anchor_odd = 0 for anchor_parity "even" (anchors at
  * (even row, even column) and (odd row, odd column)), 1 for "odd".  Pure data movement: any bit pattern is preserved.
  * STREAM-ORDERED, unlike the calls of sections 2 and 3: the one kernel is enqueued on `stream` (NULL = default stream), behind
  * whatever the caller enqueued there before, and the call returns WITHOUT waiting for it.  `dst` is complete for work enqueued on

@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Registers, scratch, occupancy and code identity of every kernel in two sets of gfx950 assembly files (profiles/bf16_planes.md).
+
+    hipcc <the flags of csrc/build.sh> --cuda-device-only -S fgmm_tab.hip -o OLD/fgmm_tab.s      (per .hip file, old and new tree)
+    python scripts/kernel_regs.py OLD NEW [--all]
+
+For every kernel of OLD: its VGPRs, SGPRs, scratch bytes and occupancy in both sets, and whether its instructions are the SAME TEXT
+(labels renumbered: inserting instantiations shifts the function numbers in .LBB<n>_<m>).  Kernels only NEW has are summarised per
+template.  Needs no GPU."""
+import hashlib
+import re
+import subprocess
+import sys
+from pathlib import Path
+
+
+def demangle(names):
+    try:
+        out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+        return dict(zip(names, out))
+    except (OSError, subprocess.CalledProcessError):
+        return {n: n for n in names}
+
+
+LABEL = re.compile(r"\.L(BB|tmp|func_begin|func_end)\d+(_\d+)?")
+FIELDS = {"next_free_vgpr": "vgpr", "next_free_sgpr": "sgpr", "private_segment_fixed_size": "scratch", "group_segment_fixed_size": "lds"}
+
+
+def kernels(d):
+    """name -> dict(vgpr, sgpr, scratch, lds, occ, sha) for every kernel of the directory's .s files (one pass over the lines)"""
+    res, sha, occ = {}, {}, {}
+    for f in sorted(Path(d).glob("*.s")):
+        cur = h = last = desc = pending = None
+        with open(f) as fh:
+            for line in fh:
+                t = line.strip()
+                if desc is not None:  # inside a kernel descriptor (it lies between the code and the function's end label)
+                    if t.startswith(".end_amdhsa_kernel"):
+                        desc = None
+                    elif t.startswith(".amdhsa_"):
+                        k, _, v = t[len(".amdhsa_"):].partition(" ")
+                        if k in FIELDS:
+                            res[desc][FIELDS[k]] = int(v)
+                elif t.startswith(".amdhsa_kernel "):
+                    desc = t.split()[1]
+                    res[desc] = {}
+                elif cur is not None:
+                    if t.startswith(".Lfunc_end"):
+                        sha[cur], last, cur = h.hexdigest()[:12], cur, None
+                    elif t and not t.startswith((";", ".loc", ".file", ".cfi")):
+                        h.update(LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) or ""), t.split(";")[0].rstrip()).encode() + b"\n")
+                elif t.startswith(".type") and t.endswith(",@function"):
+                    pending = t.split()[1].split(",")[0]
+                elif pending and line.startswith(pending + ":"):
+                    cur, h, pending = pending, hashlib.sha1(), None
+                elif t.startswith("; Occupancy:") and last:
+                    occ[last] = int(t.split()[-1])
+                    last = None
+    for name, r in res.items():
+        r["sha"], r["occ"] = sha.get(name, "?"), occ.get(name)
+    return res
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    show_all = "--all" in sys.argv
+    old, new = kernels(args[0]), kernels(args[1])
+    dm = demangle(sorted(set(old) | set(new)))
+    keys = ("vgpr", "sgpr", "scratch", "occ")
+    differ = []
+    for name in sorted(old):
+        if name not in new:
+            differ.append((name, "missing in NEW"))
+            continue
+        o, n = old[name], new[name]
+        same_regs = all(o.get(k) == n.get(k) for k in keys)
+        if not same_regs or o["sha"] != n["sha"]:
+            differ.append((name, f"old {[o.get(k) for k in keys]} {o['sha']}  new {[n.get(k) for k in keys]} {n['sha']}"))
+        if show_all:
+            print(f"{dm[name][:150]:150s} " + " ".join(f"{k}={o.get(k)}" for k in keys) + (" same text" if o["sha"] == n["sha"] else " TEXT DIFFERS"))
+    print(f"{len(old)} kernels in OLD, {len(new)} in NEW; of OLD's: {len(old) - len(differ)} with the same instructions, registers, scratch and occupancy; "
+          f"{len(differ)} that differ")
+    for name, why in differ:
+        print("  DIFFERS", dm[name], why)
+    # the kernels only NEW has: each bfloat16 instantiation (DF16b in the mangled name) beside its float16 sibling (DF16_)
+    fam = {}
+    for name in sorted(set(new) - set(old)):
+        sib = name.replace("DF16b", "DF16_")
+        g = re.match(r"_ZN4fgmm\d+(\w+?_kernel)I", name)
+        st = fam.setdefault(g.group(1) if g else name, dict(n=0, equal=0, diffs=[]))
+        st["n"] += 1
+        if sib == name or sib not in new:
+            st["diffs"].append(f"{name}: no float16 sibling")
+            continue
+        a, b = new[name], new[sib]
+        if all(a.get(k) == b.get(k) for k in keys):
+            st["equal"] += 1
+        else:
+            st["diffs"].append(f"{name}: bf16 {[a.get(k) for k in keys]}  f16 {[b.get(k) for k in keys]}")
+    for g, st in sorted(fam.items()):
+        print(f"  new: {g:22s} {st['n']:3d} bfloat16 kernels, {st['equal']:3d} with their float16 sibling's [vgpr, sgpr, scratch, occ]")
+        for dline in st["diffs"]:
+            print("       ", dline)
+
+
+if __name__ == "__main__":
+    main()
