@@ -104,7 +104,8 @@ void fgmm_ctx::trim() {
   if (h_ws) (void)dev::free_pinned(h_ws);
   if (d_stage) (void)dev::free_device(d_stage);
   if (d_rate_log2) (void)dev::free_device(d_rate_log2);
-  d_rate_log2 = nullptr;
+  if (d_xs) (void)dev::free_device(d_xs);
+  d_rate_log2 = nullptr, d_xs = nullptr, d_xs_cap = 0;
   for (auto &c : chunks) (void)dev::free_pinned(c.p);
   chunks.clear();
   d_ws = h_ws = d_stage = nullptr;
@@ -453,43 +454,40 @@ int fgmm_ctx_threads(const fgmm_ctx *ctx) { return ctx && ctx->pool ? ctx->pool-
 
 // ---- section 2: entropy-model level ---------------------------------------------------------------------
 
-// the packed weights of a parameter head (fgmm_head.hip), owned by the caller through fgmm_head_create / _destroy
+// the packed weights of a parameter head (fgmm_head.hip), owned by the caller through fgmm_head_create / _destroy.  Nothing in it
+// changes once fgmm_head_create_ex has returned: any context on its device may use it, concurrently
 struct fgmm_head {
   int device = 0;
   float *packed = nullptr; // [wp | bp]
-  fgmm::HeadW w{};
-  // bf16x6: the exact form's packing as well [wp | bp | a flag word], for the items with a feature outside the bf16x6 domain
+  // bf16x6: the exact form's packing as well [wp | bp], for the items with a feature outside the bf16x6 domain
   float *packed32 = nullptr;
-  fgmm::HeadW w32{};
-  // bf16x6: the features' split copy of the call in progress (grown on demand; calls are serialised by the context's lock)
-  mutable void *xs = nullptr;
-  mutable size_t xs_cap = 0;
+  fgmm::HeadPair p{}; // (w, and for bf16x6 exact: what the kernels take of the two)
 };
 
 // FGMM_HEAD_BF16X6: split the features of a call's items into their three bf16 parts (fgmm_head16.hip) -> the pointers the kernels'
 // descriptors carry as `xs`, each followed by the item's domain word (head16_oob_word: 1 = a feature outside the bf16x6 domain, the
 // exact kernels take that item).  One launch when the items are evenly spaced and of one size (stacked tensors), one per item otherwise.
-static int head16_split(const fgmm_head *head, void *stream, const float *const *x, const int64_t *hw, int count, std::vector<const void *> &out) {
+// The copy is the context's (d_xs, grown on demand: the caller holds the context's lock), not the head's.
+static int head16_split(fgmm_ctx *ctx, int c_in, void *stream, const float *const *x, const int64_t *hw, int count, std::vector<const void *> &out) {
   out.assign((size_t)count, nullptr);
   std::vector<size_t> at((size_t)count + 1, 0);
-  for (int i = 0; i < count; ++i) at[(size_t)i + 1] = at[(size_t)i] + head16_split_elems(head->w.c_in, hw[i]) + kHead16FlagElems;
+  for (int i = 0; i < count; ++i) at[(size_t)i + 1] = at[(size_t)i] + head16_split_elems(c_in, hw[i]) + kHead16FlagElems;
   const size_t bytes = at[(size_t)count] * sizeof(uint16_t);
-  if (bytes > head->xs_cap) {
-    if (head->xs) (void)dev::free_device(head->xs);
-    head->xs = nullptr, head->xs_cap = 0;
-    void *p = nullptr;
-    if (dev::malloc_device(&p, bytes + 256) != 0) return fail(FGMM_ERR_NOMEM, "%zu bytes of device memory for the split features", bytes);
-    head->xs = p, head->xs_cap = bytes;
+  if (bytes > ctx->d_xs_cap) {
+    if (ctx->d_xs) (void)dev::free_device(ctx->d_xs);
+    ctx->d_xs = nullptr, ctx->d_xs_cap = 0;
+    if (dev::malloc_device(&ctx->d_xs, bytes + 256) != 0) return fail(FGMM_ERR_NOMEM, "%zu bytes of device memory for the split features", bytes);
+    ctx->d_xs_cap = bytes;
   }
-  uint16_t *base = static_cast<uint16_t *>(head->xs);
+  uint16_t *base = static_cast<uint16_t *>(ctx->d_xs);
   for (int i = 0; i < count; ++i) out[(size_t)i] = base + at[(size_t)i];
   bool even = count > 0;
   for (int i = 1; i < count && even; ++i) even = hw[i] == hw[0] && x[i] - x[i - 1] == x[1] - x[0];
   if (even && hw[0] > 0) {
-    LAUNCH_TRY(launch_head16_split(x[0], base, hw[0], head->w.c_in, count, count > 1 ? (int64_t)(x[1] - x[0]) : 0, (int64_t)at[1], stream));
+    LAUNCH_TRY(launch_head16_split(x[0], base, hw[0], c_in, count, count > 1 ? (int64_t)(x[1] - x[0]) : 0, (int64_t)at[1], stream));
   } else {
     for (int i = 0; i < count; ++i)
-      if (hw[i] > 0) LAUNCH_TRY(launch_head16_split(x[i], base + at[(size_t)i], hw[i], head->w.c_in, 1, 0, 0, stream));
+      if (hw[i] > 0) LAUNCH_TRY(launch_head16_split(x[i], base + at[(size_t)i], hw[i], c_in, 1, 0, 0, stream));
   }
   return FGMM_OK;
 }
@@ -503,15 +501,13 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
   if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   std::vector<EncItem> v((size_t)count);
   std::vector<const void *> xsplit;
-  fgmm::HeadW heads[2] = {head ? head->w : fgmm::HeadW{}, head ? head->w32 : fgmm::HeadW{}}; // (bf16x6: the head, its exact form)
-  if (head && head->w.arith == FGMM_HEAD_BF16X6 && count) { // the features' three bf16 parts, once for all of the call's blocks
+  if (head && head->p.w.arith == FGMM_HEAD_BF16X6 && count) { // the features' three bf16 parts, once for all of the call's blocks
     std::vector<int64_t> hws((size_t)count);
     for (int i = 0; i < count; ++i) {
       if (items[i].hw < 0 || (items[i].M * items[i].hw && !x[i])) return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
       hws[(size_t)i] = (int64_t)items[i].M * items[i].hw ? items[i].hw : 0;
     }
-    if (int rc = head16_split(head, stream, x, hws.data(), count, xsplit)) return rc;
-    heads[0].oob = heads[1].oob = 1;
+    if (int rc = head16_split(ctx, head->p.w.c_in, stream, x, hws.data(), count, xsplit)) return rc;
   }
   for (int i = 0; i < count; ++i) {
     const fgmm_item &s = items[i];
@@ -519,7 +515,7 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
     EncItem &e = v[i];
     if (head) {
       // the parameters come out of the head's matrix product: the item names its features instead of parameter planes
-      if (s.M != head->w.M) return fail(FGMM_ERR_INVALID, "item %d: M = %d, the head was made for M = %d", i, s.M, head->w.M);
+      if (s.M != head->p.w.M) return fail(FGMM_ERR_INVALID, "item %d: M = %d, the head was made for M = %d", i, s.M, head->p.w.M);
       if (s.hw < 0 || (s.M * s.hw && (!s.y || !x[i]))) return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
       e.x = x[i];
       e.xs = xsplit.empty() ? nullptr : xsplit[(size_t)i];
@@ -545,7 +541,7 @@ static int compress_batch_impl(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
       return fail(FGMM_ERR_INVALID, "item %d: ckpt_stride must be 0 or a power of two >= 256, the same for a whole batch", i);
     e.ckpt_stride = s.ckpt_stride;
   }
-  const int rc = encode_batch(ctx, (dev::Stream)stream, v, mode, head ? heads : nullptr, sink);
+  const int rc = encode_batch(ctx, (dev::Stream)stream, v, mode, head ? &head->p : nullptr, sink);
   if (rc != FGMM_OK) // a failed call returns no buffer: what the bitstreams that had finished hold is released here, not leaked by a
     for (auto &e : v) { // binding that raises on the status
       if (!sink) free(e.bytes); // (a sink's storage is the caller's)
@@ -586,9 +582,9 @@ int fgmm_head_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const 
   fgmm_head *h = new (std::nothrow) fgmm_head;
   if (!h) return fail(FGMM_ERR_NOMEM, "head");
   h->device = ctx->device;
-  h->w.M = M, h->w.c_in = c_in;
-  h->w.n_cg = (M + kHeadCG - 1) / kHeadCG, h->w.n_kt = (c_in + kHeadBK - 1) / kHeadBK;
-  const size_t floats = head_packed_floats(M, c_in), bias_floats = (size_t)h->w.n_cg * 12 * kHeadCG;
+  h->p.w.M = M, h->p.w.c_in = c_in;
+  h->p.w.n_cg = (M + kHeadCG - 1) / kHeadCG, h->p.w.n_kt = (c_in + kHeadBK - 1) / kHeadBK;
+  const size_t floats = head_packed_floats(M, c_in), bias_floats = (size_t)h->p.w.n_cg * 12 * kHeadCG;
   const bool b16 = (flags & FGMM_HEAD_BF16X6) != 0;
   const size_t bytes = b16 ? head16_packed_bytes(M, c_in) : floats * sizeof(float);
   void *p = nullptr, *p32 = nullptr;
@@ -598,16 +594,16 @@ int fgmm_head_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const 
     return fail(FGMM_ERR_NOMEM, "%zu bytes of device memory for the packed weights", bytes);
   }
   h->packed = static_cast<float *>(p);
-  h->w.arith = b16 ? FGMM_HEAD_BF16X6 : 0;
-  h->w.wp = p;
-  h->w.bp = b16 ? reinterpret_cast<const float *>(static_cast<const char *>(p) + (bytes - bias_floats * sizeof(float))) : h->packed + (floats - bias_floats);
+  h->p.w.arith = b16 ? FGMM_HEAD_BF16X6 : 0;
+  h->p.w.wp = p;
+  h->p.w.bp = b16 ? reinterpret_cast<const float *>(static_cast<const char *>(p) + (bytes - bias_floats * sizeof(float))) : h->packed + (floats - bias_floats);
   int e;
   uint32_t bad = 0;
   if (b16) { // the bf16x6 packing, which flags weights outside its domain (the word after it), and the exact form's (the items with
              // features outside it)
     h->packed32 = static_cast<float *>(p32);
-    h->w32 = h->w;
-    h->w32.arith = 0, h->w32.wp = h->packed32, h->w32.bp = h->packed32 + (floats - bias_floats);
+    h->p.exact = h->p.w;
+    h->p.exact.arith = 0, h->p.exact.wp = h->packed32, h->p.exact.bp = h->packed32 + (floats - bias_floats);
     const uint32_t *d_bad = reinterpret_cast<const uint32_t *>(static_cast<const char *>(p) + bytes);
     e = launch_head16_pack(weight, bias, M, c_in, p, stream);
     if (!e) e = launch_head_pack(weight, bias, M, c_in, h->packed32, h->packed32 + (floats - bias_floats), stream);
@@ -634,7 +630,6 @@ void fgmm_head_destroy(fgmm_head *h) {
     DeviceGuard g(h->device);
     (void)dev::free_device(h->packed);
     if (h->packed32) (void)dev::free_device(h->packed32);
-    if (h->xs) (void)dev::free_device(h->xs);
   }
   delete h;
 }
@@ -655,7 +650,7 @@ int fgmm_head_params_batch(fgmm_ctx *ctx, void *stream, const fgmm_head *head, c
   for (int i = 0; i < count; ++i)
     if (hw[i] < 0 || (hw[i] && (!x[i] || !out[i]))) return fail(FGMM_ERR_INVALID, "item %d: null tensor / negative size", i);
   std::vector<const void *> xsplit;
-  if (head->w.arith == FGMM_HEAD_BF16X6 && (rc = head16_split(head, stream, x, hw, count, xsplit))) return rc;
+  if (head->p.w.arith == FGMM_HEAD_BF16X6 && (rc = head16_split(ctx, head->p.w.c_in, stream, x, hw, count, xsplit))) return rc;
   for (int i = 0; i < count; ++i) {
     hd[i] = HeadDesc{x[i], xsplit.empty() ? nullptr : xsplit[(size_t)i], out[i], hw[i]};
     hw_max = std::max(hw_max, hw[i]);
@@ -663,14 +658,7 @@ int fgmm_head_params_batch(fgmm_ctx *ctx, void *stream, const fgmm_head *head, c
   }
   DEV_TRY(dev::copy_async(ctx->d_ws, hd, bytes, dev::kH2D, (dev::Stream)stream));
   const HeadDesc *dd = reinterpret_cast<const HeadDesc *>(ctx->d_ws);
-  if (head->w.arith == FGMM_HEAD_BF16X6) { // then the exact form, for the items with a feature outside the bf16x6 domain
-    HeadW w16 = head->w, w32 = head->w32;
-    w16.oob = w32.oob = 1;
-    LAUNCH_TRY(launch_head16_params(dd, w16, count, hw_max, stream));
-    LAUNCH_TRY(launch_head_params(dd, w32, count, hw_max, vec, stream));
-  } else {
-    LAUNCH_TRY(launch_head_params(dd, head->w, count, hw_max, vec, stream));
-  }
+  LAUNCH_TRY(launch_head_planes(dd, head->p, count, hw_max, vec, stream));
   DEV_TRY(dev::stream_sync((dev::Stream)stream)); // (the descriptors' staging area belongs to the next call)
   return FGMM_OK;
 }

@@ -375,6 +375,8 @@ struct fgmm_ctx {
   char *d_stage = nullptr;
   size_t d_stage_cap = 0;
   int ensure_stage(size_t bytes);
+  void *d_xs = nullptr; // a bf16x6 head's call: the split copy of its features (head16_split, fgmm_capi.cpp): grown on demand, reused
+  size_t d_xs_cap = 0;
   uint32_t *d_rate_log2 = nullptr; // device copy of rate_log2_table() (fgmm_estimate.cpp uploads it on first use; trim() releases it)
   size_t stage_budget() const; // bytes the staging area may take
   int ensure_streams();
@@ -438,8 +440,8 @@ struct EncItem {
   int64_t job_n = 0, job_bypass = 0;
   double t_sub = 0, t_start = 0, t_end = 0, t_waited = 0, t_lastland = 0; // job timeline (the call log; trace level 2)
 };
-// head: the fused parameter head; a bf16x6 head is head[0] and its exact form head[1] (for the items whose domain word is set)
-int encode_batch(fgmm_ctx *ctx, dev::Stream stream, std::vector<EncItem> &items, int mode, const HeadW *head = nullptr, const fgmm_sink *sink = nullptr);
+// head: the fused parameter head
+int encode_batch(fgmm_ctx *ctx, dev::Stream stream, std::vector<EncItem> &items, int mode, const HeadPair *head = nullptr, const fgmm_sink *sink = nullptr);
 
 // ---- one bitstream of a batched decode --------------------------------------------------------------------------------------
 struct DecItem {

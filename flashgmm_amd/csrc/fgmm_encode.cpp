@@ -223,7 +223,7 @@ struct EncodeCall {
   dev::Stream stream;
   std::vector<EncItem> &items;
   int mode, count;
-  const HeadW *head; // the parameters come out of the head's matrix product (fgmm_head.hip) instead of planes
+  const HeadPair *head; // the parameters come out of the head's matrix product (fgmm_head.hip) instead of planes
   const fgmm_sink *sink; // the bitstreams go into the caller's storage (include/flashgmm_amd.h: fgmm_sink)
   std::unique_ptr<SinkDesk> desk; // ... asked for through the desk when the encoders run on the pool
   Trace tr;
@@ -248,7 +248,7 @@ struct EncodeCall {
   std::vector<EncItem *> job_items;
   double marks[5] = {0, 0, 0, 0, 0}; // the call log: enqueued | kernels + side information here | jobs out | last table (segment) seen landed | last job done
 
-  EncodeCall(fgmm_ctx *c, dev::Stream s, std::vector<EncItem> &it, int m, const HeadW *h, const fgmm_sink *k)
+  EncodeCall(fgmm_ctx *c, dev::Stream s, std::vector<EncItem> &it, int m, const HeadPair *h, const fgmm_sink *k)
       : ctx(c), stream(s), items(it), mode(m), count((int)it.size()), head(h), sink(k), tr("encode", (int)c->opt.trace) {
     if (sink && count > 1) desk.reset(new SinkDesk(sink, count)); // (a one-item call codes on the calling thread: it asks the sink itself)
   }
@@ -389,12 +389,7 @@ struct EncodeCall {
     if (head) { // the fused head: matrix product + table entries in one kernel, no parameter planes
       bool vec = true;
       for (auto &it : items) vec = vec && (it.hw & 3) == 0 && aligned16(it.x);
-      if (head->arith == FGMM_HEAD_BF16X6) { // then the exact form, for the items with a feature outside the bf16x6 domain
-        LAUNCH_TRY(launch_head16_symtab(dd, head[0], count, M_max, hw_max, mode, items[0].clamp != 0, stream));
-        LAUNCH_TRY(launch_head_symtab(dd, head[1], count, M_max, hw_max, mode, items[0].clamp != 0, vec, stream));
-      } else {
-        LAUNCH_TRY(launch_head_symtab(dd, *head, count, M_max, hw_max, mode, items[0].clamp != 0, vec, stream));
-      }
+      LAUNCH_TRY(launch_head_entries(dd, *head, count, M_max, hw_max, mode, items[0].clamp != 0, vec, stream));
       return ctx->prof_end(0, stream);
     }
     const int vec = vec4 ? (ctx->opt.enc_vec == 1 ? 1 : ctx->opt.enc_vec == 2 ? 2 : vec8 ? 8 : 4) : 1; // option "enc_vec" = 1, 2, 4: A/B narrower loads
@@ -705,7 +700,24 @@ struct EncodeCall {
 
 } // namespace
 
-int encode_batch(fgmm_ctx *ctx, dev::Stream stream, std::vector<EncItem> &items, int mode, const HeadW *head, const fgmm_sink *sink) {
+// A head's kernels for a call.  bf16x6: its own, then the exact ones for the items they left (a feature outside the bf16x6 domain) -
+// `oob` tells both which items are theirs.  An exact head: its kernels alone
+template <typename F16, typename F32> static int head_pair_run(const HeadPair &head, const F16 &bf16x6, const F32 &exact) {
+  if (head.w.arith != FGMM_HEAD_BF16X6) return exact(head.w);
+  HeadW w16 = head.w, w32 = head.exact;
+  w16.oob = w32.oob = 1;
+  if (int e = bf16x6(w16)) return e;
+  return exact(w32);
+}
+int launch_head_planes(const HeadDesc *d, const HeadPair &head, int count, int64_t hw_max, bool vec, void *stream) {
+  return head_pair_run(head, [&](const HeadW &w) { return launch_head16_params(d, w, count, hw_max, stream); }, [&](const HeadW &w) { return launch_head_params(d, w, count, hw_max, vec, stream); });
+}
+int launch_head_entries(const EncDesc *d, const HeadPair &head, int count, int M_max, int64_t hw_max, int mode, bool clamped, bool vec, void *stream) {
+  return head_pair_run(head, [&](const HeadW &w) { return launch_head16_symtab(d, w, count, M_max, hw_max, mode, clamped, stream); },
+                       [&](const HeadW &w) { return launch_head_symtab(d, w, count, M_max, hw_max, mode, clamped, vec, stream); });
+}
+
+int encode_batch(fgmm_ctx *ctx, dev::Stream stream, std::vector<EncItem> &items, int mode, const HeadPair *head, const fgmm_sink *sink) {
   if (items.empty()) return FGMM_OK;
   EncodeCall call(ctx, stream, items, mode, head, sink);
   const int rc = call.run();

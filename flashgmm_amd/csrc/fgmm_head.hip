@@ -26,11 +26,7 @@
 //            then gives every lane, for ITS position, registers 4 j + k = parameter (t, k) of channel 8 g + 2 j + (lane >> 5): a lane
 //            owns all twelve parameters of its latents - the epilogue needs no lane movement and no LDS.
 //   blocks that share an x tile (the channel groups of one position tile) get consecutive slots on ONE XCD: its L2 holds the tile.
-#include "fgmm_dev.h"
-
-#ifndef FGMM_HEAD_EXP
-#define FGMM_HEAD_EXP 0 // experiments (wrong results): bit 0 = no global loads in the K loop, bit 1 = no LDS writes, bit 2 = no barrier
-#endif
+#include "fgmm_headframe.h"
 
 namespace fgmm {
 namespace {
@@ -43,8 +39,6 @@ constexpr int kALd = kBK + 4;         // LDS row pitch of the W tile (floats): 1
 constexpr int kBLd = kPB + 32;        // ... of the x tile: the two lane halves read rows k, k + 1 -> banks 32 apart
 constexpr int kTiles = kRows / 32;    // 6 row tiles
 
-typedef float f16_t __attribute__((ext_vector_type(16)));
-
 // packed weights: [channel group][K tile][192 rows][32 columns]; column h * 16 + s of a tile = input channel tile * 32 + 2 s + h
 __global__ __launch_bounds__(256) void head_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, int M, int c_in, int n_cg, int n_kt,
                                                         float *__restrict__ wp, float *__restrict__ bp) {
@@ -56,10 +50,7 @@ __global__ __launch_bounds__(256) void head_pack_kernel(const float *__restrict_
     const int r = (int)((is_bias ? e : e / kBK) % kRows);
     const int kt = is_bias ? 0 : (int)((e / (kBK * kRows)) % n_kt);
     const int cg = (int)(is_bias ? e / kRows : e / ((int64_t)kBK * kRows * n_kt));
-    const int tile = r >> 5, ri = r & 31;
-    const int g = tile / 3, t = tile % 3, cl = ri >> 2, k = ri & 3;
-    const int c = cg * kCG + g * 8 + cl;
-    const int64_t o = (int64_t)t * 4 * M + (int64_t)k * M + c; // output channel of the convolution: chunk t, component k, latent channel c
+    const auto [c, o] = head_pack_row(r, cg, M);
     if (is_bias) {
       bp[e] = (c < M && bias) ? bias[o] : 0.0f;
     } else {
@@ -79,61 +70,17 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
   __shared__ __attribute__((aligned(16))) float sA[kRows * kALd];
   __shared__ __attribute__((aligned(16))) float sB[kBK * kBLd];
   __shared__ int s_rank[kCG];
-  // ---- which (item, position tile, channel group): consecutive logical slots on one XCD (blocks are dealt to the 8 XCDs round robin)
-  const int per_xcd = (int)gridDim.x >> 3;
-  const int L = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
+  const int L = head_slot();
   if (L >= total) return;
-  const int item = L / (pt_max * cg_max);
-  const int rem = L - item * (pt_max * cg_max);
-  const int pt = rem / cg_max, cg = rem - pt * cg_max;
-  const float *x;
-  int64_t hw;
-  int M;
-  if constexpr (FUSED) {
-    x = edescs[item].x, hw = edescs[item].hw, M = edescs[item].M;
-  } else {
-    x = hdescs[item].x, hw = hdescs[item].hw, M = hw_.M;
-  }
-  const int64_t P0 = (int64_t)pt * kPB;
-  if (P0 >= hw || cg * kCG >= M) return;
-  if (hw_.oob && !*head16_oob_word(FUSED ? edescs[item].xs : hdescs[item].xs, hw_.c_in, hw)) return; // a bf16x6 call: only the items
-                                                                                                      // outside its domain are this kernel's
+  const HeadPlace<float> b = head_place<FUSED, kPB, float>(edescs, hdescs, hw_, L, pt_max, cg_max);
+  if (b.P0 >= b.hw || b.cg * kCG >= b.M) return;
+  if (hw_.oob && !head_item_oob<FUSED>(edescs, hdescs, hw_, b.item, b.hw)) return; // a bf16x6 call: only the items outside its domain are this kernel's
+  const int item = b.item, cg = b.cg, M = b.M;
+  const int64_t hw = b.hw, P0 = b.P0;
+  const float *x = b.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
-  if constexpr (FUSED) {
-    // compact (coded) channel of each of the block's 16 channels, -1 = no coded symbol: a prefix sum over quant_stats' census
-    const EncDesc &d = edescs[item];
-    // (every thread takes channels tid, tid + 256 ...: one ballot per wave and chunk, the sixteen ranks are popcounts below a channel)
-    __shared__ unsigned long long s_nzmask[4];
-    int below = 0; // coded channels in the chunks before the one that holds this block's channels
-    const int c_first = cg * kCG;
-    for (int base = 0; base <= c_first; base += 256) {
-      const int c = base + tid;
-      const unsigned long long m = __ballot(c < M && d.chan_nz[c] != 0);
-      if (base + 256 <= c_first) {
-        below += __popcll(m); // (per wave; summed over the waves below)
-        continue;
-      }
-      if (lane == 0) s_nzmask[wave] = m;
-    }
-    __shared__ int s_below[4];
-    if (lane == 0) s_below[wave] = below;
-    __syncthreads();
-    if (tid < kCG) {
-      const int c = c_first + tid, off = c & 255; // (the block's channels lie in one chunk: 256 is a multiple of 16)
-      int r = -1;
-      if (c < M && ((s_nzmask[off >> 6] >> (off & 63)) & 1ull)) {
-        r = s_below[0] + s_below[1] + s_below[2] + s_below[3];
-        for (int wv = 0; wv < (off >> 6); ++wv) r += __popcll(s_nzmask[wv]);
-        r += __popcll(s_nzmask[off >> 6] & ((1ull << (off & 63)) - 1ull));
-      }
-      s_rank[tid] = r;
-    }
-    __syncthreads();
-    bool any = false;
-#pragma unroll
-    for (int i = 0; i < kCG; ++i) any = any || s_rank[i] >= 0;
-    if (!any) return; // sixteen channels that round to zero everywhere: nothing to code, nothing to multiply
-  }
+  if constexpr (FUSED)
+    if (!head_ranks<256>(edescs[item], cg, M, s_rank)) return;
   // the lane's eight latents, fetched now: their latency lies under the K loop instead of in front of the epilogue
   float yv[8];
   if constexpr (FUSED) {
@@ -150,9 +97,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
   {
     const float *bp = hw_.bp + (int64_t)cg * kRows;
 #pragma unroll
-    for (int tl = 0; tl < kTiles; ++tl)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tl][r] = bp[tl * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
+    for (int tl = 0; tl < kTiles; ++tl) head_bias_tile(bp, tl, h, acc[tl]);
   }
   // ---- K loop
   const int n_kt = hw_.n_kt, c_in = hw_.c_in;
@@ -237,9 +182,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
     // 96 products per wave and tile in four groups of 24; before a group, what a LATER step needs is issued: the global loads of the
     // next tile (the last tile loads itself again: harmless) and the fragments of the next group
     FGMM_FENCE();
-#if !(FGMM_HEAD_EXP & 1)
     load_tile(kt + 1 < n_kt ? kt + 1 : kt);
-#endif
     read_frag(f1, 1);
     FGMM_FENCE();
     multiply(f0);
@@ -253,15 +196,9 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
     multiply(f0);
     multiply(f1);
     FGMM_FENCE();
-#if !(FGMM_HEAD_EXP & 4)
     __syncthreads(); // every wave has read the tile
-#endif
-#if !(FGMM_HEAD_EXP & 2)
     store_tile();
-#endif
-#if !(FGMM_HEAD_EXP & 4)
     __syncthreads();
-#endif
     read_frag(f0, 0); // (after the last tile: a read that nobody uses)
   }
 #undef FGMM_FENCE
@@ -273,31 +210,14 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
     for (int g = 0; g < 2; ++g)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int cl = g * 8 + 2 * j + h;
-        const int rank = s_rank[cl];
-        uint32_t *row_out = nullptr;
-        if (rank >= 0) {
-          const int seg = (rank >= d.seg_b[0]) + (rank >= d.seg_b[1]) + (rank >= d.seg_b[2]);
-          row_out = (seg ? d.packed_seg[seg] : d.packed) + (int64_t)(rank - seg * d.cps) * hw;
-        }
+        const int rank = s_rank[g * 8 + 2 * j + h];
+        uint32_t *row_out = head_row(d, rank, hw);
         const int64_t p = P0 + wave * 32 + col;
         int bp = 0;
-        if (rank >= 0 && p < hw) {
-          float sg[4], mu[4], pi[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            sg[k] = acc[g * 3 + 0][4 * j + k];
-            mu[k] = acc[g * 3 + 1][4 * j + k];
-            pi[k] = acc[g * 3 + 2][4 * j + k];
-          }
-          softmax4(pi);
-          const float vq = __builtin_rintf(yv[g * 4 + j]);
-          stg<uint32_t>(row_out + p, sym_entry<MODE, CLAMPED>(vq, (int)vq, mu, sg, pi, bp));
-        }
+        if (rank >= 0 && p < hw) bp = head_entry<MODE, CLAMPED>(row_out + p, acc[g * 3], acc[g * 3 + 1], acc[g * 3 + 2], j, yv[g * 4 + j]);
         nbypass += __popcll(__ballot(bp));
       }
-    // bypass census: the host sums the item's slots; one atomic per wave that saw any (rare: 0.2 % of the symbols)
-    if (lane == 0 && nbypass) atomicAdd(d.meta + ((L * 4 + wave) % (int)d.meta_slots), (uint32_t)nbypass);
+    head_census<4>(d, L, nbypass);
   } else {
     float *out = hdescs[item].out;
 #pragma unroll
@@ -310,23 +230,22 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
 #pragma unroll
           for (int t = 0; t < 3; ++t)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) out[((int64_t)t * 4 * M + (int64_t)k * M + c) * hw + p] = acc[g * 3 + t][4 * j + k];
+            for (int k = 0; k < 4; ++k) out[head_plane_at(t, k, c, M, hw, p)] = acc[g * 3 + t][4 * j + k];
         }
       }
   }
 }
 
-template <int MODE, bool CLAMPED, bool VEC>
-int launch_fused(const EncDesc *descs, const HeadW &w, int count, int M_max, int64_t hw_max, hipStream_t st) {
-  const int pt_max = (int)((hw_max + kPB - 1) / kPB), cg_max = (M_max + kCG - 1) / kCG;
-  const int64_t total = (int64_t)count * pt_max * cg_max;
-  if (total <= 0) return 0;
-  if (total > (1ll << 30)) return (int)hipErrorInvalidValue;
-  const unsigned grid = (unsigned)((total + 7) / 8 * 8);
-  auto kernel = head_kernel<MODE, CLAMPED, true, VEC>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, descs, (const HeadDesc *)nullptr, w, pt_max, cg_max, (int)total);
-  return (int)hipGetLastError();
-}
+template <bool FUSED> struct Go { // F::go of head_launch (fgmm_headframe.h); the un-fused form has one mode
+  const EncDesc *edescs;
+  const HeadDesc *hdescs;
+  const HeadW &w;
+  hipStream_t st;
+  template <int MODE, bool CLAMPED, bool VEC> int go(const HeadGrid &g) const {
+    hipLaunchKernelGGL((head_kernel<FUSED ? MODE : 0, FUSED ? CLAMPED : true, FUSED, VEC>), dim3(g.blocks), dim3(256), 0, st, edescs, hdescs, w, g.pt_max, g.cg_max, g.total);
+    return (int)hipGetLastError();
+  }
+};
 
 } // namespace
 
@@ -339,33 +258,10 @@ int launch_head_pack(const float *w, const float *bias, int M, int c_in, float *
 }
 
 int launch_head_params(const HeadDesc *d_descs, const HeadW &w, int count, int64_t hw_max, bool vec, void *stream) {
-  const int pt_max = (int)((hw_max + kPB - 1) / kPB), cg_max = w.n_cg;
-  const int64_t total = (int64_t)count * pt_max * cg_max;
-  if (total <= 0) return 0;
-  if (total > (1ll << 30)) return (int)hipErrorInvalidValue;
-  const unsigned grid = (unsigned)((total + 7) / 8 * 8);
-  auto kernel = vec ? head_kernel<0, true, false, true> : head_kernel<0, true, false, false>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const EncDesc *)nullptr, d_descs, w, pt_max, cg_max, (int)total);
-  return (int)hipGetLastError();
+  return head_launch<kPB>(Go<false>{nullptr, d_descs, w, (hipStream_t)stream}, count, w.n_cg, hw_max, 0, true, vec);
 }
-
 int launch_head_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_max, int64_t hw_max, int mode, bool clamped, bool vec, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  switch ((mode * 2 + (clamped ? 1 : 0)) * 2 + (vec ? 1 : 0)) {
-  case 0: return launch_fused<0, false, false>(d_descs, w, count, M_max, hw_max, st);
-  case 1: return launch_fused<0, false, true>(d_descs, w, count, M_max, hw_max, st);
-  case 2: return launch_fused<0, true, false>(d_descs, w, count, M_max, hw_max, st);
-  case 3: return launch_fused<0, true, true>(d_descs, w, count, M_max, hw_max, st);
-  case 4: return launch_fused<1, false, false>(d_descs, w, count, M_max, hw_max, st);
-  case 5: return launch_fused<1, false, true>(d_descs, w, count, M_max, hw_max, st);
-  case 6: return launch_fused<1, true, false>(d_descs, w, count, M_max, hw_max, st);
-  case 7: return launch_fused<1, true, true>(d_descs, w, count, M_max, hw_max, st);
-  case 8: return launch_fused<2, false, false>(d_descs, w, count, M_max, hw_max, st);
-  case 9: return launch_fused<2, false, true>(d_descs, w, count, M_max, hw_max, st);
-  case 10: return launch_fused<2, true, false>(d_descs, w, count, M_max, hw_max, st);
-  case 11: return launch_fused<2, true, true>(d_descs, w, count, M_max, hw_max, st);
-  }
-  return (int)hipErrorInvalidValue;
+  return head_launch<kPB>(Go<true>{d_descs, nullptr, w, (hipStream_t)stream}, count, (M_max + kCG - 1) / kCG, hw_max, mode, clamped, vec);
 }
 
 } // namespace fgmm

@@ -17,9 +17,9 @@
 // features as well - head16_split_kernel writes it once per call, [K tile][part][position][16 channels], 1.5 x the features' bytes: the
 // twelve channel-group blocks of a position tile would otherwise each split the same tile (the first cut did: 0.87 ms per Kodak batch,
 // a third of it that arithmetic) - so that staging is sixteen-byte copies only and a lane's eight k values are one 16-byte read.  Rows
-// of 24 bf16 (48 bytes) in LDS: the 16-byte reads and writes of 16 consecutive lanes fall on 64 different banks.  Epilogue and block
-// placement as in fgmm_head.hip.
-#include "fgmm_dev.h"
+// of 24 bf16 (48 bytes) in LDS: the 16-byte reads and writes of 16 consecutive lanes fall on 64 different banks.  Block placement, rank
+// prologue and epilogues are fgmm_head.hip's: fgmm_headframe.h.
+#include "fgmm_headframe.h"
 
 namespace fgmm {
 namespace {
@@ -30,7 +30,6 @@ constexpr int kA16 = 3 * kRows * kPitch, kB16 = 3 * kPB * kPitch;    // bf16 ele
 constexpr int kBuf16 = kA16 + kB16;                                  // one staged (W tile, x tile) pair: 64 512 bytes
 constexpr size_t kLds16 = 2 * sizeof(uint16_t) * (size_t)kBuf16;     // two of them: 129 024 bytes
 
-typedef float f16_t __attribute__((ext_vector_type(16)));
 typedef __bf16 bf8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
 
@@ -62,10 +61,7 @@ __global__ __launch_bounds__(256) void head16_pack_kernel(const float *__restric
     const int r = (int)((is_bias ? e : e / kBK) % kRows);
     const int kt = is_bias ? 0 : (int)((e / (kBK * kRows)) % n_kt);
     const int cg = (int)(is_bias ? e / kRows : e / ((int64_t)kBK * kRows * n_kt));
-    const int tile = r >> 5, ri = r & 31;
-    const int g = tile / 3, t = tile % 3, cl = ri >> 2, k = ri & 3;
-    const int c = cg * kCG + g * 8 + cl;
-    const int64_t o = (int64_t)t * 4 * M + (int64_t)k * M + c;
+    const auto [c, o] = head_pack_row(r, cg, M);
     if (is_bias) {
       bp[e] = (c < M && bias) ? bias[o] : 0.0f;
     } else {
@@ -124,59 +120,18 @@ __global__ __launch_bounds__(kThreads) void head16_kernel(const EncDesc *__restr
                                                            int cg_max, int total) {
   extern __shared__ __attribute__((aligned(16))) uint16_t s16[];
   __shared__ int s_rank[kCG];
-  const int per_xcd = (int)gridDim.x >> 3;
-  const int L = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
+  const int L = head_slot();
   if (L >= total) return;
-  const int item = L / (pt_max * cg_max);
-  const int rem = L - item * (pt_max * cg_max);
-  const int pt = rem / cg_max, cg = rem - pt * cg_max;
-  const uint16_t *xs; // the item's features, split by head16_split_kernel (the descriptor's xs)
-  int64_t hw;
-  int M;
-  if constexpr (FUSED) {
-    xs = static_cast<const uint16_t *>(edescs[item].xs), hw = edescs[item].hw, M = edescs[item].M;
-  } else {
-    xs = static_cast<const uint16_t *>(hdescs[item].xs), hw = hdescs[item].hw, M = hw_.M;
-  }
-  const int64_t P0 = (int64_t)pt * kPB;
-  if (P0 >= hw || cg * kCG >= M) return;
-  if (hw_.oob && *head16_oob_word(xs, hw_.c_in, hw)) return; // a feature outside the domain: the exact kernel, launched next, takes it
+  const HeadPlace<uint16_t> b = head_place<FUSED, kPB, uint16_t>(edescs, hdescs, hw_, L, pt_max, cg_max);
+  if (b.P0 >= b.hw || b.cg * kCG >= b.M) return;
+  if (head_item_oob<FUSED>(edescs, hdescs, hw_, b.item, b.hw)) return; // a feature outside the domain: the exact kernel, launched next, takes the item
+  const int item = b.item, cg = b.cg, M = b.M;
+  const int64_t hw = b.hw, P0 = b.P0;
+  const uint16_t *xs = b.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
   const int rh = wave & 1, pq = wave >> 1;
-  if constexpr (FUSED) { // the compact channel of each of the block's 16 channels (fgmm_head.hip; chunks of 512 channels here)
-    const EncDesc &d = edescs[item];
-    __shared__ unsigned long long s_nzmask[kWaves];
-    __shared__ int s_below[kWaves];
-    int below = 0;
-    const int c_first = cg * kCG;
-    for (int base = 0; base <= c_first; base += kThreads) {
-      const int c = base + tid;
-      const unsigned long long m = __ballot(c < M && d.chan_nz[c] != 0);
-      if (base + kThreads <= c_first) {
-        below += __popcll(m);
-        continue;
-      }
-      if (lane == 0) s_nzmask[wave] = m;
-    }
-    if (lane == 0) s_below[wave] = below;
-    __syncthreads();
-    if (tid < kCG) {
-      const int c = c_first + tid, off = c & (kThreads - 1);
-      int r = -1;
-      if (c < M && ((s_nzmask[off >> 6] >> (off & 63)) & 1ull)) {
-        r = 0;
-        for (int wv = 0; wv < kWaves; ++wv) r += s_below[wv];
-        for (int wv = 0; wv < (off >> 6); ++wv) r += __popcll(s_nzmask[wv]);
-        r += __popcll(s_nzmask[off >> 6] & ((1ull << (off & 63)) - 1ull));
-      }
-      s_rank[tid] = r;
-    }
-    __syncthreads();
-    bool any = false;
-#pragma unroll
-    for (int i = 0; i < kCG; ++i) any = any || s_rank[i] >= 0;
-    if (!any) return;
-  }
+  if constexpr (FUSED)
+    if (!head_ranks<kThreads>(edescs[item], cg, M, s_rank)) return;
   // the lane's eight latents (4 channels x 2 position tiles), fetched under the K loop
   float yv[8];
   if constexpr (FUSED) {
@@ -192,12 +147,10 @@ __global__ __launch_bounds__(kThreads) void head16_kernel(const EncDesc *__restr
   {
     const float *bp = hw_.bp + (int64_t)cg * kRows;
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float b = bp[(rh * 3 + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
-        acc[t][0][r] = b, acc[t][1][r] = b;
-      }
+    for (int t = 0; t < 3; ++t) {
+      head_bias_tile(bp, rh * 3 + t, h, acc[t][0]);
+      acc[t][1] = acc[t][0];
+    }
   }
   const int n_kt = (hw_.c_in + kBK - 1) / kBK;
   const uint16_t *wp = static_cast<const uint16_t *>(hw_.wp) + (int64_t)cg * n_kt * 3 * (kRows * kBK);
@@ -277,39 +230,23 @@ __global__ __launch_bounds__(kThreads) void head16_kernel(const EncDesc *__restr
     if (kt + 1 < n_kt) step(kt + 1, g1, g0);
   }
 #undef FGMM_FENCE
-  // ---- epilogue (as fgmm_head.hip): the lane's eight latents, all twelve parameters in registers
+  // ---- epilogue: the lane's eight latents (4 channels x 2 position tiles), all twelve parameters in registers
   if constexpr (FUSED) {
     const EncDesc &d = edescs[item];
     int nbypass = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int cl = rh * 8 + 2 * j + h;
-      const int rank = s_rank[cl];
-      uint32_t *row_out = nullptr;
-      if (rank >= 0) {
-        const int seg = (rank >= d.seg_b[0]) + (rank >= d.seg_b[1]) + (rank >= d.seg_b[2]);
-        row_out = (seg ? d.packed_seg[seg] : d.packed) + (int64_t)(rank - seg * d.cps) * hw;
-      }
+      const int rank = s_rank[rh * 8 + 2 * j + h];
+      uint32_t *row_out = head_row(d, rank, hw);
 #pragma unroll
       for (int np = 0; np < 2; ++np) {
         const int64_t p = P0 + pq * 64 + np * 32 + col;
         int bp = 0;
-        if (rank >= 0 && p < hw) {
-          float sg[4], mu[4], pi[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            sg[k] = acc[0][np][4 * j + k];
-            mu[k] = acc[1][np][4 * j + k];
-            pi[k] = acc[2][np][4 * j + k];
-          }
-          softmax4(pi);
-          const float vq = __builtin_rintf(yv[j * 2 + np]);
-          stg<uint32_t>(row_out + p, sym_entry<MODE, CLAMPED>(vq, (int)vq, mu, sg, pi, bp));
-        }
+        if (rank >= 0 && p < hw) bp = head_entry<MODE, CLAMPED>(row_out + p, acc[0][np], acc[1][np], acc[2][np], j, yv[j * 2 + np]);
         nbypass += __popcll(__ballot(bp));
       }
     }
-    if (lane == 0 && nbypass) atomicAdd(d.meta + ((L * kWaves + wave) % (int)d.meta_slots), (uint32_t)nbypass);
+    head_census<kWaves>(d, L, nbypass);
   } else {
     float *out = hdescs[item].out;
 #pragma unroll
@@ -322,27 +259,26 @@ __global__ __launch_bounds__(kThreads) void head16_kernel(const EncDesc *__restr
 #pragma unroll
           for (int t = 0; t < 3; ++t)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) out[((int64_t)t * 4 * M + (int64_t)k * M + c) * hw + p] = acc[t][np][4 * j + k];
+            for (int k = 0; k < 4; ++k) out[head_plane_at(t, k, c, M, hw, p)] = acc[t][np][4 * j + k];
         }
       }
     }
   }
 }
 
-template <typename K> int lds16(K kernel) {
-  return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds16);
-}
-
-template <int MODE, bool CLAMPED> int launch_fused16(const EncDesc *descs, const HeadW &w, int count, int M_max, int64_t hw_max, hipStream_t st) {
-  const int pt_max = (int)((hw_max + kPB - 1) / kPB), cg_max = (M_max + kCG - 1) / kCG;
-  const int64_t total = (int64_t)count * pt_max * cg_max;
-  if (total <= 0) return 0;
-  if (total > (1ll << 30)) return (int)hipErrorInvalidValue;
-  auto kernel = head16_kernel<MODE, CLAMPED, true>;
-  if (int e = lds16(kernel)) return e;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 7) / 8 * 8)), dim3(kThreads), kLds16, st, descs, (const HeadDesc *)nullptr, w, pt_max, cg_max, (int)total);
-  return (int)hipGetLastError();
-}
+// F::go of head_launch (fgmm_headframe.h); the kernels have no VEC form
+template <bool FUSED> struct Go16 {
+  const EncDesc *edescs;
+  const HeadDesc *hdescs;
+  const HeadW &w;
+  hipStream_t st;
+  template <int MODE, bool CLAMPED, bool> int go(const HeadGrid &g) const {
+    auto kernel = head16_kernel<FUSED ? MODE : 0, FUSED ? CLAMPED : true, FUSED>;
+    if (int e = (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds16)) return e;
+    hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(kThreads), kLds16, st, edescs, hdescs, w, g.pt_max, g.cg_max, g.total);
+    return (int)hipGetLastError();
+  }
+};
 
 } // namespace
 
@@ -377,28 +313,10 @@ int launch_head16_split(const float *x0, void *xs0, int64_t hw, int c_in, int co
 }
 
 int launch_head16_params(const HeadDesc *d_descs, const HeadW &w, int count, int64_t hw_max, void *stream) {
-  const int pt_max = (int)((hw_max + kPB - 1) / kPB), cg_max = w.n_cg;
-  const int64_t total = (int64_t)count * pt_max * cg_max;
-  if (total <= 0) return 0;
-  if (total > (1ll << 30)) return (int)hipErrorInvalidValue;
-  auto kernel = head16_kernel<0, true, false>;
-  if (int e = lds16(kernel)) return e;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 7) / 8 * 8)), dim3(kThreads), kLds16, (hipStream_t)stream, (const EncDesc *)nullptr, d_descs, w, pt_max, cg_max,
-                     (int)total);
-  return (int)hipGetLastError();
+  return head_launch<kPB>(Go16<false>{nullptr, d_descs, w, (hipStream_t)stream}, count, w.n_cg, hw_max, 0, true, false);
 }
-
 int launch_head16_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_max, int64_t hw_max, int mode, bool clamped, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  switch (mode * 2 + (clamped ? 1 : 0)) {
-  case 0: return launch_fused16<0, false>(d_descs, w, count, M_max, hw_max, st);
-  case 1: return launch_fused16<0, true>(d_descs, w, count, M_max, hw_max, st);
-  case 2: return launch_fused16<1, false>(d_descs, w, count, M_max, hw_max, st);
-  case 3: return launch_fused16<1, true>(d_descs, w, count, M_max, hw_max, st);
-  case 4: return launch_fused16<2, false>(d_descs, w, count, M_max, hw_max, st);
-  case 5: return launch_fused16<2, true>(d_descs, w, count, M_max, hw_max, st);
-  }
-  return (int)hipErrorInvalidValue;
+  return head_launch<kPB>(Go16<true>{d_descs, nullptr, w, (hipStream_t)stream}, count, (M_max + kCG - 1) / kCG, hw_max, mode, clamped, false);
 }
 
 } // namespace fgmm

@@ -96,6 +96,9 @@ struct HeadW {              // the PACKED weights of a head (device): see head_p
   // skip the items it flags, the exact kernels launched after them take only those.  0: every item is the kernel's
   int32_t oob;
 };
+struct HeadPair { // a head as the calls take it: its own packing, and for a bf16x6 head (w.arith) the exact packing of the same weights,
+  HeadW w, exact; // for the items with a feature outside the bf16x6 domain
+};
 struct HeadDesc { // one item of the un-fused form
   const float *x; // device [c_in, hw]
   const void *xs; // bf16x6: the split copy of x (head16_split_kernel)
@@ -122,10 +125,15 @@ FGMM_HD static inline const uint32_t *head16_oob_word(const void *xs, int c_in, 
   return reinterpret_cast<const uint32_t *>(static_cast<const uint16_t *>(xs) + (int64_t)((c_in + kHead16BK - 1) / kHead16BK) * 3 * hw * kHead16BK);
 }
 int launch_head16_split(const float *x0, void *xs0, int64_t hw, int c_in, int count, int64_t x_stride, int64_t xs_stride, void *stream);
+// one arithmetic's kernels (fgmm_head.hip, fgmm_head16.hip; stubs in tests/fake/fake_device.cpp).  vec: every hw % 4 == 0, x 16-byte aligned
 int launch_head16_params(const HeadDesc *d_descs, const HeadW &w, int count, int64_t hw_max, void *stream);
 int launch_head16_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_max, int64_t hw_max, int mode, bool clamped, void *stream);
-int launch_head_params(const HeadDesc *d_descs, const HeadW &w, int count, int64_t hw_max, bool vec, void *stream); // vec: every hw % 4 == 0, x 16-byte aligned
+int launch_head_params(const HeadDesc *d_descs, const HeadW &w, int count, int64_t hw_max, bool vec, void *stream);
 int launch_head_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_max, int64_t hw_max, int mode, bool clamped, bool vec, void *stream);
+// what the calls use (host code, fgmm_encode.cpp): the head's parameter planes / the head's table entries - a bf16x6 head's kernels,
+// then the exact ones for the items they left (`oob` set in both); an exact head's kernels alone
+int launch_head_planes(const HeadDesc *d_descs, const HeadPair &head, int count, int64_t hw_max, bool vec, void *stream);
+int launch_head_entries(const EncDesc *d_descs, const HeadPair &head, int count, int M_max, int64_t hw_max, int mode, bool clamped, bool vec, void *stream);
 
 // ---- GPU-side decode of CHECKPOINTED bitstreams (segdec_kernel): one wave per segment ---------------------------
 struct SegDesc {

@@ -330,7 +330,9 @@ int fgmm_gmc_compress_batch_to(fgmm_ctx *ctx, void *stream, fgmm_item *items, in
  *    BLAS's or MIOpen's summation order is not part of any contract; the reference silently relies on it being the same on both
  *    sides).  Streams coded from these parameters decode from these parameters.
  * ---------------------------------------------------------------------------------------------------------- */
-typedef struct fgmm_head fgmm_head; /* a head's weights, packed for the kernel, on the context's device */
+typedef struct fgmm_head fgmm_head; /* a head's weights, packed for the kernel, on the context's device.  Immutable once created: a head
+                                     * may be used from any context on its device, from several at the same time (what a call needs
+                                     * beside the weights - the bf16x6 form's split features - is the calling context's) */
 /* weight: device float32 [3*K*M, c_in] row-major (Conv2d.weight [3*K*M, c_in, 1, 1]); bias: device float32 [3*K*M] or NULL.
  * The weights are copied (packed) before the call returns. */
 int fgmm_head_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int K, int c_in, fgmm_head **out);

@@ -4,8 +4,10 @@
     hipcc <the flags of csrc/build.sh> --cuda-device-only -S fgmm_tab.hip -o OLD/fgmm_tab.s      (per .hip file, old and new tree)
     python scripts/kernel_regs.py OLD NEW [--all]
 
-For every kernel of OLD: its VGPRs, SGPRs, scratch bytes and occupancy in both sets, and whether its instructions are the SAME TEXT
-(labels renumbered: inserting instantiations shifts the function numbers in .LBB<n>_<m>).  Kernels only NEW has are summarised per
+For every kernel of OLD: its VGPRs, SGPRs, scratch bytes, LDS bytes and occupancy in both sets, and whether its instructions are the
+SAME TEXT (labels renumbered: inserting instantiations shifts the function numbers in .LBB<n>_<m>).  A kernel with matrix instructions
+gets a second verdict for the span from its first to its last v_mfma - the K loop of the parameter head (profiles/head_frame_refactor.md):
+"same mfma span" says that a change around the loop left the loop's own schedule alone.  Kernels only NEW has are summarised per
 template.  Needs no GPU."""
 import hashlib
 import re
@@ -27,10 +29,11 @@ FIELDS = {"next_free_vgpr": "vgpr", "next_free_sgpr": "sgpr", "private_segment_f
 
 
 def kernels(d):
-    """name -> dict(vgpr, sgpr, scratch, lds, occ, sha) for every kernel of the directory's .s files (one pass over the lines)"""
-    res, sha, occ = {}, {}, {}
+    """name -> dict(vgpr, sgpr, scratch, lds, occ, sha, span) for every kernel of the directory's .s files (one pass over the lines);
+    span: the hash of the lines from the first to the last v_mfma, None without one"""
+    res, sha, span, occ = {}, {}, {}, {}
     for f in sorted(Path(d).glob("*.s")):
-        cur = h = last = desc = pending = None
+        cur = text = last = desc = pending = None
         with open(f) as fh:
             for line in fh:
                 t = line.strip()
@@ -46,18 +49,20 @@ def kernels(d):
                     res[desc] = {}
                 elif cur is not None:
                     if t.startswith(".Lfunc_end"):
-                        sha[cur], last, cur = h.hexdigest()[:12], cur, None
+                        mf = [i for i, ln in enumerate(text) if ln.startswith(b"v_mfma")]
+                        span[cur] = hashlib.sha1(b"".join(text[mf[0]:mf[-1] + 1])).hexdigest()[:12] if mf else None
+                        sha[cur], last, cur = hashlib.sha1(b"".join(text)).hexdigest()[:12], cur, None
                     elif t and not t.startswith((";", ".loc", ".file", ".cfi")):
-                        h.update(LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) or ""), t.split(";")[0].rstrip()).encode() + b"\n")
+                        text.append(LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) or ""), t.split(";")[0].rstrip()).encode() + b"\n")
                 elif t.startswith(".type") and t.endswith(",@function"):
                     pending = t.split()[1].split(",")[0]
                 elif pending and line.startswith(pending + ":"):
-                    cur, h, pending = pending, hashlib.sha1(), None
+                    cur, text, pending = pending, [], None
                 elif t.startswith("; Occupancy:") and last:
                     occ[last] = int(t.split()[-1])
                     last = None
     for name, r in res.items():
-        r["sha"], r["occ"] = sha.get(name, "?"), occ.get(name)
+        r["sha"], r["span"], r["occ"] = sha.get(name, "?"), span.get(name), occ.get(name)
     return res
 
 
@@ -66,8 +71,8 @@ def main():
     show_all = "--all" in sys.argv
     old, new = kernels(args[0]), kernels(args[1])
     dm = demangle(sorted(set(old) | set(new)))
-    keys = ("vgpr", "sgpr", "scratch", "occ")
-    differ = []
+    keys = ("vgpr", "sgpr", "scratch", "lds", "occ")
+    differ, regs_differ, n_mfma, span_differ = [], 0, 0, 0
     for name in sorted(old):
         if name not in new:
             differ.append((name, "missing in NEW"))
@@ -76,10 +81,16 @@ def main():
         same_regs = all(o.get(k) == n.get(k) for k in keys)
         if not same_regs or o["sha"] != n["sha"]:
             differ.append((name, f"old {[o.get(k) for k in keys]} {o['sha']}  new {[n.get(k) for k in keys]} {n['sha']}"))
+        regs_differ += not same_regs
+        if o["span"]:
+            n_mfma += 1
+            span_differ += o["span"] != n["span"]
         if show_all:
-            print(f"{dm[name][:150]:150s} " + " ".join(f"{k}={o.get(k)}" for k in keys) + (" same text" if o["sha"] == n["sha"] else " TEXT DIFFERS"))
-    print(f"{len(old)} kernels in OLD, {len(new)} in NEW; of OLD's: {len(old) - len(differ)} with the same instructions, registers, scratch and occupancy; "
-          f"{len(differ)} that differ")
+            verdict = "same mfma span" if o["span"] == n["span"] else "MFMA SPAN DIFFERS"
+            print(f"{dm[name][:150]:150s} " + " ".join(f"{k}={o.get(k)}" for k in keys) + (" same text" if o["sha"] == n["sha"] else " TEXT DIFFERS")
+                  + (f" {verdict}" if o["span"] else ""))
+    print(f"{len(old)} kernels in OLD, {len(new)} in NEW; of OLD's: {len(old) - len(differ)} with the same instructions, registers, scratch, LDS and occupancy; "
+          f"{len(differ)} that differ, {regs_differ} of them in {list(keys)}; {n_mfma} with matrix instructions, {span_differ} whose first-to-last v_mfma span differs")
     for name, why in differ:
         print("  DIFFERS", dm[name], why)
     # the kernels only NEW has: each bfloat16 instantiation (DF16b in the mangled name) beside its float16 sibling (DF16_)

@@ -82,6 +82,41 @@ def test_fused_head_bytes_equal_the_unfused_path(mode, shape):
     assert torch.equal(out, fused.y_q) and torch.equal(fused.y_q[:, 0], torch.round(y))
 
 
+@pytest.mark.parametrize("arith", ["f32", "bf16x6"])
+def test_fused_head_ranks_across_channel_chunks(arith):
+    """the fused kernels' compact-channel ranks where the census is read in more than one chunk (256 channels per chunk in the exact
+    form, 512 in bf16x6): M = 530 is 34 channel groups, the last of 2 channels, with coded channels on both sides of 256 and of 512,
+    a first group and the group before 512 with none (those blocks leave early), and dead channels right at the boundaries.  c_in = 17
+    is one ragged exact K tile and two bf16 ones, hw = 35 is no multiple of 4.  Fused == un-fused for every item, the zero bitmap is
+    the pattern built, and the streams decode to round(y)"""
+    M, c_in, h, w, N = 530, 17, 5, 7, 2
+    conv, x, _ = make_head(61, M, c_in, h, w, N)
+    dead = np.zeros(M, bool)
+    for lo, hi in ((0, 16), (240, 255), (257, 272), (496, 512), (529, 530)):
+        dead[lo:hi] = True
+    dead[[37, 100, 333, 420]] = True
+    assert not dead[[255, 256, 512, 528]].any() and dead[[254, 257, 511, 529]].all()
+    rng = np.random.default_rng(62)
+    yn = (rng.standard_normal((N, M, h, w)) * 1.2).astype(np.float32)
+    c = np.arange(M)
+    yn[:, c, (c % (h * w)) // w, (c % (h * w)) % w] = np.where(c % 2, 3.0, -3.0).astype(np.float32)  # a live channel holds +-3 somewhere
+    yn[:, dead] = 0.0
+    y = torch.from_numpy(yn).cuda()
+    head = ParameterHead(conv, arithmetic=arith)
+    gmc = GaussianMixtureConditional(K=4, mode="polya")
+    fused = gmc.compress_head_batch(y, x, head)
+    s, m, lg = head.params(x)
+    plain = gmc.compress_batch(y, s, m, lg, weights_are_logits=True)
+    want_zb = torch.from_numpy((~dead).astype(np.int64))
+    for i in range(N):
+        (bf, af, zf), qf = fused[i]
+        (bp, ap, zp), qp = plain[i]
+        assert bytes(bf) == bytes(bp) and af == ap and torch.equal(zf, zp) and torch.equal(qf, qp), i
+        assert torch.equal(zf.cpu(), want_zb), i
+    out = gmc.decompress_batch(fused.strings, fused.abs_maxes, fused.zero_bitmaps, s, m, lg, weights_are_logits=True, stacked_output=True)
+    assert torch.equal(out, fused.y_q) and torch.equal(fused.y_q[:, 0], torch.round(y))
+
+
 def test_fused_head_with_checkpoints_and_segmented_tables():
     """the fused kernel writes the SAME table layout the host encoders expect: segmented tables (a worker per bitstream, tail first)
     and checkpointed streams"""
