@@ -94,12 +94,26 @@ class fgmm_rdcurve_skip(C.Structure):
     _fields_ = [("n_skipped", C.c_uint64 * FGMM_RDCURVE_MAX), ("n_eligible", C.c_int64)]
 
 
+class fgmm_like_item(C.Structure):
+    """one item of fgmm_gmc_likelihood_batch (include/flashgmm_amd.h section 3g)"""
+    _fields_ = [("y", C.c_void_p), ("params", fgmm_params), ("M", C.c_int32), ("K", C.c_int32), ("hw", C.c_int64),
+                ("like_out", C.c_void_p), ("v_out", C.c_void_p), ("bits_q", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
+class fgmm_like_grad_item(C.Structure):
+    """one item of fgmm_gmc_likelihood_backward_batch (section 3g)"""
+    _fields_ = [("y", C.c_void_p), ("params", fgmm_params), ("M", C.c_int32), ("K", C.c_int32), ("hw", C.c_int64),
+                ("g_like", C.c_void_p), ("g_bits", C.c_double), ("dy", C.c_void_p), ("dscales", C.c_void_p), ("dmeans", C.c_void_p),
+                ("dweights", C.c_void_p), ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
 def _item_dtype(struct=fgmm_item):
     """numpy view of ``fgmm_item[]`` (offsets taken from the ctypes declaration): lets a batch be filled column by
     column instead of field by field."""
     import numpy as np
     names, formats, offsets = [], [], []
-    kinds = {C.c_void_p: "<u8", C.c_int64: "<i8", C.c_int32: "<i4", C.c_size_t: "<u8", C.c_uint64: "<u8"}
+    kinds = {C.c_void_p: "<u8", C.c_int64: "<i8", C.c_int32: "<i4", C.c_size_t: "<u8", C.c_uint64: "<u8", C.c_double: "<f8"}
     for name, typ in struct._fields_:
         base = getattr(struct, name).offset
         if typ is fgmm_params:
@@ -116,6 +130,9 @@ ITEM_DTYPE = _item_dtype()
 RATE_ITEM_DTYPE = _item_dtype(fgmm_rate_item)
 RDOQ_ITEM_DTYPE = _item_dtype(fgmm_rdoq_item)
 RDCURVE_ITEM_DTYPE = _item_dtype(fgmm_rdcurve_item)
+LIKE_ITEM_DTYPE = _item_dtype(fgmm_like_item)
+LIKE_GRAD_ITEM_DTYPE = _item_dtype(fgmm_like_grad_item)
+FGMM_LIKE_Q = 32  # unit of the likelihood call's bits_q: 2^-32 bit
 FGMM_RATE_Q = 24  # unit of the size estimate's costs: 2^-24 bit
 
 SINK_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)  # fgmm_sink.alloc(user, item, nbytes) -> address
@@ -192,6 +209,8 @@ SIGNATURES = {
                                       C.POINTER(fgmm_rdcurve_skip)]),
     "fgmm_gmc_rdoq_budget_batch_s": (_i, [_p, _p, C.POINTER(fgmm_rdoq_item), _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_uint64), C.c_double, _i,
                                           C.POINTER(fgmm_budget_result), C.POINTER(fgmm_rdo_weights), C.POINTER(fgmm_rdo_skip)]),
+    "fgmm_gmc_likelihood_batch": (_i, [_p, _p, C.POINTER(fgmm_like_item), _i, _i, C.c_float, C.c_float]),
+    "fgmm_gmc_likelihood_backward_batch": (_i, [_p, _p, C.POINTER(fgmm_like_grad_item), _i, _i, C.c_float, C.c_float]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

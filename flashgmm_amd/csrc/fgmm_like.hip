@@ -1,0 +1,206 @@
+// fgmm_like.hip — the entropy model's forward(): the differentiable likelihood of a latent under its 4-component Gaussian mixture, its
+// rate and its gradients (include/flashgmm_amd.h section 3g), for CDNA4 / gfx950 (MI355X), wave64.
+//
+//   like_kernel       (y, sigma, mu, pi) -> the bounded likelihood per latent (optional map), v (optional), the item's bit count
+//   like_bwd_kernel   (y | v, sigma, mu, pi, g | g_bits) -> dy (optional) and the twelve float32 gradient planes
+//
+// Both run the encode frame (fgmm_encframe.h): placement in either grid, VEC-wide loads of float32 / float16 / bfloat16 planes widened
+// exactly as they arrive, wave_sum64 / add64.  The EncDesc has no chan_list: every channel is evaluated, there is no census.  What torch
+// eager does with about ten element-wise kernels per component - each reading and writing an [B, M, h, w] temporary that autograd keeps
+// for the backward pass - is 52 B in and 4 B out per latent here (0 out for the rate alone), and the backward kernel recomputes
+// everything from the inputs: 56 B in, 52 B out, nothing saved in between.
+//
+// The arithmetic is section 3g's, literally: binary32, no contraction (-ffp-contract=off), correctly rounded '/'; erfcf, expf and the
+// binary64 log2 are the device library's.  The rate is summed in 64-bit integers - across the wave by shuffles, then one atomic per
+// wave into the item's word: integer sums do not depend on the order the atomics arrive in, every run gives the same bits.
+#include <hip/hip_runtime.h>
+
+#include "fgmm_encframe.h"
+
+namespace fgmm {
+
+constexpr float kLikeC = (float)(-0.70710678118654752440);       // (float)(-(2^-0.5))            entropy_models.py:676
+constexpr float kLikeInvSqrt2Pi = (float)0.39894228040143267794; // (float)(1 / sqrt(2 pi))
+constexpr float kLikeLn2 = 0x1.62e430p-1f;
+
+// one component: s = max(sigma, sb) keeping a NaN sigma (LowerBound, bound_ops.py:36-37), the two standardised edges, p = u - l
+__device__ __forceinline__ float like_term(float v, float mu, float sigma, float sb, float &s, float &xu, float &xl) {
+  s = max_nan(sigma, sb);
+  const float a = __builtin_fabsf(v - mu);
+  xu = (0.5f - a) / s;
+  xl = (-0.5f - a) / s;
+  const float u = 0.5f * erfcf(kLikeC * xu);
+  const float l = 0.5f * erfcf(kLikeC * xl);
+  return u - l;
+}
+__device__ __forceinline__ float like_phi(float x) { return expf(-0.5f * x * x) * kLikeInvSqrt2Pi; }
+__device__ __forceinline__ float like_bound(float L, float lb) { return lb > 0.0f ? max_nan(L, lb) : L; }
+__device__ __forceinline__ bool like_counts(float out) { return out > 0.0f && out < INFINITY; } // (false for NaN)
+
+template <int VEC, typename PT, bool LINEAR>
+__global__ __launch_bounds__(kBlock) void like_kernel(const EncDesc *__restrict__ descs, const LikeDesc *__restrict__ ldescs, int round, float sb,
+                                                      float lb) {
+  const EncDesc &d = descs[blockIdx.z];
+  const LikeDesc &r = ldescs[blockIdx.z];
+  const int64_t hw = d.hw;
+  int c;
+  int64_t p0;
+  bool active;
+  if (!enc_place<VEC, LINEAR>(hw, d.M, c, p0, active)) return;
+  unsigned long long bits = 0, left_out = 0; // the lane's latents: |term| < 2^40, so a wave's sum is far from wrapping
+  if (active) {
+    float v[VEC], out[VEC];
+    enc_load_y<VEC>(d, c, p0, v);
+    EncPlanes<PT, VEC> P;
+    P.load(d, c, p0);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float mu[4], sg[4], pi[4];
+      P.get(e, 0, mu, sg, pi);
+      if (round) v[e] = __builtin_rintf(v[e]); // round-half-even == torch.round
+      float L = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float s, xu, xl;
+        const float p = like_term(v[e], mu[k], sg[k], sb, s, xu, xl);
+        L = L + p * pi[k];
+      }
+      out[e] = like_bound(L, lb);
+      if (like_counts(out[e])) bits += (unsigned long long)llrint(-log2((double)out[e]) * 0x1p32);
+      else ++left_out;
+      if constexpr (VEC == 1) break; // (one position: no loop, see EncPlanes<PT, 1>)
+    }
+    if (r.like_out) enc_st<float, VEC>(r.like_out + (int64_t)c * hw + p0, out);
+    if (r.v_out) enc_st<float, VEC>(r.v_out + (int64_t)c * hw + p0, v);
+  }
+  bits = wave_sum64(bits);
+  left_out = wave_sum64(left_out);
+  if ((threadIdx.x & 63) == 0) {
+    if (bits) add64(r.sums, bits);
+    if (left_out) add64(r.sums + 1, left_out);
+  }
+}
+
+template <int VEC, typename PT, bool LINEAR>
+__global__ __launch_bounds__(kBlock) void like_bwd_kernel(const EncDesc *__restrict__ descs, const LikeGradDesc *__restrict__ gdescs, int round,
+                                                          float sb, float lb) {
+  const EncDesc &d = descs[blockIdx.z];
+  const LikeGradDesc &r = gdescs[blockIdx.z];
+  const int64_t hw = d.hw;
+  int c;
+  int64_t p0;
+  bool active;
+  if (!enc_place<VEC, LINEAR>(hw, d.M, c, p0, active)) return;
+  if (!active) return; // (no wave reduction here)
+  float v[VEC], g[VEC];
+  enc_load_y<VEC>(d, c, p0, v);
+  if (r.g_like) enc_ld<float, VEC>(r.g_like + (int64_t)c * hw + p0, g);
+  EncPlanes<PT, VEC> P;
+  P.load(d, c, p0);
+  const float gb = r.g_bits;
+  float ds[4][VEC], dm[4][VEC], dw[4][VEC], dy[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) {
+    float mu[4], sg[4], pi[4];
+    P.get(e, 0, mu, sg, pi);
+    const float ve = round ? __builtin_rintf(v[e]) : v[e];
+    float p[4], da[4], ga[4];
+    float L = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float s, xu, xl;
+      p[k] = like_term(ve, mu[k], sg[k], sb, s, xu, xl);
+      L = L + p[k] * pi[k];
+      const float fu = like_phi(xu), fl = like_phi(xl);
+      da[k] = -pi[k] * (fu - fl) / s;
+      ga[k] = -pi[k] * (fu * xu - fl * xl) / s;
+    }
+    float ge;
+    if (r.g_like) {
+      ge = g[e];
+    } else { // the gradient of the item's bit count: a latent that is left out of the sum has none
+      const float out = like_bound(L, lb);
+      ge = like_counts(out) ? -gb / (out * kLikeLn2) : 0.0f;
+    }
+    const float gL = (L >= lb || ge < 0.0f || lb <= 0.0f) ? ge : 0.0f; // bound_ops.py:40-42
+    float dv = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      dw[k][e] = gL * p[k];
+      const float sgn = (float)((ve > mu[k]) - (ve < mu[k])); // torch's abs: 0 at 0
+      dm[k][e] = -gL * da[k] * sgn;
+      dv = dv + gL * da[k] * sgn;
+      const float G = gL * ga[k];
+      ds[k][e] = (sg[k] >= sb || G < 0.0f) ? G : 0.0f;
+    }
+    dy[e] = round ? 0.0f : dv;
+    if constexpr (VEC == 1) break;
+  }
+  const int64_t at = (int64_t)c * hw + p0, plane = (int64_t)d.M * hw;
+  if (r.dy) enc_st<float, VEC>(r.dy + at, dy);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (r.dscales) enc_st<float, VEC>(r.dscales + k * plane + at, ds[k]);
+    if (r.dmeans) enc_st<float, VEC>(r.dmeans + k * plane + at, dm[k]);
+    if (r.dweights) enc_st<float, VEC>(r.dweights + k * plane + at, dw[k]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// launchers: a ladder over VEC (1, 4, and 8 for two-byte planes where the kernel has it) x plane type x grid
+// ---------------------------------------------------------------------------------------------------------
+struct LikeLaunch {
+  const EncDesc *d;
+  const LikeDesc *r;
+  int round;
+  float sb, lb;
+  static constexpr bool kVec8 = true;
+  template <int VEC, typename PT, bool LINEAR> void go(dim3 grid, hipStream_t s) const {
+    hipLaunchKernelGGL((like_kernel<VEC, PT, LINEAR>), grid, dim3(kBlock), 0, s, d, r, round, sb, lb);
+  }
+};
+struct LikeBwdLaunch {
+  const EncDesc *d;
+  const LikeGradDesc *r;
+  int round;
+  float sb, lb;
+  static constexpr bool kVec8 = false; // twelve VEC-wide gradient planes per lane: 4 positions keep the kernel out of scratch
+  template <int VEC, typename PT, bool LINEAR> void go(dim3 grid, hipStream_t s) const {
+    hipLaunchKernelGGL((like_bwd_kernel<VEC, PT, LINEAR>), grid, dim3(kBlock), 0, s, d, r, round, sb, lb);
+  }
+};
+template <int VEC, typename PT, bool LINEAR, typename F> static int like_launch_v(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, hipStream_t s) {
+  const int64_t per_block = (int64_t)kBlock * VEC;
+  const dim3 grid = LINEAR ? dim3((unsigned)((n_max + per_block - 1) / per_block), 1u, (unsigned)count)
+                           : dim3((unsigned)((hw_max + per_block - 1) / per_block), (unsigned)M_max, (unsigned)count);
+  f.template go<VEC, PT, LINEAR>(grid, s);
+  return (int)hipGetLastError();
+}
+template <typename PT, bool LINEAR, typename F> static int like_launch_t(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, int vec, hipStream_t s) {
+  if constexpr (F::kVec8 && sizeof(PT) == 2)
+    if (vec == 8) return like_launch_v<8, PT, LINEAR>(f, count, M_max, hw_max, n_max, s);
+  if (vec >= 4) return like_launch_v<4, PT, LINEAR>(f, count, M_max, hw_max, n_max, s);
+  return like_launch_v<1, PT, LINEAR>(f, count, M_max, hw_max, n_max, s);
+}
+template <typename F> static int like_launch(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream) {
+  if (count <= 0 || M_max <= 0 || hw_max <= 0) return 0;
+  if (linear && (n_max + kBlock - 1) / kBlock > 0x7FFFFFFFll) linear = false;        // grid.x
+  if (count > 65535 || (!linear && M_max > 65535)) return (int)hipErrorInvalidValue; // grid.z; grid.y is M_max on the tiled grid only
+  hipStream_t s = (hipStream_t)stream;
+  if (planes == FGMM_BF16)
+    return linear ? like_launch_t<__bf16, true>(f, count, M_max, hw_max, n_max, vec, s) : like_launch_t<__bf16, false>(f, count, M_max, hw_max, n_max, vec, s);
+  if (planes == FGMM_F16)
+    return linear ? like_launch_t<_Float16, true>(f, count, M_max, hw_max, n_max, vec, s) : like_launch_t<_Float16, false>(f, count, M_max, hw_max, n_max, vec, s);
+  return linear ? like_launch_t<float, true>(f, count, M_max, hw_max, n_max, vec, s) : like_launch_t<float, false>(f, count, M_max, hw_max, n_max, vec, s);
+}
+
+int launch_like(const EncDesc *d_descs, const LikeDesc *d_ldescs, int round, float scale_bound, float likelihood_bound, int count, int M_max,
+                int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream) {
+  return like_launch(LikeLaunch{d_descs, d_ldescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec, planes, stream);
+}
+int launch_like_bwd(const EncDesc *d_descs, const LikeGradDesc *d_gdescs, int round, float scale_bound, float likelihood_bound, int count, int M_max,
+                    int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream) {
+  return like_launch(LikeBwdLaunch{d_descs, d_gdescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec > 4 ? 4 : vec, planes, stream);
+}
+
+} // namespace fgmm

@@ -268,7 +268,8 @@ class _LatentItems:
     ``keep`` the input tensors whose storage the items name; for the outputs' shapes ``shape``, the ``(1, M, h, w)`` of every item
     of a stacked batch, or ``ys``, the latents of a sequence."""
 
-    DTYPES = {_lib.fgmm_rate_item: _lib.RATE_ITEM_DTYPE, _lib.fgmm_rdoq_item: _lib.RDOQ_ITEM_DTYPE, _lib.fgmm_rdcurve_item: _lib.RDCURVE_ITEM_DTYPE}
+    DTYPES = {_lib.fgmm_rate_item: _lib.RATE_ITEM_DTYPE, _lib.fgmm_rdoq_item: _lib.RDOQ_ITEM_DTYPE, _lib.fgmm_rdcurve_item: _lib.RDCURVE_ITEM_DTYPE,
+              _lib.fgmm_like_item: _lib.LIKE_ITEM_DTYPE, _lib.fgmm_like_grad_item: _lib.LIKE_GRAD_ITEM_DTYPE}
     __slots__ = ("arr", "items", "N", "keep", "dev", "shape", "ys")
 
     def __init__(self, struct, N, keep, dev=None, shape=None, ys=None):
@@ -497,12 +498,86 @@ class ParameterHead:
         return tuple(out.chunk(3, 1))
 
 
+class _LikelihoodFn(torch.autograd.Function):
+    """``GaussianMixtureConditional.forward`` / ``rate_bits`` on the GPU (include/flashgmm_amd.h section 3g): one kernel forward, one
+    backward that recomputes everything from the inputs - nothing but the inputs is saved.  ``x`` ``[B, M, h, w]`` float32 is the
+    latent (``rnd``: rounded by the kernel) or the already-noised values.  -> ``(main, v, n_nonfinite)``: ``main`` the likelihood map
+    ``[B, M, h, w]`` (``want_map``) or the items' bits as float64 ``[B]``; ``v`` the rounded latent (``rnd``; else None);
+    ``n_nonfinite`` int64 ``[B]`` on the CPU, the latents left out of the bits."""
+
+    @staticmethod
+    def forward(ctx, gmc, x, scales, means, weights, rnd: bool, want_map: bool):
+        L = gmc._latent_items(_lib.fgmm_like_item, x, scales, means, weights, False)
+        if L.N == 0:
+            raise RuntimeError("the likelihood needs a batch of at least one item")
+        N, (_, M, h, w), dev = L.N, L.shape, L.dev
+        step = np.arange(N, dtype=np.uint64) * np.uint64(M * h * w * 4)
+        like = v = None
+        if want_map:
+            like = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
+            L.items["like_out"] = np.uint64(like.data_ptr()) + step
+        if rnd:
+            v = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
+            L.items["v_out"] = np.uint64(v.data_ptr()) + step
+        rc = _lib.lib().fgmm_gmc_likelihood_batch(_lib.ctx(L.di), L.stream(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
+        _lib.check(rc, "GaussianMixtureConditional.forward")
+        nonfinite = torch.from_numpy(L.items["n_nonfinite"].astype(np.int64))
+        main = like if want_map else torch.from_numpy(L.items["bits_q"].astype(np.float64) * 2.0 ** -_lib.FGMM_LIKE_Q).to(dev)
+        ctx.save_for_backward(x, scales, means, weights)
+        ctx.gmc, ctx.rnd, ctx.want_map = gmc, rnd, want_map
+        ctx.mark_non_differentiable(nonfinite)
+        if v is not None:
+            ctx.mark_non_differentiable(v)
+        return main, v, nonfinite
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_main, g_v, g_nonfinite):
+        x, scales, means, weights = ctx.saved_tensors
+        gmc, rnd = ctx.gmc, ctx.rnd
+        need_x, need_s, need_m, need_w = ctx.needs_input_grad[1:5]
+        need_x = need_x and not rnd  # round() has gradient zero: None
+        if g_main is None or not (need_x or need_s or need_m or need_w):
+            return (None,) * 7
+        L = gmc._latent_items(_lib.fgmm_like_grad_item, x, scales, means, weights, False)
+        N, (_, M, h, w), dev = L.N, L.shape, L.dev
+        rng = np.arange(N, dtype=np.uint64)
+        keep = []
+
+        def out(field, need, planes):
+            if not need:
+                return None
+            t = torch.empty((N, planes * M, h, w), dtype=torch.float32, device=dev)
+            L.items[field] = np.uint64(t.data_ptr()) + rng * np.uint64(planes * M * h * w * 4)
+            return t
+
+        dy, ds, dm, dw = out("dy", need_x, 1), out("dscales", need_s, gmc.K), out("dmeans", need_m, gmc.K), out("dweights", need_w, gmc.K)
+        if ctx.want_map:
+            g = g_main.to(torch.float32).contiguous()
+            keep.append(g)
+            L.items["g_like"] = np.uint64(g.data_ptr()) + rng * np.uint64(M * h * w * 4)
+        else:
+            L.items["g_bits"] = g_main.detach().to("cpu", torch.float64).numpy()
+        rc = _lib.lib().fgmm_gmc_likelihood_backward_batch(_lib.ctx(L.di), L.stream(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
+        _lib.check(rc, "GaussianMixtureConditional.forward (backward)")
+        cast = lambda t, like: None if t is None else t.to(like.dtype)  # noqa: E731
+        return None, dy, cast(ds, scales), cast(dm, means), cast(dw, weights), None, None
+
+
 class GaussianMixtureConditional(nn.Module):
     """Entropy model of a K-component Gaussian mixture conditional; ``compress`` / ``decompress`` only need K = 4
-    (the reference's coder is bound for K = 4 only, rans_interface.cpp:60,982)."""
+    (the reference's coder is bound for K = 4 only, rans_interface.cpp:60,982).  Calling the module (``forward``) gives the
+    differentiable likelihoods evaluation and training use, ``rate_bits`` their fused rate (section 3g)."""
 
-    def __init__(self, K: int = 4, mode=None, clamp_scales: bool = True, checkpoint_stride: int = 0):
+    def __init__(self, K: int = 4, mode=None, clamp_scales: bool = True, checkpoint_stride: int = 0, scale_bound: float = 0.11,
+                 likelihood_bound: float = 1e-9):
         super().__init__()
+        # forward()'s two LowerBounds, the reference's defaults (entropy_models.py:113, 636); compress / decompress do not use them
+        self.scale_bound, self.likelihood_bound = float(scale_bound), float(likelihood_bound)
+        if not 0.0 < self.scale_bound < float("inf"):
+            raise ValueError("Invalid parameters")  # (entropy_models.py:656-657)
+        if not 0.0 <= self.likelihood_bound < float("inf"):
+            raise ValueError("likelihood_bound must be finite and >= 0 (0: no bound)")
         self.K = int(K)
         self.mode = mode  # None -> APPROX_MODE env var at call time
         self.clamp_scales = bool(clamp_scales)  # entropy_models.py:817 clamp(0.11, 256)
@@ -525,6 +600,48 @@ class GaussianMixtureConditional(nn.Module):
             return t.reshape(*reshape_size)[:, :, nonzero].permute(1, 0, 2, 3).reshape(self.K, -1).permute(1, 0)
 
         return rs(scales).clamp(0.11, 256), rs(means), rs(weights)
+
+    # ------------------------------------------------------------------------------------------------
+    def _check_k(self):
+        if self.K != _lib.FGMM_K:
+            raise RuntimeError(f"K = {self.K}: the kernels are bound for K = 4 only (as the reference's coder)")
+
+    def likelihood(self, values: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, round: bool = False) -> Tuple[Tensor, Tensor]:
+        """The building block of ``forward``: -> ``(v, likelihood)`` with ``v = torch.round(values)`` (``round=True``) or ``values``
+        itself, and the bounded mixture likelihood of ``v`` (include/flashgmm_amd.h section 3g).  Differentiable in ``scales``,
+        ``means``, ``weights`` and, without rounding, ``values``."""
+        self._check_k()
+        like, v, _ = _LikelihoodFn.apply(self, values, scales, means, weights, bool(round), True)
+        return (v if round else values), like
+
+    def forward(self, inputs: Tensor, scales: Tensor, means: Tensor, weights: Tensor, training: Optional[bool] = None) -> Tuple[Tensor, Tensor]:
+        """As the reference's (entropy_models.py:792-808): -> ``(outputs, likelihood)``.  ``inputs`` ``[B, M, h, w]`` float32,
+        ``scales / means / weights`` ``[B, K*M, h, w]`` float32, float16 or bfloat16, ``weights`` the mixture weights themselves (the
+        softmax over K stays torch's, so autograd differentiates it).  ``training`` (default ``self.training``): ``outputs`` is
+        ``inputs`` plus uniform noise in [-0.5, 0.5) drawn by torch; otherwise ``torch.round(inputs)``.  One fused HIP kernel
+        evaluates the likelihood, one recomputes it for the gradients (returned in the inputs' dtypes); in evaluation mode ``inputs``
+        receives no gradient, as through ``torch.round``."""
+        self._check_k()
+        if training is None:
+            training = self.training
+        if training:
+            outputs = inputs + torch.empty_like(inputs).uniform_(-0.5, 0.5)  # quantize(inputs, "noise") (entropy_models.py:163-167)
+            return self.likelihood(outputs, scales, means, weights)
+        return self.likelihood(inputs, scales, means, weights, round=True)
+
+    def rate_bits(self, inputs: Tensor, scales: Tensor, means: Tensor, weights: Tensor, training: Optional[bool] = None, *,
+                  return_nonfinite: bool = False):
+        """The fused rate of ``forward``: -> ``(outputs, bits)``, ``bits`` a float64 tensor ``[B]`` on the inputs' device - per item
+        ``sum(-log2(likelihood))``, summed on the GPU as integers in units of 2^-32 bit (the same bits on every run), differentiable
+        like the sum it stands for.  No likelihood map is written or kept.  Latents whose likelihood is NaN, infinite or <= 0 are left
+        out of the sum; ``return_nonfinite=True`` adds their count as a third value, an int64 ``[B]`` CPU tensor."""
+        self._check_k()
+        if training is None:
+            training = self.training
+        outputs = inputs + torch.empty_like(inputs).uniform_(-0.5, 0.5) if training else inputs
+        bits, v, nonfinite = _LikelihoodFn.apply(self, outputs, scales, means, weights, not training, False)
+        outputs = outputs if training else v
+        return (outputs, bits, nonfinite) if return_nonfinite else (outputs, bits)
 
     # ------------------------------------------------------------------------------------------------
     def _item(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, keep: list, flags: int = 0):

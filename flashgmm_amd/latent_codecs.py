@@ -9,7 +9,8 @@ the reference's (compressai/latent_codecs/gaussian_mixture_conditional.py:43-202
 mixture logits, the logits are soft-maxed over K on the ``[1, K, M, h, w]`` view (:183-202) — all views / stock torch ops
 on the GPU — and handed to the entropy model in place.  Both quantizers of the reference are kept ("noise": code round(y);
 "weighted_mean_ste": code round(y - sum_k pi_k mu_k) against re-centred means, :135-145, :167-179).
-``forward`` (training-time likelihoods, :99-125) is outside the entropy-coding path and not provided.
+``forward`` (:99-125) returns the differentiable likelihoods and ``y_hat`` from ``GaussianMixtureConditional.forward``, the fused
+likelihood kernel; the checkerboard, channel-group and hyper codecs below keep their ``forward`` stubs.
 
 ``CheckerboardLatentCodec`` and ``ChannelGroupsLatentCodec`` mirror the two codecs that drive the path in the
 reference's GMM models (compressai/latent_codecs/checkerboard.py:275-330, channel_groups.py:111-158;
@@ -279,9 +280,21 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
             res.append({"y_hat": y_hat if add is None else y_hat + add})
         return res
 
-    def forward(self, y: Tensor, ctx_params: Tensor):
-        raise NotImplementedError("training-time likelihoods are outside the entropy-coding path; use the reference's "
-                                  "GaussianMixtureConditionalLatentCodec.forward (pure torch)")
+    def forward(self, y: Tensor, ctx_params: Tensor) -> Dict[str, Any]:
+        """As the reference's (latent_codecs/gaussian_mixture_conditional.py:99-125): ``{"likelihoods": {"y": ...}, "y_hat": ...}``
+        from ``GaussianMixtureConditional.forward`` (the fused likelihood kernel, differentiable), for both quantizers.  The planes
+        are the parameter network's as they are, the weights torch's softmax over K (autograd differentiates both): ``param_dtype``
+        and ``fuse_softmax`` are choices of the coding path and do not apply here."""
+        scales_hat, means_hat, weights = self._chunk(self.entropy_parameters(ctx_params))
+        weights = self._reshape_gmm_weight(weights)
+        if self.quantizer == "noise":
+            y_hat, y_likelihoods = self.gaussian_mixture_conditional(y, scales_hat, means_hat, weights)
+        else:
+            weighted_sum, means_hat = self._recentre(means_hat, weights)
+            d = y - weighted_sum
+            y_hat = ((torch.round(d) - d).detach() + d) + weighted_sum  # quantize_ste (compressai/ops/ops.py:66-80)
+            y_hat, y_likelihoods = self.gaussian_mixture_conditional(y_hat, scales_hat, means_hat, weights)
+        return {"likelihoods": {"y": y_likelihoods}, "y_hat": y_hat}
 
 
 class CheckerboardLatentCodec(nn.Module):

@@ -52,6 +52,7 @@ extern "C" {
 #define FGMM_HAS_RDO_SKIP 1    /* section 3f: fgmm_gmc_rdoq_batch_s, fgmm_gmc_rdcurve_batch_s, fgmm_gmc_rdoq_budget_batch_s (added without a bump, as 3b - 3e) */
 #define FGMM_HAS_RDO_WEIGHTS 1 /* section 3e: fgmm_gmc_rdoq_batch_w, fgmm_gmc_rdcurve_batch_w, fgmm_gmc_rdoq_budget_batch_w (added without a bump, as 3b - 3d) */
 #define FGMM_HAS_BF16 1        /* section 2: FGMM_BF16 parameter planes in every call that takes planes (added without a bump, as 3b - 3f) */
+#define FGMM_HAS_LIKELIHOOD 1  /* section 3g: fgmm_gmc_likelihood_batch, fgmm_gmc_likelihood_backward_batch (added without a bump, as 3b - 3f) */
 #define FGMM_RDO_W_MAX 256.0f  /* largest factor of a weighted call's chan_w / pos_w */
 
 typedef enum {
@@ -743,6 +744,71 @@ int fgmm_gmc_rdoq_budget_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *it
                                  const int32_t *group_or_null, int n_groups, const uint64_t *budget_bytes, double lambda_max, int refine,
                                  fgmm_budget_result *results /* per group */, const fgmm_rdo_weights *w /* [count] or NULL */,
                                  fgmm_rdo_skip *skip /* [count] or NULL */);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3g. The entropy model's forward(): the DIFFERENTIABLE likelihood of a latent under its mixture, its rate, and the gradients of
+ *    either - what evaluation (bpp from the likelihoods) and training (the rate term of the loss) run on
+ *    (entropy_models.py:674-678, 720-737, 774-808).  One kernel forward, one backward; the backward recomputes everything from the
+ *    inputs, nothing is kept in between.  Per latent, in binary32, every operation one IEEE operation (no contraction, correctly
+ *    rounded '/'), K = 4; sb = scale_bound and lb = likelihood_bound are binary32 values of the caller's:
+ *      v   = round ? rintf(y) : y                          (quantize "dequantize" with means=None, or the caller's noised input)
+ *      s_k = max(sigma_k, sb) as torch.max does it: a NaN sigma stays NaN                        (LowerBound, bound_ops.py:36-37)
+ *      a_k = fabsf(v - mu_k)
+ *      xu  = (0.5f - a_k) / s_k        xl = (-0.5f - a_k) / s_k
+ *      u   = 0.5f * erfcf(c * xu)      l  = 0.5f * erfcf(c * xl)       c = (float)(-(2^-0.5))
+ *      p_k = u - l
+ *      L   = (((0 + p_0*pi_0) + p_1*pi_1) + p_2*pi_2) + p_3*pi_3      (separate multiply and add, k ascending: :777-788)
+ *      out = lb > 0 ? max(L, lb) : L                                   (NaN stays NaN)
+ *    There is no upper clamp of sigma here, unlike the coder's.
+ *    Rate: bits_q is the sum, over the latents with a finite out > 0, of llrint(-log2((double)out) * 2^32) - units of 2^-32 bit,
+ *    summed in 64-bit integers (the same bits on every run; a term is negative where out > 1, which weights that do not sum to 1
+ *    allow).  Latents whose out is NaN, infinite or <= 0 are left out of the sum and counted in n_nonfinite.
+ *    Backward: the upstream gradient g arrives w.r.t. out.  With phi(x) = expf(-0.5f*x*x) * (float)(1/sqrt(2*pi)):
+ *      gL       = ((L >= lb) || (g < 0) || lb <= 0) ? g : 0                                      (bound_ops.py:40-42)
+ *      dpi_k    = gL * p_k
+ *      da_k     = -pi_k * (phi(xu) - phi(xl)) / s_k
+ *      sg       = (v > mu_k) - (v < mu_k)                                                        (torch's abs: 0 at 0)
+ *      dmu_k    = -gL * da_k * sg            dv += gL * da_k * sg      (dv from 0, k ascending)
+ *      G_k      = gL * ( -pi_k * (phi(xu)*xu - phi(xl)*xl) / s_k )     (the gradient arriving at s_k)
+ *      dsigma_k = ((sigma_k >= sb) || (G_k < 0)) ? G_k : 0
+ *      dy       = round ? 0 : dv
+ *    With g_like NULL the upstream gradient is the scalar g_bits on the item's bit count (bits, not bits_q), and the kernel forms
+ *    g = -gb / (out * ln2f) itself, gb = (float)g_bits, ln2f = 0x1.62e430p-1f, out the bounded value; 0 for a latent that is left
+ *    out of the sum.  The rule above is then applied with that g.
+ *    Planes are float32, float16 or bfloat16 (one dtype per batch, widened exactly on load: the result of either call is that of the
+ *    same call on float32 planes holding the widened values, bit for bit); flags must be 0 - FGMM_PARAMS_LOGITS is refused, the
+ *    softmax over K stays the caller's so that autograd differentiates it.  The gradient planes are float32 whatever the planes are.
+ *    y, like_out, v_out, g_like, dy: float32 [M*hw].  Refused with FGMM_ERR_INVALID before any launch: K != 4, flags != 0, a null y,
+ *    a scale_bound that is not positive and finite, a likelihood_bound that is negative or not finite, a backward item whose outputs
+ *    are all NULL.  The caller's-stream contract is section 2's: the work is ordered after `stream`, the call returns with every
+ *    output complete.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *y;          /* device [M*hw] */
+  fgmm_params params;      /* flags must be 0 */
+  int32_t M, K;
+  int64_t hw;
+  float *like_out;         /* DEVICE float32[M*hw] out: the bounded likelihood, or NULL (the rate alone) */
+  float *v_out;            /* DEVICE float32[M*hw] out: v, or NULL */
+  int64_t bits_q;          /* out: units of 2^-32 bit */
+  int64_t n_nonfinite;     /* out: latents left out of bits_q */
+  int32_t status, pad_;    /* out */
+} fgmm_like_item;
+int fgmm_gmc_likelihood_batch(fgmm_ctx *ctx, void *stream, fgmm_like_item *items, int count, int round, float scale_bound,
+                              float likelihood_bound);
+typedef struct {
+  const float *y;          /* device [M*hw]: what the forward call was given (round == 0: the noised v) */
+  fgmm_params params;      /* flags must be 0 */
+  int32_t M, K;
+  int64_t hw;
+  const float *g_like;     /* device float32[M*hw]: the gradient w.r.t. like_out, or NULL: g_bits is used */
+  double g_bits;           /* the gradient w.r.t. the item's bit count, bits_q * 2^-32 */
+  float *dy;               /* DEVICE float32[M*hw] out, or NULL */
+  float *dscales, *dmeans, *dweights; /* DEVICE float32[K*M*hw] out, contiguous [K, M, hw]; each may be NULL */
+  int32_t status, pad_;    /* out */
+} fgmm_like_grad_item;
+int fgmm_gmc_likelihood_backward_batch(fgmm_ctx *ctx, void *stream, fgmm_like_grad_item *items, int count, int round, float scale_bound,
+                                       float likelihood_bound);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
