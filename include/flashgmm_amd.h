@@ -772,6 +772,7 @@ int fgmm_gmc_rdoq_budget_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *it
  *      G_k      = gL * ( -pi_k * (phi(xu)*xu - phi(xl)*xl) / s_k )     (the gradient arriving at s_k)
  *      dsigma_k = ((sigma_k >= sb) || (G_k < 0)) ? G_k : 0
  *      dy       = round ? 0 : dv
+ *    Both rules are selects: a NaN or +inf g or G_k that its rule does not pass gives 0 here, where the reference's `mask * g` gives NaN.
  *    With g_like NULL the upstream gradient is the scalar g_bits on the item's bit count (bits, not bits_q), and the kernel forms
  *    g = -gb / (out * ln2f) itself, gb = (float)g_bits, ln2f = 0x1.62e430p-1f, out the bounded value; 0 for a latent that is left
  *    out of the sum.  The rule above is then applied with that g.

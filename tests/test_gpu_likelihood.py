@@ -88,28 +88,36 @@ def make(seed, B, M, h, w, dtype=torch.float32):
 
 
 def grads_through_map(gmc, y, s, m, w, g, rnd=False):
-    """-> (v, likelihood, [dy, dscales, dmeans, dweights]) of one ``likelihood`` call and its backward at g (dy None with rounding)"""
-    leaves = [t.detach().clone().requires_grad_(True) for t in (y, s, m, w)]
+    """-> (v, likelihood, [dy, dscales, dmeans, dweights]) of one ``likelihood`` call and its backward at g (dy None with rounding).
+    The leaves are the tensors themselves (detached, not cloned: a clone would be a fresh, aligned and dense allocation, and the call
+    would no longer see the addresses and strides the test built)"""
+    leaves = [t.detach().requires_grad_(True) for t in (y, s, m, w)]
     v, like = gmc.likelihood(*leaves, round=rnd)
     like.backward(g)
     return v.detach(), like.detach(), [t.grad for t in leaves]
 
 
 # ---- the two entry points through ctypes ---------------------------------------------------------------------------------------------
-def _fill(it, y, s, m, w, K=4, flags=0):
-    M, hw = y.shape[0], y[0].numel()
+def _fill(it, y, s, m, w, K=4, flags=0, size=None):
+    M, hw, sk, sc = (tuple(size) + (size[0] * size[1], size[1]))[:4] if size is not None else (y.shape[0], y[0].numel(), y.numel(), y[0].numel())
     it.y = y.data_ptr()
-    it.params = _lib.fgmm_params(s.data_ptr(), m.data_ptr(), w.data_ptr(), M * hw, hw, {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[s.dtype], flags)
+    it.params = _lib.fgmm_params(s.data_ptr(), m.data_ptr(), w.data_ptr(), sk, sc, {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[s.dtype], flags)
     it.M, it.K, it.hw = M, K, hw
 
 
-def raw_forward(items, rnd, want_map=True, sb=R.SB, lb=R.LB, K=4, flags=0, fill=None):
+def raw_forward(items, rnd, want_map=True, sb=R.SB, lb=R.LB, K=4, flags=0, fill=None, outs=None, sizes=None):
     """fgmm_gmc_likelihood_batch on items (y [M, h, w], scales, means, weights [4M, h, w]), all contiguous device tensors ->
-    (rc, [(like, v, bits_q, n_nonfinite)]); `fill`: the outputs are pre-filled with it (refusals must leave them alone)"""
+    (rc, [(like, v, bits_q, n_nonfinite)]); `fill`: the outputs are pre-filled with it (refusals must leave them alone); `outs`: per
+    item the caller's own (like, v) tensors, None for a NULL output; `sizes`: per item (M, hw) or (M, hw, stride_k, stride_c) in place of the tensors' own"""
     arr = (_lib.fgmm_like_item * len(items))()
-    outs = []
-    for it, (y, s, m, w) in zip(arr, items):
-        _fill(it, y, s, m, w, K, flags)
+    given, outs = outs, []
+    for i, (it, (y, s, m, w)) in enumerate(zip(arr, items)):
+        _fill(it, y, s, m, w, K, flags, sizes[i] if sizes else None)
+        if given is not None:
+            like, v = given[i]
+            it.like_out, it.v_out = (t.data_ptr() if t is not None else None for t in (like, v))
+            outs.append((like, v))
+            continue
         like, v = (torch.empty_like(y, dtype=torch.float32) if fill is None else torch.full_like(y, fill, dtype=torch.float32) for _ in range(2))
         it.like_out, it.v_out = (like.data_ptr() if want_map else None), v.data_ptr()
         outs.append((like, v))
@@ -119,14 +127,15 @@ def raw_forward(items, rnd, want_map=True, sb=R.SB, lb=R.LB, K=4, flags=0, fill=
     return rc, [(like, v, int(it.bits_q), int(it.n_nonfinite)) for it, (like, v) in zip(arr, outs)]
 
 
-def raw_backward(items, gs, rnd, g_bits=None, sb=R.SB, lb=R.LB):
-    """fgmm_gmc_likelihood_backward_batch -> (rc, [(dy, dscales, dmeans, dweights)]); gs: the items' g_like, or None with g_bits"""
+def raw_backward(items, gs, rnd, g_bits=None, sb=R.SB, lb=R.LB, outs=None, sizes=None):
+    """fgmm_gmc_likelihood_backward_batch -> (rc, [(dy, dscales, dmeans, dweights)]); gs: the items' g_like, or None with g_bits;
+    `outs`: per item the caller's own four tensors, None for a NULL output; `sizes`: per item (M, hw) or (M, hw, stride_k, stride_c) in place of the tensors' own"""
     arr = (_lib.fgmm_like_grad_item * len(items))()
-    outs = []
+    given, outs = outs, []
     for i, (it, (y, s, m, w)) in enumerate(zip(arr, items)):
-        _fill(it, y, s, m, w)
-        o = [torch.empty_like(y)] + [torch.empty(s.shape, dtype=torch.float32, device=DEV) for _ in range(3)]
-        it.dy, it.dscales, it.dmeans, it.dweights = (t.data_ptr() for t in o)
+        _fill(it, y, s, m, w, size=sizes[i] if sizes else None)
+        o = given[i] if given is not None else [torch.empty_like(y)] + [torch.empty(s.shape, dtype=torch.float32, device=DEV) for _ in range(3)]
+        it.dy, it.dscales, it.dmeans, it.dweights = (t.data_ptr() if t is not None else None for t in o)
         if gs is not None:
             it.g_like = gs[i].data_ptr()
         else:

@@ -135,3 +135,121 @@ def test_corpus_has_what_it_claims(gold, restated):
     assert R.near_bound(gold["L64"]).mean() <= 0.01
     t = [torch.from_numpy(gold[k]) for k in ("y", "scales", "means", "weights")]
     assert R.near_bound(R.forward(*t, rnd=True, dtype=torch.float64)["L"].numpy()).mean() <= 0.01
+
+
+# ---- what tests/test_gpu_likelihood_edges.py stands on -----------------------------------------------------------------------------------
+def test_launch_form_table_and_every_instantiation():
+    """``R.launch_form`` (LikeShape restated) on the table of cases: each lands on the form it is there for, and the two GPU modules
+    together reach every (kernel, positions per lane, plane type, grid) the launcher's ladder can pick - 16 forward, 12 backward."""
+    seen = set()
+    for name, dts, items, fwd, bwd in R.CASES:
+        for dt in dts:
+            assert R.launch_form(items, dt != "f32", False) == fwd, (name, dt, "forward")
+            assert R.launch_form(items, dt != "f32", True) == bwd, (name, dt, "backward")
+        seen |= {(back, form[0], dt, form[1]) for dt in dts for back, form in ((False, fwd), (True, bwd))}
+    every = {(back, vec, dt, lin) for back in (False, True) for dt in R.ALL for lin in (True, False)
+             for vec in ((1, 4) if back or dt == "f32" else (1, 4, 8))}
+    assert len(every) == 28 and seen == every, sorted(every - seen)
+    new = {(back, form[0], dt, form[1]) for name, dts, _, fwd, bwd in R.CASES if not name.startswith("old_") for dt in dts
+           for back, form in ((False, fwd), (True, bwd))}
+    assert {(back, 1, dt, lin) for back in (False, True) for dt in R.TWO for lin in (True, False)} <= new  # the eight the old module leaves out
+    # the decisions one by one
+    it = R.dense_item
+    assert R.launch_form([it(2, 512)], True, False) == (8, True) and R.launch_form([it(2, 512)], True, True) == (4, True)  # the backward cap
+    assert R.launch_form([it(2, 512), it(2, 256)], True, False) == (4, True)      # 8 -> 4: one item does not fill 8, all fill 4
+    assert R.launch_form([it(2, 512), it(2, 264)], True, False) == (8, False)     # ... 4 would not keep the linear grid either: 8 stays
+    assert R.launch_form([it(2, 512), it(2, 260)], True, False) == (4, False)     # hw % 8 != 0
+    assert R.launch_form([it(2, 512)], False, False) == (4, True)                 # float32 planes have no 8
+    assert R.launch_form([it(2, 512, planes_off=8)], True, False) == (4, True)    # two-byte planes at 8 bytes: 4 yes, 8 no
+    assert R.launch_form([it(2, 512, planes_off=8)], False, False) == (1, True)
+    assert R.launch_form([it(2, 512, planes_off=4)], True, False) == (1, True)
+    assert R.launch_form([it(2, 512, stride_c=516)], True, False) == (4, True) and R.launch_form([it(2, 512, stride_c=514)], True, False) == (1, True)
+    assert R.launch_form([it(2, 512), it(1, 64, rest_off=(0, 0, 8))], False, True) == (1, True)  # one output of one item
+    assert R.launch_form([it(2, 512), it(1, 32)], False, False) == (4, False) and R.launch_form([it(2, 512), it(0, 0)], False, False) == (4, True)
+
+
+def test_g_from_bits_and_its_left_out_rule():
+    out = torch.tensor([0.25, 1e-9, 2.0, 0.0, -0.5, float("inf"), float("nan")], dtype=torch.float32)
+    ln2 = np.float32(R.LN2F)
+    for gb in (1.5, -0.375):
+        got = R.g_from_bits(out, gb).numpy()
+        want = [-np.float32(gb) / (np.float32(x) * ln2) for x in (0.25, 1e-9, 2.0)] + [0.0] * 4
+        assert got.dtype == np.float32 and np.array_equal(got, np.array(want, np.float32)), gb
+    assert R.counts(out).tolist() == [True, True, True, False, False, False, False]
+
+
+def test_edge_inputs_are_the_corpus_with_planted_latents():
+    y, sg, mu, pi, g, planted = R.edge_inputs()
+    plain = R.corpus()
+    assert [k for k, _, _ in planted[:len(R.KINDS)]] == list(R.KINDS) and set(R.KINDS) >= {
+        "nan_sigma", "nan_weight", "y_pinf", "y_ninf", "mu_pinf", "y_mu_pinf", "sigma_pinf", "sigma_zero"}
+    rows = [i for _, i, _ in planted]
+    assert len(set(rows)) == len(rows)
+    in_region = lambda i, r: R.REGIONS[r][0] <= i < R.REGIONS[r][1]  # noqa: E731
+    for kind in R.KINDS:
+        at = [i for k, i, _ in planted if k == kind]
+        assert sum(in_region(i, "a") for i in at) >= 4 and sum(in_region(i, "e") for i in at) >= 4 and all(in_region(i, "a") or in_region(i, "e") for i in at)
+    hole = R.planted_mask(planted)
+    assert hole.sum() == len(rows)
+    for a, b in zip((y, sg, mu, pi, g), plain):
+        m = hole if a.shape[1] == 8 else np.tile(hole, (1, 4, 1, 1))
+        assert np.array_equal(a[~m], b[~m]) and a.dtype == np.float32
+    assert np.array_equal(g, plain[4])
+    # what is planted is what the list says, and bfloat16 holds it
+    for kind, i, k in planted:
+        s_, m_, p_ = (a.reshape(4, -1)[k, i] for a in (sg, mu, pi))
+        yi = y.reshape(-1)[i]
+        ok = {"nan_sigma": np.isnan(s_), "nan_weight": np.isnan(p_), "y_pinf": yi == np.inf, "y_ninf": yi == -np.inf, "mu_pinf": m_ == np.inf and np.isfinite(yi),
+              "y_mu_pinf": yi == np.inf and m_ == np.inf, "sigma_pinf": s_ == np.inf, "sigma_zero": s_ == 0, "weight_pinf": p_ == np.inf}[kind]
+        assert ok, (kind, i, k)
+    # every class of likelihood turns up: NaN, +inf, and finite
+    out = R.forward(*(torch.from_numpy(a) for a in (y, sg, mu, pi)), rnd=False)["out"]
+    assert set(R.classes(out)[hole].tolist()) == {0, 1, 4} and int((~R.counts(out)).sum()) == int((R.classes(out) != 4).sum()) > 0
+
+
+@pytest.mark.parametrize("rnd", [False, True])
+def test_select_and_mask_multiply_differ_where_a_non_finite_gradient_is_not_passed(rnd):
+    """Section 3g selects (`rule ? G : 0`), the reference multiplies (`mask * G`, bound_ops.py:40-42): a NaN or +inf G_k that the rule
+    does not pass is 0 in the one and NaN in the other.  On the planted latents of the issue's eight kinds, in binary32, the classes of
+    the restated formulas (R.backward) and of autograd through the reference's operations (R.reference_gradients) differ at exactly
+    those elements of dscales, and nowhere in dy, dmeans and dweights.  (A +inf weight is left out here: the two group phi / s
+    differently, and inf - inf is NaN in one of them only.)"""
+    y, sg, mu, pi, g, planted = R.edge_inputs()
+    t = [torch.from_numpy(a) for a in (y, sg, mu, pi, g)]
+    b = R.backward(R.forward(*t[:4], rnd=rnd), t[4])
+    _, ref = R.reference_gradients(*t, rnd=rnd, dtype=torch.float32)
+    hole = R.planted_mask([p for p in planted if p[0] != "weight_pinf"])
+    dropped = ~b["pass_scale"].numpy() & ~np.isfinite(b["G"].numpy())
+    assert dropped[np.tile(hole, (1, 4, 1, 1))].sum() >= 8 and not dropped[~np.tile(R.planted_mask(planted), (1, 4, 1, 1))].any()
+    assert torch.isfinite(t[4]).all()  # (the other select, gL, never meets a non-finite g here: a left-out latent's g is 0, not NaN)
+    for name in R.GRADS:
+        m = hole if name == "dy" else np.tile(hole, (1, 4, 1, 1))
+        differ = (R.classes(b[name]) != R.classes(ref[name])) & m
+        assert np.array_equal(differ, dropped & m if name == "dscales" else np.zeros_like(m)), name
+        if name == "dscales":
+            assert np.all(b[name].numpy()[differ] == 0) and np.all(np.isnan(ref[name].numpy()[differ]))
+
+
+@pytest.mark.parametrize("sb,lb", R.BOUNDS)
+def test_corpus_at_other_bounds(sb, lb):
+    y, sg, mu, pi, g = R.corpus(sb=sb)
+    plain = R.corpus()
+    b = R.plane_mask("b")  # (region (b)'s latents and means are drawn around its sigmas; every other region is the corpus's)
+    assert np.array_equal(y[~R.region_mask("b")], plain[0][~R.region_mask("b")]) and np.array_equal(g, plain[4])
+    assert all(np.array_equal(a[~b], p[~b]) for a, p in zip((sg, mu, pi), plain[1:4]))
+    sb32 = np.float32(sb)
+    assert set(np.unique(sg[b]).tolist()) == {float(np.float32(0.02 * (sb / R.SB))), float(np.nextafter(sb32, np.float32(0))), float(sb32),
+                                              float(np.nextafter(sb32, np.float32(1)))}
+    t = [torch.from_numpy(a) for a in (y, sg, mu, pi)]
+    for rnd in (False, True):  # rows a float32 and a float64 evaluation may bound differently: at most 1 %
+        L = R.forward(*t, rnd=rnd, sb=sb, lb=lb, dtype=torch.float64)["L"].numpy()
+        assert (~R.near_bound(L, lb)).mean() >= 0.99, (sb, lb, rnd)
+    f = R.forward(*t, rnd=False, sb=sb, lb=lb)
+    L = f["L"].numpy()
+    if lb == 0:  # what is left out of the rate: region (c)'s exact zeros and region (g)'s negative L; and every gradient passes
+        assert np.array_equal(f["out"].numpy(), L) and np.all(L[R.region_mask("c")] == 0) and (L[R.region_mask("g")] < 0).sum() >= 8
+        assert R.backward(f, torch.from_numpy(g))["pass_like"].all()
+        # (in region (c) every p_k is exactly 0 in binary32, so no gradient there can show a pass-through decision: all are 0 * g)
+        assert not f["p"].numpy()[0][:, R.region_mask("c")[0]].any()
+    if lb == 0.5:
+        assert (L[R.region_mask("a")] < np.float32(0.5)).mean() > 0.5
