@@ -201,6 +201,9 @@ FGMM_HD static inline uint32_t tab_hdr_nonmono(uint32_t h) { return h >> 31; }
 FGMM_HD static inline unsigned long long tab_hdr8_pack(int32_t a, uint32_t cnt, uint32_t nonmono) {
   return (unsigned long long)(uint32_t)a | ((unsigned long long)((cnt & 0x7FFFFFFFu) | (nonmono << 31)) << 32);
 }
+FGMM_HD static inline int32_t tab_hdr8_a(unsigned long long h) { return (int32_t)(uint32_t)h; }
+FGMM_HD static inline uint32_t tab_hdr8_cnt(unsigned long long h) { return (uint32_t)(h >> 32) & 0x7FFFFFFFu; }
+FGMM_HD static inline uint32_t tab_hdr8_nonmono(unsigned long long h) { return (uint32_t)(h >> 63); }
 // ef_min: rows with at least this many entries are Elias-Fano coded; kTabEfMin when PCIe is the bottleneck, kTabNoEf (no
 // such row) when a call is bound by its host decoders: a uint16 row is searched faster, an Elias-Fano row is smaller
 constexpr uint32_t kTabNoEf = 0x7FFFFFFFu;

@@ -22,14 +22,18 @@
 //   cdftab_count/scan/fill  generic two-pass path, lane = latent, any half-width (8-byte headers past 16382), rows
 //                         sequential in latent order: the building-block API and items too wide for the LDS kernel.
 // Both produce the same virtual table; tests compare them with each other and with the oracle.
+//   segdec_kernel         rANS decode of checkpointed bitstreams on the GPU, no tables (below)
+// What the kernels share stands once in fgmm_decframe.h: the compact channel lookup, a latent's twelve parameters and their LDS slot,
+// the evaluation window, the row trimming, the evaluation of two consecutive edges, and the launchers' ladder.
 #include <algorithm>
 
-#include "fgmm_dev.h"
+#include "fgmm_decframe.h"
 
 namespace fgmm {
 
 // ---------------------------------------------------------------------------------------------------------
-// one latent's parameters in registers (generic path; phase 0 of tab_kernel)
+// one latent's parameters in registers (generic path): the scalar clamped evaluation, mix4_clamped over rcp_refined - another
+// function than the packed one of the frame's FGMM_DEC_EVAL_PAIR; the tests hold the two to each other
 // ---------------------------------------------------------------------------------------------------------
 template <int MODE, bool CLAMPED, typename PT> struct TabLatent {
   float mu[4], sg[4], pi[4], rs[4];
@@ -62,84 +66,6 @@ template <int MODE, bool CLAMPED, typename PT> struct TabLatent {
   }
 };
 
-// ---- evaluation window: skip the part of [-max_bs, max_bs+1] where every component is saturated -------------
-// Saturation lemmas (fgmm_math.h Sat<MODE>, proved by exhaustive scan: fgmm_selftest_saturation):
-//   all z_k <= -ZL  =>  F[v] == 0          all z_k >= +ZR  =>  F[v] == quant16((pi0+pi1)+(pi2+pi3))
-// z_k(v) = ((float)v - 0.5f - mu_k) / sg_k is non-decreasing in v for finite mu and 0 < sg < inf (every IEEE
-// operation is monotone), so it is enough to VERIFY the condition, with the kernel's own arithmetic, at one v:
-// it then holds for every v beyond it.  Any latent whose parameters fall outside the lemmas' domain is
-// evaluated over the full range instead.  Indices < j_lo are all zero, indices >= j_hi are all T_sat.
-template <int MODE>
-__device__ __forceinline__ void tab_window(const float (&mu)[4], const float (&sg)[4], const float (&pi)[4], int prune, int max_bs, int W,
-                                           int &j_lo, int &j_hi, uint32_t &T_sat) {
-  j_lo = 0;
-  j_hi = W;
-  T_sat = 0;
-  if (prune) {
-    bool ok = true;
-    float tl = INFINITY, tr = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      ok = ok && (sg[k] > 0.0f) && (sg[k] < INFINITY) && (fabsf(mu[k]) < INFINITY) && Sat<MODE>::weight_ok(pi[k]);
-      tl = fminf(tl, __builtin_fmaf(-Sat<MODE>::ZL, sg[k], mu[k]));
-      tr = fmaxf(tr, __builtin_fmaf(Sat<MODE>::ZR, sg[k], mu[k]));
-    }
-    if (ok) {
-      const float lim = (float)max_bs + 4.0f;
-      // left: largest candidate v with v - 0.5 <= tl, minus one for the rounding of tl itself
-      const int vL = (int)fminf(fmaxf(floorf(tl + 0.5f) - 1.0f, -lim), lim);
-      const int vR = (int)fminf(fmaxf(ceilf(tr + 0.5f) + 1.0f, -lim), lim);
-      bool okL = true, okR = true;
-      const float xl = (float)vL - 0.5f, xr = (float)vR - 0.5f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        okL = okL && ((xl - mu[k]) / sg[k] <= -Sat<MODE>::ZL);
-        okR = okR && ((xr - mu[k]) / sg[k] >= Sat<MODE>::ZR);
-      }
-      const int64_t lo = (int64_t)vL + max_bs + 1, hi = (int64_t)vR + max_bs;
-      if (okL) j_lo = (int)std::min<int64_t>(std::max<int64_t>(lo, 0), W); // indices < j_lo are v <= vL: all zero
-      if (okR) j_hi = (int)std::min<int64_t>(std::max<int64_t>(hi, j_lo), W); // indices >= j_hi are v >= vR: all T_sat
-      T_sat = quant16((pi[0] + pi[1]) + (pi[2] + pi[3]));
-    }
-  }
-}
-
-// trimming state of one row, fed edge by edge in index order (both paths run exactly this)
-struct TrimState {
-  int lead, run_start;
-  bool allzero, nonmono;
-  uint32_t prev;
-  __device__ __forceinline__ void init(int j_lo) {
-    lead = j_lo - 1;
-    run_start = 0;
-    allzero = true;
-    nonmono = false;
-    prev = 0;
-  }
-  __device__ __forceinline__ void step(int j, uint32_t E) {
-    lead = (allzero && E == 0) ? j : lead; // index of the last leading zero
-    allzero = allzero && E == 0;
-    run_start = (j == 0 || E != prev) ? j : run_start;
-    nonmono |= (j > 0) && (E < prev);
-    prev = E;
-  }
-  // after the evaluated window: the saturated right part as one virtual step (F[j_hi .. W-1] == T_sat)
-  __device__ __forceinline__ void finish(int j_hi, int W, uint32_t T_sat, int &a_idx, uint32_t &cnt) {
-    if (j_hi < W) {
-      if (allzero) {
-        if (T_sat == 0) lead = W - 1; else allzero = false;
-      }
-      if (j_hi == 0 || T_sat != prev) run_start = j_hi;
-      nonmono |= (j_hi > 0) && (T_sat < prev);
-    }
-    // the row starts at the first non-zero edge: F[v < a] = 0 is implied by the format, and the host takes "cf below the
-    // first entry" as the interval [0, first entry) of the symbol before it
-    a_idx = lead + 1;
-    if (a_idx > run_start) a_idx = run_start;
-    cnt = (uint32_t)(run_start - a_idx + 1);
-  }
-};
-
 constexpr int kGenericMaxWindow = 1 << 20; // generic path: longest evaluation window of one latent (a lane walks it alone)
 
 // ---------------------------------------------------------------------------------------------------------
@@ -154,9 +80,8 @@ __global__ __launch_bounds__(kBlock) void cdftab_count_kernel(const DecDesc *__r
   if ((int64_t)blockIdx.x * kBlock >= hw) return;
   const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool active = p < hw;
-  const int c = d.chan_list ? d.chan_list[cj] : cj;
   TabLatent<MODE, CLAMPED, PT> L;
-  L.load(d, c, active ? p : 0);
+  L.load(d, dec_channel(d, cj), active ? p : 0);
   const int max_bs = d.max_bs;
   const int W = 2 * max_bs + 2;
 
@@ -235,9 +160,8 @@ __global__ __launch_bounds__(kBlock) void cdftab_fill_kernel(const DecDesc *__re
   if (d.pool_used[1] || d.pool_used[3]) return; // pool too small / a window refused: the host sees the flags
   const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool active = p < hw;
-  const int c = d.chan_list ? d.chan_list[cj] : cj;
   TabLatent<MODE, CLAMPED, PT> L;
-  L.load(d, c, active ? p : 0);
+  L.load(d, dec_channel(d, cj), active ? p : 0);
 
   int a_idx = 0;
   uint32_t cnt = 0, nonmono = 0;
@@ -245,9 +169,9 @@ __global__ __launch_bounds__(kBlock) void cdftab_fill_kernel(const DecDesc *__re
     const int64_t i = (int64_t)cj * hw + p;
     if (d.hdr_form == 8) {
       const unsigned long long h = static_cast<const unsigned long long *>(d.hdr)[i];
-      a_idx = (int)((int64_t)(int32_t)(uint32_t)h + d.max_bs);
-      cnt = (uint32_t)(h >> 32) & 0x7FFFFFFFu;
-      nonmono = (uint32_t)(h >> 63);
+      a_idx = (int)((int64_t)tab_hdr8_a(h) + d.max_bs);
+      cnt = tab_hdr8_cnt(h);
+      nonmono = tab_hdr8_nonmono(h);
     } else {
       const uint32_t h = static_cast<const uint32_t *>(d.hdr)[i];
       a_idx = tab_hdr_a(h) + d.max_bs;
@@ -404,38 +328,14 @@ __global__ __launch_bounds__(kBlock, FGMM_TAB_WAVES) void tab_kernel(const DecDe
   if (tid < nl) {
     const int64_t i = i0 + tid;
     const int64_t cj = i / d.hw, p = i - cj * d.hw;
-    const int c = d.chan_list ? d.chan_list[cj] : (int)cj;
-    const int64_t base = (int64_t)c * d.stride_c + p * d.stride_p;
+    const int c = dec_channel(d, cj);
     float mu[4], sg[4], pi[4], rs[4];
-    bool tame = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sg[k] = ld1<PT>(d.scales, base + k * d.stride_k);
-      mu[k] = ld1<PT>(d.means, base + k * d.stride_k);
-      pi[k] = ld1<PT>(d.weights, base + k * d.stride_k);
-    }
-    if (d.logits) softmax4(pi);
-    if constexpr (CLAMPED) {
-      Sigma4 S4;
-      S4.set(sg[0], sg[1], sg[2], sg[3]);
-      tame = S4.tame;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sg[k] = tame ? S4.sg[k] : clamp_scale(sg[k]); // a NaN sigma stays NaN (the IEEE path is taken for this latent)
-        rs[k] = S4.rs[k];
-      }
-    } else {
-      tame = false; // un-clamped sigma: IEEE division, scalar evaluation
-#pragma unroll
-      for (int k = 0; k < 4; ++k) rs[k] = 0.0f;
-    }
+    bool tame;
+    FGMM_DEC_PARAMS(CLAMPED, PT, d, c, p, mu, sg, pi, rs, tame);
     int j_lo, j_hi;
     uint32_t T_sat;
     tab_window<MODE>(mu, sg, pi, d.prune, max_bs, W, j_lo, j_hi, T_sat);
-    S.P[4 * tid + 0] = (float4_t){mu[0], mu[1], mu[2], mu[3]};
-    S.P[4 * tid + 1] = (float4_t){sg[0], sg[1], sg[2], sg[3]};
-    S.P[4 * tid + 2] = (float4_t){pi[0], pi[1], pi[2], pi[3]};
-    S.P[4 * tid + 3] = (float4_t){rs[0], rs[1], rs[2], rs[3]};
+    FGMM_DEC_PARAMS_STORE(S.P, tid, mu, sg, pi, rs);
     S.win[tid] = (uint32_t)j_lo | ((uint32_t)(j_hi - j_lo) << 16);
     S.tsat[tid] = (uint16_t)T_sat;
     S.flags[tid] = tame ? 1 : 0;
@@ -469,31 +369,9 @@ __global__ __launch_bounds__(kBlock, FGMM_TAB_WAVES) void tab_kernel(const DecDe
         l_beg = l_end;
         l_end = S.offP[l + 1];
       }
-      const float4_t m4 = S.P[4 * l + 0], s4 = S.P[4 * l + 1], p4 = S.P[4 * l + 2], r4 = S.P[4 * l + 3];
-      const float mu[4] = {m4[0], m4[1], m4[2], m4[3]}, pi[4] = {p4[0], p4[1], p4[2], p4[3]};
-      const int j = (int)(S.win[l] & 0xFFFFu) + 2 * (int)(t - l_beg);
-      const float x0 = (float)(j - max_bs) - 0.5f, x1 = (float)(j + 1 - max_bs) - 0.5f;
-      float c0 = 0.0f, c1 = 0.0f;
-      bool fast = false;
-      if constexpr (CLAMPED) {
-        Sigma4 S4;
-        S4.tame = true;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          S4.sg[k] = s4[k];
-          S4.rs[k] = r4[k];
-        }
-        bool ok = (S.flags[l] & 1) != 0;
-        const f2 cc = mix4_clamped2<MODE>((f2){x0, x1}, mu, S4, pi, ok);
-        c0 = cc.x;
-        c1 = cc.y;
-        fast = ok;
-      }
-      if (__builtin_expect(!fast, 0)) { // un-clamped sigma, NaN sigma, far-off or non-finite mean: IEEE evaluation
-        c0 = mix4_slow<MODE>(x0, mu[0], mu[1], mu[2], mu[3], s4[0], s4[1], s4[2], s4[3], pi[0], pi[1], pi[2], pi[3]);
-        c1 = mix4_slow<MODE>(x1, mu[0], mu[1], mu[2], mu[3], s4[0], s4[1], s4[2], s4[3], pi[0], pi[1], pi[2], pi[3]);
-      }
-      S.E32[t] = quant16(c0) | (quant16(c1) << 16);
+      uint32_t q0, q1;
+      FGMM_DEC_EVAL_PAIR(MODE, CLAMPED, S.P, l, (int)(S.win[l] & 0xFFFFu) + 2 * (int)(t - l_beg), (S.flags[l] & 1) != 0, max_bs, q0, q1);
+      S.E32[t] = q0 | (q1 << 16);
     }
   }
   __syncthreads();
@@ -843,32 +721,9 @@ __global__ __launch_bounds__(192) FGMM_SEG_OCC void segdec_kernel(const SegDesc 
         l_beg = l_end;
         l_end = l + 1 < nk ? offP[l + 1] : NP;
       }
-      const float4_t m4 = P[4 * l + 0], s4 = P[4 * l + 1], p4 = P[4 * l + 2], r4 = P[4 * l + 3];
-      const float mu_[4] = {m4[0], m4[1], m4[2], m4[3]}, pi_[4] = {p4[0], p4[1], p4[2], p4[3]};
-      const uint32_t wl = winL[l], tl_ = tsfL[l];
-      const int j = (int)(wl & 0xFFFFu) + 2 * (int)(t - l_beg);
-      const float x0 = (float)(j - max_bs) - 0.5f, x1 = (float)(j + 1 - max_bs) - 0.5f;
-      float c0 = 0.0f, c1 = 0.0f;
-      bool fast = false;
-      if constexpr (CLAMPED) {
-        Sigma4 S4;
-        S4.tame = true;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          S4.sg[k] = s4[k];
-          S4.rs[k] = r4[k];
-        }
-        bool ok = (tl_ >> 16) != 0;
-        const f2 cc = mix4_clamped2<MODE>((f2){x0, x1}, mu_, S4, pi_, ok);
-        c0 = cc.x;
-        c1 = cc.y;
-        fast = ok;
-      }
-      if (__builtin_expect(!fast, 0)) { // un-clamped sigma, NaN sigma, far-off or non-finite mean: IEEE evaluation
-        c0 = mix4_slow<MODE>(x0, mu_[0], mu_[1], mu_[2], mu_[3], s4[0], s4[1], s4[2], s4[3], pi_[0], pi_[1], pi_[2], pi_[3]);
-        c1 = mix4_slow<MODE>(x1, mu_[0], mu_[1], mu_[2], mu_[3], s4[0], s4[1], s4[2], s4[3], pi_[0], pi_[1], pi_[2], pi_[3]);
-      }
-      const uint32_t q0 = quant16(c0), q1 = quant16(c1), pk = q0 | (q1 << 16);
+      uint32_t wl, tl_, q0, q1; // (the window and the tail | tame words, read together after the slot)
+      FGMM_DEC_EVAL_PAIR(MODE, CLAMPED, P, l, (wl = winL[l], tl_ = tsfL[l], (int)(wl & 0xFFFFu) + 2 * (int)(t - l_beg)), (tl_ >> 16) != 0, max_bs, q0, q1);
+      const uint32_t pk = q0 | (q1 << 16);
       E32[t] = pk;
       // ... and which rows DECREASE somewhere.  A count of the edges <= cf is the symbol's interval only in a monotone row; the
       // reference's bisection may answer differently when the row decreases anywhere (rans_interface.cpp:833-854), so such a
@@ -897,38 +752,14 @@ __global__ __launch_bounds__(192) FGMM_SEG_OCC void segdec_kernel(const SegDesc 
     // ---- A. lane = latent base + lane: parameters -> LDS, evaluation window; how many latents fit the edge budget
     const int64_t i = std::min(base + lane, hi - 1);
     const int64_t cj = i / d.hw, p = i - cj * d.hw;
-    const int c = d.chan_list ? ldg<int32_t>(d.chan_list + cj) : (int)cj;
-    const int64_t pbase = (int64_t)c * d.stride_c + p * d.stride_p;
+    const int c = dec_channel<true>(d, cj);
     float mu[4], sgm[4], pi[4], rs[4];
-    bool tame = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sgm[k] = ld1<PT>(d.scales, pbase + k * d.stride_k);
-      mu[k] = ld1<PT>(d.means, pbase + k * d.stride_k);
-      pi[k] = ld1<PT>(d.weights, pbase + k * d.stride_k);
-    }
-    if (d.logits) softmax4(pi);
-    if constexpr (CLAMPED) {
-      Sigma4 S4;
-      S4.set(sgm[0], sgm[1], sgm[2], sgm[3]);
-      tame = S4.tame;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sgm[k] = tame ? S4.sg[k] : clamp_scale(sgm[k]);
-        rs[k] = S4.rs[k];
-      }
-    } else {
-      tame = false;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) rs[k] = 0.0f;
-    }
+    bool tame;
+    FGMM_DEC_PARAMS(CLAMPED, PT, d, c, p, mu, sgm, pi, rs, tame);
     int j_lo, j_hi;
     uint32_t T_sat;
     tab_window<MODE>(mu, sgm, pi, 1, max_bs, W, j_lo, j_hi, T_sat);
-    P[4 * lane + 0] = (float4_t){mu[0], mu[1], mu[2], mu[3]};
-    P[4 * lane + 1] = (float4_t){sgm[0], sgm[1], sgm[2], sgm[3]};
-    P[4 * lane + 2] = (float4_t){pi[0], pi[1], pi[2], pi[3]};
-    P[4 * lane + 3] = (float4_t){rs[0], rs[1], rs[2], rs[3]};
+    FGMM_DEC_PARAMS_STORE(P, lane, mu, sgm, pi, rs);
     const uint32_t win = (uint32_t)j_lo | ((uint32_t)(j_hi - j_lo) << 16);
     const int nk_max = (int)std::min<int64_t>(64, hi - base);
     const uint32_t pairs = (int)lane < nk_max ? (uint32_t)(j_hi - j_lo + 1) >> 1 : 0u;
@@ -1233,19 +1064,6 @@ extern "C" int fgmm_debug_segtimes(unsigned long long *out) { return (int)hipMem
 // ---------------------------------------------------------------------------------------------------------
 static inline int launch_err() { return (int)hipGetLastError(); }
 
-// Two or three waves per segment: a second producer shortens a segment by a fifth (its widest rows by more) and costs the chip
-// a tenth of its throughput (the producers' handshake, fewer segments per CU).  A launch that fills the chip less than twice over
-// ends when its slowest segment does - three waves; a larger one is bound by the work - two.
-template <bool CLAMPED, typename PT>
-static int launch_segdec_c(const SegDesc *d, const SegRef *segs, int64_t n_segs, int mode, hipStream_t s) {
-  const dim3 grid((unsigned)n_segs), block(n_segs <= 4096 ? 192 : 128); // one segment per workgroup
-  switch (mode) {
-  case MODE_AS: hipLaunchKernelGGL((segdec_kernel<MODE_AS, CLAMPED, PT>), grid, block, 0, s, d, segs, n_segs); break;
-  case MODE_LOGISTIC: hipLaunchKernelGGL((segdec_kernel<MODE_LOGISTIC, CLAMPED, PT>), grid, block, 0, s, d, segs, n_segs); break;
-  default: hipLaunchKernelGGL((segdec_kernel<MODE_POLYA, CLAMPED, PT>), grid, block, 0, s, d, segs, n_segs); break;
-  }
-  return launch_err();
-}
 // channels without a coded symbol are zero in y_hat (entropy_models.py:903-908): one launch for all items of a call
 __global__ __launch_bounds__(kBlock) void segzero_kernel(const SegDesc *__restrict__ descs) {
   const SegDesc &d = descs[blockIdx.y];
@@ -1263,47 +1081,32 @@ int launch_segzero(const SegDesc *d_descs, int count, int64_t max_dead, void *st
   }
   return 0;
 }
+// Two or three waves per segment: a second producer shortens a segment by a fifth (its widest rows by more) and costs the chip
+// a tenth of its throughput (the producers' handshake, fewer segments per CU).  A launch that fills the chip less than twice over
+// ends when its slowest segment does - three waves; a larger one is bound by the work - two.
 int launch_segdec(const SegDesc *d_descs, const SegRef *d_segs, int64_t n_segs, int mode, bool clamped, bool f16, void *stream) {
   if (n_segs <= 0) return 0;
   if (n_segs > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  const bool bf16 = (mode & kPlanesBf16) != 0; // (fgmm_internal.h: the plane type of a launch)
-  mode &= kModeMask;
-  if (bf16) return clamped ? launch_segdec_c<true, __bf16>(d_descs, d_segs, n_segs, mode, s) : launch_segdec_c<false, __bf16>(d_descs, d_segs, n_segs, mode, s);
-  if (f16) return clamped ? launch_segdec_c<true, _Float16>(d_descs, d_segs, n_segs, mode, s) : launch_segdec_c<false, _Float16>(d_descs, d_segs, n_segs, mode, s);
-  return clamped ? launch_segdec_c<true, float>(d_descs, d_segs, n_segs, mode, s) : launch_segdec_c<false, float>(d_descs, d_segs, n_segs, mode, s);
-}
-
-template <bool CLAMPED, typename PT>
-static int launch_cdftab_c(const DecDesc *d_descs, int count, int n_ch_max, int64_t hw_max, int mode, int pass, hipStream_t s) {
-  dim3 grid((unsigned)((hw_max + kBlock - 1) / kBlock), (unsigned)n_ch_max, (unsigned)count);
-#define FGMM_TAB_LAUNCH(M)                                                                                          \
-  if (pass & 1) {                                                                                                   \
-    hipLaunchKernelGGL((cdftab_count_kernel<M, CLAMPED, PT>), grid, dim3(kBlock), 0, s, d_descs);                   \
-    hipLaunchKernelGGL(cdftab_scan_kernel, dim3((unsigned)count), dim3(kBlock), 0, s, d_descs);                     \
-  }                                                                                                                 \
-  if (pass & 2) hipLaunchKernelGGL((cdftab_fill_kernel<M, CLAMPED, PT>), grid, dim3(kBlock), 0, s, d_descs);
-  switch (mode) {
-  case MODE_AS: FGMM_TAB_LAUNCH(MODE_AS) break;
-  case MODE_LOGISTIC: FGMM_TAB_LAUNCH(MODE_LOGISTIC) break;
-  default: FGMM_TAB_LAUNCH(MODE_POLYA) break;
-  }
-#undef FGMM_TAB_LAUNCH
-  return launch_err();
+  const dim3 grid((unsigned)n_segs), block(n_segs <= 4096 ? 192 : 128); // one segment per workgroup
+  return dec_launch([&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL((segdec_kernel<R::MODE, R::CLAMPED, typename R::PT>), grid, block, 0, (hipStream_t)stream, d_descs, d_segs, n_segs);
+  }, mode, clamped, f16);
 }
 
 static int launch_cdftab_pass(const DecDesc *d_descs, int count, int n_ch_max, int64_t hw_max, int mode, bool clamped, bool f16,
                               int pass, void *stream) {
   if (count <= 0 || n_ch_max <= 0 || hw_max <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const bool bf16 = (mode & kPlanesBf16) != 0;
-  mode &= kModeMask;
-  if (bf16) return clamped ? launch_cdftab_c<true, __bf16>(d_descs, count, n_ch_max, hw_max, mode, pass, s)
-                           : launch_cdftab_c<false, __bf16>(d_descs, count, n_ch_max, hw_max, mode, pass, s);
-  if (f16) return clamped ? launch_cdftab_c<true, _Float16>(d_descs, count, n_ch_max, hw_max, mode, pass, s)
-                          : launch_cdftab_c<false, _Float16>(d_descs, count, n_ch_max, hw_max, mode, pass, s);
-  return clamped ? launch_cdftab_c<true, float>(d_descs, count, n_ch_max, hw_max, mode, pass, s)
-                 : launch_cdftab_c<false, float>(d_descs, count, n_ch_max, hw_max, mode, pass, s);
+  const dim3 grid((unsigned)((hw_max + kBlock - 1) / kBlock), (unsigned)n_ch_max, (unsigned)count);
+  return dec_launch([&](auto r) {
+    using R = decltype(r);
+    if (pass & 1) {
+      hipLaunchKernelGGL((cdftab_count_kernel<R::MODE, R::CLAMPED, typename R::PT>), grid, dim3(kBlock), 0, s, d_descs);
+      hipLaunchKernelGGL(cdftab_scan_kernel, dim3((unsigned)count), dim3(kBlock), 0, s, d_descs);
+    }
+    if (pass & 2) hipLaunchKernelGGL((cdftab_fill_kernel<R::MODE, R::CLAMPED, typename R::PT>), grid, dim3(kBlock), 0, s, d_descs);
+  }, mode, clamped, f16);
 }
 int launch_cdftab_count(const DecDesc *d_descs, int count, int n_ch_max, int64_t hw_max, int mode, bool clamped, bool f16,
                         void *stream) {
@@ -1318,30 +1121,16 @@ int launch_cdftab(const DecDesc *d_descs, int count, int n_ch_max, int64_t hw_ma
   return launch_cdftab_pass(d_descs, count, n_ch_max, hw_max, mode, clamped, f16, 3, stream);
 }
 
-template <bool CLAMPED, typename PT>
-static int launch_tab_c(const DecDesc *d, int count, int blocks_max, int tl_max, int cap_e, int mode, hipStream_t s) {
-  const dim3 grid((unsigned)blocks_max, (unsigned)count);
-  const size_t lds = tab_smem_bytes(tl_max, cap_e);
-  switch (mode) {
-  case MODE_AS: hipLaunchKernelGGL((tab_kernel<MODE_AS, CLAMPED, PT>), grid, dim3(kBlock), lds, s, d, tl_max, cap_e); break;
-  case MODE_LOGISTIC: hipLaunchKernelGGL((tab_kernel<MODE_LOGISTIC, CLAMPED, PT>), grid, dim3(kBlock), lds, s, d, tl_max, cap_e); break;
-  default: hipLaunchKernelGGL((tab_kernel<MODE_POLYA, CLAMPED, PT>), grid, dim3(kBlock), lds, s, d, tl_max, cap_e); break;
-  }
-  return launch_err();
-}
 int launch_tab(const DecDesc *d_descs, int count, int blocks_max, int tl_max, int cap_e, int mode, bool clamped, bool f16,
                void *stream) {
   if (count <= 0 || blocks_max <= 0) return 0;
   if (tl_max < 1 || tl_max > kTabMaxTl || cap_e < 32 || cap_e > 32768 || (cap_e & 31) || tab_smem_bytes(tl_max, cap_e) > 160 * 1024) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  const bool bf16 = (mode & kPlanesBf16) != 0;
-  mode &= kModeMask;
-  if (bf16) return clamped ? launch_tab_c<true, __bf16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s)
-                           : launch_tab_c<false, __bf16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s);
-  if (f16) return clamped ? launch_tab_c<true, _Float16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s)
-                          : launch_tab_c<false, _Float16>(d_descs, count, blocks_max, tl_max, cap_e, mode, s);
-  return clamped ? launch_tab_c<true, float>(d_descs, count, blocks_max, tl_max, cap_e, mode, s)
-                 : launch_tab_c<false, float>(d_descs, count, blocks_max, tl_max, cap_e, mode, s);
+  const dim3 grid((unsigned)blocks_max, (unsigned)count);
+  const size_t lds = tab_smem_bytes(tl_max, cap_e);
+  return dec_launch([&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL((tab_kernel<R::MODE, R::CLAMPED, typename R::PT>), grid, dim3(kBlock), lds, (hipStream_t)stream, d_descs, tl_max, cap_e);
+  }, mode, clamped, f16);
 }
 
 } // namespace fgmm

@@ -499,7 +499,7 @@ def _c_logistic_rcp_guard(rng, n):
 
 def _c_sat_edges(rng, n):
     """(v - 0.5 - mu_k) / sigma_k within a few ulp of -ZL and +ZR of each mode at a v inside the range, for one component and for
-    all four, sigma 0.11 and 256 among them (fgmm_tab.hip tab_window: the rounding of vL / vR and their - 1.0f / + 1.0f)"""
+    all four, sigma 0.11 and 256 among them (fgmm_decframe.h tab_window: the rounding of vL / vR and their - 1.0f / + 1.0f)"""
     v = _near_symbols(rng, n)
     sg, mu, pi = _ordinary_at(rng, v)
     zs = np.array([c for zl, zr in SAT_Z.values() for c in (-zl, zr)], F32)
@@ -516,7 +516,7 @@ def _c_sat_edges(rng, n):
 
 def _c_window_weights(rng, n):
     """weights for which tab_window must refuse the pruning lemma (fgmm_math.h Sat<MODE>::weight_ok) or T_sat = quant16(sum pi)
-    is unusual (fgmm_tab.hip tab_window): 1 + ulp, -0.0, tiny negative, a sum above one whose quant16 wraps past 65535, a sum
+    is unusual (fgmm_decframe.h tab_window): 1 + ulp, -0.0, tiny negative, a sum above one whose quant16 wraps past 65535, a sum
     below one, all zero, one NaN, +inf, and a weight of tens to millions"""
     v = _near_symbols(rng, n)
     sg, mu, pi = _ordinary_at(rng, v)

@@ -29,7 +29,7 @@ FREE_BS = 4000       # a half-width at which no window of these corpora is clipp
 
 # ---- the planner, restated ------------------------------------------------------------------------------------------------------
 def window_of(mode, mu, sg, pi, max_bs, clamp=True):
-    """fgmm_tab.hip tab_window with prune = 1 in float32 numpy: rows ``mu, sg, pi [n, 4]`` -> ``(j_lo, j_hi)`` int64 [n], the indices
+    """fgmm_decframe.h tab_window with prune = 1 in float32 numpy: rows ``mu, sg, pi [n, 4]`` -> ``(j_lo, j_hi)`` int64 [n], the indices
     (v = j - max_bs) between the saturated tails.  sigma goes through ``edge_corpus.clamp_sigma`` first when ``clamp``.
 
     The kernel computes ``tl`` and ``tr`` with one fmaf each, numpy with a rounded product and a rounded sum: where the two differ

@@ -236,7 +236,7 @@ def filler():
 @pytest.mark.parametrize("mode", MODES)
 def test_two_wave_launch_decodes_the_edge_items_as_the_three_wave_launch_does(oracle, ctx_options, mode):
     """a call of more than 4096 segments takes the launch shape with ONE producer (blockDim == 128: no seam, no second handshake; the
-    threshold is launch_segdec_c's `n_segs <= 4096 ? 192 : 128` in fgmm_tab.hip - if it moves, FILLER_SHAPE has to move with it):
+    threshold is launch_segdec's `n_segs <= 4096 ? 192 : 128` in fgmm_tab.hip - if it moves, FILLER_SHAPE has to move with it):
     the edge items next to a filler of 4128 segments are settled there too, equal to their three-wave results and the oracle's; the
     filler equals what the table path makes of the same bytes without their notes"""
     ctx_options(gpu_decode=1)
