@@ -241,7 +241,7 @@ _native = None  # flashgmm_amd._native (csrc/fgmm_pybind.cpp), False when it can
 
 def native():
     """The compiled boundary (``flashgmm_amd._native``, pybind11 over the same C ABI: items built in C++, the GIL released across
-    the call) or None - then the ctypes path of this module does the same work.  Not used with FGMM_LIB (an A/B build of the
+    the call) or None - then ``boundary()`` gives the stand-in over this module's ctypes functions.  Not used with FGMM_LIB (an A/B build of the
     library: the module is linked against the in-tree one) or FGMM_NATIVE=0."""
     global _native
     if _native is None:
@@ -256,6 +256,17 @@ def native():
             except ImportError:
                 pass
     return _native or None
+
+
+def boundary():
+    """What ``GaussianMixtureConditional`` makes its batched calls through: ``native()`` or, where that is None, its stand-in
+    ``flashgmm_amd._boundary`` - the same callables over this module's ctypes functions.  Looked up at every call."""
+    nat = native()
+    if nat is not None:
+        return nat
+    from . import _boundary
+
+    return _boundary
 
 
 def ctx_addr(device: int = -1) -> int:
@@ -311,42 +322,6 @@ def take_bytes(ptr: C.c_void_p, length: int) -> bytes:
     data = C.string_at(ptr, length)
     lib().fgmm_free(ptr)
     return data
-
-
-_py = C.pythonapi
-_py.PyBytes_FromStringAndSize.restype = C.py_object
-_py.PyBytes_FromStringAndSize.argtypes = [C.c_void_p, C.c_ssize_t]
-_py.PyBytes_AsString.restype = C.c_void_p
-_py.PyBytes_AsString.argtypes = [C.py_object]
-
-
-def take_bytes_many(device: int, ptrs, lens, cls=None) -> list:
-    """library-allocated buffers -> ``bytes`` objects (or instances of the bytes subclass ``cls``), the buffers released.
-    The copies are done by the context's host workers, straight into the objects' own storage: ``bytes`` objects allocated
-    uninitialised (``PyBytes_FromStringAndSize(NULL, n)``: the C API's way to fill a bytes object before anyone else sees it),
-    subclass instances as ``bytes.__new__(cls, n)`` (zero pages until written) - one copy, not one per layer of glue."""
-    n = len(ptrs)
-    if n == 0:
-        return []
-    if cls is None:
-        if sum(lens) < (1 << 18):
-            return [take_bytes(p, l) for p, l in zip(ptrs, lens)]
-        objs = [_py.PyBytes_FromStringAndSize(None, int(l)) for l in lens]
-    else:
-        objs = [bytes.__new__(cls, int(l)) for l in lens]
-    dst = (C.c_void_p * n)(*[_py.PyBytes_AsString(o) if l else None for o, l in zip(objs, lens)])
-    src = (C.c_void_p * n)(*ptrs)
-    ln = (C.c_size_t * n)(*lens)
-    check(lib().fgmm_ctx_take_buffers(ctx(device), dst, src, ln, n), "fgmm_ctx_take_buffers")
-    return objs
-
-
-def take_buffers_into(device: int, dst_addrs, src_ptrs, lens) -> None:
-    """library-allocated buffers copied to the given addresses and released (one native call)"""
-    n = len(src_ptrs)
-    if n:
-        check(lib().fgmm_ctx_take_buffers(ctx(device), (C.c_void_p * n)(*dst_addrs), (C.c_void_p * n)(*src_ptrs), (C.c_size_t * n)(*lens), n),
-              "fgmm_ctx_take_buffers")
 
 
 def mode_id(mode) -> int:

@@ -5,8 +5,10 @@
 // numpy record arrays), the GIL is released across the native call - the reference holds it (no gil_scoped_release anywhere in its
 // module) - and the bitstreams come back as `bytes` objects allocated at their final size and filled by the encoders' flush
 // (fgmm_sink: no buffer of the library's, no copy after the call).  Nothing here computes: every function is argument plumbing around
-// fgmm_gmc_compress_batch / fgmm_gmc_decompress_batch / fgmm_gmc_compress_head_batch / fgmm_gmc_rdoq_batch / fgmm_gmc_rdcurve_batch / fgmm_gmc_rdoq_budget_batch and their _w forms.  flashgmm_amd/_lib.py (ctypes) binds the same
-// ABI and stays the fallback.
+// fgmm_gmc_compress_batch / fgmm_gmc_decompress_batch / fgmm_gmc_compress_head_batch / fgmm_gmc_rdoq_batch / fgmm_gmc_rdcurve_batch / fgmm_gmc_rdoq_budget_batch and their _w forms.  This file - the comments of the
+// functions and the m.def list at its end - is the documentation of the interface: flashgmm_amd/_boundary.py copies it, callable for
+// callable, over the ctypes binding of the same ABI (flashgmm_amd/_lib.py) and stands in where this module cannot be used
+// (_lib.boundary()); flashgmm_amd/entropy_models.py calls whichever of the two is there.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -61,6 +63,18 @@ void fill_items(std::vector<fgmm_item> &it, const Stacked &s) {
     f.params.stride_k = s.stride_k, f.params.stride_c = s.stride_c;
     f.params.dtype = s.dtype, f.params.flags = s.flags;
     f.M = s.M, f.K = FGMM_K, f.hw = s.hw;
+  }
+}
+
+// ... and what a stacked compress call adds: the latents, where y_q and the zero bitmaps go (dense: rows of M), the checkpoint stride
+void fill_compress(std::vector<fgmm_item> &it, uintptr_t y, uintptr_t yq, uintptr_t zero_bitmap, int ckpt_stride) {
+  for (size_t i = 0; i < it.size(); ++i) {
+    fgmm_item &f = it[i];
+    const size_t n = (size_t)f.M * (size_t)f.hw;
+    f.y = ptr<const float>(y) + i * n;
+    f.yq_out = ptr<float>(yq) + i * n;
+    f.zero_bitmap = ptr<int64_t>(zero_bitmap) + i * (size_t)f.M;
+    f.ckpt_stride = ckpt_stride;
   }
 }
 
@@ -148,6 +162,46 @@ py::tuple finish_compress(fgmm_ctx *ctx, std::vector<fgmm_item> &it, int ckpt_st
   return py::make_tuple(strings, abs_max);
 }
 
+// THE tail of a compress call: the sink, `call(sink)` - the library's entry point - with the GIL released, the status, the results
+template <typename Call> py::tuple run_compress(fgmm_ctx *ctx, std::vector<fgmm_item> &it, int ckpt_stride, py::object bytes_cls, const char *what, Call call) {
+  py::list strings(it.size());
+  PySink to(strings, bytes_cls);
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = call(&to.sink);
+  }
+  if (rc) raise(what, rc);
+  return finish_compress(ctx, it, ckpt_stride, strings);
+}
+
+// The bitstreams of a decompress call, BORROWED: read in place, with a reference to every object - and to the `_ck` record of those
+// that carry out-of-band notes - held here for the duration of the native call, so that the pointers do not depend on the caller's
+// container staying as it is.  ckpt_cls: None, or the bytes subclass whose instances carry notes in `_ck` (CheckpointedBytes):
+// (., ., count, address, stride).
+struct Borrowed {
+  std::vector<py::object> keep;
+  PyTypeObject *cls;
+  explicit Borrowed(const py::object &ckpt_cls) : cls(ckpt_cls.is_none() ? nullptr : reinterpret_cast<PyTypeObject *>(ckpt_cls.ptr())) {}
+  void read(fgmm_item &f, py::object b, size_t i) {
+    if (!PyBytes_Check(b.ptr())) throw std::runtime_error("decompress: bitstream " + std::to_string(i) + " is not a bytes object");
+    f.bytes = reinterpret_cast<uint8_t *>(PyBytes_AS_STRING(b.ptr()));
+    f.bytes_len = (size_t)PyBytes_GET_SIZE(b.ptr());
+    if (cls && PyObject_TypeCheck(b.ptr(), cls)) {
+      static PyObject *ck_name = PyUnicode_InternFromString("_ck");
+      PyObject *rec = PyObject_GetAttr(b.ptr(), ck_name);
+      if (!rec) throw py::error_already_set();
+      py::tuple t = py::cast<py::tuple>(py::reinterpret_steal<py::object>(rec));
+      if (t.size() != 5) throw std::runtime_error("decompress: bitstream " + std::to_string(i) + ": malformed checkpoint record");
+      f.n_ckpt = py::cast<int64_t>(t[2]);
+      f.ckpt = ptr<fgmm_ckpt>(py::cast<uintptr_t>(t[3]));
+      f.ckpt_stride = py::cast<int32_t>(t[4]);
+      keep.push_back(std::move(t));
+    }
+    keep.push_back(std::move(b));
+  }
+};
+
 // GaussianMixtureConditional.compress for N stacked items (entropy_models.py:833-867, batched):
 //   -> (list of N bytes, list of N abs_max); y_q and the zero bitmaps are written through yq / zero_bitmap (device float32 [N, M, hw] /
 //   HOST int64 [N, M]).  ckpt_stride > 0: bytes_cls must be CheckpointedBytes, every bitstream object carries its notes (adopt_ckpts)
@@ -157,22 +211,10 @@ py::tuple compress_stacked(uintptr_t ctx_, uintptr_t stream, uintptr_t y, uintpt
   fgmm_ctx *ctx = ptr<fgmm_ctx>(ctx_);
   std::vector<fgmm_item> it((size_t)N);
   fill_items(it, Stacked{scales, means, weights, item_stride, stride_k, stride_c, dtype, flags, N, M, hw});
-  for (int i = 0; i < N; ++i) {
-    fgmm_item &f = it[(size_t)i];
-    f.y = ptr<const float>(y) + (size_t)i * (size_t)M * (size_t)hw;
-    f.yq_out = ptr<float>(yq) + (size_t)i * (size_t)M * (size_t)hw;
-    f.zero_bitmap = ptr<int64_t>(zero_bitmap) + (size_t)i * (size_t)M;
-    f.ckpt_stride = ckpt_stride;
-  }
-  py::list strings((size_t)N);
-  PySink to(strings, bytes_cls);
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    rc = fgmm_gmc_compress_batch_to(ctx, ptr<void>(stream), it.data(), N, mode, clamp_scales, &to.sink);
-  }
-  if (rc) raise("GaussianMixtureConditional.compress", rc);
-  return finish_compress(ctx, it, ckpt_stride, strings);
+  fill_compress(it, y, yq, zero_bitmap, ckpt_stride);
+  return run_compress(ctx, it, ckpt_stride, bytes_cls, "GaussianMixtureConditional.compress", [&](fgmm_sink *to) {
+    return fgmm_gmc_compress_batch_to(ctx, ptr<void>(stream), it.data(), N, mode, clamp_scales, to);
+  });
 }
 
 // ... with the parameter head fused (fgmm_gmc_compress_head_batch): x device float32 [N, c_in, hw]
@@ -182,29 +224,16 @@ py::tuple compress_head_stacked(uintptr_t ctx_, uintptr_t stream, uintptr_t y, u
   std::vector<fgmm_item> it((size_t)N);
   std::vector<const float *> xs((size_t)N);
   fill_items(it, Stacked{0, 0, 0, 0, 0, 0, FGMM_F32, FGMM_PARAMS_LOGITS, N, M, hw});
-  for (int i = 0; i < N; ++i) {
-    fgmm_item &f = it[(size_t)i];
-    f.y = ptr<const float>(y) + (size_t)i * (size_t)M * (size_t)hw;
-    f.yq_out = ptr<float>(yq) + (size_t)i * (size_t)M * (size_t)hw;
-    f.zero_bitmap = ptr<int64_t>(zero_bitmap) + (size_t)i * (size_t)M;
-    f.ckpt_stride = ckpt_stride;
-    xs[(size_t)i] = ptr<const float>(x) + (size_t)i * (size_t)c_in * (size_t)hw;
-  }
-  py::list strings((size_t)N);
-  PySink to(strings, bytes_cls);
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    rc = fgmm_gmc_compress_head_batch_to(ctx, ptr<void>(stream), it.data(), xs.data(), N, ptr<const fgmm_head>(head), mode, clamp_scales, &to.sink);
-  }
-  if (rc) raise("GaussianMixtureConditional.compress_head_batch", rc);
-  return finish_compress(ctx, it, ckpt_stride, strings);
+  fill_compress(it, y, yq, zero_bitmap, ckpt_stride);
+  for (int i = 0; i < N; ++i) xs[(size_t)i] = ptr<const float>(x) + (size_t)i * (size_t)c_in * (size_t)hw;
+  return run_compress(ctx, it, ckpt_stride, bytes_cls, "GaussianMixtureConditional.compress_head_batch", [&](fgmm_sink *to) {
+    return fgmm_gmc_compress_head_batch_to(ctx, ptr<void>(stream), it.data(), xs.data(), N, ptr<const fgmm_head>(head), mode, clamp_scales, to);
+  });
 }
 
 // GaussianMixtureConditional.decompress for N stacked items (entropy_models.py:872-910, batched): the bitstreams are read in place
-// (borrowed pointers into the bytes objects, which the caller's list keeps alive across the call); y_hat is written through `y_hat`
-// (device float32 [N, M, hw]).  zero_bitmap: HOST int64, row i at zero_bitmap + i * zb_row_stride elements.  ckpt_cls: None, or the
-// bytes subclass whose instances carry out-of-band notes in `_ck` (CheckpointedBytes): (., ., count, address, stride).
+// (Borrowed); y_hat is written through `y_hat` (device float32 [N, M, hw]).  zero_bitmap: HOST int64, row i at zero_bitmap +
+// i * zb_row_stride elements.  ckpt_cls: as Borrowed takes it.
 void decompress_stacked(uintptr_t ctx_, uintptr_t stream, py::sequence strings, py::sequence abs_maxes, uintptr_t zero_bitmap, int64_t zb_row_stride,
                         uintptr_t scales, uintptr_t means, uintptr_t weights, int N, int M, int64_t hw, int64_t item_stride, int64_t stride_k, int64_t stride_c,
                         int dtype, int flags, int mode, int clamp_scales, uintptr_t y_hat, py::object ckpt_cls) {
@@ -212,26 +241,13 @@ void decompress_stacked(uintptr_t ctx_, uintptr_t stream, py::sequence strings, 
   if ((int)py::len(strings) != N || (int)py::len(abs_maxes) != N) throw std::runtime_error("decompress: " + std::to_string(N) + " items in the parameter tensors, " + std::to_string(py::len(strings)) + " bitstreams");
   std::vector<fgmm_item> it((size_t)N);
   fill_items(it, Stacked{scales, means, weights, item_stride, stride_k, stride_c, dtype, flags, N, M, hw});
-  PyTypeObject *cls = ckpt_cls.is_none() ? nullptr : reinterpret_cast<PyTypeObject *>(ckpt_cls.ptr());
-  static PyObject *ck_name = PyUnicode_InternFromString("_ck");
+  Borrowed streams(ckpt_cls);
   for (int i = 0; i < N; ++i) {
     fgmm_item &f = it[(size_t)i];
-    py::object b = strings[(size_t)i];
-    if (!PyBytes_Check(b.ptr())) throw std::runtime_error("decompress: bitstream " + std::to_string(i) + " is not a bytes object");
-    f.bytes = reinterpret_cast<uint8_t *>(PyBytes_AS_STRING(b.ptr()));
-    f.bytes_len = (size_t)PyBytes_GET_SIZE(b.ptr());
+    streams.read(f, strings[(size_t)i], (size_t)i);
     f.abs_max = py::cast<int32_t>(abs_maxes[(size_t)i]);
     f.zero_bitmap = ptr<int64_t>(zero_bitmap) + (size_t)i * (size_t)zb_row_stride;
     f.yq_out = ptr<float>(y_hat) + (size_t)i * (size_t)M * (size_t)hw;
-    if (cls && PyObject_TypeCheck(b.ptr(), cls)) {
-      PyObject *rec = PyObject_GetAttr(b.ptr(), ck_name);
-      if (!rec) throw py::error_already_set();
-      py::tuple t = py::cast<py::tuple>(py::reinterpret_steal<py::object>(rec));
-      if (t.size() != 5) throw std::runtime_error("decompress: bitstream " + std::to_string(i) + ": malformed checkpoint record");
-      f.n_ckpt = py::cast<int64_t>(t[2]);
-      f.ckpt = ptr<fgmm_ckpt>(py::cast<uintptr_t>(t[3]));
-      f.ckpt_stride = py::cast<int32_t>(t[4]);
-    }
   }
   int rc;
   {
@@ -322,70 +338,50 @@ py::list rdoq_budget_items(uintptr_t ctx_, uintptr_t stream, uintptr_t items, in
 }
 
 // ---- items of any mix of shapes (the sequence form of compress_batch / decompress_batch: ELIC's ten groups per image) --------------
-// one item = a tuple of integers; compress: (y, scales, means, weights, M, hw, stride_k, stride_c, yq, zero_bitmap),
-// decompress: (scales, means, weights, M, hw, stride_k, stride_c, y_hat, zero_bitmap): device addresses, HOST zero bitmap
-void item_common(fgmm_item &f, const py::tuple &t, size_t at, int dtype, int flags) {
+// one item = a tuple of integers; compress: (y, scales, means, weights, M, hw, stride_k, stride_c, yq, zero_bitmap, dtype),
+// decompress: (scales, means, weights, M, hw, stride_k, stride_c, y_hat, zero_bitmap, dtype): device addresses, HOST zero bitmap, the
+// fgmm_dtype of the item's own planes (a batch that mixes them is the library's to refuse)
+void item_common(fgmm_item &f, const py::tuple &t, size_t at, int flags) {
   std::memset(&f, 0, sizeof f);
   f.params.scales = ptr<const void>(py::cast<uintptr_t>(t[at]));
   f.params.means = ptr<const void>(py::cast<uintptr_t>(t[at + 1]));
   f.params.weights = ptr<const void>(py::cast<uintptr_t>(t[at + 2]));
   f.M = py::cast<int32_t>(t[at + 3]), f.K = FGMM_K, f.hw = py::cast<int64_t>(t[at + 4]);
   f.params.stride_k = py::cast<int64_t>(t[at + 5]), f.params.stride_c = py::cast<int64_t>(t[at + 6]);
-  f.params.dtype = dtype, f.params.flags = flags;
+  f.params.dtype = py::cast<int32_t>(t[at + 9]), f.params.flags = flags;
   f.yq_out = ptr<float>(py::cast<uintptr_t>(t[at + 7]));
   f.zero_bitmap = ptr<int64_t>(py::cast<uintptr_t>(t[at + 8]));
 }
 
-py::tuple compress_items(uintptr_t ctx_, uintptr_t stream, py::sequence items, int dtype, int flags, int mode, int clamp_scales, int ckpt_stride,
-                         py::object bytes_cls) {
+py::tuple compress_items(uintptr_t ctx_, uintptr_t stream, py::sequence items, int flags, int mode, int clamp_scales, int ckpt_stride, py::object bytes_cls) {
   fgmm_ctx *ctx = ptr<fgmm_ctx>(ctx_);
   const size_t n = py::len(items);
   std::vector<fgmm_item> it(n);
   for (size_t i = 0; i < n; ++i) {
     py::tuple t = py::cast<py::tuple>(items[i]);
-    if (t.size() != 10) throw std::runtime_error("compress_items: an item is (y, scales, means, weights, M, hw, stride_k, stride_c, yq, zero_bitmap)");
-    item_common(it[i], t, 1, dtype, flags);
+    if (t.size() != 11) throw std::runtime_error("compress_items: an item is (y, scales, means, weights, M, hw, stride_k, stride_c, yq, zero_bitmap, dtype)");
+    item_common(it[i], t, 1, flags);
     it[i].y = ptr<const float>(py::cast<uintptr_t>(t[0]));
     it[i].ckpt_stride = ckpt_stride;
   }
-  py::list strings(n);
-  PySink to(strings, bytes_cls);
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    rc = fgmm_gmc_compress_batch_to(ctx, ptr<void>(stream), it.data(), (int)n, mode, clamp_scales, &to.sink);
-  }
-  if (rc) raise("GaussianMixtureConditional.compress", rc);
-  return finish_compress(ctx, it, ckpt_stride, strings);
+  return run_compress(ctx, it, ckpt_stride, bytes_cls, "GaussianMixtureConditional.compress", [&](fgmm_sink *to) {
+    return fgmm_gmc_compress_batch_to(ctx, ptr<void>(stream), it.data(), (int)n, mode, clamp_scales, to);
+  });
 }
 
-void decompress_items(uintptr_t ctx_, uintptr_t stream, py::sequence strings, py::sequence abs_maxes, py::sequence items, int dtype, int flags, int mode,
-                      int clamp_scales, py::object ckpt_cls) {
+void decompress_items(uintptr_t ctx_, uintptr_t stream, py::sequence strings, py::sequence abs_maxes, py::sequence items, int flags, int mode, int clamp_scales,
+                      py::object ckpt_cls) {
   fgmm_ctx *ctx = ptr<fgmm_ctx>(ctx_);
   const size_t n = py::len(items);
   if (py::len(strings) != n || py::len(abs_maxes) != n) throw std::runtime_error("decompress: " + std::to_string(n) + " items, " + std::to_string(py::len(strings)) + " bitstreams");
   std::vector<fgmm_item> it(n);
-  PyTypeObject *cls = ckpt_cls.is_none() ? nullptr : reinterpret_cast<PyTypeObject *>(ckpt_cls.ptr());
-  static PyObject *ck_name = PyUnicode_InternFromString("_ck");
+  Borrowed streams(ckpt_cls);
   for (size_t i = 0; i < n; ++i) {
     py::tuple t = py::cast<py::tuple>(items[i]);
-    if (t.size() != 9) throw std::runtime_error("decompress_items: an item is (scales, means, weights, M, hw, stride_k, stride_c, y_hat, zero_bitmap)");
-    fgmm_item &f = it[i];
-    item_common(f, t, 0, dtype, flags);
-    py::object b = strings[i];
-    if (!PyBytes_Check(b.ptr())) throw std::runtime_error("decompress: bitstream " + std::to_string(i) + " is not a bytes object");
-    f.bytes = reinterpret_cast<uint8_t *>(PyBytes_AS_STRING(b.ptr()));
-    f.bytes_len = (size_t)PyBytes_GET_SIZE(b.ptr());
-    f.abs_max = py::cast<int32_t>(abs_maxes[i]);
-    if (cls && PyObject_TypeCheck(b.ptr(), cls)) {
-      PyObject *rec = PyObject_GetAttr(b.ptr(), ck_name);
-      if (!rec) throw py::error_already_set();
-      py::tuple c = py::cast<py::tuple>(py::reinterpret_steal<py::object>(rec));
-      if (c.size() != 5) throw std::runtime_error("decompress: bitstream " + std::to_string(i) + ": malformed checkpoint record");
-      f.n_ckpt = py::cast<int64_t>(c[2]);
-      f.ckpt = ptr<fgmm_ckpt>(py::cast<uintptr_t>(c[3]));
-      f.ckpt_stride = py::cast<int32_t>(c[4]);
-    }
+    if (t.size() != 10) throw std::runtime_error("decompress_items: an item is (scales, means, weights, M, hw, stride_k, stride_c, y_hat, zero_bitmap, dtype)");
+    item_common(it[i], t, 0, flags);
+    streams.read(it[i], strings[i], i);
+    it[i].abs_max = py::cast<int32_t>(abs_maxes[i]);
   }
   int rc;
   {
@@ -406,13 +402,13 @@ PYBIND11_MODULE(_native, m) {
   m.def("compress_head_stacked", &compress_head_stacked, "ctx"_a, "stream"_a, "y"_a, "x"_a, "head"_a, "N"_a, "M"_a, "c_in"_a, "hw"_a, "mode"_a, "clamp_scales"_a,
         "ckpt_stride"_a, "yq"_a, "zero_bitmap"_a, "bytes_cls"_a = py::none());
   m.def("rdoq_stacked", &rdoq_stacked, "ctx"_a, "stream"_a, "y"_a, "scales"_a, "means"_a, "weights"_a, "N"_a, "M"_a, "hw"_a, "item_stride"_a, "stride_k"_a,
-        "stride_c"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "lambda"_a, "y_rdo"_a, "zero_bitmap"_a, "chan_after"_a = 0);
+        "stride_c"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "lam"_a, "y_rdo"_a, "zero_bitmap"_a, "chan_after"_a = 0);
   m.def("rdcurve_items", &rdcurve_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "lambdas"_a, "weights"_a = 0, "skip"_a = 0);
-  m.def("rdoq_items", &rdoq_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "lambda"_a, "weights"_a = 0, "skip"_a = 0);
+  m.def("rdoq_items", &rdoq_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "lam"_a, "weights"_a = 0, "skip"_a = 0);
   m.def("rdoq_budget_items", &rdoq_budget_items, "ctx"_a, "stream"_a, "items"_a, "count"_a, "mode"_a, "clamp_scales"_a, "groups"_a, "budgets"_a, "lambda_max"_a,
         "refine"_a, "weights"_a = 0, "skip"_a = 0);
-  m.def("compress_items", &compress_items, "ctx"_a, "stream"_a, "items"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "ckpt_stride"_a, "bytes_cls"_a = py::none());
-  m.def("decompress_items", &decompress_items, "ctx"_a, "stream"_a, "strings"_a, "abs_maxes"_a, "items"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a,
+  m.def("compress_items", &compress_items, "ctx"_a, "stream"_a, "items"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "ckpt_stride"_a, "bytes_cls"_a = py::none());
+  m.def("decompress_items", &decompress_items, "ctx"_a, "stream"_a, "strings"_a, "abs_maxes"_a, "items"_a, "flags"_a, "mode"_a, "clamp_scales"_a,
         "ckpt_cls"_a = py::none());
   m.def("decompress_stacked", &decompress_stacked, "ctx"_a, "stream"_a, "strings"_a, "abs_maxes"_a, "zero_bitmap"_a, "zb_row_stride"_a, "scales"_a, "means"_a,
         "weights"_a, "N"_a, "M"_a, "hw"_a, "item_stride"_a, "stride_k"_a, "stride_c"_a, "dtype"_a, "flags"_a, "mode"_a, "clamp_scales"_a, "y_hat"_a,

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from . import _lib
+from . import _boundary, _lib
 
 __all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve"]
 
@@ -39,9 +39,10 @@ class CheckpointedBytes(bytes):
     sequential decode, never a wrong symbol).  Anything that only knows ``bytes`` — the reference's decoder, a file — sees
     the plain stream; ``flashgmm_amd.container`` stores the checkpoints next to it."""
 
-    # _ck = (notes, first, count, address, stride): `notes` is an ndarray of CKPT_DTYPE (first = 0), or the ``bytes`` blob a compiled
-    # compress call filled with the notes of ALL its bitstreams - this one's are records first .. first + count of it, the view is made
-    # when someone asks for ``.ckpt``; address: of the first note (what a decode call hands the library)
+    # _ck = (notes, first, count, address, stride): `notes` is an ndarray of CKPT_DTYPE (first = 0), or the ``bytes`` blob a compress
+    # call filled with the notes of ALL its bitstreams (adopt_ckpts of either binding sets the record on an instance whose bytes are
+    # already in place) - this one's are records first .. first + count of it, the view is made when someone asks for ``.ckpt``;
+    # address: of the first note (what a decode call reads off the record and hands the library)
     def __new__(cls, data: bytes, ckpt: np.ndarray, stride: int):
         self = super().__new__(cls, data)
         if not (isinstance(ckpt, np.ndarray) and ckpt.dtype == CKPT_DTYPE and ckpt.flags.c_contiguous):
@@ -65,13 +66,6 @@ class CheckpointedBytes(bytes):
     @property
     def _ckpt_addr(self) -> int:
         return self._ck[3]
-
-    @classmethod
-    def _adopt(cls, blank: "CheckpointedBytes", ckpt: np.ndarray, stride: int, addr: int = -1) -> "CheckpointedBytes":
-        """attach the notes to an instance whose bytes are already in place (``_lib.take_bytes_many(..., cls=CheckpointedBytes)``:
-        the library's workers copied the bitstream into it - no second copy through ``__new__``)"""
-        blank._ck = (ckpt, 0, len(ckpt), addr if addr >= 0 else (ckpt.ctypes.data if len(ckpt) else 0), int(stride))
-        return blank
 
     def __reduce__(self):
         return (CheckpointedBytes, (bytes(self), self.ckpt, self.ckpt_stride))
@@ -262,6 +256,11 @@ class RdCurve:
         return f"RdCurve(lambdas={self.lambdas}, nbytes={self.nbytes}, n_changed={self.n_changed})"
 
 
+def _ctx_stream(dev: torch.device) -> Tuple[int, int]:
+    """-> (address of the device's context, the caller's current stream): what every native call begins with"""
+    return _lib.ctx_addr(dev.index if dev.index is not None else -1), torch.cuda.current_stream(dev).cuda_stream
+
+
 class _LatentItems:
     """The items of one call that prices latents, built by ``GaussianMixtureConditional._latent_items`` from either input form:
     ``arr`` the ``struct[N]`` ctypes passes, ``items`` the same memory as a numpy record array (filled and read column by column),
@@ -277,12 +276,8 @@ class _LatentItems:
         self.items, self.N = np.frombuffer(self.arr, self.DTYPES[struct]), N
         self.keep, self.dev, self.shape, self.ys = keep, dev, shape, ys
 
-    @property
-    def di(self) -> int:
-        return self.dev.index if self.dev.index is not None else -1
-
-    def stream(self) -> int:
-        return torch.cuda.current_stream(self.dev).cuda_stream
+    def call(self) -> Tuple[int, int]:
+        return _ctx_stream(self.dev)
 
     def output(self, field: str, dtype, per_latent: bool = False):
         """allocates the output ``field`` of every item - per latent ``[1, M, h, w]`` on the device, else per channel ``[M]`` on the
@@ -382,24 +377,9 @@ def _rdo_skip_cols(arr, flags):
     return [(int(a.n_skipped), int(a.n_eligible), None if t is None else t != 0, int(a.ddist_q)) for a, t in zip(arr, flags)]
 
 
-def _take_ckpts_many(device: int, ptrs, counts):
-    """the library-allocated fgmm_ckpt arrays of a batch -> [(ndarray view, its address)], the arrays released: ONE array for the
-    batch and one native call instead of a copy and a free per bitstream"""
-    total = int(sum(counts))
-    if total == 0:
-        return [(_NO_CKPT, 0)] * len(ptrs)
-    pool = np.empty(total, CKPT_DTYPE)
-    base = pool.ctypes.data
-    out, dst, src, lens, at = [], [], [], [], 0
-    for p, n in zip(ptrs, counts):
-        if p and n > 0:
-            out.append((pool[at:at + n], base + 16 * at))
-            dst.append(base + 16 * at); src.append(p); lens.append(16 * n)
-            at += n
-        else:
-            out.append((_NO_CKPT, 0))
-    _lib.take_buffers_into(device, dst, src, lens)
-    return out
+def _addr(arr) -> int:
+    """the address of an optional ctypes array as the boundary takes it (None: 0)"""
+    return C.addressof(arr) if arr is not None else 0
 
 
 def _plane_view(t: Tensor, K: int) -> Tuple[Tensor, int, int]:
@@ -519,7 +499,7 @@ class _LikelihoodFn(torch.autograd.Function):
         if rnd:
             v = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
             L.items["v_out"] = np.uint64(v.data_ptr()) + step
-        rc = _lib.lib().fgmm_gmc_likelihood_batch(_lib.ctx(L.di), L.stream(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
+        rc = _lib.lib().fgmm_gmc_likelihood_batch(*L.call(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
         _lib.check(rc, "GaussianMixtureConditional.forward")
         nonfinite = torch.from_numpy(L.items["n_nonfinite"].astype(np.int64))
         main = like if want_map else torch.from_numpy(L.items["bits_q"].astype(np.float64) * 2.0 ** -_lib.FGMM_LIKE_Q).to(dev)
@@ -558,7 +538,7 @@ class _LikelihoodFn(torch.autograd.Function):
             L.items["g_like"] = np.uint64(g.data_ptr()) + rng * np.uint64(M * h * w * 4)
         else:
             L.items["g_bits"] = g_main.detach().to("cpu", torch.float64).numpy()
-        rc = _lib.lib().fgmm_gmc_likelihood_backward_batch(_lib.ctx(L.di), L.stream(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
+        rc = _lib.lib().fgmm_gmc_likelihood_backward_batch(*L.call(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
         _lib.check(rc, "GaussianMixtureConditional.forward (backward)")
         cast = lambda t, like: None if t is None else t.to(like.dtype)  # noqa: E731
         return None, dy, cast(ds, scales), cast(dm, means), cast(dw, weights), None, None
@@ -644,19 +624,9 @@ class GaussianMixtureConditional(nn.Module):
         return (outputs, bits, nonfinite) if return_nonfinite else (outputs, bits)
 
     # ------------------------------------------------------------------------------------------------
-    def _item(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, keep: list, flags: int = 0):
-        """one item of the sequence form as an ``fgmm_item`` (the ctypes binding) -> (item, M, hw, device)"""
-        yp, sp, mp, wp, M, hw, sk, sc, dev, dt = self._item_ints(y, scales, means, weights, keep)
-        it = _lib.fgmm_item()
-        it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _abi_dtype(dt), flags)
-        it.M, it.K, it.hw = M, self.K, hw
-        if y is not None:
-            it.y = yp
-        return it, M, hw, dev
-
     def _item_ints(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, keep: list):
-        """one item of the sequence form for the compiled boundary -> (pointers and strides as integers, M, hw, device, dtype); the
-        tensors whose storage the pointers name are appended to ``keep``"""
+        """THE validation of one item of the sequence form -> (pointers and strides as integers, M, hw, device, fgmm_dtype of the planes);
+        the tensors whose storage the pointers name are appended to ``keep``"""
         if not scales.is_cuda:
             raise RuntimeError(
                 "flashgmm_amd runs the GMM entropy-coding path on the GPU only: tensors must be on a HIP device "
@@ -686,7 +656,7 @@ class GaussianMixtureConditional(nn.Module):
             yc = y.contiguous()
             yp = yc.data_ptr()
             keep.append(yc)
-        return yp, s.data_ptr(), m.data_ptr(), w.data_ptr(), M, hw, sk, sc, s.device, s.dtype
+        return yp, s.data_ptr(), m.data_ptr(), w.data_ptr(), M, hw, sk, sc, s.device, _abi_dtype(s.dtype)
 
     def _stacked_view(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor):
         """THE validation of stacked inputs -> (y, scales, means, weights, N, M, h, w, item stride, stride_c)"""
@@ -712,118 +682,42 @@ class GaussianMixtureConditional(nn.Module):
             y = y.contiguous()
         return y, scales, means, weights, N, M, h, w, st[0], (st[1] if KM > 1 else h * w)
 
-    def _stacked_fill(self, items, y, scales, means, weights, N, M, h, w, s_item, sc, flags: int = 0):
-        """the input fields of N items (a numpy record array over ``fgmm_item[]`` or an item type that begins alike) from what
-        ``_stacked_view`` returns: one set of strides for the whole batch; the item pointers are the batch-dimension offsets"""
-        rng = np.arange(N, dtype=np.uint64)
-        step = rng * np.uint64(s_item * scales.element_size())
-        items["scales"] = np.uint64(scales.data_ptr()) + step
-        items["means"] = np.uint64(means.data_ptr()) + step
-        items["weights"] = np.uint64(weights.data_ptr()) + step
-        items["stride_k"], items["stride_c"] = M * sc, sc
-        items["dtype"] = _abi_dtype(scales.dtype)
-        items["flags"] = flags
-        items["M"], items["K"], items["hw"] = M, self.K, h * w
-        if y is not None:
-            items["y"] = np.uint64(y.data_ptr()) + rng * np.uint64(M * h * w * 4)
-
-    def _stacked_items(self, y: Optional[Tensor], scales: Tensor, means: Tensor, weights: Tensor, flags: int = 0):
-        """``fgmm_item[N]`` (as a numpy record array) for N items given as ONE tensor each: y ``[N, M, h, w]``, parameters
-        ``[N, K*M, h, w]``: ``_stacked_view``, then ``_stacked_fill``"""
-        view = self._stacked_view(y, scales, means, weights)
-        y, scales, means, weights, N, M, h, w = view[:8]
-        items = np.zeros(N, _lib.ITEM_DTYPE)
-        self._stacked_fill(items, *view, flags)
-        return items, [scales, means, weights] + ([y] if y is not None else []), N, M, h, w, scales.device
-
     def _compress_stacked(self, y: Tensor, scales: Tensor, means: Tensor, weights: Tensor, flags: int = 0):
-        nat = _lib.native()
-        if nat is not None and scales.dim() == 4 and scales.shape[0] > 0:
-            y, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(y, scales, means, weights)
-            dev = scales.device
-            di = dev.index if dev.index is not None else -1
-            yq = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
-            zb = torch.empty((N, M), dtype=torch.int64)
-            strings, amax = nat.compress_stacked(
-                _lib.ctx_addr(di), torch.cuda.current_stream(dev).cuda_stream, y.data_ptr(), scales.data_ptr(), means.data_ptr(), weights.data_ptr(),
-                N, M, h * w, s_item, M * sc, sc, _abi_dtype(scales.dtype), flags, self._mode(),
-                int(self.clamp_scales), self.checkpoint_stride, yq.data_ptr(), zb.data_ptr(), CheckpointedBytes if self.checkpoint_stride else None)
-            return CompressedBatch(strings, amax, zb, yq)
-        items, keep, N, M, h, w, dev = self._stacked_items(y, scales, means, weights, flags)
-        if N == 0:
-            return CompressedBatch([], [], torch.empty((0, M), dtype=torch.int64), torch.empty((0, 1, M, h, w), dtype=torch.float32, device=dev))
+        y, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(y, scales, means, weights)
+        dev = scales.device
         yq = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
         zb = torch.empty((N, M), dtype=torch.int64)
-        items["yq_out"] = np.uint64(yq.data_ptr()) + np.arange(N, dtype=np.uint64) * np.uint64(M * h * w * 4)
-        items["zero_bitmap"] = np.uint64(zb.data_ptr()) + np.arange(N, dtype=np.uint64) * np.uint64(M * 8)
-        items["ckpt_stride"] = self.checkpoint_stride
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.lib().fgmm_gmc_compress_batch(_lib.ctx(dev.index if dev.index is not None else -1), stream,
-                                                C.cast(items.ctypes.data, C.POINTER(_lib.fgmm_item)), N, self._mode(),
-            int(self.clamp_scales))
-        _lib.check(rc, "GaussianMixtureConditional.compress")
-        ptrs, lens, amax = items["bytes"].tolist(), items["bytes_len"].tolist(), items["abs_max"].tolist()
-        datas = _lib.take_bytes_many(dev.index if dev.index is not None else -1, ptrs, lens, CheckpointedBytes if self.checkpoint_stride else None)
-        cks = _take_ckpts_many(dev.index if dev.index is not None else -1, items["ckpt"].tolist(), items["n_ckpt"].tolist()) if self.checkpoint_stride else None
-        if cks is not None:
-            datas = [CheckpointedBytes._adopt(d, ck[0], self.checkpoint_stride, ck[1]) for d, ck in zip(datas, cks)]
-        return CompressedBatch(datas, amax, zb, yq)
+        if N == 0:
+            return CompressedBatch([], [], zb, yq)
+        strings, amax = _lib.boundary().compress_stacked(
+            *_ctx_stream(dev), y.data_ptr(), scales.data_ptr(), means.data_ptr(), weights.data_ptr(),
+            N, M, h * w, s_item, M * sc, sc, _abi_dtype(scales.dtype), flags, self._mode(),
+            int(self.clamp_scales), self.checkpoint_stride, yq.data_ptr(), zb.data_ptr(), CheckpointedBytes if self.checkpoint_stride else None)
+        return CompressedBatch(strings, amax, zb, yq)
 
     def _decompress_stacked(self, strings: Sequence[bytes], abs_maxes: Sequence[int], zero_bitmaps, scales: Tensor,
                             means: Tensor, weights: Tensor, flags: int = 0, stacked_output: bool = False):
-        nat = _lib.native()
-        if nat is not None and scales.dim() == 4 and scales.shape[0] > 0 and isinstance(zero_bitmaps, Tensor):
-            _, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(None, scales, means, weights)
-            zb = zero_bitmaps
-            if len(strings) != N or len(abs_maxes) != N or len(zb) != N:
-                raise RuntimeError(f"{N} items in the parameter tensors, {len(strings)} bitstreams")
+        _, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(None, scales, means, weights)
+        if len(strings) != N or len(abs_maxes) != N or len(zero_bitmaps) != N:
+            raise RuntimeError(f"{N} items in the parameter tensors, {len(strings)} bitstreams")
+        dev = scales.device
+        y_hat = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
+        if N > 0:
+            zb = zero_bitmaps if isinstance(zero_bitmaps, Tensor) else torch.stack([z.to("cpu", torch.int64) for z in zero_bitmaps])
             if zb.device.type != "cpu" or zb.dtype != torch.int64:
                 zb = zb.to("cpu", torch.int64)
             if tuple(zb.shape) != (N, M):
                 raise RuntimeError(f"zero bitmaps have shape {tuple(zb.shape)}, expected ({N}, {M})")
             if M > 1 and zb.stride(1) != 1:
                 zb = zb.contiguous()
-            dev = scales.device
             if not isinstance(strings, list) or not all(type(s_) is bytes or isinstance(s_, bytes) for s_ in strings):
                 strings = [s_ if isinstance(s_, bytes) else bytes(s_) for s_ in strings]
-            y_hat = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
-            nat.decompress_stacked(_lib.ctx_addr(dev.index if dev.index is not None else -1), torch.cuda.current_stream(dev).cuda_stream, strings, abs_maxes,
-                                   zb.data_ptr(), zb.stride(0) if N > 1 else M, scales.data_ptr(), means.data_ptr(), weights.data_ptr(), N, M, h * w, s_item,
-                                   M * sc, sc, _abi_dtype(scales.dtype), flags, self._mode(), int(self.clamp_scales),
-                                   y_hat.data_ptr(), CheckpointedBytes)  # (the out-of-band notes of the bitstreams that carry them: read off the objects)
-            return y_hat if stacked_output else list(y_hat.unbind(0))
-        items, keep, N, M, h, w, dev = self._stacked_items(None, scales, means, weights, flags)
-        if len(strings) != N or len(abs_maxes) != N or len(zero_bitmaps) != N:
-            raise RuntimeError(f"{N} items in the parameter tensors, {len(strings)} bitstreams")
-        if N == 0:
-            return torch.empty((0, 1, M, h, w), dtype=torch.float32, device=dev) if stacked_output else []
-        if isinstance(zero_bitmaps, Tensor):
-            zb = zero_bitmaps
-        else:
-            zb = torch.stack([z.to("cpu", torch.int64) for z in zero_bitmaps])
-        if zb.device.type != "cpu" or zb.dtype != torch.int64:
-            zb = zb.to("cpu", torch.int64)
-        if tuple(zb.shape) != (N, M):
-            raise RuntimeError(f"zero bitmaps have shape {tuple(zb.shape)}, expected ({N}, {M})")
-        if M > 1 and zb.stride(1) != 1:
-            zb = zb.contiguous()
-        zb_row = zb.stride(0) if N > 1 else M  # rows may be a strided view of a larger batch (a codec stage: every second one)
-        data = [s_ if isinstance(s_, bytes) else bytes(s_) for s_ in strings]
-        bufs = (C.c_char_p * N)(*data)  # borrowed pointers into the bytes objects (kept alive by `data`)
-        y_hat = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
-        items["bytes"] = np.frombuffer(bufs, dtype=np.uint64)
-        items["bytes_len"] = [len(d) for d in data]
-        if any(isinstance(d, CheckpointedBytes) for d in data):  # out-of-band checkpoints of the streams that carry them
-            cks = [(d._ck[3], d._ck[2], d._ck[4]) if isinstance(d, CheckpointedBytes) else (0, 0, 0) for d in data]  # (address, count, stride)
-            items["ckpt"], items["n_ckpt"], items["ckpt_stride"] = (np.array(c, dtype=np.uint64) for c in zip(*cks))
-        items["abs_max"] = np.asarray(abs_maxes, dtype=np.int64)
-        items["yq_out"] = np.uint64(y_hat.data_ptr()) + np.arange(N, dtype=np.uint64) * np.uint64(M * h * w * 4)
-        items["zero_bitmap"] = np.uint64(zb.data_ptr()) + np.arange(N, dtype=np.uint64) * np.uint64(zb_row * 8)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.lib().fgmm_gmc_decompress_batch(_lib.ctx(dev.index if dev.index is not None else -1), stream,
-                                                  C.cast(items.ctypes.data, C.POINTER(_lib.fgmm_item)), N, self._mode(),
-            int(self.clamp_scales))
-        _lib.check(rc, "GaussianMixtureConditional.decompress")
+            # (zb's rows may be a strided view of a larger batch - a codec stage: every second one; the out-of-band notes of the
+            # bitstreams that carry them are read off the objects)
+            _lib.boundary().decompress_stacked(*_ctx_stream(dev), strings, abs_maxes,
+                                               zb.data_ptr(), zb.stride(0) if N > 1 else M, scales.data_ptr(), means.data_ptr(), weights.data_ptr(), N, M, h * w, s_item,
+                                               M * sc, sc, _abi_dtype(scales.dtype), flags, self._mode(), int(self.clamp_scales),
+                                               y_hat.data_ptr(), CheckpointedBytes)
         return y_hat if stacked_output else list(y_hat.unbind(0))
 
     def compress_batch(self, ys, scales, means, weights, *, weights_are_logits: bool = False):
@@ -844,66 +738,27 @@ class GaussianMixtureConditional(nn.Module):
         if isinstance(ys, Tensor):
             return self._compress_stacked(ys, scales, means, weights, flags)
         n_items = len(ys)
-        nat = _lib.native()
-        if nat is not None and n_items > 0:  # the compiled boundary: items as tuples of integers, the bitstreams made by the call (fgmm_sink)
-            keep = []
-            tuples, outs, dev, dt = [], [], None, None
-            ms = []
-            for i in range(n_items):
-                yp, sp, mp, wp, M, hw, sk, sc, d, dti = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
-                dev, dt = dev or d, dt or dti
-                if d != dev:
-                    raise RuntimeError("all items of a batch must be on one device")
-                if dti != dt:
-                    raise RuntimeError("all items of a batch must have parameters of one dtype")
-                yq = torch.empty_like(keep[-1])
-                outs.append(yq)
-                ms.append(M)
-                tuples.append([yp, sp, mp, wp, M, hw, sk, sc, yq.data_ptr(), 0])
-            zb_all = torch.empty(sum(ms), dtype=torch.int64)  # the zero bitmaps of all items: one allocation, a view per item
-            at, base = 0, zb_all.data_ptr()
-            for t, M in zip(tuples, ms):
-                t[9] = base + 8 * at
-                at += M
-            di = dev.index if dev.index is not None else -1
-            strings, amax = nat.compress_items(_lib.ctx_addr(di), torch.cuda.current_stream(dev).cuda_stream, [tuple(t) for t in tuples],
-                                               _abi_dtype(dt), flags, self._mode(), int(self.clamp_scales),
-                                               self.checkpoint_stride, CheckpointedBytes if self.checkpoint_stride else None)
-            bitmaps = zb_all.split(ms)
-            return [((strings[i], amax[i], bitmaps[i]), outs[i].view_as(ys[i])) for i in range(n_items)]
-        items = (_lib.fgmm_item * n_items)()
-        keep: list = []
-        outs, bitmaps = [], []
-        dev = None
+        if n_items == 0:
+            return []
+        keep, tuples, outs, ms, dev = [], [], [], [], None  # the items as tuples of integers (fgmm_pybind.cpp: compress_items)
         for i in range(n_items):
-            it, M, hw, d = self._item(ys[i], scales[i], means[i], weights[i], keep, flags)
+            yp, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(ys[i], scales[i], means[i], weights[i], keep)
             dev = dev or d
             if d != dev:
                 raise RuntimeError("all items of a batch must be on one device")
             yq = torch.empty_like(keep[-1])
-            zb = torch.empty(M, dtype=torch.int64)
-            it.yq_out, it.zero_bitmap = yq.data_ptr(), zb.data_ptr()
-            it.ckpt_stride = self.checkpoint_stride
-            items[i] = it
             outs.append(yq)
-            bitmaps.append(zb)
-        if n_items == 0:
-            return []
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.lib().fgmm_gmc_compress_batch(_lib.ctx(dev.index if dev.index is not None else -1), stream, items,
-                                                n_items, self._mode(), int(self.clamp_scales))
-        _lib.check(rc, "GaussianMixtureConditional.compress")
-        res = []
-        datas = _lib.take_bytes_many(dev.index if dev.index is not None else -1, [items[i].bytes for i in range(n_items)],
-                                     [int(items[i].bytes_len) for i in range(n_items)], CheckpointedBytes if self.checkpoint_stride else None)
-        cks = _take_ckpts_many(dev.index if dev.index is not None else -1, [items[i].ckpt for i in range(n_items)],
-                               [int(items[i].n_ckpt) for i in range(n_items)]) if self.checkpoint_stride else None
-        for i in range(n_items):
-            data = datas[i]
-            if cks is not None:
-                data = CheckpointedBytes._adopt(data, cks[i][0], self.checkpoint_stride, cks[i][1])
-            res.append(((data, int(items[i].abs_max), bitmaps[i]), outs[i].view_as(ys[i])))
-        return res
+            ms.append(M)
+            tuples.append([yp, sp, mp, wp, M, hw, sk, sc, yq.data_ptr(), 0, dt])
+        zb_all = torch.empty(sum(ms), dtype=torch.int64)  # the zero bitmaps of all items: one allocation, a view per item
+        at, base = 0, zb_all.data_ptr()
+        for t, M in zip(tuples, ms):
+            t[9] = base + 8 * at
+            at += M
+        strings, amax = _lib.boundary().compress_items(*_ctx_stream(dev), [tuple(t) for t in tuples], flags, self._mode(), int(self.clamp_scales),
+                                                       self.checkpoint_stride, CheckpointedBytes if self.checkpoint_stride else None)
+        bitmaps = zb_all.split(ms)
+        return [((strings[i], amax[i], bitmaps[i]), outs[i].view_as(ys[i])) for i in range(n_items)]
 
     def compress_head_batch(self, y: Tensor, x: Tensor, head: "ParameterHead") -> CompressedBatch:
         """``compress_batch`` with the parameter head FUSED into the encode-side CDF kernel: ``y [N, M, h, w]`` latents, ``x [N, c_in, h, w]``
@@ -921,34 +776,13 @@ class GaussianMixtureConditional(nn.Module):
         if N == 0:
             return CompressedBatch([], [], torch.empty((0, M), dtype=torch.int64), torch.empty((0, 1, M, h, w), dtype=torch.float32, device=dev))
         y = y.contiguous()
-        nat = _lib.native()
-        if nat is not None:
-            yq = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
-            zb = torch.empty((N, M), dtype=torch.int64)
-            strings, amax = nat.compress_head_stacked(
-                _lib.ctx_addr(dev.index if dev.index is not None else -1), torch.cuda.current_stream(dev).cuda_stream, y.data_ptr(), x.data_ptr(), head._h.value,
-                N, M, head.c_in, h * w, self._mode(), int(self.clamp_scales), self.checkpoint_stride, yq.data_ptr(), zb.data_ptr(),
-                CheckpointedBytes if self.checkpoint_stride else None)
-            return CompressedBatch(strings, amax, zb, yq)
-        items = np.zeros(N, _lib.ITEM_DTYPE)
-        rng = np.arange(N, dtype=np.uint64)
-        items["y"] = np.uint64(y.data_ptr()) + rng * np.uint64(M * h * w * 4)
-        items["M"], items["K"], items["hw"] = M, self.K, h * w
         yq = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
         zb = torch.empty((N, M), dtype=torch.int64)
-        items["yq_out"] = np.uint64(yq.data_ptr()) + rng * np.uint64(M * h * w * 4)
-        items["zero_bitmap"] = np.uint64(zb.data_ptr()) + rng * np.uint64(M * 8)
-        items["ckpt_stride"] = self.checkpoint_stride
-        xs = (C.c_void_p * N)(*[x.data_ptr() + i * head.c_in * h * w * 4 for i in range(N)])
-        di = dev.index if dev.index is not None else -1
-        rc = _lib.lib().fgmm_gmc_compress_head_batch(_lib.ctx(di), torch.cuda.current_stream(dev).cuda_stream,
-                                                     C.cast(items.ctypes.data, C.POINTER(_lib.fgmm_item)), xs, N, head._h, self._mode(), int(self.clamp_scales))
-        _lib.check(rc, "GaussianMixtureConditional.compress_head_batch")
-        datas = _lib.take_bytes_many(di, items["bytes"].tolist(), items["bytes_len"].tolist(), CheckpointedBytes if self.checkpoint_stride else None)
-        if self.checkpoint_stride:
-            cks = _take_ckpts_many(di, items["ckpt"].tolist(), items["n_ckpt"].tolist())
-            datas = [CheckpointedBytes._adopt(d, ck[0], self.checkpoint_stride, ck[1]) for d, ck in zip(datas, cks)]
-        return CompressedBatch(datas, items["abs_max"].tolist(), zb, yq)
+        strings, amax = _lib.boundary().compress_head_stacked(
+            *_ctx_stream(dev), y.data_ptr(), x.data_ptr(), head._h.value,
+            N, M, head.c_in, h * w, self._mode(), int(self.clamp_scales), self.checkpoint_stride, yq.data_ptr(), zb.data_ptr(),
+            CheckpointedBytes if self.checkpoint_stride else None)
+        return CompressedBatch(strings, amax, zb, yq)
 
     def estimate_bits_batch(self, ys, scales, means, weights, *, weights_are_logits: bool = False, per_channel: bool = False,
                             per_latent: bool = False) -> List[RateEstimate]:
@@ -964,7 +798,7 @@ class GaussianMixtureConditional(nn.Module):
         bitmaps = L.output("zero_bitmap", torch.int64)
         chans = L.output("chan_bits_q", torch.int64) if per_channel else [None] * L.N
         maps = L.output("bits_map", torch.float32, per_latent=True) if per_latent else [None] * L.N
-        rc = _lib.lib().fgmm_gmc_estimate_batch(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales))
+        rc = _lib.lib().fgmm_gmc_estimate_batch(*L.call(), L.arr, L.N, self._mode(), int(self.clamp_scales))
         _lib.check(rc, "GaussianMixtureConditional.estimate_bits")
         items = L.items
         cols = zip(items["bits_q"].tolist(), items["bytes_pred"].tolist(), items["n_symbols"].tolist(), items["n_bypass"].tolist(),
@@ -1001,18 +835,18 @@ class GaussianMixtureConditional(nn.Module):
             raise ValueError(f"lam = {lam!r}: must be finite and >= 0")
         wl = _rdo_weight_lists(ys, channel_weights, position_weights)
         flags = _lib.FGMM_PARAMS_LOGITS if weights_are_logits else 0
-        nat = _lib.native()
-        if wl is None and not channel_skip and isinstance(ys, Tensor) and nat is not None and scales.dim() == 4 and scales.shape[0] > 0:  # the compiled boundary: items built in C++
+        if wl is None and not channel_skip and isinstance(ys, Tensor):  # the plain stacked call: no item array on this side
             y, scales, means, weights, N, M, h, w, s_item, sc = self._stacked_view(ys, scales, means, weights)
+            if N == 0:
+                return []
             dev = scales.device
             out = torch.empty((N, 1, M, h, w), dtype=torch.float32, device=dev)
             zb = torch.empty((N, M), dtype=torch.int64)
             cb = torch.empty((N, M), dtype=torch.int64) if per_channel else None
-            di = dev.index if dev.index is not None else -1
-            ch, before, after, am = nat.rdoq_stacked(_lib.ctx_addr(di), torch.cuda.current_stream(dev).cuda_stream, y.data_ptr(), scales.data_ptr(),
-                                                     means.data_ptr(), weights.data_ptr(), N, M, h * w, s_item, M * sc, sc,
-                                                     _abi_dtype(scales.dtype), flags, self._mode(),
-                                                     int(self.clamp_scales), lam, out.data_ptr(), zb.data_ptr(), cb.data_ptr() if per_channel else 0)
+            ch, before, after, am = _lib.boundary().rdoq_stacked(*_ctx_stream(dev), y.data_ptr(), scales.data_ptr(),
+                                                                 means.data_ptr(), weights.data_ptr(), N, M, h * w, s_item, M * sc, sc,
+                                                                 _abi_dtype(scales.dtype), flags, self._mode(),
+                                                                 int(self.clamp_scales), lam, out.data_ptr(), zb.data_ptr(), cb.data_ptr() if per_channel else 0)
             return [RdoQuantized(*c) for c in zip(out.unbind(0), ch, before, after, am, zb.unbind(0), cb.unbind(0) if per_channel else [None] * N)]
         L = self._latent_items(_lib.fgmm_rdoq_item, ys, scales, means, weights, weights_are_logits)
         if L.N == 0:
@@ -1021,12 +855,7 @@ class GaussianMixtureConditional(nn.Module):
         chans = L.output("chan_bits_q_after", torch.int64) if per_channel else [None] * L.N
         warr = _rdo_weights_array(wl)
         sarr, sflags = _rdo_skip_array(L, per_channel) if channel_skip else (None, None)
-        if nat is not None:
-            nat.rdoq_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), lam,
-                           C.addressof(warr) if warr is not None else 0, C.addressof(sarr) if sarr is not None else 0)
-        else:
-            rc = _lib.lib().fgmm_gmc_rdoq_batch_s(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales), lam, warr, sarr)
-            _lib.check(rc, "GaussianMixtureConditional.quantize_rdo")
+        _lib.boundary().rdoq_items(*L.call(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), lam, _addr(warr), _addr(sarr))
         items = L.items
         cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
                    bitmaps, chans)
@@ -1042,14 +871,13 @@ class GaussianMixtureConditional(nn.Module):
 
     def _latent_items(self, struct, ys, scales, means, weights, logits: bool) -> _LatentItems:
         """THE item builder of the calls that price latents (estimate, RDOQ, curve, budget): ``struct[N]`` with the input fields
-        set - stacked tensors column by column (``_stacked_view``, ``_stacked_fill``: one validation, the pointers batch-dimension
+        set - stacked tensors column by column (``_stacked_view``, ``_boundary.fill_items``: one validation, the pointers batch-dimension
         offsets), sequences through ``_item_ints`` item by item"""
         flags = _lib.FGMM_PARAMS_LOGITS if logits else 0
         if isinstance(ys, Tensor):
-            view = self._stacked_view(ys, scales, means, weights)
-            N, M, h, w = view[4:8]
-            L = _LatentItems(struct, N, list(view[:4]), view[1].device, shape=(1, M, h, w))
-            self._stacked_fill(L.items, *view, flags)
+            y, s, m, wt, N, M, h, w, s_item, sc = self._stacked_view(ys, scales, means, weights)
+            L = _LatentItems(struct, N, [y, s, m, wt], s.device, shape=(1, M, h, w))
+            _boundary.fill_items(L.items, s.data_ptr(), m.data_ptr(), wt.data_ptr(), s_item, M * sc, sc, _abi_dtype(s.dtype), flags, M, h * w, y.data_ptr())
             return L
         L = _LatentItems(struct, len(ys), [], ys=ys)
         keep, dev = L.keep, None
@@ -1059,7 +887,7 @@ class GaussianMixtureConditional(nn.Module):
             if d != dev:
                 raise RuntimeError("all items of a batch must be on one device")
             it.y = yp
-            it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, _abi_dtype(dt), flags)
+            it.params = _lib.fgmm_params(sp, mp, wp, sk, sc, dt, flags)
             it.M, it.K, it.hw = M, self.K, hw
         L.dev = dev
         return L
@@ -1081,20 +909,14 @@ class GaussianMixtureConditional(nn.Module):
         L = self._latent_items(_lib.fgmm_rdcurve_item, ys, scales, means, weights, weights_are_logits)
         if L.N == 0:
             return []
-        nat, items, warr = _lib.native(), L.items, _rdo_weights_array(wl)
+        call, items, warr = _lib.boundary().rdcurve_items, L.items, _rdo_weights_array(wl)
         names = ("bits_q_after", "n_changed", "ddist_q")
         cols = [[] for _ in names]
         sarr = (_lib.fgmm_rdcurve_skip * L.N)() if channel_skip else None
         n_skipped = [[] for _ in range(L.N)]
         for at in range(0, len(lambdas), _lib.FGMM_RDCURVE_MAX):
             chunk = lambdas[at:at + _lib.FGMM_RDCURVE_MAX]
-            if nat is not None:
-                nat.rdcurve_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), chunk,
-                                  C.addressof(warr) if warr is not None else 0, C.addressof(sarr) if sarr is not None else 0)
-            else:
-                rc = _lib.lib().fgmm_gmc_rdcurve_batch_s(_lib.ctx(L.di), L.stream(), L.arr, L.N, self._mode(), int(self.clamp_scales),
-                                                         (C.c_double * len(chunk))(*chunk), len(chunk), warr, sarr)
-                _lib.check(rc, "GaussianMixtureConditional.rd_curve")
+            call(*L.call(), C.addressof(L.arr), L.N, self._mode(), int(self.clamp_scales), chunk, _addr(warr), _addr(sarr))
             for i in range(L.N if channel_skip else 0):
                 n_skipped[i].extend(sarr[i].n_skipped[:len(chunk)])
             for col, name in zip(cols, names):
@@ -1155,18 +977,9 @@ class GaussianMixtureConditional(nn.Module):
             return []
         outs, bitmaps = L.output("y_rdo", torch.float32, per_latent=True), L.output("zero_bitmap", torch.int64)
         chans = L.output("chan_bits_q_after", torch.int64) if per_channel else [None] * N
-        nat = _lib.native()
         sarr, sflags = _rdo_skip_array(L, per_channel) if channel_skip else (None, None)
-        if nat is not None:
-            res = nat.rdoq_budget_items(_lib.ctx_addr(L.di), L.stream(), C.addressof(L.arr), N, self._mode(), int(self.clamp_scales), groups, budgets,
-                                        lambda_max, refine, C.addressof(warr) if warr is not None else 0, C.addressof(sarr) if sarr is not None else 0)
-        else:
-            out_res = (_lib.fgmm_budget_result * n_groups)()
-            rc = _lib.lib().fgmm_gmc_rdoq_budget_batch_s(_lib.ctx(L.di), L.stream(), L.arr, N, self._mode(), int(self.clamp_scales),
-                                                         (C.c_int32 * N)(*groups) if groups is not None else None, n_groups,
-                                                         (C.c_uint64 * n_groups)(*budgets), lambda_max, refine, out_res, warr, sarr)
-            _lib.check(rc, "GaussianMixtureConditional.quantize_to_budget")
-            res = [(r.lambda_, r.bytes_pred, r.passes, r.status) for r in out_res]
+        res = _lib.boundary().rdoq_budget_items(*L.call(), C.addressof(L.arr), N, self._mode(), int(self.clamp_scales), groups, budgets,
+                                                lambda_max, refine, _addr(warr), _addr(sarr))
         got = []
         cols = zip(outs, items["n_changed"].tolist(), items["bits_q_before"].tolist(), items["bits_q_after"].tolist(), items["abs_max"].tolist(),
                    bitmaps, chans)
@@ -1203,38 +1016,11 @@ class GaussianMixtureConditional(nn.Module):
         if stacked_output:
             raise RuntimeError("stacked_output needs stacked parameters ([N, K*M, h, w] tensors)")
         n_items = len(strings)
-        nat = _lib.native()
-        if nat is not None and n_items > 0:
-            keep = []
-            tuples, outs, dev, dt = [], [], None, None
-            for i in range(n_items):
-                _, sp, mp, wp, M, hw, sk, sc, d, dti = self._item_ints(None, scales[i], means[i], weights[i], keep)
-                dev, dt = dev or d, dt or dti
-                if d != dev:
-                    raise RuntimeError("all items of a batch must be on one device")
-                if dti != dt:
-                    raise RuntimeError("all items of a batch must have parameters of one dtype")
-                zb = zero_bitmaps[i]
-                if zb.device.type != "cpu" or zb.dtype != torch.int64 or not zb.is_contiguous():
-                    zb = zb.to("cpu", torch.int64).contiguous()
-                if zb.numel() != M:
-                    raise RuntimeError(f"zero_bitmap has {zb.numel()} entries, expected {M}")
-                shp = scales[i].shape
-                y_hat = torch.empty((1, M, shp[2], shp[3]), dtype=torch.float32, device=d)
-                keep.append(zb)
-                outs.append(y_hat)
-                tuples.append((sp, mp, wp, M, hw, sk, sc, y_hat.data_ptr(), zb.data_ptr()))
-            data = strings if isinstance(strings, list) and all(isinstance(s_, bytes) for s_ in strings) else [s_ if isinstance(s_, bytes) else bytes(s_) for s_ in strings]
-            nat.decompress_items(_lib.ctx_addr(dev.index if dev.index is not None else -1), torch.cuda.current_stream(dev).cuda_stream, data,
-                                 [int(a) for a in abs_maxes], tuples, _abi_dtype(dt), flags, self._mode(),
-                                 int(self.clamp_scales), CheckpointedBytes)
-            return outs
-        items = (_lib.fgmm_item * n_items)()
-        keep: list = []
-        outs = []
-        dev = None
+        if n_items == 0:
+            return []
+        keep, tuples, outs, dev = [], [], [], None  # the items as tuples of integers (fgmm_pybind.cpp: decompress_items)
         for i in range(n_items):
-            it, M, hw, d = self._item(None, scales[i], means[i], weights[i], keep, flags)
+            _, sp, mp, wp, M, hw, sk, sc, d, dt = self._item_ints(None, scales[i], means[i], weights[i], keep)
             dev = dev or d
             if d != dev:
                 raise RuntimeError("all items of a batch must be on one device")
@@ -1243,24 +1029,14 @@ class GaussianMixtureConditional(nn.Module):
                 zb = zb.to("cpu", torch.int64).contiguous()
             if zb.numel() != M:
                 raise RuntimeError(f"zero_bitmap has {zb.numel()} entries, expected {M}")
-            data = strings[i] if isinstance(strings[i], bytes) else bytes(strings[i])
-            buf = C.c_char_p(data)  # borrowed pointer into the bytes object (kept alive below), no copy
             shp = scales[i].shape
             y_hat = torch.empty((1, M, shp[2], shp[3]), dtype=torch.float32, device=d)
-            it.yq_out, it.zero_bitmap = y_hat.data_ptr(), zb.data_ptr()
-            it.abs_max = int(abs_maxes[i])
-            it.bytes, it.bytes_len = C.cast(buf, C.c_void_p), len(data)
-            if isinstance(data, CheckpointedBytes) and data._ck[2]:
-                it.ckpt, it.n_ckpt, it.ckpt_stride = data._ck[3], data._ck[2], data._ck[4]
-            items[i] = it
-            keep += [zb, buf, data]
+            keep.append(zb)
             outs.append(y_hat)
-        if n_items == 0:
-            return []
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.lib().fgmm_gmc_decompress_batch(_lib.ctx(dev.index if dev.index is not None else -1), stream, items,
-                                                  n_items, self._mode(), int(self.clamp_scales))
-        _lib.check(rc, "GaussianMixtureConditional.decompress")
+            tuples.append((sp, mp, wp, M, hw, sk, sc, y_hat.data_ptr(), zb.data_ptr(), dt))
+        data = strings if isinstance(strings, list) and all(isinstance(s_, bytes) for s_ in strings) else [s_ if isinstance(s_, bytes) else bytes(s_) for s_ in strings]
+        _lib.boundary().decompress_items(*_ctx_stream(dev), data, [int(a) for a in abs_maxes], tuples, flags, self._mode(),
+                                         int(self.clamp_scales), CheckpointedBytes)
         return outs
 
     def decompress(self, strings: bytes, abs_max: int, zero_bitmap: Tensor, scales: Tensor, means: Tensor,

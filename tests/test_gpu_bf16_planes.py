@@ -203,18 +203,22 @@ def test_batches_stacked_and_as_sequences_in_both_bindings(monkeypatch, binding)
 
 
 def test_a_batch_of_mixed_plane_types_is_refused(monkeypatch):
-    monkeypatch.setattr(_lib, "_native", False)  # the ctypes binding hands each item's dtype to the library as it is
+    """either binding hands each item's dtype to the library as it is, and the library refuses the mix"""
     gmc = GaussianMixtureConditional(K=4, mode="polya")
     y, p16, p32, _ = inputs("v8_tiled", False)
     h16 = [t.half() for t in p32]
     (b, am, zb), _ = gmc.compress(y, *p16)
-    for other in (h16, p32):
-        cols = [[a, o] for a, o in zip(p16, other)]
-        for call in (lambda: gmc.compress_batch([y, y], *cols), lambda: gmc.estimate_bits_batch([y, y], *cols),
-                     lambda: gmc.quantize_rdo_batch([y, y], *cols, 0.5), lambda: gmc.rd_curve_batch([y, y], *cols, [0.5]),
-                     lambda: gmc.quantize_to_budget_batch([y, y], *cols, 100), lambda: gmc.decompress_batch([b, b], [am, am], [zb, zb], *cols)):
-            with pytest.raises(_lib.FgmmError, match="FGMM_ERR_INVALID"):
-                call()
+    for error in (RuntimeError, _lib.FgmmError):  # the compiled binding, then ctypes
+        if error is _lib.FgmmError:
+            monkeypatch.setattr(_lib, "_native", False)
+        assert (_lib.native() is None) == (error is _lib.FgmmError)
+        for other in (h16, p32):
+            cols = [[a, o] for a, o in zip(p16, other)]
+            for call in (lambda: gmc.compress_batch([y, y], *cols), lambda: gmc.estimate_bits_batch([y, y], *cols),
+                         lambda: gmc.quantize_rdo_batch([y, y], *cols, 0.5), lambda: gmc.rd_curve_batch([y, y], *cols, [0.5]),
+                         lambda: gmc.quantize_to_budget_batch([y, y], *cols, 100), lambda: gmc.decompress_batch([b, b], [am, am], [zb, zb], *cols)):
+                with pytest.raises(error, match="FGMM_ERR_INVALID"):
+                    call()
 
 
 # ---- the decode side --------------------------------------------------------------------------------------------------------------------

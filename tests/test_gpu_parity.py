@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from flashgmm_amd import CheckpointedBytes, GaussianMixtureConditional, _lib, ans
+from flashgmm_amd import CheckpointedBytes, GaussianMixtureConditional, _boundary, _lib, ans
 from tests import synth as T
 from helpers import expand_trimmed, hdr_form
 
@@ -583,14 +583,13 @@ def test_sink_puts_the_bitstreams_into_the_callers_storage(monkeypatch):
     lat = [T.make_latent(4300 + i, M=32 + 8 * (i % 2), h=16, w=8 + 4 * (i % 3), clamp=False, zero_frac=0.25 if i != 3 else 1.0) for i in range(7)]
     dev_t = [[torch.from_numpy(l[k]).to("cuda:0") for k in range(4)] for l in lat]
     plain = gmc.compress_batch(*[[t[k] for t in dev_t] for k in range(4)])
-    items = (_lib.fgmm_item * 7)()
-    keep = []
-    for i, t in enumerate(dev_t):
-        it, M, hw, _ = gmc._item(t[0], t[1], t[2], t[3], keep)
+    keep, tuples = [], []
+    for t in dev_t:  # the tuples compress_batch builds for compress_items
+        yp, sp, mp, wp, M, hw, sk, sc, _, dt = gmc._item_ints(t[0], t[1], t[2], t[3], keep)
         yq, zb = torch.empty_like(t[0]), torch.empty(M, dtype=torch.int64)
-        it.yq_out, it.zero_bitmap = yq.data_ptr(), zb.data_ptr()
-        items[i] = it
+        tuples.append((yp, sp, mp, wp, M, hw, sk, sc, yq.data_ptr(), zb.data_ptr(), dt))
         keep += [yq, zb]
+    items, _ = _boundary.sequence_items(tuples, 1, 0)
     store, asked, threads = {}, [], set()
 
     def alloc(user, item, nbytes, refuse=-1):

@@ -26,15 +26,18 @@ MODES = ["polya", "as", "logistic"]
 
 def test_compiled_python_boundary_loads_and_matches_the_library():
     """flashgmm_amd._native (pybind11, csrc/fgmm_pybind.cpp) is built beside the library, resolves it through its $ORIGIN rpath, reports
-    the library's ABI version and exposes the three batched calls; FGMM_NATIVE=0 turns it off (the ctypes binding then does the work)"""
+    the library's ABI version and exposes the nine batched calls; FGMM_NATIVE=0 turns it off (_lib.boundary() then gives the stand-in over
+    the ctypes binding, flashgmm_amd/_boundary.py)"""
     import subprocess
     import sys
 
     nat = _lib.native()
     assert nat is not None, "flashgmm_amd/_native*.so missing or not loadable: flashgmm_amd/csrc/build.sh builds it"
     assert nat.abi_version == _lib.lib().fgmm_abi_version()
-    for fn in ("compress_stacked", "compress_head_stacked", "decompress_stacked"):
+    for fn in ("compress_stacked", "compress_head_stacked", "decompress_stacked", "compress_items", "decompress_items", "rdoq_stacked", "rdoq_items",
+               "rdcurve_items", "rdoq_budget_items"):
         assert callable(getattr(nat, fn))
+    assert _lib.boundary() is nat
     out = subprocess.run([sys.executable, "-c", "from flashgmm_amd import _lib; print(_lib.native())"], env=dict(os.environ, FGMM_NATIVE="0"),
                          capture_output=True, text=True, cwd=ROOT)
     assert out.stdout.strip() == "None", out.stderr[-500:]
