@@ -211,6 +211,8 @@ SIGNATURES = {
                                           C.POINTER(fgmm_budget_result), C.POINTER(fgmm_rdo_weights), C.POINTER(fgmm_rdo_skip)]),
     "fgmm_gmc_likelihood_batch": (_i, [_p, _p, C.POINTER(fgmm_like_item), _i, _i, C.c_float, C.c_float]),
     "fgmm_gmc_likelihood_backward_batch": (_i, [_p, _p, C.POINTER(fgmm_like_grad_item), _i, _i, C.c_float, C.c_float]),
+    "fgmm_gmc_likelihood_logits_batch": (_i, [_p, _p, C.POINTER(fgmm_like_item), _i, _i, C.c_float, C.c_float]),
+    "fgmm_gmc_likelihood_logits_backward_batch": (_i, [_p, _p, C.POINTER(fgmm_like_grad_item), _i, _i, C.c_float, C.c_float]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

@@ -358,7 +358,7 @@ constexpr int kRdCurveSumsS = kRdCurveRow + FGMM_RDCURVE_MAX + 1;
 int launch_rdcurve(const EncDesc *d_descs, const RdCurveDesc *d_cdescs, const uint32_t *d_log2, bool weighted, bool skip, int count, int M_max, int64_t hw_max, int64_t n_max,
                    bool linear, int mode, int vec, bool clamped, int planes, void *stream);
 
-// ---- the differentiable likelihood of the entropy model's forward() (fgmm_like.hip, fgmm_like.cpp; header section 3g) ------------
+// ---- the differentiable likelihood of the entropy model's forward() (fgmm_like.hip, fgmm_like.cpp; header sections 3g, 3h) -------
 struct LikeDesc {            // item i of a like_kernel launch, beside its EncDesc (chan_list null: every channel, no census)
   float *like_out;           // device [M * hw] or null: the bounded likelihood per latent
   float *v_out;              // device [M * hw] or null: v, the value the likelihood was taken at
@@ -370,11 +370,12 @@ struct LikeGradDesc {        // item i of a like_bwd_kernel launch, beside its E
   float *dy;                 // device [M * hw] or null
   float *dscales, *dmeans, *dweights; // device float32 [K * M * hw] contiguous, each may be null
 };
-// the addressing of launch_rate.  vec: 8 (two-byte planes only), 4 or 1; the backward launcher runs 4 positions per lane at most
+// the addressing of launch_rate.  vec: 8 (two-byte planes only), 4 or 1; the backward launcher runs 4 positions per lane at most.
+// logits: section 3h's form of either kernel - the weights planes hold logits, dweights receives the logits' gradient
 int launch_like(const EncDesc *d_descs, const LikeDesc *d_ldescs, int round, float scale_bound, float likelihood_bound, int count, int M_max,
-                int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream);
+                int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, bool logits, void *stream);
 int launch_like_bwd(const EncDesc *d_descs, const LikeGradDesc *d_gdescs, int round, float scale_bound, float likelihood_bound, int count, int M_max,
-                    int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream);
+                    int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, bool logits, void *stream);
 
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the

@@ -4,6 +4,11 @@
 //   like_kernel       (y, sigma, mu, pi) -> the bounded likelihood per latent (optional map), v (optional), the item's bit count
 //   like_bwd_kernel   (y | v, sigma, mu, pi, g | g_bits) -> dy (optional) and the twelve float32 gradient planes
 //
+// Each has a LOGITS form (section 3h): the weights planes hold the parameter head's logits, pi = softmax4 over K is the frame's
+// (EncPlanes::get, fgmm_math.h - the sequence the coder kernels run), section 3g then runs unchanged on that pi, and the backward
+// kernel stores the gradient with respect to the logits where the plain form stores dweights.  The form is a template parameter: the
+// plain instantiations are the code they were (profiles/likelihood_logits.md).
+//
 // Both run the encode frame (fgmm_encframe.h): placement in either grid, VEC-wide loads of float32 / float16 / bfloat16 planes widened
 // exactly as they arrive, wave_sum64 / add64.  The EncDesc has no chan_list: every channel is evaluated, there is no census.  What torch
 // eager does with about ten element-wise kernels per component - each reading and writing an [B, M, h, w] temporary that autograd keeps
@@ -37,7 +42,7 @@ __device__ __forceinline__ float like_phi(float x) { return expf(-0.5f * x * x) 
 __device__ __forceinline__ float like_bound(float L, float lb) { return lb > 0.0f ? max_nan(L, lb) : L; }
 __device__ __forceinline__ bool like_counts(float out) { return out > 0.0f && out < INFINITY; } // (false for NaN)
 
-template <int VEC, typename PT, bool LINEAR>
+template <int VEC, typename PT, bool LINEAR, bool LOGITS>
 __global__ __launch_bounds__(kBlock) void like_kernel(const EncDesc *__restrict__ descs, const LikeDesc *__restrict__ ldescs, int round, float sb,
                                                       float lb) {
   const EncDesc &d = descs[blockIdx.z];
@@ -56,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void like_kernel(const EncDesc *__restrict_
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       float mu[4], sg[4], pi[4];
-      P.get(e, 0, mu, sg, pi);
+      P.get(e, LOGITS, mu, sg, pi);
       if (round) v[e] = __builtin_rintf(v[e]); // round-half-even == torch.round
       float L = 0.0f;
 #pragma unroll
@@ -81,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void like_kernel(const EncDesc *__restrict_
   }
 }
 
-template <int VEC, typename PT, bool LINEAR>
+template <int VEC, typename PT, bool LINEAR, bool LOGITS>
 __global__ __launch_bounds__(kBlock) void like_bwd_kernel(const EncDesc *__restrict__ descs, const LikeGradDesc *__restrict__ gdescs, int round,
                                                           float sb, float lb) {
   const EncDesc &d = descs[blockIdx.z];
@@ -102,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void like_bwd_kernel(const EncDesc *__restr
 #pragma unroll
   for (int e = 0; e < VEC; ++e) {
     float mu[4], sg[4], pi[4];
-    P.get(e, 0, mu, sg, pi);
+    P.get(e, LOGITS, mu, sg, pi);
     const float ve = round ? __builtin_rintf(v[e]) : v[e];
     float p[4], da[4], ga[4];
     float L = 0.0f;
@@ -133,6 +138,11 @@ __global__ __launch_bounds__(kBlock) void like_bwd_kernel(const EncDesc *__restr
       const float G = gL * ga[k];
       ds[k][e] = (sg[k] >= sb || G < 0.0f) ? G : 0.0f;
     }
+    if constexpr (LOGITS) { // section 3h: dl_k = pi_k * (dpi_k - sum_j pi_j * dpi_j), the sum k ascending, on the dpi_k just formed
+      const float t = ((pi[0] * dw[0][e] + pi[1] * dw[1][e]) + pi[2] * dw[2][e]) + pi[3] * dw[3][e];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dw[k][e] = pi[k] * (dw[k][e] - t);
+    }
     dy[e] = round ? 0.0f : dv;
     if constexpr (VEC == 1) break;
   }
@@ -149,24 +159,24 @@ __global__ __launch_bounds__(kBlock) void like_bwd_kernel(const EncDesc *__restr
 // ---------------------------------------------------------------------------------------------------------
 // launchers: a ladder over VEC (1, 4, and 8 for two-byte planes where the kernel has it) x plane type x grid
 // ---------------------------------------------------------------------------------------------------------
-struct LikeLaunch {
+template <bool LOGITS> struct LikeLaunch {
   const EncDesc *d;
   const LikeDesc *r;
   int round;
   float sb, lb;
   static constexpr bool kVec8 = true;
   template <int VEC, typename PT, bool LINEAR> void go(dim3 grid, hipStream_t s) const {
-    hipLaunchKernelGGL((like_kernel<VEC, PT, LINEAR>), grid, dim3(kBlock), 0, s, d, r, round, sb, lb);
+    hipLaunchKernelGGL((like_kernel<VEC, PT, LINEAR, LOGITS>), grid, dim3(kBlock), 0, s, d, r, round, sb, lb);
   }
 };
-struct LikeBwdLaunch {
+template <bool LOGITS> struct LikeBwdLaunch {
   const EncDesc *d;
   const LikeGradDesc *r;
   int round;
   float sb, lb;
   static constexpr bool kVec8 = false; // twelve VEC-wide gradient planes per lane: 4 positions keep the kernel out of scratch
   template <int VEC, typename PT, bool LINEAR> void go(dim3 grid, hipStream_t s) const {
-    hipLaunchKernelGGL((like_bwd_kernel<VEC, PT, LINEAR>), grid, dim3(kBlock), 0, s, d, r, round, sb, lb);
+    hipLaunchKernelGGL((like_bwd_kernel<VEC, PT, LINEAR, LOGITS>), grid, dim3(kBlock), 0, s, d, r, round, sb, lb);
   }
 };
 template <int VEC, typename PT, bool LINEAR, typename F> static int like_launch_v(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, hipStream_t s) {
@@ -195,12 +205,15 @@ template <typename F> static int like_launch(const F &f, int count, int M_max, i
 }
 
 int launch_like(const EncDesc *d_descs, const LikeDesc *d_ldescs, int round, float scale_bound, float likelihood_bound, int count, int M_max,
-                int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream) {
-  return like_launch(LikeLaunch{d_descs, d_ldescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec, planes, stream);
+                int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, bool logits, void *stream) {
+  if (logits) return like_launch(LikeLaunch<true>{d_descs, d_ldescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec, planes, stream);
+  return like_launch(LikeLaunch<false>{d_descs, d_ldescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec, planes, stream);
 }
 int launch_like_bwd(const EncDesc *d_descs, const LikeGradDesc *d_gdescs, int round, float scale_bound, float likelihood_bound, int count, int M_max,
-                    int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream) {
-  return like_launch(LikeBwdLaunch{d_descs, d_gdescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec > 4 ? 4 : vec, planes, stream);
+                    int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, bool logits, void *stream) {
+  vec = vec > 4 ? 4 : vec;
+  if (logits) return like_launch(LikeBwdLaunch<true>{d_descs, d_gdescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec, planes, stream);
+  return like_launch(LikeBwdLaunch<false>{d_descs, d_gdescs, round, scale_bound, likelihood_bound}, count, M_max, hw_max, n_max, linear, vec, planes, stream);
 }
 
 } // namespace fgmm

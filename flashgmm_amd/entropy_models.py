@@ -478,33 +478,66 @@ class ParameterHead:
         return tuple(out.chunk(3, 1))
 
 
+def _like_forward(gmc, x, scales, means, weights, rnd: bool, want_map: bool, logits: bool):
+    """the forward call of section 3g, or 3h (``logits``) -> ``(main, v, n_nonfinite)`` as ``_LikelihoodFn`` returns them"""
+    L = gmc._latent_items(_lib.fgmm_like_item, x, scales, means, weights, logits)
+    if L.N == 0:
+        raise RuntimeError("the likelihood needs a batch of at least one item")
+    N, (_, M, h, w), dev = L.N, L.shape, L.dev
+    step = np.arange(N, dtype=np.uint64) * np.uint64(M * h * w * 4)
+    like = v = None
+    if want_map:
+        like = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
+        L.items["like_out"] = np.uint64(like.data_ptr()) + step
+    if rnd:
+        v = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
+        L.items["v_out"] = np.uint64(v.data_ptr()) + step
+    call = _lib.lib().fgmm_gmc_likelihood_logits_batch if logits else _lib.lib().fgmm_gmc_likelihood_batch
+    rc = call(*L.call(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
+    _lib.check(rc, "GaussianMixtureConditional.forward")
+    nonfinite = torch.from_numpy(L.items["n_nonfinite"].astype(np.int64))
+    main = like if want_map else torch.from_numpy(L.items["bits_q"].astype(np.float64) * 2.0 ** -_lib.FGMM_LIKE_Q).to(dev)
+    return main, v, nonfinite
+
+
+def _like_backward(gmc, x, scales, means, weights, rnd: bool, want_map: bool, logits: bool, g_main, need_x: bool, planes):
+    """the backward call of section 3g, or 3h (``logits``) -> dy ``[N, M, h, w]`` float32 (``need_x``; else None).  ``planes``: None,
+    or per item the byte addresses ``(dscales, dmeans, dweights)`` as three uint64 arrays ``[N]`` - the caller's float32 ``[K, M, h, w]``
+    blocks the twelve gradient planes of an item are written to"""
+    L = gmc._latent_items(_lib.fgmm_like_grad_item, x, scales, means, weights, logits)
+    N, (_, M, h, w), dev = L.N, L.shape, L.dev
+    rng = np.arange(N, dtype=np.uint64)
+    dy = None
+    if need_x:
+        dy = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
+        L.items["dy"] = np.uint64(dy.data_ptr()) + rng * np.uint64(M * h * w * 4)
+    if planes is not None:
+        L.items["dscales"], L.items["dmeans"], L.items["dweights"] = planes
+    if want_map:
+        g = g_main.to(torch.float32).contiguous()  # (held until the call returns: the call waits for its kernel)
+        L.items["g_like"] = np.uint64(g.data_ptr()) + rng * np.uint64(M * h * w * 4)
+    else:
+        L.items["g_bits"] = g_main.detach().to("cpu", torch.float64).numpy()
+    call = _lib.lib().fgmm_gmc_likelihood_logits_backward_batch if logits else _lib.lib().fgmm_gmc_likelihood_backward_batch
+    rc = call(*L.call(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
+    _lib.check(rc, "GaussianMixtureConditional.forward (backward)")
+    return dy
+
+
 class _LikelihoodFn(torch.autograd.Function):
     """``GaussianMixtureConditional.forward`` / ``rate_bits`` on the GPU (include/flashgmm_amd.h section 3g): one kernel forward, one
     backward that recomputes everything from the inputs - nothing but the inputs is saved.  ``x`` ``[B, M, h, w]`` float32 is the
     latent (``rnd``: rounded by the kernel) or the already-noised values.  -> ``(main, v, n_nonfinite)``: ``main`` the likelihood map
     ``[B, M, h, w]`` (``want_map``) or the items' bits as float64 ``[B]``; ``v`` the rounded latent (``rnd``; else None);
-    ``n_nonfinite`` int64 ``[B]`` on the CPU, the latents left out of the bits."""
+    ``n_nonfinite`` int64 ``[B]`` on the CPU, the latents left out of the bits.  ``logits``: section 3h - ``weights`` holds the
+    parameter head's logits, the softmax over K and its derivative run in the kernels, and the gradient returned in the ``weights``
+    slot is the logits'."""
 
     @staticmethod
-    def forward(ctx, gmc, x, scales, means, weights, rnd: bool, want_map: bool):
-        L = gmc._latent_items(_lib.fgmm_like_item, x, scales, means, weights, False)
-        if L.N == 0:
-            raise RuntimeError("the likelihood needs a batch of at least one item")
-        N, (_, M, h, w), dev = L.N, L.shape, L.dev
-        step = np.arange(N, dtype=np.uint64) * np.uint64(M * h * w * 4)
-        like = v = None
-        if want_map:
-            like = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
-            L.items["like_out"] = np.uint64(like.data_ptr()) + step
-        if rnd:
-            v = torch.empty((N, M, h, w), dtype=torch.float32, device=dev)
-            L.items["v_out"] = np.uint64(v.data_ptr()) + step
-        rc = _lib.lib().fgmm_gmc_likelihood_batch(*L.call(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
-        _lib.check(rc, "GaussianMixtureConditional.forward")
-        nonfinite = torch.from_numpy(L.items["n_nonfinite"].astype(np.int64))
-        main = like if want_map else torch.from_numpy(L.items["bits_q"].astype(np.float64) * 2.0 ** -_lib.FGMM_LIKE_Q).to(dev)
+    def forward(ctx, gmc, x, scales, means, weights, rnd: bool, want_map: bool, logits: bool):
+        main, v, nonfinite = _like_forward(gmc, x, scales, means, weights, rnd, want_map, logits)
         ctx.save_for_backward(x, scales, means, weights)
-        ctx.gmc, ctx.rnd, ctx.want_map = gmc, rnd, want_map
+        ctx.gmc, ctx.rnd, ctx.want_map, ctx.logits = gmc, rnd, want_map, logits
         ctx.mark_non_differentiable(nonfinite)
         if v is not None:
             ctx.mark_non_differentiable(v)
@@ -518,30 +551,55 @@ class _LikelihoodFn(torch.autograd.Function):
         need_x, need_s, need_m, need_w = ctx.needs_input_grad[1:5]
         need_x = need_x and not rnd  # round() has gradient zero: None
         if g_main is None or not (need_x or need_s or need_m or need_w):
-            return (None,) * 7
-        L = gmc._latent_items(_lib.fgmm_like_grad_item, x, scales, means, weights, False)
-        N, (_, M, h, w), dev = L.N, L.shape, L.dev
-        rng = np.arange(N, dtype=np.uint64)
-        keep = []
+            return (None,) * 8
+        N, KM, h, w = scales.shape
+        rng = np.arange(N, dtype=np.uint64) * np.uint64(KM * h * w * 4)
 
-        def out(field, need, planes):
+        def out(need):
             if not need:
-                return None
-            t = torch.empty((N, planes * M, h, w), dtype=torch.float32, device=dev)
-            L.items[field] = np.uint64(t.data_ptr()) + rng * np.uint64(planes * M * h * w * 4)
-            return t
+                return None, np.zeros(N, np.uint64)
+            t = torch.empty((N, KM, h, w), dtype=torch.float32, device=scales.device)
+            return t, np.uint64(t.data_ptr()) + rng
 
-        dy, ds, dm, dw = out("dy", need_x, 1), out("dscales", need_s, gmc.K), out("dmeans", need_m, gmc.K), out("dweights", need_w, gmc.K)
-        if ctx.want_map:
-            g = g_main.to(torch.float32).contiguous()
-            keep.append(g)
-            L.items["g_like"] = np.uint64(g.data_ptr()) + rng * np.uint64(M * h * w * 4)
-        else:
-            L.items["g_bits"] = g_main.detach().to("cpu", torch.float64).numpy()
-        rc = _lib.lib().fgmm_gmc_likelihood_backward_batch(*L.call(), L.arr, N, int(rnd), gmc.scale_bound, gmc.likelihood_bound)
-        _lib.check(rc, "GaussianMixtureConditional.forward (backward)")
+        (ds, ps), (dm, pm), (dw, pw) = out(need_s), out(need_m), out(need_w)
+        dy = _like_backward(gmc, x, scales, means, weights, rnd, ctx.want_map, ctx.logits, g_main, need_x, (ps, pm, pw))
         cast = lambda t, like: None if t is None else t.to(like.dtype)  # noqa: E731
-        return None, dy, cast(ds, scales), cast(dm, means), cast(dw, weights), None, None
+        return None, dy, cast(ds, scales), cast(dm, means), cast(dw, weights), None, None, None
+
+
+class _LikelihoodParamsFn(torch.autograd.Function):
+    """``GaussianMixtureConditional.forward_params`` / ``rate_bits_params`` (section 3h): ``_LikelihoodFn`` with ``logits`` on the three
+    thirds of the parameter head's output ``params`` ``[B, 3*K*M, h, w]`` (scales | means | logits), passed as the strided views they
+    are.  The backward writes the thirty-six gradient planes of an item straight into ONE ``[B, 3*K*M, h, w]`` float32 tensor, the
+    gradient of ``params``: no ``chunk`` backward runs, nothing is concatenated."""
+
+    @staticmethod
+    def forward(ctx, gmc, x, params, rnd: bool, want_map: bool):
+        main, v, nonfinite = _like_forward(gmc, x, *params.chunk(3, 1), rnd, want_map, True)
+        ctx.save_for_backward(x, params)
+        ctx.gmc, ctx.rnd, ctx.want_map = gmc, rnd, want_map
+        ctx.mark_non_differentiable(nonfinite)
+        if v is not None:
+            ctx.mark_non_differentiable(v)
+        return main, v, nonfinite
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_main, g_v, g_nonfinite):
+        x, params = ctx.saved_tensors
+        need_x, need_p = ctx.needs_input_grad[1:3]
+        need_x = need_x and not ctx.rnd
+        if g_main is None or not (need_x or need_p):
+            return (None,) * 5
+        dp = planes = None
+        if need_p:
+            N, KM3, h, w = params.shape
+            dp = torch.empty((N, KM3, h, w), dtype=torch.float32, device=params.device)
+            third = (KM3 // 3) * h * w * 4
+            base = np.uint64(dp.data_ptr()) + np.arange(N, dtype=np.uint64) * np.uint64(3 * third)
+            planes = (base, base + np.uint64(third), base + np.uint64(2 * third))
+        dy = _like_backward(ctx.gmc, x, *params.chunk(3, 1), ctx.rnd, ctx.want_map, True, g_main, need_x, planes)
+        return None, dy, (None if dp is None else dp.to(params.dtype)), None, None
 
 
 class GaussianMixtureConditional(nn.Module):
@@ -586,40 +644,74 @@ class GaussianMixtureConditional(nn.Module):
         if self.K != _lib.FGMM_K:
             raise RuntimeError(f"K = {self.K}: the kernels are bound for K = 4 only (as the reference's coder)")
 
-    def likelihood(self, values: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, round: bool = False) -> Tuple[Tensor, Tensor]:
+    def likelihood(self, values: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, round: bool = False,
+                   weights_are_logits: bool = False) -> Tuple[Tensor, Tensor]:
         """The building block of ``forward``: -> ``(v, likelihood)`` with ``v = torch.round(values)`` (``round=True``) or ``values``
         itself, and the bounded mixture likelihood of ``v`` (include/flashgmm_amd.h section 3g).  Differentiable in ``scales``,
-        ``means``, ``weights`` and, without rounding, ``values``."""
+        ``means``, ``weights`` and, without rounding, ``values``.  ``weights_are_logits`` (section 3h): ``weights`` holds the parameter
+        head's logits, the softmax over K runs in the kernel - the coder's own sequence - and the gradient ``weights`` receives is the
+        logits'."""
         self._check_k()
-        like, v, _ = _LikelihoodFn.apply(self, values, scales, means, weights, bool(round), True)
+        like, v, _ = _LikelihoodFn.apply(self, values, scales, means, weights, bool(round), True, bool(weights_are_logits))
         return (v if round else values), like
 
-    def forward(self, inputs: Tensor, scales: Tensor, means: Tensor, weights: Tensor, training: Optional[bool] = None) -> Tuple[Tensor, Tensor]:
+    def forward(self, inputs: Tensor, scales: Tensor, means: Tensor, weights: Tensor, training: Optional[bool] = None, *,
+                weights_are_logits: bool = False) -> Tuple[Tensor, Tensor]:
         """As the reference's (entropy_models.py:792-808): -> ``(outputs, likelihood)``.  ``inputs`` ``[B, M, h, w]`` float32,
         ``scales / means / weights`` ``[B, K*M, h, w]`` float32, float16 or bfloat16, ``weights`` the mixture weights themselves (the
         softmax over K stays torch's, so autograd differentiates it).  ``training`` (default ``self.training``): ``outputs`` is
         ``inputs`` plus uniform noise in [-0.5, 0.5) drawn by torch; otherwise ``torch.round(inputs)``.  One fused HIP kernel
         evaluates the likelihood, one recomputes it for the gradients (returned in the inputs' dtypes); in evaluation mode ``inputs``
-        receives no gradient, as through ``torch.round``."""
+        receives no gradient, as through ``torch.round``.  ``weights_are_logits``: as in ``likelihood``."""
         self._check_k()
         if training is None:
             training = self.training
         if training:
             outputs = inputs + torch.empty_like(inputs).uniform_(-0.5, 0.5)  # quantize(inputs, "noise") (entropy_models.py:163-167)
-            return self.likelihood(outputs, scales, means, weights)
-        return self.likelihood(inputs, scales, means, weights, round=True)
+            return self.likelihood(outputs, scales, means, weights, weights_are_logits=weights_are_logits)
+        return self.likelihood(inputs, scales, means, weights, round=True, weights_are_logits=weights_are_logits)
 
     def rate_bits(self, inputs: Tensor, scales: Tensor, means: Tensor, weights: Tensor, training: Optional[bool] = None, *,
-                  return_nonfinite: bool = False):
+                  return_nonfinite: bool = False, weights_are_logits: bool = False):
         """The fused rate of ``forward``: -> ``(outputs, bits)``, ``bits`` a float64 tensor ``[B]`` on the inputs' device - per item
         ``sum(-log2(likelihood))``, summed on the GPU as integers in units of 2^-32 bit (the same bits on every run), differentiable
         like the sum it stands for.  No likelihood map is written or kept.  Latents whose likelihood is NaN, infinite or <= 0 are left
-        out of the sum; ``return_nonfinite=True`` adds their count as a third value, an int64 ``[B]`` CPU tensor."""
+        out of the sum; ``return_nonfinite=True`` adds their count as a third value, an int64 ``[B]`` CPU tensor.
+        ``weights_are_logits``: as in ``likelihood``."""
         self._check_k()
         if training is None:
             training = self.training
         outputs = inputs + torch.empty_like(inputs).uniform_(-0.5, 0.5) if training else inputs
-        bits, v, nonfinite = _LikelihoodFn.apply(self, outputs, scales, means, weights, not training, False)
+        bits, v, nonfinite = _LikelihoodFn.apply(self, outputs, scales, means, weights, not training, False, bool(weights_are_logits))
+        outputs = outputs if training else v
+        return (outputs, bits, nonfinite) if return_nonfinite else (outputs, bits)
+
+    def _check_params(self, params: Tensor):
+        if params.dim() != 4 or params.size(1) % (3 * self.K):
+            raise RuntimeError(f"params must be [B, 3*K*M, h, w], scales | means | logits; got {tuple(params.shape)}")
+
+    def forward_params(self, inputs: Tensor, params: Tensor, training: Optional[bool] = None) -> Tuple[Tensor, Tensor]:
+        """``forward`` on the parameter head's output as it is (section 3h): ``params`` ``[B, 3*K*M, h, w]`` float32, float16 or
+        bfloat16, ordered scales | means | logits as ``chunk(3, 1)`` splits it.  The softmax over K and its derivative run in the two
+        kernels, on the three thirds in place; the backward writes ONE float32 ``[B, 3*K*M, h, w]`` tensor, the gradient of ``params``
+        (cast to its dtype where that is not float32) - no softmax, ``chunk`` or concatenation runs in torch on either pass.
+        -> ``(outputs, likelihood)``, bit for bit those of ``forward(inputs, *params.chunk(3, 1), weights_are_logits=True)``."""
+        self._check_k()
+        self._check_params(params)
+        if training is None:
+            training = self.training
+        outputs = inputs + torch.empty_like(inputs).uniform_(-0.5, 0.5) if training else inputs
+        like, v, _ = _LikelihoodParamsFn.apply(self, outputs, params, not training, True)
+        return (outputs if training else v), like
+
+    def rate_bits_params(self, inputs: Tensor, params: Tensor, training: Optional[bool] = None, *, return_nonfinite: bool = False):
+        """``rate_bits`` on the parameter head's output as it is: ``params`` and the gradient it receives as in ``forward_params``."""
+        self._check_k()
+        self._check_params(params)
+        if training is None:
+            training = self.training
+        outputs = inputs + torch.empty_like(inputs).uniform_(-0.5, 0.5) if training else inputs
+        bits, v, nonfinite = _LikelihoodParamsFn.apply(self, outputs, params, not training, False)
         outputs = outputs if training else v
         return (outputs, bits, nonfinite) if return_nonfinite else (outputs, bits)
 

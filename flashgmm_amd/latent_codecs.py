@@ -58,8 +58,16 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
                  entropy_parameters: Optional[nn.Module] = None, quantizer: str = "noise",
                  chunks: Tuple[str, ...] = ("scales", "means", "weights"), mode=None, param_dtype: torch.dtype = torch.float32,
                  fuse_softmax: bool = False, checkpoint_stride: int = 0, rdo_lambda: float = 0.0, target_bytes: Optional[int] = None,
-                 rdo_channel_weights: Optional[Tensor] = None, rdo_channel_skip: bool = False, **kwargs: Any):
+                 rdo_channel_weights: Optional[Tensor] = None, rdo_channel_skip: bool = False, fuse_forward_softmax: bool = False,
+                 **kwargs: Any):
         super().__init__()
+        # fuse_forward_softmax: forward() hands the parameter network's output to GaussianMixtureConditional.forward_params as it is -
+        # the softmax over K and its derivative run inside the two likelihood kernels (include/flashgmm_amd.h section 3h), on the pi
+        # the coder's kernels make of the same logits, and the gradient of the output is written as one tensor.  It does not touch
+        # the coding path (fuse_softmax is that path's switch)
+        if fuse_forward_softmax and quantizer != "noise":
+            raise ValueError("fuse_forward_softmax needs quantizer='noise' (the re-centring quantizer uses pi itself)")
+        self.fuse_forward_softmax = bool(fuse_forward_softmax)
         # rdo_channel_skip: the two quantisations below may also drop a coded channel whole where that lowers distortion + lambda * bits
         # (include/flashgmm_amd.h section 3f).  It has an effect only together with rdo_lambda > 0 or target_bytes
         self.rdo_channel_skip = bool(rdo_channel_skip)
@@ -284,7 +292,11 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         """As the reference's (latent_codecs/gaussian_mixture_conditional.py:99-125): ``{"likelihoods": {"y": ...}, "y_hat": ...}``
         from ``GaussianMixtureConditional.forward`` (the fused likelihood kernel, differentiable), for both quantizers.  The planes
         are the parameter network's as they are, the weights torch's softmax over K (autograd differentiates both): ``param_dtype``
-        and ``fuse_softmax`` are choices of the coding path and do not apply here."""
+        and ``fuse_softmax`` are choices of the coding path and do not apply here.  With ``fuse_forward_softmax`` the softmax over K
+        runs in the likelihood kernels instead: ``GaussianMixtureConditional.forward_params`` on the parameter network's output."""
+        if self.fuse_forward_softmax:
+            y_hat, y_likelihoods = self.gaussian_mixture_conditional.forward_params(y, self.entropy_parameters(ctx_params))
+            return {"likelihoods": {"y": y_likelihoods}, "y_hat": y_hat}
         scales_hat, means_hat, weights = self._chunk(self.entropy_parameters(ctx_params))
         weights = self._reshape_gmm_weight(weights)
         if self.quantizer == "noise":

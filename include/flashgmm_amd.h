@@ -53,6 +53,7 @@ extern "C" {
 #define FGMM_HAS_RDO_WEIGHTS 1 /* section 3e: fgmm_gmc_rdoq_batch_w, fgmm_gmc_rdcurve_batch_w, fgmm_gmc_rdoq_budget_batch_w (added without a bump, as 3b - 3d) */
 #define FGMM_HAS_BF16 1        /* section 2: FGMM_BF16 parameter planes in every call that takes planes (added without a bump, as 3b - 3f) */
 #define FGMM_HAS_LIKELIHOOD 1  /* section 3g: fgmm_gmc_likelihood_batch, fgmm_gmc_likelihood_backward_batch (added without a bump, as 3b - 3f) */
+#define FGMM_HAS_LIKELIHOOD_LOGITS 1 /* section 3h: fgmm_gmc_likelihood_logits_batch, fgmm_gmc_likelihood_logits_backward_batch (added without a bump, as 3b - 3g) */
 #define FGMM_RDO_W_MAX 256.0f  /* largest factor of a weighted call's chan_w / pos_w */
 
 typedef enum {
@@ -786,7 +787,7 @@ int fgmm_gmc_rdoq_budget_batch_s(fgmm_ctx *ctx, void *stream, fgmm_rdoq_item *it
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
   const float *y;          /* device [M*hw] */
-  fgmm_params params;      /* flags must be 0 */
+  fgmm_params params;      /* flags must be 0 (section 3h: FGMM_PARAMS_LOGITS) */
   int32_t M, K;
   int64_t hw;
   float *like_out;         /* DEVICE float32[M*hw] out: the bounded likelihood, or NULL (the rate alone) */
@@ -799,7 +800,7 @@ int fgmm_gmc_likelihood_batch(fgmm_ctx *ctx, void *stream, fgmm_like_item *items
                               float likelihood_bound);
 typedef struct {
   const float *y;          /* device [M*hw]: what the forward call was given (round == 0: the noised v) */
-  fgmm_params params;      /* flags must be 0 */
+  fgmm_params params;      /* flags must be 0 (section 3h: FGMM_PARAMS_LOGITS) */
   int32_t M, K;
   int64_t hw;
   const float *g_like;     /* device float32[M*hw]: the gradient w.r.t. like_out, or NULL: g_bits is used */
@@ -810,6 +811,36 @@ typedef struct {
 } fgmm_like_grad_item;
 int fgmm_gmc_likelihood_backward_batch(fgmm_ctx *ctx, void *stream, fgmm_like_grad_item *items, int count, int round, float scale_bound,
                                        float likelihood_bound);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3h. 3g FROM THE PARAMETER HEAD'S LOGITS: the softmax over K and its derivative run inside the two kernels, so that evaluation-mode
+ *    bits, the size estimate, RDOQ and the coder all see the same pi for the same logits, and no plane of weights, of their gradient
+ *    or of the softmax's backward exists between the head and the kernels.  Same item structures and signatures as 3g; every item
+ *    carries params.flags == FGMM_PARAMS_LOGITS, its `weights` planes hold the logits l_k, and `dweights` receives the gradient with
+ *    respect to the LOGITS.  Per latent, in binary32, every operation one IEEE operation (no contraction), K = 4:
+ *      pi  = softmax4(l_0 .. l_3): the one sequence of section 2 that every kernel runs under FGMM_PARAMS_LOGITS and that
+ *            fgmm_softmax4_hip exposes -
+ *              m   = max(l_0 .. l_3)                                         (fmaxf: a NaN logit does not win)
+ *              e_k = exp(l_k - m) by the library's fixed sequence, exactly 0 where !(l_k - m >= -41)   (a NaN logit too)
+ *              s   = (e_0 + e_1) + (e_2 + e_3)
+ *              pi_k = e_k / s, correctly rounded
+ *      Forward: section 3g, unchanged, on that pi -> out, v, bits_q, n_nonfinite.
+ *      Backward: section 3g, unchanged, on that pi -> gL, dy, dsigma_k, dmu_k; and with dpi_k = gL * p_k (3g's dweights, not stored here)
+ *        t    = ((pi_0*dpi_0 + pi_1*dpi_1) + pi_2*dpi_2) + pi_3*dpi_3       (separate multiply and add)
+ *        dl_k = pi_k * (dpi_k - t)                                           (stored where 3g stores dweights)
+ *    The result of either call is, bit for bit, that of the 3g call on float32 planes holding fgmm_softmax4_hip's weights of the
+ *    (widened) logits, dl_k formed from its dweights as above.  Non-finite logits give what softmax4 gives, nothing is special-cased:
+ *    a NaN logit gets weight 0; four logits of -inf, or a +inf among them, give NaN weights, hence a NaN out, which is left out of
+ *    bits_q and counted.  Planes are float32, float16 or bfloat16 as in 3g, two-byte logits widened exactly; the condition of the
+ *    coding calls that two-byte weights sum to at most 1 does not exist for logits.  The launch form - positions per lane, grid - is
+ *    decided exactly as in 3g.  One call is one form: refused with FGMM_ERR_INVALID before any launch, nothing written, is an item
+ *    whose flags are not exactly FGMM_PARAMS_LOGITS (a batch that mixes the two forms included), and everything 3g refuses; the two
+ *    entry points of 3g keep refusing the flag.  The caller's-stream contract is section 2's, as in 3g.
+ * ---------------------------------------------------------------------------------------------------------- */
+int fgmm_gmc_likelihood_logits_batch(fgmm_ctx *ctx, void *stream, fgmm_like_item *items, int count, int round, float scale_bound,
+                                     float likelihood_bound);
+int fgmm_gmc_likelihood_logits_backward_batch(fgmm_ctx *ctx, void *stream, fgmm_like_grad_item *items, int count, int round, float scale_bound,
+                                              float likelihood_bound);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
