@@ -8,12 +8,13 @@ is an integer or a float's bit pattern: every comparison is for EQUALITY.
 
   batch A  (16, 16, 16), (4, 16, 32)                    every hw a multiple of 256: the linear grid, 4-wide; fp32 and fp16 planes
   batch B  (8, 4, 4), M = 0, (12, 8, 13), (16, 16, 16)  the tiled grid, 4-wide; an empty item in the middle; unequal M and hw
-  batch C  batch B, the (12, 8, 13) item's y one float into its storage: the whole batch 1-wide"""
+  batch C  batch B, the (12, 8, 13) item's y one float into its storage: the whole batch 1-wide, tiled (hw = 16)"""
 import numpy as np
 import pytest
 import torch
 
 from flashgmm_amd import GaussianMixtureConditional, _lib
+from tests import enc_ref as F
 from tests import rdcurve_ref as V
 from tests import synth as T
 from tests.test_gpu_enc_frame import dv
@@ -25,6 +26,7 @@ LAMBDAS = [0.0, 0.1, 0.5, 16.0]
 A = [(16, 16, 16), (4, 16, 32)]
 B = [(8, 4, 4), (0, 4, 4), (12, 8, 13), (16, 16, 16)]
 BATCHES = {"A": (A, False, None), "A fp16": (A, True, None), "B": (B, False, None), "C": (B, False, 2)}
+FORMS = {"A": (4, F.LIN), "A fp16": (4, F.LIN), "B": (4, F.TILED), "C": (1, F.TILED)}  # asserted on the batch's tensors
 
 
 def make_batch(shapes, f16=False, off=None):
@@ -69,6 +71,7 @@ def test_a_batch_is_its_items(name):
     gmc = GaussianMixtureConditional(K=4, mode="polya", clamp_scales=True)
     cols = make_batch(shapes, f16, off)
     n = len(shapes)
+    assert F.form_of(*cols) == FORMS[name]
     # ---- the batch against single items ------------------------------------------------------------------------------------------------
     est = gmc.estimate_bits_batch(*cols, per_channel=True, per_latent=True)
     assert [ekey(e) for e in est] == [ekey(gmc.estimate_bits(*item(cols, i), per_channel=True, per_latent=True)) for i in range(n)]

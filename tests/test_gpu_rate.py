@@ -12,6 +12,7 @@ import torch
 
 from flashgmm_amd import GaussianMixtureConditional, RateEstimate, _lib
 from tests import edge_corpus as E
+from tests import enc_ref as F
 from tests import rate_ref as R
 from tests import synth as T
 
@@ -118,8 +119,9 @@ def test_symtab_bits_hip_equals_the_host_function():
 # ---- (b) ------------------------------------------------------------------------------------------------------------------------
 SHAPES = [(8, 4, 4),     # hw = 16: a quarter of a wave, the 4-wide loads
           (32, 16, 8),   # hw = 128: 4-wide, half a block per channel
-          (12, 8, 13),   # hw = 104, odd: the 1-wide path, a partial last wave
+          (12, 8, 13),   # hw = 104 = 4 * 26: 4-wide too, tiled, a partial wave (planes with hw % 4 != 0: tests/test_gpu_enc_forms.py)
           (16, 16, 16)]  # hw = 256 = 64 * 4: the linear grid
+FORMS = [(4, F.TILED), (4, F.TILED), (4, F.TILED), (4, F.LIN)]  # the launch form of a batch of each shape, asserted on the call's tensors
 
 
 @pytest.mark.parametrize("clamp", [True, False])
@@ -127,9 +129,12 @@ SHAPES = [(8, 4, 4),     # hw = 16: a quarter of a wave, the 4-wide loads
 def test_estimate_bits_batch_against_the_oracle(oracle, mode, clamp):
     gmc = GaussianMixtureConditional(K=4, mode=mode, clamp_scales=clamp)
     tally = [0, 0]
-    for shape in SHAPES:
+    for shape, form in zip(SHAPES, FORMS):
         cases = [T.make_latent(seed, *shape, clamp=not clamp, zero_frac=zf) for seed, zf in ((3, 0.0), (4, 0.5), (5, 0.0), (6, 0.5))]
-        est = gmc.estimate_bits_batch(*([dv(a) for a in col] for col in zip(*cases)), per_channel=True, per_latent=True)
+        cols = [[dv(a) for a in col] for col in zip(*cases)]
+        assert F.form_of(*cols) == form, shape
+        est = gmc.estimate_bits_batch(*cols, per_channel=True, per_latent=True)
+        assert F.form_of(*cols, outs=[e.latent_bits for e in est]) == form, shape
         assert len(est) == len(cases)
         for i, (e, c) in enumerate(zip(est, cases)):
             check(e, reference(oracle, mode, *c, clamp), tally, (shape, i))
@@ -144,7 +149,9 @@ def test_estimate_bits_batch_against_the_oracle(oracle, mode, clamp):
     y, s, m, w = T.make_latent(8, 4, 8, 8, clamp=not clamp, zero_frac=0.3)
     buf = torch.zeros(y.size + 1, dtype=torch.float32, device=DEV)
     buf[1:] = dv(y).reshape(-1)
-    e = gmc.estimate_bits(buf[1:].view(1, 4, 8, 8), dv(s), dv(m), dv(w), per_channel=True, per_latent=True)
+    t = (buf[1:].view(1, 4, 8, 8), dv(s), dv(m), dv(w))
+    assert F.form_of_one(*t, pos_w=False) == (1, F.LIN)
+    e = gmc.estimate_bits(*t, per_channel=True, per_latent=True)
     check(e, reference(oracle, mode, y, s, m, w, clamp), tally, "misaligned")
     assert tally[1] * 10 <= tally[0], tally
 

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from flashgmm_amd import BudgetQuantized, GaussianMixtureConditional, RdCurve, _lib
+from tests import enc_ref as F
 from tests import rdcurve_ref as V
 from tests import rdoq_ref as Q
 from tests import synth as T
@@ -50,13 +51,16 @@ def test_curve_against_the_reference(oracle, mode, clamp):
     cases = [T.make_latent(seed, *shape, clamp=not clamp, zero_frac=zf) for shape in Q.SHAPES for seed, zf in Q.SEEDS]
     cols = [[dv(a) for a in col] for col in zip(*cases)]
     refs = [V.curve(V.price(oracle, L, mode, *c, clamp=clamp), LAMBDAS) for c in cases]
-    got = gmc.rd_curve_batch(*cols, LAMBDAS)  # (mixed shapes: the 1-wide path on the tile grid)
+    assert F.form_of(*cols) == (4, F.TILED)  # mixed shapes, every hw a multiple of 4: 4-wide on the tiled grid
+    got = gmc.rd_curve_batch(*cols, LAMBDAS)
     assert len(got) == len(cases)
     for i, (g, r) in enumerate(zip(got, refs)):
         check_curve(g, r, LAMBDAS, i)
         assert (g.bits_q_after[0], g.n_changed[0], g.ddist_q[0]) == (g.bits_q_before, 0, 0)  # lambda = 0
     assert any(max(g.n_changed) > 0 for g in got)
-    # single calls (each shape on its own grid: 4-wide, 1-wide, linear) and stacked [2, ...] tensors agree with the batch
+    # single calls (each shape on its own grid: 4-wide, tiled at hw = 16, 128 and 104, linear at 256) and stacked [2, ...] tensors agree
+    # with the batch
+    assert [F.form_of_one(*(col[i] for col in cols), pos_w=False) for i in range(0, len(cases), 2)] == [(4, F.TILED)] * 3 + [(4, F.LIN)]
     singles = [gmc.rd_curve(*(col[i] for col in cols), LAMBDAS) for i in range(len(cases))]
     assert [ckey(s) for s in singles] == [ckey(g) for g in got]
     for k in range(len(Q.SHAPES)):

@@ -2,8 +2,9 @@
 of rdoq_kernel and rdcurve_kernel, rdoq_skip_kernel, the skip form of rdcurve_fold_kernel) against tests/rdo_skip_ref.py.  Every output
 is compared for EQUALITY: the chosen latents bit for bit, the counts, the integer sums, the flags.  That the sweep's cases skip a
 channel, keep an eligible one and meet a channel beyond FGMM_SKIP_VMAX is checked on the CPU by tests/test_rdo_skip_cpu.py.  Shapes:
-tests/rdoq_ref.SHAPES (hw = 16 less than a wave, hw = 104 1-wide, hw = 256 a whole block on the linear grid), and BIG, the smallest
-4-wide plane that spans two workgroups."""
+tests/rdoq_ref.SHAPES (hw = 16 less than a wave, hw = 104 a partial wave, both 4-wide on the tiled grid, hw = 256 a whole block on the
+linear grid), and BIG, the smallest 4-wide plane that spans two workgroups; 1-wide only where a tensor is handed over misaligned.  Planes
+with hw % 4 != 0: tests/test_gpu_enc_forms.py.  Where a comment names a launch form, ``enc_ref.form_of`` asserts it on the call's tensors."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 from flashgmm_amd import BudgetQuantized, GaussianMixtureConditional, RdCurve, RdoQuantized, _lib
+from tests import enc_ref as F
 from tests import rdcurve_ref as V
 from tests import rdo_skip_ref as S
 from tests import rdo_weights_ref as W
@@ -97,7 +99,7 @@ def priced_cases(oracle, mode, clamp):
 def test_skip_quantize_rdo_against_the_reference(oracle, mode, clamp, weighted):
     L = _lib.lib()
     gmc = GaussianMixtureConditional(K=4, mode=mode, clamp_scales=clamp)
-    cases, cws, pws, priced, _, _, _ = priced_cases(oracle, mode, clamp)
+    cases, cws, pws, priced, _, _, hws = priced_cases(oracle, mode, clamp)
     n8 = len(cases) - 1  # the mixed batch: the eight cases; BIG goes alone, on its own grid
     cols = [[dv(a) for a in col] for col in zip(*cases)]
     cw_d, pw_d = [dv(a) for a in cws], [dv(a) for a in pws]
@@ -111,6 +113,8 @@ def test_skip_quantize_rdo_against_the_reference(oracle, mode, clamp, weighted):
     for lam in Q.LAMBDAS:
         refs = [S.rdoq(oracle, L, mode, *c, lam, clamp=clamp, cw=cw if weighted else None, pw=pw if weighted else None, priced=p)
                 for c, cw, pw, p in zip(cases, cws, pws, priced)]
+        pos = (lambda sel: [pw_d[i] for i in sel]) if weighted else (lambda sel: None)
+        assert F.form_of(*(col[:n8] for col in cols), pos_w=pos(range(n8))) == F.form_of(*(col[n8:] for col in cols), pos_w=pos([n8])) == (4, F.TILED)
         got = gmc.quantize_rdo_batch(*(col[:n8] for col in cols), lam, **kw(range(n8)))  # mixed shapes
         got += gmc.quantize_rdo_batch(*(col[n8:] for col in cols), lam, **kw([n8]))  # two workgroups per channel
         assert len(got) == len(cases)
@@ -125,11 +129,16 @@ def test_skip_quantize_rdo_against_the_reference(oracle, mode, clamp, weighted):
         assert [skey(s) for s in singles] == [skey(g) for g in got[:n8]], lam
         # the 1-wide path: a pos_w that is not 16-byte aligned (weighted), a latent that is not (unweighted) - BIG included
         for i in (3, 4, 6, n8):
+            linear = hws[i] % 64 == 0  # (1-wide: a wave takes 64 positions)
             if weighted:
+                off = misaligned(pw_d[i])
+                assert F.form_of_one(*(col[i] for col in cols), pos_w=off) == (1, linear)
                 s = gmc.quantize_rdo(*(col[i] for col in cols), lam, channel_skip=True, per_channel=True, channel_weights=cw_d[i],
-                                     position_weights=misaligned(pw_d[i]))
+                                     position_weights=off)
             else:
-                s = gmc.quantize_rdo(misaligned(cols[0][i]), *(col[i] for col in cols[1:]), lam, channel_skip=True, per_channel=True)
+                off = misaligned(cols[0][i])
+                assert F.form_of_one(off, *(col[i] for col in cols[1:]), pos_w=False) == (1, linear)
+                s = gmc.quantize_rdo(off, *(col[i] for col in cols[1:]), lam, channel_skip=True, per_channel=True)
             assert skey(s) == skey(got[i]), (lam, i)
         # stacked tensors: the two seeds of one shape as [2, ...] tensors
         for k in range(len(Q.SHAPES)):
@@ -263,7 +272,9 @@ def test_skip_curve_against_the_reference_and_against_quantize_rdo(oracle, mode,
                 q.bits_q_before, q.bits_q_after, q.n_changed, q.ddist_q, q.n_skipped, q.n_eligible), (j, lam)
     # a single call on the 1-wide path, 17 lambdas (two chunks), the same bits on every run
     for i in (0, 3, 6, n8):
-        one = gmc.rd_curve(misaligned(cols[0][i]), *(col[i] for col in cols[1:]), LAMBDAS16, channel_skip=True,
+        off = misaligned(cols[0][i])
+        assert F.form_of_one(off, *(col[i] for col in cols[1:]), pos_w=pw_d[i] if weighted else False) == (1, hws[i] % 64 == 0)
+        one = gmc.rd_curve(off, *(col[i] for col in cols[1:]), LAMBDAS16, channel_skip=True,
                            channel_weights=cw_d[i] if weighted else None, position_weights=pw_d[i] if weighted else None)
         assert ckey(one) + (one.n_skipped, one.n_eligible) == ckey(got[i]) + (got[i].n_skipped, got[i].n_eligible), i
     more = gmc.rd_curve_batch(*(col[:n8] for col in cols), LAMBDAS16 + [0.4], **kw(range(n8)))

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from flashgmm_amd import BudgetQuantized, GaussianMixtureConditional, RdCurve, RdoQuantized, _lib
+from tests import enc_ref as F
 from tests import rdcurve_ref as V
 from tests import rdo_weights_ref as W
 from tests import rdoq_ref as Q
@@ -98,9 +99,12 @@ def test_weighted_quantize_rdo_against_the_reference(oracle, mode, clamp):
         singles = [gmc.quantize_rdo(*(col[i] for col in cols), lam, per_channel=True, channel_weights=cw_d[i],
                                     position_weights=pw_d[i] if i % 2 else pw_d[i][None, None]) for i in range(len(cases))]
         assert [key(s) for s in singles] == [key(g) for g in got], lam
-        # a pos_w that is not 16-byte aligned sends the call down the 1-wide path: hw = 104 and the 4-wide shapes alike
-        for i in (3, 4, 6):
-            s = gmc.quantize_rdo(*(col[i] for col in cols), lam, per_channel=True, channel_weights=cw_d[i], position_weights=misaligned(pw_d[i]))
+        # a pos_w that is not 16-byte aligned sends the call down the 1-wide path (every shape here is 4-wide otherwise): hw = 128 and
+        # hw = 256 on the linear grid, hw = 104 on the tiled one
+        for i, aligned, form in ((3, (4, F.TILED), (1, F.LIN)), (4, (4, F.TILED), (1, F.TILED)), (6, (4, F.LIN), (1, F.LIN))):
+            off = misaligned(pw_d[i])
+            assert F.form_of_one(*(col[i] for col in cols), pos_w=pw_d[i]) == aligned and F.form_of_one(*(col[i] for col in cols), pos_w=off) == form
+            s = gmc.quantize_rdo(*(col[i] for col in cols), lam, per_channel=True, channel_weights=cw_d[i], position_weights=off)
             assert key(s) == key(got[i]), (lam, i)
         # stacked tensors: the two seeds of one shape as [2, ...] tensors, a shared [M] and an [N, 1, h, w]
         for k in range(len(Q.SHAPES)):
@@ -184,7 +188,9 @@ def test_weighted_curve_against_the_reference(oracle, mode, clamp):
             assert (g.bits_q_before, g.bits_q_after[j], g.n_changed[j]) == (q.bits_q_before, q.bits_q_after, q.n_changed), (j, lam)
     # single calls, a misaligned pos_w (1-wide), 17 lambdas (two chunks), the same bits on every run
     for i in (0, 3, 6):
-        one = gmc.rd_curve(*(col[i] for col in cols), LAMBDAS16, channel_weights=kw["channel_weights"][i], position_weights=misaligned(kw["position_weights"][i]))
+        off = misaligned(kw["position_weights"][i])
+        assert F.form_of_one(*(col[i] for col in cols), pos_w=off) == (1, i != 0)  # hw = 16 tiled; 128 and 256 fill 1-wide waves: linear
+        one = gmc.rd_curve(*(col[i] for col in cols), LAMBDAS16, channel_weights=kw["channel_weights"][i], position_weights=off)
         assert ckey(one) == ckey(got[i]), i
     more = gmc.rd_curve_batch(*cols, LAMBDAS16 + [0.4], **kw)
     assert [ckey(c)[2][:16] for c in more] == [ckey(g)[2] for g in got] and all(len(c.ddist_q) == 17 for c in more)
@@ -310,6 +316,7 @@ def test_bad_factors_fail_the_call_and_name_the_item(oracle):
         pw_bad = pw.copy()
         pw_bad[-1, -1] = bad  # in pos_w at the last position, on the 1-wide path, of item 0
         kw = dict(channel_weights=good["channel_weights"], position_weights=[misaligned(dv(pw_bad)), dv(pw)])
+        assert F.form_of(*cols, pos_w=kw["position_weights"]) == (1, F.TILED)
         with pytest.raises(RuntimeError, match=r"FGMM_ERR_INVALID.*item 0\b"):
             gmc.quantize_rdo_batch(*cols, 0.5, **kw)
         with pytest.raises(RuntimeError, match=r"FGMM_ERR_INVALID.*item 0\b"):

@@ -10,6 +10,7 @@ import torch
 
 from flashgmm_amd import GaussianMixtureConditional, RdoQuantized, _lib
 from tests import edge_corpus as E
+from tests import enc_ref as F
 from tests import rate_ref as R
 from tests import rdoq_ref as Q
 from tests import synth as T
@@ -51,7 +52,8 @@ def test_quantize_rdo_against_the_reference(oracle, mode, clamp):
     away = byp = 0
     for lam in Q.LAMBDAS:
         refs = [Q.rdoq(oracle, L, mode, *c, lam, clamp=clamp) for c in cases]
-        got = gmc.quantize_rdo_batch(*cols, lam, per_channel=True)  # (mixed shapes: the 1-wide path on the tile grid)
+        assert F.form_of(*cols) == (4, F.TILED)  # mixed shapes, every hw a multiple of 4: 4-wide on the tiled grid
+        got = gmc.quantize_rdo_batch(*cols, lam, per_channel=True)
         assert len(got) == len(cases)
         for i, (g, r) in enumerate(zip(got, refs)):
             check(g, r, (lam, i))
@@ -61,7 +63,9 @@ def test_quantize_rdo_against_the_reference(oracle, mode, clamp):
                 assert r["n_changed"] * 20 >= r["n_coded"] > 0, (i, r["n_changed"], r["n_coded"])
             if lam == 0.0:
                 assert g.n_changed == 0 and g.bits_q_after == g.bits_q_before
-        # single calls (each shape on its own grid: 4-wide, 1-wide, linear) agree with the batch; without the channel sums too
+        # single calls (each shape on its own grid: 4-wide, tiled at hw = 16, 128 and 104, linear at 256) agree with the batch; without
+        # the channel sums too
+        assert [F.form_of_one(*(col[i] for col in cols), pos_w=False) for i in range(0, len(cases), 2)] == [(4, F.TILED)] * 3 + [(4, F.LIN)]
         singles = [gmc.quantize_rdo(*(col[i] for col in cols), lam, per_channel=True) for i in range(len(cases))]
         assert [key(s) for s in singles] == [key(g) for g in got], lam
         for s, r in zip(singles, refs):
@@ -199,7 +203,7 @@ def test_edge_parameters(oracle, mode, clamp):
     means: un-clamped they go through the IEEE evaluation, clamped through the guards of the packed fast path (edge by edge)"""
     L = _lib.lib()
     gmc = GaussianMixtureConditional(K=4, mode=mode, clamp_scales=clamp)
-    M, h, w = 6, 8, 13  # hw = 104: the 1-wide path; 8 x 16 below: the 4-wide one
+    M, h, w = 6, 8, 13  # hw = 104 and, below, 8 x 16: both 4-wide, tiled - 26 lanes of one wave, and two full waves
     for fam in ("neg_sigma", "zero_sigma", "nonfinite_sigma", "tiny_and_huge_sigma", "huge_mu", "nonfinite_mu", "wide_sigma"):
         for (hh, ww) in ((h, w), (8, 16)):
             n = M * hh * ww
@@ -208,7 +212,9 @@ def test_edge_parameters(oracle, mode, clamp):
             y = (np.clip(p["v"], -60, 60) + rng.uniform(-0.5, 0.5, n)).astype(np.float32).reshape(1, M, hh, ww)
             planes = [np.ascontiguousarray(p[k].reshape(M, hh, ww, 4).transpose(3, 0, 1, 2).reshape(1, 4 * M, hh, ww)) for k in ("s", "m", "w")]
             ref = Q.rdoq(oracle, L, mode, y, *planes, 0.5, clamp=clamp)
-            check(gmc.quantize_rdo(dv(y), *(dv(a) for a in planes), 0.5, per_channel=True), ref, (fam, hh, ww))
+            t = [dv(y)] + [dv(a) for a in planes]
+            assert F.form_of_one(*t, pos_w=False) == (4, F.TILED)
+            check(gmc.quantize_rdo(*t, 0.5, per_channel=True), ref, (fam, hh, ww))
 
 
 # ---- (e) arguments ----------------------------------------------------------------------------------------------------------------------
