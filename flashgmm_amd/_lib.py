@@ -108,6 +108,12 @@ class fgmm_like_grad_item(C.Structure):
                 ("dweights", C.c_void_p), ("status", C.c_int32), ("pad_", C.c_int32)]
 
 
+class fgmm_centroid_item(C.Structure):
+    """one item of fgmm_gmc_centroid_batch (include/flashgmm_amd.h section 3i)"""
+    _fields_ = [("y", C.c_void_p), ("params", fgmm_params), ("M", C.c_int32), ("K", C.c_int32), ("hw", C.c_int64),
+                ("rec", C.c_void_p), ("n_kept", C.c_int64), ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
 def _item_dtype(struct=fgmm_item):
     """numpy view of ``fgmm_item[]`` (offsets taken from the ctypes declaration): lets a batch be filled column by
     column instead of field by field."""
@@ -132,6 +138,7 @@ RDOQ_ITEM_DTYPE = _item_dtype(fgmm_rdoq_item)
 RDCURVE_ITEM_DTYPE = _item_dtype(fgmm_rdcurve_item)
 LIKE_ITEM_DTYPE = _item_dtype(fgmm_like_item)
 LIKE_GRAD_ITEM_DTYPE = _item_dtype(fgmm_like_grad_item)
+CENTROID_ITEM_DTYPE = _item_dtype(fgmm_centroid_item)
 FGMM_LIKE_Q = 32  # unit of the likelihood call's bits_q: 2^-32 bit
 FGMM_RATE_Q = 24  # unit of the size estimate's costs: 2^-24 bit
 
@@ -213,6 +220,7 @@ SIGNATURES = {
     "fgmm_gmc_likelihood_backward_batch": (_i, [_p, _p, C.POINTER(fgmm_like_grad_item), _i, _i, C.c_float, C.c_float]),
     "fgmm_gmc_likelihood_logits_batch": (_i, [_p, _p, C.POINTER(fgmm_like_item), _i, _i, C.c_float, C.c_float]),
     "fgmm_gmc_likelihood_logits_backward_batch": (_i, [_p, _p, C.POINTER(fgmm_like_grad_item), _i, _i, C.c_float, C.c_float]),
+    "fgmm_gmc_centroid_batch": (_i, [_p, _p, C.POINTER(fgmm_centroid_item), _i, C.c_float, C.c_float]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

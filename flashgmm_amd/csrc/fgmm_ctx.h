@@ -570,6 +570,47 @@ int rdoq_check_items(const fgmm_rdoq_item *items, int count); // check_latent_it
 int rdoq_run(fgmm_ctx *ctx, dev::Stream stream, fgmm_rdoq_item *items, int count, int mode, int clamp, const double *lambdas, int lambda_stride,
              const fgmm_rdo_weights *w = nullptr, bool w_check = true, fgmm_rdo_skip *sk = nullptr);
 
+// ---- fgmm_like.cpp, fgmm_centroid.cpp: the calls on the encode frame without a census (sections 3g - 3i) --------------------------------
+// the EncDesc of an item of these calls: its latent and planes, no census (chan_list null), no table
+inline void like_desc(EncDesc &d, const float *y, const fgmm_params &p, int M, int64_t hw) {
+  memset(&d, 0, sizeof d);
+  d.y = y;
+  d.scales = p.scales, d.means = p.means, d.weights = p.weights;
+  d.stride_k = p.stride_k, d.stride_c = p.stride_c, d.stride_p = 1;
+  d.hw = hw;
+  d.M = M;
+  d.seg_b[0] = d.seg_b[1] = d.seg_b[2] = INT32_MAX;
+}
+// positions per lane (8, two-byte planes only; 4; 1) and the grid every item of the batch allows
+struct LikeShape {
+  int M_max = 0, vec = 1;
+  int64_t hw_max = 0, n_max = 0;
+  bool linear = true, vec4 = true, vec8 = true;
+  static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+  void item(const EncDesc &d, bool two_byte, std::initializer_list<const void *> others) {
+    bool ok4 = true, ok16 = true;
+    for (const void *o : others) ok4 = ok4 && enc_vec4_ok(d, o, two_byte), ok16 = ok16 && aligned16(o);
+    vec4 = vec4 && ok4;
+    vec8 = vec8 && ok4 && ok16 && two_byte && (d.hw & 7) == 0 && (d.stride_c & 7) == 0 && (d.stride_k & 7) == 0 && aligned16(d.scales) &&
+           aligned16(d.means) && aligned16(d.weights);
+    M_max = std::max(M_max, d.M);
+    hw_max = std::max(hw_max, d.hw);
+    n_max = std::max(n_max, (int64_t)d.M * d.hw);
+  }
+  void done(const EncDesc *hd, int count, int vec_cap) {
+    vec = vec4 ? (vec8 && vec_cap >= 8 ? 8 : 4) : 1;
+    auto fills = [&](int v) { // every wave of the linear grid full at v positions per lane
+      for (int i = 0; i < count; ++i)
+        if (hd[i].hw % (64 * v)) return false;
+      return true;
+    };
+    // 8 per lane only where that keeps the linear grid: a 768-position Kodak plane fills 96 of the 256 lanes of its tiled block at 8 per
+    // lane, and every wave of the linear grid at 4
+    if (vec == 8 && !fills(8) && fills(4)) vec = 4;
+    linear = fills(vec);
+  }
+};
+
 constexpr size_t kCounterBytes = kTabCounters * sizeof(unsigned long long); // per launch unit, see DecDesc::counters
 
 } // namespace fgmm

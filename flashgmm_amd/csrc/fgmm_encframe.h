@@ -245,6 +245,53 @@ __device__ __forceinline__ unsigned long long rdo_skip_dz(float y, float vq, dou
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Section 3g's terms of one mixture component, ONE text for the likelihood kernels (fgmm_like.hip) and centroid_kernel
+// (fgmm_centroid.hip, section 3i): s = max(sigma, sb) keeping a NaN sigma (LowerBound, bound_ops.py:36-37), the two standardised edges,
+// p = u - l; and the density at an edge
+// ---------------------------------------------------------------------------------------------------------
+constexpr float kLikeC = (float)(-0.70710678118654752440);       // (float)(-(2^-0.5))            entropy_models.py:676
+constexpr float kLikeInvSqrt2Pi = (float)0.39894228040143267794; // (float)(1 / sqrt(2 pi))
+__device__ __forceinline__ float like_term(float v, float mu, float sigma, float sb, float &s, float &xu, float &xl) {
+  s = max_nan(sigma, sb);
+  const float a = __builtin_fabsf(v - mu);
+  xu = (0.5f - a) / s;
+  xl = (-0.5f - a) / s;
+  const float u = 0.5f * erfcf(kLikeC * xu);
+  const float l = 0.5f * erfcf(kLikeC * xl);
+  return u - l;
+}
+__device__ __forceinline__ float like_phi(float x) { return expf(-0.5f * x * x) * kLikeInvSqrt2Pi; }
+
+// ---------------------------------------------------------------------------------------------------------
+// the ladder of the kernels without a mode (like_kernel, like_bwd_kernel, centroid_kernel): VEC (1, 4, and 8 for two-byte planes where
+// F::kVec8 says the kernel has it) x plane type x grid.  F::go<VEC, PT, LINEAR>(grid, stream) does the kernel's hipLaunchKernelGGL
+// ---------------------------------------------------------------------------------------------------------
+template <int VEC, typename PT, bool LINEAR, typename F> static int like_launch_v(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, hipStream_t s) {
+  const int64_t per_block = (int64_t)kBlock * VEC;
+  const dim3 grid = LINEAR ? dim3((unsigned)((n_max + per_block - 1) / per_block), 1u, (unsigned)count)
+                           : dim3((unsigned)((hw_max + per_block - 1) / per_block), (unsigned)M_max, (unsigned)count);
+  f.template go<VEC, PT, LINEAR>(grid, s);
+  return (int)hipGetLastError();
+}
+template <typename PT, bool LINEAR, typename F> static int like_launch_t(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, int vec, hipStream_t s) {
+  if constexpr (F::kVec8 && sizeof(PT) == 2)
+    if (vec == 8) return like_launch_v<8, PT, LINEAR>(f, count, M_max, hw_max, n_max, s);
+  if (vec >= 4) return like_launch_v<4, PT, LINEAR>(f, count, M_max, hw_max, n_max, s);
+  return like_launch_v<1, PT, LINEAR>(f, count, M_max, hw_max, n_max, s);
+}
+template <typename F> static int like_launch(const F &f, int count, int M_max, int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, void *stream) {
+  if (count <= 0 || M_max <= 0 || hw_max <= 0) return 0;
+  if (linear && (n_max + kBlock - 1) / kBlock > 0x7FFFFFFFll) linear = false;        // grid.x
+  if (count > 65535 || (!linear && M_max > 65535)) return (int)hipErrorInvalidValue; // grid.z; grid.y is M_max on the tiled grid only
+  hipStream_t s = (hipStream_t)stream;
+  if (planes == FGMM_BF16)
+    return linear ? like_launch_t<__bf16, true>(f, count, M_max, hw_max, n_max, vec, s) : like_launch_t<__bf16, false>(f, count, M_max, hw_max, n_max, vec, s);
+  if (planes == FGMM_F16)
+    return linear ? like_launch_t<_Float16, true>(f, count, M_max, hw_max, n_max, vec, s) : like_launch_t<_Float16, false>(f, count, M_max, hw_max, n_max, vec, s);
+  return linear ? like_launch_t<float, true>(f, count, M_max, hw_max, n_max, vec, s) : like_launch_t<float, false>(f, count, M_max, hw_max, n_max, vec, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // the launchers' ladder.  F::go<MODE, VEC, CLAMPED, PT, LINEAR>(grid, stream) does the kernel's hipLaunchKernelGGL with its own
 // arguments.  ALL_VEC: VEC = 2, and 8 for two-byte planes, exist too (symtab_kernel's A/B forms and its fp16 / bf16 default); else vec >= 4 is 4
 // and anything below is 1.  M_max, hw_max, n_max: the largest M, hw and M * hw of the batch.

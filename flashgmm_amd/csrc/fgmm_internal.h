@@ -377,6 +377,15 @@ int launch_like(const EncDesc *d_descs, const LikeDesc *d_ldescs, int round, flo
 int launch_like_bwd(const EncDesc *d_descs, const LikeGradDesc *d_gdescs, int round, float scale_bound, float likelihood_bound, int count, int M_max,
                     int64_t hw_max, int64_t n_max, bool linear, int vec, int planes, bool logits, void *stream);
 
+// ---- centroid reconstruction of a decoded latent (fgmm_centroid.hip, fgmm_centroid.cpp; header section 3i) ----------------------
+struct CentroidDesc {        // item i of a centroid_kernel launch, beside its EncDesc (chan_list null: every channel, no census)
+  float *rec;                // device [M * hw]: the reconstruction; may be the EncDesc's y
+  unsigned long long *kept;  // device [1], zeroed by the host: latents with keep
+};
+// the addressing of launch_like's forward.  logits: the weights planes hold logits
+int launch_centroid(const EncDesc *d_descs, const CentroidDesc *d_cdescs, float scale_bound, float p_min, int count, int M_max, int64_t hw_max,
+                    int64_t n_max, bool linear, int vec, int planes, bool logits, void *stream);
+
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the
 // encoder asks it for storage of the stream's exact size once that is known and copies the stream there out of its scratch: the

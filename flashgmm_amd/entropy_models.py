@@ -268,7 +268,8 @@ class _LatentItems:
     of a stacked batch, or ``ys``, the latents of a sequence."""
 
     DTYPES = {_lib.fgmm_rate_item: _lib.RATE_ITEM_DTYPE, _lib.fgmm_rdoq_item: _lib.RDOQ_ITEM_DTYPE, _lib.fgmm_rdcurve_item: _lib.RDCURVE_ITEM_DTYPE,
-              _lib.fgmm_like_item: _lib.LIKE_ITEM_DTYPE, _lib.fgmm_like_grad_item: _lib.LIKE_GRAD_ITEM_DTYPE}
+              _lib.fgmm_like_item: _lib.LIKE_ITEM_DTYPE, _lib.fgmm_like_grad_item: _lib.LIKE_GRAD_ITEM_DTYPE,
+              _lib.fgmm_centroid_item: _lib.CENTROID_ITEM_DTYPE}
     __slots__ = ("arr", "items", "N", "keep", "dev", "shape", "ys")
 
     def __init__(self, struct, N, keep, dev=None, shape=None, ys=None):
@@ -902,6 +903,35 @@ class GaussianMixtureConditional(nn.Module):
         """-> the ``RateEstimate`` of ``compress(y, scales, means, weights)``: its size, without coding"""
         return self.estimate_bits_batch([y], [scales], [means], [weights], weights_are_logits=weights_are_logits, per_channel=per_channel,
                                         per_latent=per_latent)[0]
+
+    def reconstruct_batch(self, y_hats, scales, means, weights, *, weights_are_logits: bool = False, p_min: float = 2.0 ** -16,
+                          return_kept: bool = False):
+        """Centroid reconstruction of decoded latents (include/flashgmm_amd.h section 3i): per latent the conditional mean of its bin
+        ``[q - 1/2, q + 1/2)`` under its mixture, which minimises the expected squared LATENT error - the decoder-side twin of
+        ``quantize_rdo_batch``, at no bit and with no change of format.  What it buys in the image domain depends on the trained
+        synthesis transform and is not claimed.  A latent whose bin has a likelihood below ``p_min`` (default: the coder's resolution),
+        whose offset would leave the bin or whose terms are not finite keeps ``round(y_hat)``.  One kernel; the scale bound is the
+        module's ``scale_bound``, as in ``forward``.  Inputs as ``estimate_bits_batch`` takes them - sequences of ``[1, M, h, w]`` /
+        ``[1, K*M, h, w]`` tensors, or stacked; no autograd, the inputs are detached.  -> per item the float32 reconstruction
+        ``[1, M, h, w]``, or ``(reconstruction, n_kept)`` with ``return_kept`` - ``n_kept`` the latents that left the integer grid."""
+        self._check_k()
+        p_min = float(p_min)
+        if not 0.0 < p_min < float("inf"):
+            raise ValueError(f"p_min = {p_min!r}: must be positive and finite")
+        detach = lambda t: t.detach() if isinstance(t, Tensor) else [x.detach() for x in t]  # noqa: E731
+        L = self._latent_items(_lib.fgmm_centroid_item, *(detach(t) for t in (y_hats, scales, means, weights)), weights_are_logits)
+        if L.N == 0:
+            return []
+        recs = L.output("rec", torch.float32, per_latent=True)
+        rc = _lib.lib().fgmm_gmc_centroid_batch(*L.call(), L.arr, L.N, self.scale_bound, p_min)
+        _lib.check(rc, "GaussianMixtureConditional.reconstruct")
+        return list(zip(recs, L.items["n_kept"].tolist())) if return_kept else list(recs)
+
+    def reconstruct(self, y_hat: Tensor, scales: Tensor, means: Tensor, weights: Tensor, *, weights_are_logits: bool = False,
+                    p_min: float = 2.0 ** -16, return_kept: bool = False):
+        """-> the centroid reconstruction of one decoded latent (``reconstruct_batch``), ``(rec, n_kept)`` with ``return_kept``"""
+        return self.reconstruct_batch([y_hat], [scales], [means], [weights], weights_are_logits=weights_are_logits, p_min=p_min,
+                                      return_kept=return_kept)[0]
 
     def quantize_rdo_batch(self, ys, scales, means, weights, lam: float, *, weights_are_logits: bool = False,
                            per_channel: bool = False, channel_weights=None, position_weights=None, channel_skip: bool = False) -> List[RdoQuantized]:

@@ -59,8 +59,16 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
                  chunks: Tuple[str, ...] = ("scales", "means", "weights"), mode=None, param_dtype: torch.dtype = torch.float32,
                  fuse_softmax: bool = False, checkpoint_stride: int = 0, rdo_lambda: float = 0.0, target_bytes: Optional[int] = None,
                  rdo_channel_weights: Optional[Tensor] = None, rdo_channel_skip: bool = False, fuse_forward_softmax: bool = False,
-                 **kwargs: Any):
+                 centroid: bool = False, centroid_p_min: float = 2.0 ** -16, **kwargs: Any):
         super().__init__()
+        # centroid: the decompress calls add "y_rec" beside "y_hat" - per latent the conditional mean of its bin under the mixture it was
+        # decoded with (GaussianMixtureConditional.reconstruct, include/flashgmm_amd.h section 3i), which minimises the expected squared
+        # LATENT error; what that buys in the image domain depends on the trained synthesis transform and has not been measured.  A
+        # decoder-side choice: "y_hat" and the bitstreams are untouched, the encoder needs no switch.  False: no new key, nothing launched
+        self.centroid = bool(centroid)
+        self.centroid_p_min = float(centroid_p_min)
+        if not 0.0 < self.centroid_p_min < float("inf"):
+            raise ValueError("centroid_p_min must be positive and finite")
         # fuse_forward_softmax: forward() hands the parameter network's output to GaussianMixtureConditional.forward_params as it is -
         # the softmax over K and its derivative run inside the two likelihood kernels (include/flashgmm_amd.h section 3h), on the pi
         # the coder's kernels make of the same logits, and the gradient of the output is written as one tensor.  It does not touch
@@ -230,14 +238,27 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
     def decompress(self, strings: List[Any], shape: Tuple[int, int], ctx_params: Tensor, **kwargs: Any) -> Dict[str, Any]:
         (y_strings,) = strings
         scales_hat, means_hat, weights = self._params(ctx_params)
+        weighted_sum = None
         if self.quantizer == "noise":
-            y_hat = self.gaussian_mixture_conditional.decompress(*y_strings, *self._planes(scales_hat, means_hat, weights),
-                                                                 weights_are_logits=self.fuse_softmax)
+            planes = self._planes(scales_hat, means_hat, weights)
+            decoded = self.gaussian_mixture_conditional.decompress(*y_strings, *planes, weights_are_logits=self.fuse_softmax)
+            y_hat = decoded
         else:
             weighted_sum, means_rel = self._recentre(means_hat, weights)
-            y_hat = self.gaussian_mixture_conditional.decompress(*y_strings, *self._planes(scales_hat, means_rel, weights)) + weighted_sum
+            planes = self._planes(scales_hat, means_rel, weights)
+            decoded = self.gaussian_mixture_conditional.decompress(*y_strings, *planes)
+            y_hat = decoded + weighted_sum
         assert tuple(y_hat.shape[2:4]) == tuple(shape)
-        return {"y_hat": y_hat}
+        if not self.centroid:
+            return {"y_hat": y_hat}
+        return {"y_hat": y_hat, "y_rec": self._reconstruct([decoded], [planes], [weighted_sum], self.fuse_softmax)[0]}
+
+    def _reconstruct(self, decoded: List[Tensor], planes, sums, logits: bool) -> List[Tensor]:
+        """The "y_rec" of decoded items: the centroid of what the coder decoded, under the planes the coder was given (one batched call);
+        for ``weighted_mean_ste`` that is the residual under the relative means, and ``weighted_sum`` is added afterwards"""
+        ss, ms, ws = (list(t) for t in zip(*planes))
+        recs = self.gaussian_mixture_conditional.reconstruct_batch(decoded, ss, ms, ws, weights_are_logits=logits, p_min=self.centroid_p_min)
+        return [rec if add is None else rec + add for rec, add in zip(recs, sums)]
 
     # ---- the parameter head fused (SURVEY.md section 8 f2): `feat` = the input of entropy_parameters' LAST layer, `head` = a ParameterHead
     # of that layer.  The codec owning the parameter network (CheckerboardLatentCodec(fuse_head=True)) calls these.
@@ -263,7 +284,11 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
                                                                   weights_are_logits=True)
         for y_hat in outs:
             assert tuple(y_hat.shape[2:4]) == tuple(shape)
-        return [{"y_hat": y_hat} for y_hat in outs]
+        if not self.centroid:
+            return [{"y_hat": y_hat} for y_hat in outs]
+        recs = self.gaussian_mixture_conditional.reconstruct_batch(torch.cat(list(outs)), scales, means, logits, weights_are_logits=True,
+                                                                   p_min=self.centroid_p_min)  # (under the head's logits, as decoded)
+        return [{"y_hat": y_hat, "y_rec": rec} for y_hat, rec in zip(outs, recs)]
 
     def decompress_many(self, strings: List[List[Any]], shape: Tuple[int, int], ctx_params: List[Tensor]) -> List[Dict[str, Any]]:
         """``decompress`` of N independent items (the same stage of N images) in ONE batched native call: N host decoders
@@ -286,6 +311,9 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
         for y_hat, add in zip(outs, sums):
             assert tuple(y_hat.shape[2:4]) == tuple(shape)
             res.append({"y_hat": y_hat if add is None else y_hat + add})
+        if self.centroid:
+            for r, rec in zip(res, self._reconstruct(list(outs), planes, sums, self.fuse_softmax)):
+                r["y_rec"] = rec
         return res
 
     def forward(self, y: Tensor, ctx_params: Tensor) -> Dict[str, Any]:
@@ -458,16 +486,23 @@ class CheckerboardLatentCodec(nn.Module):
         c, h, w = shape
         codec = self.latent_codec["y"]
         y_hat_ = side_params.new_zeros((2, n, c, h, w // 2))
+        y_rec_ = None  # the halves' "y_rec", where the latent codec gives one (its `centroid`); the context below keeps using y_hat
         side_params_ = self.unembed(side_params)
         for i in range(2):  # sequential by construction: the non-anchor parameters need the decoded anchors
             if self.fuse_head:
                 body, head = self._head_parts()
                 feat_i = body(self.merge(self._ctx(y_hat_, i), side_params_[i]))
-                y_hat_[i] = codec.decompress_many_head([[strings[i]]], (h, w // 2), [feat_i], head)[0]["y_hat"]
-                continue
-            params_i = self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_params_[i]))
-            y_hat_[i] = codec.decompress([strings[i]], (h, w // 2), params_i)["y_hat"]
-        return {"y_hat": self.embed(y_hat_)}
+                out = codec.decompress_many_head([[strings[i]]], (h, w // 2), [feat_i], head)[0]
+            else:
+                params_i = self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_params_[i]))
+                out = codec.decompress([strings[i]], (h, w // 2), params_i)
+            y_hat_[i] = out["y_hat"]
+            if "y_rec" in out:
+                y_rec_ = torch.zeros_like(y_hat_) if y_rec_ is None else y_rec_
+                y_rec_[i] = out["y_rec"]
+        if y_rec_ is None:
+            return {"y_hat": self.embed(y_hat_)}
+        return {"y_hat": self.embed(y_hat_), "y_rec": self.embed(y_rec_)}
 
     def decompress_many(self, strings: List[List[Any]], shape: Tuple[int, ...], side_params: List[Tensor]) -> List[Dict[str, Any]]:
         """N images of one shape, STAGE-MAJOR: the anchors of every image in one batched native call, then the non-anchors
@@ -476,6 +511,7 @@ class CheckerboardLatentCodec(nn.Module):
         c, h, w = shape
         codec = self.latent_codec["y"]
         y_hat_ = [sp.new_zeros((2, 1, c, h, w // 2)) for sp in side_params]
+        y_rec_ = None  # (as in decompress)
         side_ = [self.unembed(sp) for sp in side_params]
         for i in range(2):
             if self.fuse_head:
@@ -487,7 +523,13 @@ class CheckerboardLatentCodec(nn.Module):
                 outs = codec.decompress_many([[st[i]] for st in strings], (h, w // 2), params)
             for yh, o in zip(y_hat_, outs):
                 yh[i] = o["y_hat"]
-        return [{"y_hat": self.embed(yh)} for yh in y_hat_]
+            if outs and "y_rec" in outs[0]:
+                y_rec_ = [torch.zeros_like(yh) for yh in y_hat_] if y_rec_ is None else y_rec_
+                for yr, o in zip(y_rec_, outs):
+                    yr[i] = o["y_rec"]
+        if y_rec_ is None:
+            return [{"y_hat": self.embed(yh)} for yh in y_hat_]
+        return [{"y_hat": self.embed(yh), "y_rec": self.embed(yr)} for yh, yr in zip(y_hat_, y_rec_)]
 
     def forward(self, y: Tensor, side_params: Tensor):
         raise NotImplementedError("training-time likelihoods are outside the entropy-coding path")
@@ -610,6 +652,7 @@ class ChannelGroupsLatentCodec(nn.Module):
         channels = sum(s_[0] for s_ in shape)
         y_hats = [torch.zeros((1, channels, *shape[0][1:]), device=sp.device) for sp in side_params]
         views = [yh.split(self.groups, dim=1) for yh in y_hats]
+        recs = []  # per group, per image: the group codec's "y_rec" or None
         for k in range(len(self.groups)):
             codec = self.latent_codec[f"y{k}"]
             params = [self._get_ctx_params(k, sp, v) for sp, v in zip(side_params, views)]
@@ -620,14 +663,21 @@ class ChannelGroupsLatentCodec(nn.Module):
                 outs = [codec.decompress(st, shape[k], pr) for st, pr in zip(sub, params)]
             for v, o in zip(views, outs):
                 v[k].copy_(o["y_hat"])
-        return [{"y_hat": yh} for yh in y_hats]
+            recs.append([o.get("y_rec") for o in outs])
+        res = [{"y_hat": yh} for yh in y_hats]
+        if recs and all(r is not None for rs in recs for r in rs):  # every group's codec gives a "y_rec": concatenated; the context above keeps using y_hat
+            for i, r in enumerate(res):
+                r["y_rec"] = self.merge_y(*(rs[i] for rs in recs))
+        return res
 
     def decompress(self, strings: List[Any], shape: List[Tuple[int, ...]], side_params: Tensor, **kwargs: Any) -> Dict[str, Any]:
         per_group = len(strings) // len(self.groups)
         channels = sum(s[0] for s in shape)
         y_hat = torch.zeros((1, channels, *shape[0][1:]), device=side_params.device)  # batch 1, as the reference (:139)
-        self._run(y_hat, side_params, lambda k, params: self.latent_codec[f"y{k}"].decompress(
+        results = self._run(y_hat, side_params, lambda k, params: self.latent_codec[f"y{k}"].decompress(
             strings[per_group * k: per_group * (k + 1)], shape[k], params))
+        if results and all("y_rec" in r for r in results):  # concatenated; the channel context (_run) keeps using y_hat
+            return {"y_hat": y_hat, "y_rec": self.merge_y(*(r["y_rec"] for r in results))}
         return {"y_hat": y_hat}
 
     def forward(self, y: Tensor, side_params: Tensor):

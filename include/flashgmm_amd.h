@@ -54,6 +54,7 @@ extern "C" {
 #define FGMM_HAS_BF16 1        /* section 2: FGMM_BF16 parameter planes in every call that takes planes (added without a bump, as 3b - 3f) */
 #define FGMM_HAS_LIKELIHOOD 1  /* section 3g: fgmm_gmc_likelihood_batch, fgmm_gmc_likelihood_backward_batch (added without a bump, as 3b - 3f) */
 #define FGMM_HAS_LIKELIHOOD_LOGITS 1 /* section 3h: fgmm_gmc_likelihood_logits_batch, fgmm_gmc_likelihood_logits_backward_batch (added without a bump, as 3b - 3g) */
+#define FGMM_HAS_CENTROID 1  /* section 3i: fgmm_gmc_centroid_batch (added without a bump, as 3b - 3h) */
 #define FGMM_RDO_W_MAX 256.0f  /* largest factor of a weighted call's chan_w / pos_w */
 
 typedef enum {
@@ -841,6 +842,58 @@ int fgmm_gmc_likelihood_logits_batch(fgmm_ctx *ctx, void *stream, fgmm_like_item
                                      float likelihood_bound);
 int fgmm_gmc_likelihood_logits_backward_batch(fgmm_ctx *ctx, void *stream, fgmm_like_grad_item *items, int count, int round, float scale_bound,
                                               float likelihood_bound);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3i. CENTROID RECONSTRUCTION of a decoded latent: the conditional mean of the bin [q - 1/2, q + 1/2) under the latent's mixture
+ *    (the Lloyd-Max centroid), which minimises the expected squared latent error.  The decoder holds the twelve parameters of
+ *    every latent; this spends them, as RDOQ (3c) does on the encoder side.  It costs no bit and changes no format; what it buys in
+ *    the image domain depends on the trained synthesis transform and is not claimed here.  One kernel, on the frame and with the
+ *    terms of 3g's forward.  Per latent, in binary32, every operation one IEEE operation (no contraction, correctly rounded '/'),
+ *    K = 4; sb = scale_bound and p_min are binary32 values of the caller's; xu, xl, u, l, p_k, L and phi are exactly 3g's:
+ *      v    = rintf(y)                     (y is normally the decoder's integer y_hat: rintf is then the identity)
+ *      s_k  = max(sigma_k, sb), a NaN sigma stays NaN; no upper clamp - this is the trained model's density, not the coder's Phi
+ *      t_k  = v - mu_k        a_k = fabsf(t_k)        sg_k = (t_k > 0) - (t_k < 0)
+ *      xu   = (0.5f - a_k) / s_k           xl = (-0.5f - a_k) / s_k
+ *      p_k  = 0.5f * erfcf(c * xu) - 0.5f * erfcf(c * xl)
+ *      L    = (((0 + p_0*pi_0) + p_1*pi_1) + p_2*pi_2) + p_3*pi_3                 (3g's L, NOT bounded)
+ *      phi(x) = expf((-0.5f * x) * x) * (float)(1/sqrt(2*pi))
+ *      m_k, the bin's first moment about v under component k up to its sign -
+ *        narrow component (s_k < 2):   m_k = a_k*p_k - s_k*(phi(xu) - phi(xl))
+ *        wide component (s_k >= 2):    h = 0.5f / s_k      xb = a_k * (h + h)      h2 = h*h      x2 = xb*xb
+ *                                      q   = (C23 + (h2*(x2 - 3)) * C15) + ((h2*h2) * ((x2 - 10)*x2 + 15)) * C420
+ *                                      m_k = ((a_k * phi(xb)) * (h*h2)) * q
+ *                                      C23 = (float)(2/3), C15 = (float)(1/15), C420 = (float)(1/420)
+ *      N    = sum_k (pi_k*sg_k) * m_k      (from 0, k ascending, separate multiply and add)
+ *      off  = (-N) / L
+ *      keep = (L >= p_min) && (fabsf(off) <= 0.5f) && every s_k < +inf             (any NaN makes it false)
+ *      rec  = keep ? v + off : v
+ *    The wide form is the narrow one expanded in h = 1/(2 s_k) (terms h^3, h^5, h^7 of the moment; the next one is below 3e-5 of
+ *    the first at s_k = 2, |t_k| <= 4.5 s_k).  It is there because the narrow form cancels to 1/(12 s_k^2) of its terms: in binary32
+ *    it is off by 5e-3 at sigma near 256 and by up to 0.49 at sigma up to 3000.  A component whose sigma is +inf carries no mass;
+ *    the latent then keeps v, like one with any NaN among its terms.  p_min: below the coder's resolution (2^-16, the Python
+ *    default) the symbol is bypass-coded, the model says nothing about the bin and L is rounding noise.  A non-finite y has L = 0
+ *    or NaN and comes back as rintf(y).
+ *    With FGMM_PARAMS_LOGITS in every item's params.flags the weights planes hold logits and pi = softmax4(l) as in 3h; the result
+ *    is, bit for bit, that of the plain call on float32 planes holding fgmm_softmax4_hip's weights.  Non-finite logits give what
+ *    softmax4 gives, as in 3h: a NaN or -inf logit is a component of weight 0; a +inf logit, or four of -inf, give NaN weights and
+ *    the latent keeps v.  One call is one form.  Planes are float32, float16 or bfloat16 (one dtype per batch,
+ *    widened exactly on load: the result is that of float32 planes holding the widened values, bit for bit).  The launch form -
+ *    positions per lane, grid - is decided exactly as in 3g's forward.
+ *    rec: DEVICE float32 [M*hw]; it may be y itself.  n_kept: the latents with keep, counted per wave and summed by one integer
+ *    atomic per wave - the same bits on every run.  Refused with FGMM_ERR_INVALID before any launch, nothing written: K != 4,
+ *    flags other than 0 or FGMM_PARAMS_LOGITS or differing within the batch, a null y or rec, a scale_bound that is not positive
+ *    and finite, a p_min that is not positive and finite.  The caller's-stream contract is section 2's.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *y;          /* device [M*hw] */
+  fgmm_params params;      /* flags: 0, or FGMM_PARAMS_LOGITS in every item of the batch */
+  int32_t M, K;
+  int64_t hw;
+  float *rec;              /* DEVICE float32[M*hw] out; may alias y */
+  int64_t n_kept;          /* out: latents whose reconstruction left the integer grid's v (keep) */
+  int32_t status, pad_;    /* out */
+} fgmm_centroid_item;
+int fgmm_gmc_centroid_batch(fgmm_ctx *ctx, void *stream, fgmm_centroid_item *items, int count, float scale_bound, float p_min);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
