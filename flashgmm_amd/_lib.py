@@ -114,6 +114,20 @@ class fgmm_centroid_item(C.Structure):
                 ("rec", C.c_void_p), ("n_kept", C.c_int64), ("status", C.c_int32), ("pad_", C.c_int32)]
 
 
+class fgmm_eb_call(C.Structure):
+    """the call structure of fgmm_eb_likelihood (include/flashgmm_amd.h section 3j); ``bits_q`` / ``n_nonfinite``: HOST int64 ``[B]``"""
+    _fields_ = [("x", C.c_void_p), ("theta", C.c_void_p), ("med", C.c_void_p), ("B", C.c_int32), ("C", C.c_int32), ("hw", C.c_int64),
+                ("like_out", C.c_void_p), ("v_out", C.c_void_p), ("bits_q", C.c_void_p), ("n_nonfinite", C.c_void_p),
+                ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
+class fgmm_eb_grad_call(C.Structure):
+    """the call structure of fgmm_eb_likelihood_backward (section 3j); ``g_bits``: HOST float64 ``[B]``, read when ``g_like`` is null"""
+    _fields_ = [("x", C.c_void_p), ("theta", C.c_void_p), ("med", C.c_void_p), ("B", C.c_int32), ("C", C.c_int32), ("hw", C.c_int64),
+                ("g_like", C.c_void_p), ("g_bits", C.c_void_p), ("dx", C.c_void_p), ("dtheta", C.c_void_p), ("dmed", C.c_void_p),
+                ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
 def _item_dtype(struct=fgmm_item):
     """numpy view of ``fgmm_item[]`` (offsets taken from the ctypes declaration): lets a batch be filled column by
     column instead of field by field."""
@@ -139,6 +153,8 @@ RDCURVE_ITEM_DTYPE = _item_dtype(fgmm_rdcurve_item)
 LIKE_ITEM_DTYPE = _item_dtype(fgmm_like_item)
 LIKE_GRAD_ITEM_DTYPE = _item_dtype(fgmm_like_grad_item)
 CENTROID_ITEM_DTYPE = _item_dtype(fgmm_centroid_item)
+FGMM_EB_PARAMS = 58  # float32 values per channel of section 3j's theta
+FGMM_EB_SLICE = 1024  # section 3j: elements of a channel one workgroup walks
 FGMM_LIKE_Q = 32  # unit of the likelihood call's bits_q: 2^-32 bit
 FGMM_RATE_Q = 24  # unit of the size estimate's costs: 2^-24 bit
 
@@ -221,6 +237,8 @@ SIGNATURES = {
     "fgmm_gmc_likelihood_logits_batch": (_i, [_p, _p, C.POINTER(fgmm_like_item), _i, _i, C.c_float, C.c_float]),
     "fgmm_gmc_likelihood_logits_backward_batch": (_i, [_p, _p, C.POINTER(fgmm_like_grad_item), _i, _i, C.c_float, C.c_float]),
     "fgmm_gmc_centroid_batch": (_i, [_p, _p, C.POINTER(fgmm_centroid_item), _i, C.c_float, C.c_float]),
+    "fgmm_eb_likelihood": (_i, [_p, _p, C.POINTER(fgmm_eb_call), _i, C.c_float]),
+    "fgmm_eb_likelihood_backward": (_i, [_p, _p, C.POINTER(fgmm_eb_grad_call), _i, C.c_float]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

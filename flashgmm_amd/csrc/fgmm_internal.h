@@ -386,6 +386,26 @@ struct CentroidDesc {        // item i of a centroid_kernel launch, beside its E
 int launch_centroid(const EncDesc *d_descs, const CentroidDesc *d_cdescs, float scale_bound, float p_min, int count, int M_max, int64_t hw_max,
                     int64_t n_max, bool linear, int vec, int planes, bool logits, void *stream);
 
+// ---- the entropy bottleneck's factorized density (fgmm_eb.hip, fgmm_eb.cpp; header section 3j) ------------------------------------
+constexpr int kEbRow = FGMM_EB_PARAMS + 1; // a partial row of the backward: dH | db | dt in theta's order, then the channel's sum of dv
+struct EbArgs {              // one call of either kernel: the header's call structures, the host arrays replaced by workspace
+  const float *x, *theta, *med;
+  float *like, *v;           // forward: device [B, C, hw] or null
+  unsigned long long *sums;  // forward: device [B][2], zeroed by the host: bits_q | elements left out of it
+  const float *g_like;       // backward: device [B, C, hw], or null: g is formed from gbits
+  const float *gbits;        // backward: device [B], (float)g_bits of every item (g_like null)
+  float *dx;                 // backward: device [B, C, hw] or null
+  double *rows;              // backward: device [C][S][kEbRow], one row per workgroup
+  int64_t hw, n;             // n = B * hw, a channel's elements
+  int32_t B, C, S, mode;     // S = ceil(n / FGMM_EB_SLICE)
+  float lb;
+};
+// One workgroup per (channel, slice): C * S of them.  vec: 4 or 1 positions per lane (the backward kernel takes one per lane and pass)
+int launch_eb(const EbArgs &a, int vec, void *stream);
+int launch_eb_bwd(const EbArgs &a, void *stream);
+// sums a channel's S rows in index order, applies the dM / df step -> dtheta [C][58] (may be null), dmed [C] (may be null)
+int launch_eb_finish(const float *theta, const double *rows, float *dtheta, float *dmed, int C, int S, int mode, void *stream);
+
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the
 // encoder asks it for storage of the stream's exact size once that is known and copies the stream there out of its scratch: the

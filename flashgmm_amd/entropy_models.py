@@ -23,11 +23,12 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 from torch import Tensor
 
 from . import _boundary, _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneck", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -1249,3 +1250,199 @@ class EntropyBottleneckCoder(nn.Module):
         med = self.medians.reshape(1, -1, *([1] * len(size)))
         # dequantize(outputs, means): outputs.type_as(means) + means  (:197-204)
         return torch.from_numpy(sym).to(dev).reshape(len(strings), self.channels, *size).to(torch.float32) + med
+
+
+# ---- the entropy bottleneck's density model (include/flashgmm_amd.h section 3j) ---------------------------------------------------------
+class _EbLikelihoodFn(torch.autograd.Function):
+    """``EntropyBottleneck.forward`` / ``rate_bits`` on the GPU (section 3j): one kernel forward; a backward kernel that recomputes both
+    chains from the inputs and a small one that sums its rows - nothing but the inputs is saved.  ``x`` ``[B, C, hw]`` float32 contiguous,
+    ``theta`` ``[C, 58]`` float32 (the raw parameters in the header's order), ``med`` ``[C]``.  ``mode`` 1: the kernel dequantizes
+    (``rintf(x - med) + med``); 0: ``x`` is the already-noised value.  -> ``(main, v, n_nonfinite)`` as ``_LikelihoodFn``'s."""
+
+    @staticmethod
+    def forward(ctx, x, theta, med, mode: int, want_map: bool, lb: float):
+        B, Cn, hw = x.shape
+        theta, med = theta.contiguous(), med.contiguous()
+        like = torch.empty_like(x) if want_map else None
+        v = torch.empty_like(x) if mode else None
+        bits_q, nonfinite = np.zeros(B, np.int64), np.zeros(B, np.int64)
+        call = _lib.fgmm_eb_call(x.data_ptr(), theta.data_ptr(), med.data_ptr(), B, Cn, hw, like.data_ptr() if want_map else None,
+                                 v.data_ptr() if mode else None, bits_q.ctypes.data, nonfinite.ctypes.data, 0, 0)
+        _lib.check(_lib.lib().fgmm_eb_likelihood(*_ctx_stream(x.device), C.byref(call), int(mode), lb), "EntropyBottleneck.forward")
+        ctx.save_for_backward(x, theta, med)
+        ctx.mode, ctx.want_map, ctx.lb = int(mode), want_map, lb
+        nonfinite = torch.from_numpy(nonfinite)
+        ctx.mark_non_differentiable(nonfinite)
+        if v is not None:
+            ctx.mark_non_differentiable(v)
+        main = like if want_map else torch.from_numpy(bits_q.astype(np.float64) * 2.0 ** -_lib.FGMM_LIKE_Q).to(x.device)
+        return main, v, nonfinite
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_main, g_v, g_nonfinite):
+        x, theta, med = ctx.saved_tensors
+        need_x, need_t, need_m = ctx.needs_input_grad[:3]
+        need_x, need_m = need_x and not ctx.mode, need_m and bool(ctx.mode)  # round() has gradient zero; the noised path does not see med
+        if g_main is None or not (need_x or need_t or need_m):
+            return (None,) * 6
+        B, Cn, hw = x.shape
+        dx = torch.empty_like(x) if need_x else None
+        dtheta = torch.empty_like(theta) if need_t else None
+        dmed = torch.empty_like(med) if need_m else None
+        g = g_bits = None
+        if ctx.want_map:
+            g = g_main.to(torch.float32).contiguous()  # (held until the call returns: the call waits for its kernels)
+        else:
+            g_bits = np.ascontiguousarray(g_main.detach().to("cpu", torch.float64).numpy())
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        call = _lib.fgmm_eb_grad_call(x.data_ptr(), theta.data_ptr(), med.data_ptr(), B, Cn, hw, ptr(g),
+                                      None if g_bits is None else g_bits.ctypes.data, ptr(dx), ptr(dtheta), ptr(dmed), 0, 0)
+        _lib.check(_lib.lib().fgmm_eb_likelihood_backward(*_ctx_stream(x.device), C.byref(call), ctx.mode, ctx.lb),
+                   "EntropyBottleneck.forward (backward)")
+        return dx, dtheta, dmed, None, None, None
+
+
+class _EbBound(nn.Module):
+    """holds the ``bound`` buffer of the reference's ``likelihood_lower_bound`` (bound_ops.py:71), so that state dicts carry the same keys"""
+
+    def __init__(self, bound: float):
+        super().__init__()
+        self.register_buffer("bound", torch.Tensor([float(bound)]))
+
+
+class EntropyBottleneck(nn.Module):
+    """The reference's ``EntropyBottleneck`` (compressai/entropy_models/entropy_models.py:330-510) with its density model on the GPU:
+    same parameters (``_matrix{i}``, ``_bias{i}``, ``_factor{i}``, ``quantiles``), buffers and initialisation, so that a reference
+    checkpoint loads with ``strict=True``; ``forward`` / ``rate_bits`` run the fused kernels of include/flashgmm_amd.h section 3j, which
+    form the likelihood in the mirrored form (the reference's written form is rounding noise in the upper tail in float32).  The kernels
+    are bound to ``filters=(3, 3, 3, 3)``, the reference's default and what both GMM models construct.  ``update()`` - building the
+    tables - is not here: tables define the bitstream and come with the checkpoint; ``coder()`` codes on them."""
+
+    FILTERS = (3, 3, 3, 3)
+    _TABLES = ("_offset", "_quantized_cdf", "_cdf_length")
+
+    def __init__(self, channels: int, tail_mass: float = 1e-9, init_scale: float = 10, filters: Tuple[int, ...] = (3, 3, 3, 3),
+                 likelihood_bound: float = 1e-9):
+        super().__init__()
+        self.channels, self.filters = int(channels), tuple(int(f) for f in filters)
+        self.init_scale, self.tail_mass, self.likelihood_bound = float(init_scale), float(tail_mass), float(likelihood_bound)
+        if self.filters != self.FILTERS:
+            raise ValueError(f"filters = {self.filters}: the kernels are bound to the reference's default {self.FILTERS}")
+        if self.channels < 1:
+            raise ValueError("channels must be at least 1")
+        if not 0.0 <= self.likelihood_bound < float("inf"):
+            raise ValueError("likelihood_bound must be finite and >= 0 (0: no bound)")
+        self.use_likelihood_bound = self.likelihood_bound > 0
+        if self.use_likelihood_bound:
+            self.likelihood_lower_bound = _EbBound(self.likelihood_bound)
+        for name in self._TABLES:  # filled by a checkpoint of an updated model
+            self.register_buffer(name, torch.IntTensor())
+        width = (1,) + self.filters + (1,)
+        scale = self.init_scale ** (1 / (len(self.filters) + 1))
+        for i in range(len(self.filters) + 1):  # :360-385
+            self.register_parameter(f"_matrix{i:d}", nn.Parameter(torch.full((self.channels, width[i + 1], width[i]),
+                                                                             float(np.log(np.expm1(1 / scale / width[i + 1]))))))
+            self.register_parameter(f"_bias{i:d}", nn.Parameter(torch.empty(self.channels, width[i + 1], 1).uniform_(-0.5, 0.5)))
+            if i < len(self.filters):
+                self.register_parameter(f"_factor{i:d}", nn.Parameter(torch.zeros(self.channels, width[i + 1], 1)))
+        self.quantiles = nn.Parameter(torch.tensor([-self.init_scale, 0.0, self.init_scale]).repeat(self.channels, 1, 1))
+        target = float(np.log(2 / self.tail_mass - 1))
+        self.register_buffer("target", torch.tensor([-target, 0.0, target]))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        for name in self._TABLES:  # the tables arrive with their own sizes
+            t = state_dict.get(prefix + name)
+            if t is not None and tuple(t.shape) != tuple(getattr(self, name).shape):
+                setattr(self, name, torch.empty(tuple(t.shape), dtype=getattr(self, name).dtype, device=getattr(self, name).device))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if self.use_likelihood_bound:
+            self.likelihood_bound = float(self.likelihood_lower_bound.bound.item())
+        self.__dict__.pop("_coder_cache", None)
+
+    # ------------------------------------------------------------------------------------------------
+    def _get_medians(self) -> Tensor:
+        return self.quantiles[:, :, 1:2]
+
+    def _theta(self) -> Tensor:
+        """the raw parameters as ONE float32 block ``[C, 58]`` in the header's order (its backward is the one split of the gradient)"""
+        parts = []
+        for i in range(len(self.filters) + 1):
+            parts += [getattr(self, f"_matrix{i:d}"), getattr(self, f"_bias{i:d}")]
+            if i < len(self.filters):
+                parts.append(getattr(self, f"_factor{i:d}"))
+        return torch.cat([p.reshape(self.channels, -1) for p in parts], 1)
+
+    def _logits_cumulative(self, inputs: Tensor, stop_gradient: bool = False) -> Tensor:
+        """plain torch on ``[C, 1, n]`` (:434-453): what ``loss`` runs on the three quantiles; the kernels restate it per element"""
+        logits = inputs
+        for i in range(len(self.filters) + 1):
+            names = [f"_matrix{i:d}", f"_bias{i:d}"] + ([f"_factor{i:d}"] if i < len(self.filters) else [])
+            m, b, *f = [getattr(self, n).detach() if stop_gradient else getattr(self, n) for n in names]
+            logits = torch.matmul(F.softplus(m), logits) + b
+            if f:
+                logits = logits + torch.tanh(f[0]) * torch.tanh(logits)
+        return logits
+
+    def loss(self) -> Tensor:
+        """the quantile loss (:429-432)"""
+        return torch.abs(self._logits_cumulative(self.quantiles, stop_gradient=True) - self.target).sum()
+
+    def _prepare(self, x: Tensor, training: Optional[bool]):
+        if x.dim() < 2 or x.size(1) != self.channels:
+            raise RuntimeError(f"expected [B, {self.channels}, ...], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"the hyper-latent must be float32, got {x.dtype}")
+        if not x.is_cuda:
+            raise RuntimeError("EntropyBottleneck.forward runs on the GPU: the hyper-latent must be a CUDA/HIP tensor (there is no CPU path)")
+        if x.numel() == 0:
+            raise RuntimeError("the likelihood needs at least one element")
+        if training is None:
+            training = self.training
+        values = x.reshape(x.size(0), x.size(1), -1)
+        if training:
+            values = values + torch.empty_like(values).uniform_(-0.5, 0.5)  # quantize(values, "noise") (:163-167)
+        return values.contiguous(), bool(training), self._theta().to(torch.float32), self._get_medians().reshape(-1).to(torch.float32)
+
+    def likelihood(self, values: Tensor, *, dequantize: bool = False) -> Tuple[Tensor, Tensor]:
+        """The building block of ``forward``: -> ``(v, likelihood)`` of ``values`` ``[B, C, ...]`` as they are, or (``dequantize``) of
+        ``v = round(values - medians) + medians``.  Differentiable in the parameters and, without rounding, in ``values``."""
+        vals, _, theta, med = self._prepare(values, False)
+        like, v, _ = _EbLikelihoodFn.apply(vals, theta, med, int(dequantize), True, self.likelihood_bound)
+        return (v.reshape(values.shape) if dequantize else values), like.reshape(values.shape)
+
+    def forward(self, x: Tensor, training: Optional[bool] = None) -> Tuple[Tensor, Tensor]:
+        """As the reference's (:465-510): -> ``(outputs, likelihood)``, both shaped like ``x`` ``[B, C, ...]`` float32.  ``training``
+        (default ``self.training``): ``outputs`` is ``x`` plus uniform noise in [-0.5, 0.5) drawn by torch; otherwise
+        ``round(x - medians) + medians``, formed by the kernel (it then carries no gradient)."""
+        vals, training, theta, med = self._prepare(x, training)
+        like, v, _ = _EbLikelihoodFn.apply(vals, theta, med, int(not training), True, self.likelihood_bound)
+        return (vals if training else v).reshape(x.shape), like.reshape(x.shape)
+
+    def rate_bits(self, x: Tensor, training: Optional[bool] = None, return_nonfinite: bool = False):
+        """The fused rate of ``forward``, shaped like ``GaussianMixtureConditional.rate_bits``: -> ``(outputs, bits)``, ``bits`` a float64
+        ``[B]`` on ``x``'s device - per item ``sum(-log2(likelihood))``, summed on the GPU as integers in units of 2^-32 bit,
+        differentiable like the sum it stands for; no map is written.  ``return_nonfinite=True`` adds the count of the elements whose
+        likelihood is NaN, infinite or <= 0 (left out of the sum) as an int64 ``[B]`` CPU tensor."""
+        vals, training, theta, med = self._prepare(x, training)
+        bits, v, nonfinite = _EbLikelihoodFn.apply(vals, theta, med, int(not training), False, self.likelihood_bound)
+        outputs = (vals if training else v).reshape(x.shape)
+        return (outputs, bits, nonfinite) if return_nonfinite else (outputs, bits)
+
+    # ------------------------------------------------------------------------------------------------
+    def coder(self) -> "EntropyBottleneckCoder":
+        """the coding half on this module's table buffers (built once per state of tables and medians)"""
+        if any(getattr(self, n).numel() == 0 for n in self._TABLES):
+            raise RuntimeError("the table buffers are empty: load the checkpoint of an updated model (update() is not part of this class)")
+        key = tuple(getattr(self, n)._version for n in self._TABLES) + (self.quantiles._version, self.quantiles.data_ptr())
+        cached = self.__dict__.get("_coder_cache")
+        if cached is None or cached[0] != key:
+            cached = (key, EntropyBottleneckCoder.from_entropy_bottleneck(self))
+            self.__dict__["_coder_cache"] = cached  # (not a registered submodule: its buffer stays out of the state dict)
+        return cached[1]
+
+    def compress(self, x: Tensor):
+        return self.coder().compress(x)
+
+    def decompress(self, strings, size) -> Tensor:
+        return self.coder().decompress(strings, size)

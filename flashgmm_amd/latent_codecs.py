@@ -31,7 +31,7 @@ from torch import Tensor
 
 from itertools import accumulate
 
-from .entropy_models import EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead
+from .entropy_models import EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead
 from .ops import ckbd_embed, ckbd_unembed
 
 __all__ = ["GaussianMixtureConditionalLatentCodec", "CheckerboardLatentCodec", "ChannelGroupsLatentCodec", "HyperLatentCodec",
@@ -687,8 +687,8 @@ class ChannelGroupsLatentCodec(nn.Module):
 class HyperLatentCodec(nn.Module):
     """Hyper branch (compressai/latent_codecs/hyper.py:48-108): ``z = h_a(y)`` is table-coded, ``params = h_s(z_hat)``.
     ``entropy_bottleneck`` is anything with the reference's ``compress(z) -> [bytes]`` / ``decompress(strings, size)``
-    contract: ``flashgmm_amd.EntropyBottleneckCoder`` (built from the tables of a trained ``EntropyBottleneck``), or the
-    reference's own class."""
+    contract: ``flashgmm_amd.EntropyBottleneck`` (the density model and the tables; ``forward`` needs it or the reference's class),
+    ``flashgmm_amd.EntropyBottleneckCoder`` (built from the tables of a trained ``EntropyBottleneck``), or the reference's own class."""
 
     def __init__(self, entropy_bottleneck=None, h_a: Optional[nn.Module] = None, h_s: Optional[nn.Module] = None,
                  quantizer: str = "noise", **kwargs: Any):
@@ -703,6 +703,8 @@ class HyperLatentCodec(nn.Module):
         z = self.h_a(y)
         shape = z.size()[-2:]
         eb = self.entropy_bottleneck
+        if isinstance(eb, EntropyBottleneck):  # this package's module: its coding half, on its table buffers
+            eb = eb.coder()
         if isinstance(eb, EntropyBottleneckCoder):
             # the reference decodes the strings it has just written to get z_hat (hyper.py:97-98); the table coder is lossless on
             # the symbols, so that is round(z - medians) + medians: one elementwise op where z lives, bit for bit the same
@@ -717,8 +719,15 @@ class HyperLatentCodec(nn.Module):
         z_hat = self.entropy_bottleneck.decompress(z_strings, shape)
         return {"params": self.h_s(z_hat)}
 
-    def forward(self, y: Tensor):
-        raise NotImplementedError("training-time likelihoods are outside the entropy-coding path")
+    def forward(self, y: Tensor) -> Dict[str, Any]:  # hyper.py:87-94
+        """-> ``{"likelihoods": {"z": ...}, "params": h_s(z_hat)}``; ``entropy_bottleneck`` is ``flashgmm_amd.EntropyBottleneck`` (its
+        density on the GPU, include/flashgmm_amd.h section 3j) or anything callable as the reference's class"""
+        z = self.h_a(y)
+        z_hat, z_likelihoods = self.entropy_bottleneck(z)
+        if self.quantizer == "ste":
+            d = z - self.entropy_bottleneck._get_medians()
+            z_hat = ((torch.round(d) - d).detach() + d) + self.entropy_bottleneck._get_medians()  # quantize_ste (compressai/ops/ops.py:66-80)
+        return {"likelihoods": {"z": z_likelihoods}, "params": self.h_s(z_hat)}
 
 
 class HyperpriorLatentCodec(nn.Module):

@@ -55,6 +55,10 @@ extern "C" {
 #define FGMM_HAS_LIKELIHOOD 1  /* section 3g: fgmm_gmc_likelihood_batch, fgmm_gmc_likelihood_backward_batch (added without a bump, as 3b - 3f) */
 #define FGMM_HAS_LIKELIHOOD_LOGITS 1 /* section 3h: fgmm_gmc_likelihood_logits_batch, fgmm_gmc_likelihood_logits_backward_batch (added without a bump, as 3b - 3g) */
 #define FGMM_HAS_CENTROID 1  /* section 3i: fgmm_gmc_centroid_batch (added without a bump, as 3b - 3h) */
+#define FGMM_HAS_EB 1        /* section 3j: fgmm_eb_likelihood, fgmm_eb_likelihood_backward (added without a bump, as 3b - 3i) */
+#define FGMM_EB_PARAMS 58    /* float32 values per channel of section 3j's theta */
+#define FGMM_EB_SLICE 1024   /* section 3j: elements of a channel one workgroup walks; the backward's partial rows per channel are
+                                ceil(B*hw / FGMM_EB_SLICE) */
 #define FGMM_RDO_W_MAX 256.0f  /* largest factor of a weighted call's chan_w / pos_w */
 
 typedef enum {
@@ -894,6 +898,90 @@ typedef struct {
   int32_t status, pad_;    /* out */
 } fgmm_centroid_item;
 int fgmm_gmc_centroid_batch(fgmm_ctx *ctx, void *stream, fgmm_centroid_item *items, int count, float scale_bound, float p_min);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3j. The ENTROPY BOTTLENECK's forward(): the DIFFERENTIABLE likelihood of the hyper-latent z under the factorized density
+ *    (entropy_models.py:434-463, 465-510), its rate, and the gradients of either - the z half of what 3g is for y.  Per channel
+ *    the density is a 1 -> 3 -> 3 -> 3 -> 3 -> 1 network (filters (3, 3, 3, 3), the reference's default and what both GMM models
+ *    construct), evaluated at both edges of every element's bin.  One kernel forward; one backward that recomputes everything
+ *    from the inputs and writes one partial row per workgroup, and a small kernel that sums the rows in index order: no float
+ *    atomics, the same call gives the same bits every time.  The forward in binary32, every operation one IEEE operation (no
+ *    contraction, correctly rounded '/'); expf, log1pf and tanhf are the device library's.  (The backward: see there.)
+ *    Parameters: one float32 block theta[C][58] of the RAW parameters, per channel in this order, matrices row-major [out][in]:
+ *      M0[3] b0[3] f0[3] | M1[9] b1[3] f1[3] | M2[9] b2[3] f2[3] | M3[9] b3[3] f3[3] | M4[3] b4[1]
+ *    (the reference's _matrix{i}, _bias{i}, _factor{i} of a channel, flattened, in that order), and med[C], the medians.
+ *    Per channel:   H_i = softplus of M_i as torch's: m > 20 ? m : log1pf(expf(m))          t_i = tanhf(f_i)
+ *    chain(x):      layer 0:      a_j = H0_j*x + b0_j;                                 h_j = a_j + t0_j*tanhf(a_j)
+ *                   layers 1 - 3: a_j = ((H_j0*h_0 + H_j1*h_1) + H_j2*h_2) + b_j;      h_j = a_j + t_j*tanhf(a_j)
+ *                   layer 4:      the same sum, without the tanh step                 (sums from the left, multiply and add separate)
+ *    Per element, c its channel:
+ *      v    = mode ? rintf(x - med_c) + med_c : x      (mode 1: the reference's "dequantize"; mode 0: the caller's noised values)
+ *      lo   = chain(v - 0.5f)       up = chain(v + 0.5f)
+ *      sig(a) = 1 / (1 + expf(-a))
+ *      flip = (lo + up) > 0
+ *      L    = flip ? sig(-lo) - sig(-up) : sig(up) - sig(lo)
+ *      out  = lb > 0 ? max(L, lb) : L                                                   (NaN stays NaN)
+ *    THE MIRRORED FORM: the reference forms sig(up) - sig(lo) as written, everywhere.  In binary32 that is rounding noise in the
+ *    upper tail, where both terms are near 1 (relative error above 1 on a corpus reaching x = 400, against 4e-5 for the form
+ *    here); the two forms are the same function (they differ by 3e-16 in binary64).  Evaluation-mode bits of this call are
+ *    therefore closer to the binary64 value than the reference's own binary32 run is.
+ *    Rate, as in 3g: bits_q[b] is the sum, over item b's elements with a finite out > 0, of llrint(-log2((double)out) * 2^32),
+ *    summed in 64-bit integers; the remaining elements are counted in n_nonfinite[b].
+ *    Backward: g arrives w.r.t. out, or (g_like NULL) is formed from g_bits[b] exactly as 3g forms it: g = -gb / (out * ln2f),
+ *    gb = (float)g_bits[b], 0 for an element that is left out of the sum.
+ *      gL   = ((L >= lb) || (g < 0) || lb <= 0) ? g : 0                                  (a select, as in 3g)
+ *    L, out and with them g and gL are the forward's binary32 values: the decisions are the forward call's.  THE DERIVATIVES ARE
+ *    EVALUATED IN BINARY64, on the same binary32 inputs (theta, med, v and gL widened exactly; H_i, t_i, both chains, sig, the
+ *    sums below: the same sequences in binary64 with the device library's exp, log1p and - for t_i - tanh; inside the chains
+ *    tanh(a) = 1 - 2 / (exp(a + a) + 1), absolute error a few 2^-53), and rounded to binary32 once, where they are stored.  A parameter's gradient is a sum over the channel's elements of terms of both signs that cancels to
+ *    a hundredth of their magnitude and less; in binary32 the rounding of the terms themselves, which the chain amplifies by the
+ *    logit, reaches the fifth digit of such a sum (measured on the test corpus, for this sequence and for torch's alike).
+ *      dup  = gL * (sig(up) * sig(-up))        dlo = -gL * (sig(lo) * sig(-lo))          (the flip changes neither derivative)
+ *    Each chain in reverse, recomputed, d its dup or dlo, th_j = tanh(a_j) of the layer, h the layer's input:
+ *      layer 4:      db += d;  dH_k += d*h_k;  dh_k = d*H_k
+ *      layers 3 - 1: da_j = dh_j + dh_j*(t_j*(1 - th_j*th_j));  dt_j += dh_j*th_j;  db_j += da_j;  dH_jk += da_j*h_k;
+ *                    dh_k = (H_0k*da_0 + H_1k*da_1) + H_2k*da_2
+ *      layer 0:      the same with h = the chain's x;  dv += (H_0*da_0 + H_1*da_1) + H_2*da_2
+ *    dH, db, dt are summed (binary64) over the channel's B*hw elements: per lane, then across the wave by shuffles, across the
+ *    workgroup's waves through LDS, one row per workgroup; then over the channel's ceil(B*hw / FGMM_EB_SLICE) rows in index
+ *    order, and once per channel    dM = dH * (m > 20 ? 1 : sig(m))        df = dt * (1 - t*t),   rounded to binary32.
+ *      dx     = mode ? 0 : dv
+ *      dmed_c = mode ? the sum of dv over the channel : 0   (the medians are a live parameter: `outputs += means` passes the gradient)
+ *    The geometry depends on (B, C, hw) alone, never on addresses: per-element outputs are those of the same elements in any other
+ *    shape, bit for bit; loads are 4 wide where hw and every address allow it, which changes no result.
+ *    x, like_out, v_out, g_like, dx: DEVICE float32 [B, C, hw] contiguous; theta, dtheta: DEVICE float32 [C][58]; med, dmed:
+ *    DEVICE float32 [C]; bits_q, n_nonfinite, g_bits: HOST arrays [B].  Refused with FGMM_ERR_INVALID before any launch, nothing
+ *    written: a null call, x, theta or med; B, C or hw < 1; a mode other than 0 or 1; a negative or non-finite likelihood_bound;
+ *    a backward call whose outputs are all NULL, or with neither g_like nor g_bits, or a non-finite g_bits[b] where it is used.
+ *    The caller's-stream contract is section 2's: the work is ordered after `stream`, the call returns with every output complete.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *x;          /* device [B, C, hw] */
+  const float *theta;      /* device [C][FGMM_EB_PARAMS] */
+  const float *med;        /* device [C] */
+  int32_t B, C;
+  int64_t hw;
+  float *like_out;         /* DEVICE float32[B*C*hw] out: the bounded likelihood, or NULL (the rate alone) */
+  float *v_out;            /* DEVICE float32[B*C*hw] out: v, or NULL */
+  int64_t *bits_q;         /* HOST [B] out, or NULL: units of 2^-32 bit */
+  int64_t *n_nonfinite;    /* HOST [B] out, or NULL: elements left out of bits_q */
+  int32_t status, pad_;    /* out */
+} fgmm_eb_call;
+int fgmm_eb_likelihood(fgmm_ctx *ctx, void *stream, fgmm_eb_call *call, int mode, float likelihood_bound);
+typedef struct {
+  const float *x;          /* device [B, C, hw]: what the forward call was given (mode 0: the noised v) */
+  const float *theta;      /* device [C][FGMM_EB_PARAMS] */
+  const float *med;        /* device [C] */
+  int32_t B, C;
+  int64_t hw;
+  const float *g_like;     /* device float32[B*C*hw]: the gradient w.r.t. like_out, or NULL: g_bits is used */
+  const double *g_bits;    /* HOST [B]: the gradient w.r.t. each item's bit count, bits_q * 2^-32; read when g_like is NULL */
+  float *dx;               /* DEVICE float32[B*C*hw] out, or NULL */
+  float *dtheta;           /* DEVICE float32[C][FGMM_EB_PARAMS] out, or NULL */
+  float *dmed;             /* DEVICE float32[C] out, or NULL */
+  int32_t status, pad_;    /* out */
+} fgmm_eb_grad_call;
+int fgmm_eb_likelihood_backward(fgmm_ctx *ctx, void *stream, fgmm_eb_grad_call *call, int mode, float likelihood_bound);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
