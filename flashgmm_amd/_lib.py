@@ -259,6 +259,9 @@ SIGNATURES = {
     "fgmm_pmf_to_quantized_cdf": (_i, [_p, _i, _i, _p]),
     "fgmm_ckbd_unembed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
     "fgmm_ckbd_embed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
+    "fgmm_ckbd_ctx_create": (_i, [_p, _p, _p, _p, _i, _i, _pp]),
+    "fgmm_ckbd_ctx_destroy": (None, [_p]),
+    "fgmm_ckbd_ctx_apply": (_i, [_p, _p, _p, _p, _p, _i, _i64, _i64, _i]),
 }
 
 _lib = None

@@ -1,0 +1,239 @@
+// fgmm_ckbd_ctx.hip — the checkerboard context convolution on the matrix cores, in one fixed order (SURVEY.md §8 f rank 3; header
+// section 5b).
+//
+// What it replaces: unembed(context_prediction(embed(y_hat_)))[1] of CheckerboardLatentCodec (compressai/latent_codecs/checkerboard.py:
+// 281-284, 310-313) with context_prediction = CheckerboardMaskedConv2d(M, C_out, 5, padding=2): a full-size 5x5 convolution between two
+// data movements, of which the mask keeps 12 taps and the codec half of the outputs.  Here: the compact anchors half in, the compact
+// non-anchor context out, one launch, the 12 kept taps at the non-anchor positions only - a quarter of the multiply-adds.
+//
+// Arithmetic: a non-anchor at full-size (r, c) reads, for tap t = 0 .. 11 = kernel position (i, j) = ((2 t + 1) / 5, (2 t + 1) % 5) (the
+// positions with i + j odd, row-major), the full-size position (r + i - 2, c + j - 2): inside the image always an anchor (read from the
+// anchors half at its compact place), outside +0.  Then, on v_mfma_f32_32x32x2_f32, bit for bit the chain
+//     acc = bias[o] (+0 without);  for t ascending, for c = 0 .. M - 1 ascending:  acc = fmaf(W[o][c][tap t], x(t, c), acc)
+// - head_kernel's chain (fgmm_head.hip) over c_in = 12 M gathered features, and its tiling: 256 threads = 4 waves, two blocks per CU,
+//   block  = T row tiles of 32 output channels (T x 16 accumulator registers per lane) x 128 compact positions (a wave: 32)
+//   K loop = tiles of 32 input channels of ONE tap through LDS: the gather offset of a position is constant over a tile.  Weights from a
+//            PRE-PACKED copy [row tile][K tile][32 rows][32 columns] (column h * 16 + s = channel 2 s + h of the tile), features by
+//            masked element loads of A[c][neighbour(q, t)].
+//   T      = 6 (head_kernel's block: 192 rows) where that still gives every CU a block, else 2, else 1: ONE Kodak image is 6 position
+//            tiles - at T = 6 and C_out = 384 twelve blocks on 256 CUs, each walking the whole K loop with six products per step; at
+//            T = 1, 72 blocks with one.  An output's chain does not depend on T: the same bits from every instantiation.
+// Padding (channels up to a K tile, positions up to 128, rows up to a row tile - and row tiles up to six): weights +0, features -0:
+// +0 * -0 = -0 leaves every accumulator's bits alone, -0 included.  A tap outside the image is +0 and takes part in the chain as the
+// definition says.
+#include "fgmm_headframe.h"
+
+namespace fgmm {
+namespace {
+
+constexpr int kBK = kCkbdCtxBK;     // input channels per LDS tile
+constexpr int kTileW = 32 * kBK;    // floats of one packed tile: 32 rows x 32 columns
+constexpr int kPB = 128;            // compact positions per block (4 waves x 32)
+constexpr int kALd = kBK + 4;       // LDS row pitches as in fgmm_head.hip
+constexpr int kBLd = kPB + 32;
+
+// packs the 12 kept taps, and flags a dropped tap that is not +-0 (*bad = 1; zeroed by the host)
+__global__ __launch_bounds__(256) void ckbd_ctx_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, int M, int c_out, int n_rt, int mt,
+                                                            float *__restrict__ wp, float *__restrict__ bp, uint32_t *__restrict__ bad) {
+  const int n_kt = kCkbdCtxTaps * mt;
+  const int64_t total = (int64_t)n_rt * n_kt * kTileW, n_bias = (int64_t)n_rt * 32, n_w = (int64_t)c_out * M * 25; // n_rt: a multiple of 6
+  const int64_t step = (int64_t)gridDim.x * 256, first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  for (int64_t i = first; i < total + n_bias; i += step) {
+    if (i >= total) {
+      const int64_t o = i - total;
+      bp[o] = (o < c_out && bias) ? bias[o] : 0.0f;
+      continue;
+    }
+    const int q = (int)(i % kBK), r = (int)((i / kBK) % 32);
+    const int kt = (int)((i / kTileW) % n_kt), rt = (int)(i / ((int64_t)kTileW * n_kt));
+    const int t = kt / mt, c = (kt - t * mt) * kBK + 2 * (q & 15) + (q >> 4);
+    const int64_t o = (int64_t)rt * 32 + r;
+    wp[i] = (o < c_out && c < M) ? w[(o * M + c) * 25 + 2 * t + 1] : 0.0f;
+  }
+  bool any = false;
+  for (int64_t i = first; i < n_w; i += step)
+    if (((i % 25) & 1) == 0 && (__float_as_uint(w[i]) & 0x7FFFFFFFu) != 0u) any = true;
+  if (any) *bad = 1u;
+}
+
+template <int T> // row tiles per block
+__global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_rg, int total) {
+  constexpr int kTiles = T, kRows = 32 * T;
+  __shared__ __attribute__((aligned(16))) float sA[kRows * kALd];
+  __shared__ __attribute__((aligned(16))) float sB[kBK * kBLd];
+  const int L = head_slot();
+  if (L >= total) return;
+  const int per_item = a.pt * n_rg;
+  const int item = L / per_item, rem = L - item * per_item, pt = rem / n_rg, rg = rem - pt * n_rg;
+  const int M = a.M, hgt = a.h, w2 = a.w2, wid = 2 * a.w2, hw = a.h * a.w2, P0 = pt * kPB;
+  const float *x = a.anchors + (int64_t)item * M * hw;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
+  // the thread's four positions of the feature tile (the same for its four channels: 256 is a multiple of the 32 position quads):
+  // row and full-size column of the non-anchor at compact position q
+  int pr[4], pc[4];
+  unsigned p_ok = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int q = P0 + 4 * (tid & 31) + e;
+    const int r = q / w2, j = q - r * w2;
+    pr[e] = r, pc[e] = 2 * j + 1 - ((r + a.odd) & 1);
+    p_ok |= (q < hw ? 1u : 0u) << e;
+  }
+  // ---- accumulators start at the bias
+  f16_t acc[kTiles];
+  {
+    const float *bp = a.bp + (int64_t)rg * kRows;
+#pragma unroll
+    for (int tl = 0; tl < kTiles; ++tl) head_bias_tile(bp, tl, h, acc[tl]);
+  }
+  // ---- K loop (fgmm_head.hip's: one basic block, the loads of tile i + 1 in flight under the products of tile i)
+  const int n_kt = a.n_kt, mt = a.mt;
+  const float *wp = a.wp + (int64_t)rg * kTiles * n_kt * kTileW; // row tile rg * T + j, K tile kt: at ((rg * T + j) * n_kt + kt) * kTileW
+  // Staging, branch-free: a load that would fall outside the anchors (channels past M in a tap's last tile, positions past hw, a tap
+  // outside the image) reads a valid address instead and is replaced when the tile is written: by +0 where the tap of a real channel
+  // lies outside the image (it takes part in the chain), by -0 for a padded channel (the packed weights are +0 there)
+  float4_t ra[kTiles], rb[4];
+  unsigned rb_ok = 0; // bit 4 j + e: element e of rb[j] is an anchor inside the image
+  unsigned rb_ch = 0; // bit j: the channel of rb[j] is one of the M
+  auto load_tile = [&](int kt) {
+    rb_ok = 0, rb_ch = 0;
+    const FGMM_GLOBAL float4_t *src = (const FGMM_GLOBAL float4_t *)(wp + (int64_t)kt * kTileW);
+#pragma unroll
+    for (int j = 0; j < kTiles; ++j) ra[j] = src[tid + (int64_t)j * n_kt * (kTileW / 4)]; // (256 threads x 16 bytes: one packed tile)
+    const int t = kt / mt, c0 = (kt - t * mt) * kBK;
+    const int di = (2 * t + 1) / 5 - 2, dj = (2 * t + 1) % 5 - 2;
+    int off[4];
+    unsigned in = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int rr = pr[e] + di, cc = pc[e] + dj;
+      const bool ok = ((p_ok >> e) & 1u) && (unsigned)rr < (unsigned)hgt && (unsigned)cc < (unsigned)wid;
+      off[e] = ok ? rr * w2 + (cc >> 1) : 0; // the anchor at full-size (rr, cc) is compact (rr, cc >> 1)
+      in |= (ok ? 1u : 0u) << e;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = c0 + (tid >> 5) + 8 * j;
+      const bool k_ok = c < M;
+      const FGMM_GLOBAL float *g = (const FGMM_GLOBAL float *)(x + (int64_t)(k_ok ? c : M - 1) * hw);
+      float4_t v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = g[off[e]];
+      rb[j] = v;
+      rb_ok |= (k_ok ? in : 0u) << (4 * j);
+      rb_ch |= (k_ok ? 1u : 0u) << j;
+    }
+  };
+  auto store_tile = [&]() {
+#pragma unroll
+    for (int j = 0; j < kTiles; ++j) {
+      const int f = tid + 256 * j;
+      *reinterpret_cast<float4_t *>(&sA[(f >> 3) * kALd + (f & 7) * 4]) = ra[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int f = tid + 256 * j;
+      const float fill = (rb_ch >> j) & 1u ? 0.0f : -0.0f;
+      float4_t v = rb[j];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (rb_ok >> (4 * j + e)) & 1u ? v[e] : fill;
+      *reinterpret_cast<float4_t *>(&sB[(f >> 5) * kBLd + (f & 31) * 4]) = v;
+    }
+  };
+  struct Frag {
+    float4_t a[kTiles];
+    float b[4];
+  };
+  auto read_frag = [&](Frag &f, int s4) {
+    const float *a_base = sA + col * kALd + h * 16 + s4 * 4;
+    const float *b_base = sB + h * kBLd + wave * 32 + col + 8 * s4 * kBLd;
+#pragma unroll
+    for (int tl = 0; tl < kTiles; ++tl) f.a[tl] = *reinterpret_cast<const float4_t *>(a_base + tl * 32 * kALd);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f.b[e] = b_base[2 * e * kBLd];
+  };
+  auto multiply = [&](const Frag &f) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int tl = 0; tl < kTiles; ++tl) acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tl][e], f.b[e], acc[tl], 0, 0, 0);
+  };
+#define FGMM_FENCE() __builtin_amdgcn_sched_barrier(0)
+  load_tile(0);
+  store_tile();
+  __syncthreads();
+  Frag f0, f1;
+  read_frag(f0, 0);
+  for (int kt = 0; kt < n_kt; ++kt) {
+    FGMM_FENCE();
+    load_tile(kt + 1 < n_kt ? kt + 1 : kt); // (the last tile loads itself again: harmless)
+    read_frag(f1, 1);
+    FGMM_FENCE();
+    multiply(f0);
+    FGMM_FENCE();
+    read_frag(f0, 2);
+    FGMM_FENCE();
+    multiply(f1);
+    FGMM_FENCE();
+    read_frag(f1, 3);
+    FGMM_FENCE();
+    multiply(f0);
+    multiply(f1);
+    FGMM_FENCE();
+    __syncthreads(); // every wave has read the tile
+    store_tile();
+    __syncthreads();
+    read_frag(f0, 0); // (after the last tile: a read that nobody uses)
+  }
+#undef FGMM_FENCE
+  // ---- epilogue: register reg of row tile tl is output channel (rg * T + tl) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 h at the lane's position
+  const int p = P0 + wave * 32 + col;
+  if (p < hw) {
+    float *out = a.out + (int64_t)item * a.c_out * hw + p;
+#pragma unroll
+    for (int tl = 0; tl < kTiles; ++tl)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int o = rg * kRows + tl * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        if (o < a.c_out) stg<float>(out + (int64_t)o * hw, acc[tl][reg]);
+      }
+  }
+}
+
+} // namespace
+
+int launch_ckbd_ctx_pack(const float *w, const float *bias, int M, int c_out, float *wp, float *bp, uint32_t *bad, void *stream) {
+  const int n_rt = ckbd_ctx_row_tiles(c_out), mt = (M + kBK - 1) / kBK;
+  const int64_t total = std::max<int64_t>((int64_t)ckbd_ctx_packed_floats(M, c_out), (int64_t)c_out * M * 25);
+  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+  hipLaunchKernelGGL(ckbd_ctx_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, bias, M, c_out, n_rt, mt, wp, bp, bad);
+  return (int)hipGetLastError();
+}
+
+// T: the most row tiles per block (6, 2, 1) at which the launch still has a block for every CU; 1 when none has
+int ckbd_ctx_tiles(int64_t n, int64_t pt, int c_out) {
+  const int64_t n_rt = (c_out + 31) / 32;
+  for (int T : {6, 2})
+    if (n * pt * ((n_rt + T - 1) / T) >= kCkbdCtxFill) return T;
+  return 1;
+}
+
+template <int T> static int ckbd_ctx_go(const CkbdCtxArgs &a, int64_t n, hipStream_t st) {
+  const int n_rg = ((a.c_out + 31) / 32 + T - 1) / T;
+  const int64_t total = n * a.pt * n_rg;
+  if (total <= 0) return 0;
+  if (total > (1ll << 30)) return (int)hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)((total + 7) / 8 * 8); // every XCD gets as many slots (head_slot)
+  hipLaunchKernelGGL(ckbd_ctx_kernel<T>, dim3(blocks), dim3(256), 0, st, a, n_rg, (int)total);
+  return (int)hipGetLastError();
+}
+
+int launch_ckbd_ctx(const CkbdCtxArgs &args, int64_t n, void *stream) {
+  switch (ckbd_ctx_tiles(n, args.pt, args.c_out)) {
+  case 6: return ckbd_ctx_go<6>(args, n, (hipStream_t)stream);
+  case 2: return ckbd_ctx_go<2>(args, n, (hipStream_t)stream);
+  }
+  return ckbd_ctx_go<1>(args, n, (hipStream_t)stream);
+}
+
+} // namespace fgmm

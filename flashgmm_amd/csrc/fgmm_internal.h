@@ -135,6 +135,29 @@ int launch_head_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_
 int launch_head_planes(const HeadDesc *d_descs, const HeadPair &head, int count, int64_t hw_max, bool vec, void *stream);
 int launch_head_entries(const EncDesc *d_descs, const HeadPair &head, int count, int M_max, int64_t hw_max, int mode, bool clamped, bool vec, void *stream);
 
+// ---- the checkerboard context convolution on the matrix cores (fgmm_ckbd_ctx.hip; header section 5b) --------------
+constexpr int kCkbdCtxBK = 32;    // input channels of one tap per LDS tile
+constexpr int kCkbdCtxTaps = 12;  // the kernel positions (i, j) of the 5x5 with i + j odd, row-major: flat index 2 t + 1
+constexpr int kCkbdCtxFill = 256; // blocks a launch wants before it takes more row tiles per block (one per CU)
+static inline int ckbd_ctx_row_tiles(int c_out) { return (c_out + 31) / 32 + 5 - ((c_out + 31) / 32 + 5) % 6; } // of 32 rows, padded to a multiple of 6
+static inline size_t ckbd_ctx_packed_floats(int M, int c_out) { // [n_rt][12 * mt][32][32] weights, then [n_rt][32] bias
+  const size_t n_rt = (size_t)ckbd_ctx_row_tiles(c_out), mt = ((size_t)M + kCkbdCtxBK - 1) / kCkbdCtxBK;
+  return n_rt * kCkbdCtxTaps * mt * 32 * kCkbdCtxBK + n_rt * 32;
+}
+struct CkbdCtxArgs {    // one launch, by value: items of one size
+  const float *anchors; // device [n, M, h, w2]: the anchors half
+  float *out;           // device [n, c_out, h, w2]: the non-anchor half of the convolution's output
+  const float *wp, *bp; // the packed weights and bias
+  int32_t M, c_out, h, w2, odd;
+  int32_t mt, n_kt; // K tiles per tap, in all (12 * mt)
+  int32_t pt;       // position tiles of 128 per item
+};
+// w: device [c_out, M, 5, 5]; *bad (device, zeroed by the caller) becomes 1 when a dropped tap (i + j even) of w is not +-0
+int launch_ckbd_ctx_pack(const float *w, const float *bias_or_null, int M, int c_out, float *wp, float *bp, uint32_t *bad, void *stream);
+// row tiles per block the launch of n items takes (6, 2 or 1); blocks = n * pt * ceil(ceil(c_out / 32) / that)
+int ckbd_ctx_tiles(int64_t n, int64_t pt, int c_out);
+int launch_ckbd_ctx(const CkbdCtxArgs &args, int64_t n, void *stream);
+
 // ---- GPU-side decode of CHECKPOINTED bitstreams (segdec_kernel): one wave per segment ---------------------------
 struct SegDesc {
   const void *scales, *means, *weights; // float32, float16 or bfloat16 planes

@@ -32,7 +32,7 @@ from torch import Tensor
 from itertools import accumulate
 
 from .entropy_models import EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead
-from .ops import ckbd_embed, ckbd_unembed
+from .ops import CheckerboardContext, ckbd_embed, ckbd_unembed
 
 __all__ = ["GaussianMixtureConditionalLatentCodec", "CheckerboardLatentCodec", "ChannelGroupsLatentCodec", "HyperLatentCodec",
            "HyperpriorLatentCodec"]
@@ -346,8 +346,17 @@ class CheckerboardLatentCodec(nn.Module):
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None, entropy_parameters: Optional[nn.Module] = None,
                  context_prediction: Optional[nn.Module] = None, anchor_parity: str = "even", forward_method: str = "twopass",
-                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, **kwargs: Any):
+                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, fuse_context: bool = False, **kwargs: Any):
         super().__init__()
+        # fuse_context: context_prediction - a 5x5 CheckerboardMaskedConv2d(M, C_out, padding=2) - runs inside the library
+        # (flashgmm_amd.ops.CheckerboardContext, header section 5b: compact anchors in, compact non-anchor context out, one launch on the
+        # matrix cores in ONE fixed summation order; the anchors' context is zeros and costs no convolution).  Like fuse_softmax and
+        # fuse_head it changes the last bits of the parameters: the streams are self-consistent on any ROCm / MIOpen version, but they are
+        # not the un-fused path's streams - encoder and decoder must agree on this switch.  Works alone and together with fuse_head.
+        # Inference only: the weights are detached.
+        self.fuse_context = bool(fuse_context)
+        self._context: Optional[CheckerboardContext] = None
+        self._context_key = None
         # rdo_channel_skip: channel skipping (section 3f) in the halves' quantisation at THIS codec's rdo_lambda - with rdo_lambda > 0 it
         # replaces the inner codec's setting, as the lambda does; with rdo_lambda == 0 the inner codec's own settings apply
         self.rdo_channel_skip = bool(rdo_channel_skip)
@@ -411,8 +420,22 @@ class CheckerboardLatentCodec(nn.Module):
             self._head, self._head_key = ParameterHead(last, K=self.latent_codec["y"].K, arithmetic=self._head_arith), key
         return body, self._head
 
+    def _context_op(self) -> CheckerboardContext:
+        """the CheckerboardContext of context_prediction: packed once, again when its weights have changed (the key of _head_parts)"""
+        cp = self.context_prediction
+        bias = getattr(cp, "bias", None)
+        key = (cp.weight.data_ptr(), cp.weight._version, None if bias is None else (bias.data_ptr(), bias._version))
+        if self._context is None or self._context_key != key:
+            self._context, self._context_key = CheckerboardContext(cp, self.anchor_parity), key
+        return self._context
+
     def _ctx(self, y_hat_: Tensor, i: int) -> Tensor:
         """context of half i from the halves reconstructed so far (:281-284, :310-313)"""
+        if self.fuse_context:
+            op = self._context_op()
+            if i == 0:  # _mask(., "all") for the anchors: no convolution runs for them
+                return y_hat_.new_zeros((y_hat_.shape[1], op.C_out) + tuple(y_hat_.shape[3:]))
+            return op.non_anchor(y_hat_[0])
         y_ctx_i = self.unembed(self.context_prediction(self.embed(y_hat_)))[i]
         return torch.zeros_like(y_ctx_i) if i == 0 else y_ctx_i  # _mask(., "all") for the anchors
 

@@ -56,6 +56,7 @@ extern "C" {
 #define FGMM_HAS_LIKELIHOOD_LOGITS 1 /* section 3h: fgmm_gmc_likelihood_logits_batch, fgmm_gmc_likelihood_logits_backward_batch (added without a bump, as 3b - 3g) */
 #define FGMM_HAS_CENTROID 1  /* section 3i: fgmm_gmc_centroid_batch (added without a bump, as 3b - 3h) */
 #define FGMM_HAS_EB 1        /* section 3j: fgmm_eb_likelihood, fgmm_eb_likelihood_backward (added without a bump, as 3b - 3i) */
+#define FGMM_HAS_CKBD_CONTEXT 1 /* section 5b: fgmm_ckbd_ctx_create, fgmm_ckbd_ctx_destroy, fgmm_ckbd_ctx_apply (added without a bump, as 3b - 3j) */
 #define FGMM_EB_PARAMS 58    /* float32 values per channel of section 3j's theta */
 #define FGMM_EB_SLICE 1024   /* section 3j: elements of a channel one workgroup walks; the backward's partial rows per channel are
                                 ceil(B*hw / FGMM_EB_SLICE) */
@@ -1037,6 +1038,35 @@ int fgmm_ckbd_unembed(fgmm_ctx *ctx, void *stream, const void *src, void *dst, i
                       int elem_bytes, int anchor_odd);
 int fgmm_ckbd_embed(fgmm_ctx *ctx, void *stream, const void *src, void *dst, int64_t planes, int64_t h, int64_t w,
                     int elem_bytes, int anchor_odd);
+
+/* ---- section 5b. The checkerboard CONTEXT CONVOLUTION on the matrix cores, in one fixed order -------
+ * Replaces unembed(context_prediction(embed(y_hat_)))[1] of CheckerboardLatentCodec (compressai/latent_codecs/checkerboard.py:281-284,
+ * 310-313) where context_prediction is a CheckerboardMaskedConv2d(M, C_out, kernel_size=5, padding=2): the compact anchors half in,
+ * the compact non-anchor context out, one launch.  Inference only.
+ *   A      [M, h, w/2] float32: the anchors half, as fgmm_ckbd_unembed lays out half 0; s = anchor_odd
+ *          the anchor     at compact (r, j) is full-size (r, 2j + ((r + s) & 1)),
+ *          the non-anchor at compact (r, j) is full-size (r, 2j + 1 - ((r + s) & 1))
+ *   taps   t = 0 .. 11: the kernel positions (i, j) with i + j odd, row-major - (0,1) (0,3) (1,0) (1,2) (1,4) (2,1) (2,3) (3,0) (3,2)
+ *          (3,4) (4,1) (4,3).  For a non-anchor at full-size (r, c), tap (i, j) reads full-size (r + i - 2, c + j - 2): inside the
+ *          image that is always an anchor, read from A at its compact place (the non-anchor half is never looked at); outside, +0.0,
+ *          which takes part in the chain
+ *   out[o] = the chain  acc = bias[o] (+0 without a bias); for t ascending, for c = 0 .. M-1 ascending:
+ *                       acc = fmaf(weight[o][c][tap t], x(t, c), acc)
+ * computed on v_mfma_f32_32x32x2_f32 bit for bit - signs of zero, infinities and NaN included - for the reason of section 2b: encoder
+ * and decoder derive identical parameters from identical weights on any ROCm / torch / MIOpen version, and this convolution is the
+ * largest reduction of the parameter chain (12 M terms).  The result is NOT MIOpen's in its last bits: both sides must use it. */
+typedef struct fgmm_ckbd_context fgmm_ckbd_context; /* the packed weights, on the context's device.  Immutable once created: usable
+                                                     * from any context on its device, from several at the same time */
+/* weight: device float32 [C_out, M, 5, 5] (the EFFECTIVE weight: weight * mask); bias: device float32 [C_out] or NULL.  The 12 kept
+ * taps are copied (packed) before the call returns; FGMM_ERR_INVALID if any of the 13 dropped taps of any filter is not +-0. */
+int fgmm_ckbd_ctx_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int C_out, fgmm_ckbd_context **out);
+void fgmm_ckbd_ctx_destroy(fgmm_ckbd_context *cc);
+/* anchors: device float32 [n, M, h, w/2]; out: device float32 [n, C_out, h, w/2], the non-anchor half as fgmm_ckbd_unembed lays out
+ * half 1.  STREAM-ORDERED, like the two calls of section 5: one kernel enqueued on `stream`, no workspace, no context lock, no host
+ * wait; the same rules for `anchors` and `out` as for `src` and `dst` there.  Refused, launching and writing nothing: odd w, w < 2,
+ * h < 1, n < 0, a null tensor with n > 0, sizes whose grid would overflow.  n == 0: success, no launch. */
+int fgmm_ckbd_ctx_apply(fgmm_ctx *ctx, void *stream, const fgmm_ckbd_context *cc, const float *anchors, float *out, int n, int64_t h,
+                        int64_t w, int anchor_odd);
 
 /* compressai._CXX.pmf_to_quantized_cdf (compressai/cpp_exts/ops/ops.cpp:40-109): cdf_out has n + 1 entries */
 int fgmm_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *cdf_out);
