@@ -10,7 +10,7 @@ All floating-point work runs in hand-written HIP kernels (flashgmm_amd/csrc); th
 """
 from . import _lib  # noqa: F401
 from .entropy_models import BudgetQuantized, RdCurve, CheckpointedBytes, CompressedBatch, EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead, RateEstimate, RdoQuantized, RdoSkipQuantized  # noqa: F401
-from .ops import CheckerboardContext  # noqa: F401
+from .ops import CheckerboardContext, checkerboard_context  # noqa: F401
 from . import ans  # noqa: F401
 
 __version__ = "0.1.0"

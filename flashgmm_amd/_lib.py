@@ -262,7 +262,15 @@ SIGNATURES = {
     "fgmm_ckbd_ctx_create": (_i, [_p, _p, _p, _p, _i, _i, _pp]),
     "fgmm_ckbd_ctx_destroy": (None, [_p]),
     "fgmm_ckbd_ctx_apply": (_i, [_p, _p, _p, _p, _p, _i, _i64, _i64, _i]),
+    # section 5c: (M, C_out); (ctx, stream, weight, bias, M, C_out, transposed, packed); (ctx, stream, packed, M, C_out, anchors, out, n, h, w,
+    # anchor_odd); (M, C_out, n, h, w); (ctx, stream, anchors, g, M, C_out, n, h, w, anchor_odd, dweight, dbias, workspace, workspace_bytes)
+    "fgmm_ckbd_ctx_packed_floats": (_sz, [_i, _i]),
+    "fgmm_ckbd_ctx_pack": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "fgmm_ckbd_ctx_apply_packed": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i64, _i64, _i]),
+    "fgmm_ckbd_ctx_wgrad_workspace": (_sz, [_i, _i, _i, _i64, _i64]),
+    "fgmm_ckbd_ctx_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i64, _i64, _i, _p, _p, _p, _sz]),
 }
+FGMM_CKBD_WGRAD_SLICE_MIN, FGMM_CKBD_WGRAD_SLICES_MAX = 256, 16  # section 5c: the weight gradient's slice rule
 
 _lib = None
 _lock = threading.Lock()

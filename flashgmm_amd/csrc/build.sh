@@ -18,14 +18,15 @@
 # more sum, in the same shell: not part of the fake-device build either); fgmm_eb.cpp over fgmm_eb.hip (the entropy bottleneck's forward(),
 # section 3j: the factorized density of the hyper-latent, its rate and gradients: not part of the fake-device build either); fgmm_ckbd_ctx.cpp over fgmm_ckbd_ctx.hip
 # (the checkerboard context convolution on the matrix cores, section 5b: a weights handle and a stream-ordered apply, on fgmm_headframe.h's
-# placement and bias helpers: not part of the fake-device build either).
+# placement and bias helpers: not part of the fake-device build either; fgmm_ckbd_ctx_grad.hip: its weight and bias gradients, section 5c,
+# behind the same fgmm_ckbd_ctx.cpp).
 set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OUT=${OUT:-../libflashgmm_amd.so}
 COMMON="-O3 -fPIC -std=c++17 -Wall -Wextra -Wno-unused-parameter -ffp-contract=off -fno-fast-math"
 $HIPCC $COMMON --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-rdc -Xarch_device -fno-slp-vectorize \
-    -march=x86-64-v3 -shared -o $OUT fgmm_kernels.hip fgmm_tab.hip fgmm_head.hip fgmm_head16.hip fgmm_rate.hip fgmm_rdoq.hip fgmm_rdcurve.hip fgmm_like.hip fgmm_centroid.hip fgmm_eb.hip fgmm_ckbd_ctx.hip fgmm_device_hip.cpp fgmm_rans.cpp fgmm_rate_host.cpp fgmm_capi.cpp \
+    -march=x86-64-v3 -shared -o $OUT fgmm_kernels.hip fgmm_tab.hip fgmm_head.hip fgmm_head16.hip fgmm_rate.hip fgmm_rdoq.hip fgmm_rdcurve.hip fgmm_like.hip fgmm_centroid.hip fgmm_eb.hip fgmm_ckbd_ctx.hip fgmm_ckbd_ctx_grad.hip fgmm_device_hip.cpp fgmm_rans.cpp fgmm_rate_host.cpp fgmm_capi.cpp \
     fgmm_encode.cpp fgmm_decode.cpp fgmm_decode_gpu.cpp fgmm_estimate.cpp fgmm_rdoq.cpp fgmm_rdcurve.cpp fgmm_like.cpp fgmm_centroid.cpp fgmm_eb.cpp fgmm_ckbd_ctx.cpp -lpthread "$@"
 echo "built $(realpath $OUT)"
 # The compiled Python boundary over the C ABI (fgmm_pybind.cpp -> flashgmm_amd/_native.*.so): plain C++ against the Python and pybind11

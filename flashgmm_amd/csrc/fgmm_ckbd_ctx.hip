@@ -32,7 +32,10 @@ constexpr int kPB = 128;            // compact positions per block (4 waves x 32
 constexpr int kALd = kBK + 4;       // LDS row pitches as in fgmm_head.hip
 constexpr int kBLd = kPB + 32;
 
-// packs the 12 kept taps, and flags a dropped tap that is not +-0 (*bad = 1; zeroed by the host)
+// packs the 12 kept taps, and flags a dropped tap that is not +-0 (*bad = 1; zeroed by the host; null: not looked for).  M, c_out: the
+// PACKED convolution's input and output channels.  TRANSPOSED (the data gradient's filters, section 5c): w is [M, c_out, 5, 5] - the
+// forward's weight, whose outputs are this convolution's inputs - and W'[o][c][tap t] = w[c][o][tap 11 - t] (the 5x5 turned by 180 degrees)
+template <bool TRANSPOSED>
 __global__ __launch_bounds__(256) void ckbd_ctx_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, int M, int c_out, int n_rt, int mt,
                                                             float *__restrict__ wp, float *__restrict__ bp, uint32_t *__restrict__ bad) {
   const int n_kt = kCkbdCtxTaps * mt;
@@ -48,8 +51,10 @@ __global__ __launch_bounds__(256) void ckbd_ctx_pack_kernel(const float *__restr
     const int kt = (int)((i / kTileW) % n_kt), rt = (int)(i / ((int64_t)kTileW * n_kt));
     const int t = kt / mt, c = (kt - t * mt) * kBK + 2 * (q & 15) + (q >> 4);
     const int64_t o = (int64_t)rt * 32 + r;
-    wp[i] = (o < c_out && c < M) ? w[(o * M + c) * 25 + 2 * t + 1] : 0.0f;
+    if (TRANSPOSED) wp[i] = (o < c_out && c < M) ? w[((int64_t)c * c_out + o) * 25 + 23 - 2 * t] : 0.0f;
+    else wp[i] = (o < c_out && c < M) ? w[(o * M + c) * 25 + 2 * t + 1] : 0.0f;
   }
+  if (!bad) return;
   bool any = false;
   for (int64_t i = first; i < n_w; i += step)
     if (((i % 25) & 1) == 0 && (__float_as_uint(w[i]) & 0x7FFFFFFFu) != 0u) any = true;
@@ -202,11 +207,13 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_r
 
 } // namespace
 
-int launch_ckbd_ctx_pack(const float *w, const float *bias, int M, int c_out, float *wp, float *bp, uint32_t *bad, void *stream) {
+int launch_ckbd_ctx_pack(const float *w, const float *bias, int M, int c_out, bool transposed, float *wp, float *bp, uint32_t *bad, void *stream) {
+  if (transposed) std::swap(M, c_out); // the packed convolution's sizes
   const int n_rt = ckbd_ctx_row_tiles(c_out), mt = (M + kBK - 1) / kBK;
-  const int64_t total = std::max<int64_t>((int64_t)ckbd_ctx_packed_floats(M, c_out), (int64_t)c_out * M * 25);
+  const int64_t total = std::max<int64_t>((int64_t)ckbd_ctx_packed_floats(M, c_out), bad ? (int64_t)c_out * M * 25 : 0);
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(ckbd_ctx_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, bias, M, c_out, n_rt, mt, wp, bp, bad);
+  if (transposed) hipLaunchKernelGGL(ckbd_ctx_pack_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, bias, M, c_out, n_rt, mt, wp, bp, bad);
+  else hipLaunchKernelGGL(ckbd_ctx_pack_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, bias, M, c_out, n_rt, mt, wp, bp, bad);
   return (int)hipGetLastError();
 }
 

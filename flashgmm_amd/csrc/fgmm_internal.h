@@ -152,11 +152,37 @@ struct CkbdCtxArgs {    // one launch, by value: items of one size
   int32_t mt, n_kt; // K tiles per tap, in all (12 * mt)
   int32_t pt;       // position tiles of 128 per item
 };
-// w: device [c_out, M, 5, 5]; *bad (device, zeroed by the caller) becomes 1 when a dropped tap (i + j even) of w is not +-0
-int launch_ckbd_ctx_pack(const float *w, const float *bias_or_null, int M, int c_out, float *wp, float *bp, uint32_t *bad, void *stream);
+// w: device [c_out, M, 5, 5]; *bad (device, zeroed by the caller; may be null: the dropped taps are then not looked at) becomes 1 when a
+// dropped tap (i + j even) of w is not +-0.  transposed: packs W'[c][o][i][j] = w[o][c][4 - i][4 - j] instead - a convolution from c_out to
+// M channels (wp, bp sized by ckbd_ctx_packed_floats(c_out, M)), the data gradient's (section 5c)
+int launch_ckbd_ctx_pack(const float *w, const float *bias_or_null, int M, int c_out, bool transposed, float *wp, float *bp, uint32_t *bad, void *stream);
 // row tiles per block the launch of n items takes (6, 2 or 1); blocks = n * pt * ceil(ceil(c_out / 32) / that)
 int ckbd_ctx_tiles(int64_t n, int64_t pt, int c_out);
 int launch_ckbd_ctx(const CkbdCtxArgs &args, int64_t n, void *stream);
+
+// ---- its weight and bias gradients (fgmm_ckbd_ctx_grad.hip; header section 5c) ------------------------------------
+constexpr int kCkbdWgradSliceMin = 256; // positions a slice holds before the reduction is cut into more slices (FGMM_CKBD_WGRAD_SLICE_MIN)
+constexpr int kCkbdWgradSliceMax = 16;  // slices at the most: the workspace's partial copies (FGMM_CKBD_WGRAD_SLICES_MAX)
+struct CkbdWgradSlices { int64_t S, L; }; // S slices of L positions (the last one shorter); a function of P = n * h * w/2 alone
+static inline CkbdWgradSlices ckbd_wgrad_slices(int64_t P) {
+  if (P <= 0) return {0, 32};
+  const int64_t want = (P + kCkbdWgradSliceMin - 1) / kCkbdWgradSliceMin, s0 = want < kCkbdWgradSliceMax ? want : kCkbdWgradSliceMax;
+  const int64_t L = 32 * ((P + 32 * s0 - 1) / (32 * s0));
+  return {(P + L - 1) / L, L};
+}
+static inline int64_t ckbd_wgrad_cols(int M) { return (int64_t)kCkbdCtxTaps * M + 1; } // a partial's row: [12 M] taps x channels, then the bias
+struct CkbdWgradArgs {
+  const float *anchors, *g; // device [n, M, h, w2], [n, c_out, h, w2]
+  float *partial;           // device [S][c_out][12 M + 1]
+  int32_t M, c_out, h, w2, odd;
+  int32_t mt;               // channel tiles of 32 per tap
+  int32_t col0, n_col;      // the column tiles the launch computes: of [0, 12 mt] (12 mt: the bias')
+  int32_t P, L, S;
+};
+// row tiles per block the launch takes (4, 2 or 1); blocks = S * ceil(n_col / 4) * ceil(ceil(c_out / 32) / that)
+int ckbd_wgrad_tiles(int64_t S, int n_col, int c_out);
+int launch_ckbd_wgrad(const CkbdWgradArgs &args, void *stream);
+int launch_ckbd_wgrad_finish(const float *partial, int M, int c_out, int S, float *dweight_or_null, float *dbias_or_null, void *stream);
 
 // ---- GPU-side decode of CHECKPOINTED bitstreams (segdec_kernel): one wave per segment ---------------------------
 struct SegDesc {

@@ -32,7 +32,7 @@ from torch import Tensor
 from itertools import accumulate
 
 from .entropy_models import EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead
-from .ops import CheckerboardContext, ckbd_embed, ckbd_unembed
+from .ops import CheckerboardContext, checkerboard_context, ckbd_embed, ckbd_unembed
 
 __all__ = ["GaussianMixtureConditionalLatentCodec", "CheckerboardLatentCodec", "ChannelGroupsLatentCodec", "HyperLatentCodec",
            "HyperpriorLatentCodec"]
@@ -338,7 +338,8 @@ class GaussianMixtureConditionalLatentCodec(nn.Module):
 
 
 class CheckerboardLatentCodec(nn.Module):
-    """Two-pass checkerboard context model, ``compress`` / ``decompress`` only (checkerboard.py:275-330).
+    """Two-pass checkerboard context model: ``compress`` / ``decompress`` (checkerboard.py:275-330), and the one-pass training
+    ``forward`` (checkerboard.py:154-171).
 
     ``latent_codec["y"]`` is a ``GaussianMixtureConditionalLatentCodec`` (its own ``entropy_parameters`` is the
     identity: the parameter network sits here, as in the reference's models); ``entropy_parameters`` must be
@@ -353,7 +354,7 @@ class CheckerboardLatentCodec(nn.Module):
         # matrix cores in ONE fixed summation order; the anchors' context is zeros and costs no convolution).  Like fuse_softmax and
         # fuse_head it changes the last bits of the parameters: the streams are self-consistent on any ROCm / MIOpen version, but they are
         # not the un-fused path's streams - encoder and decoder must agree on this switch.  Works alone and together with fuse_head.
-        # Inference only: the weights are detached.
+        # In compress / decompress the weights are detached; forward() runs the same operator under autograd (section 5c).
         self.fuse_context = bool(fuse_context)
         self._context: Optional[CheckerboardContext] = None
         self._context_key = None
@@ -554,8 +555,64 @@ class CheckerboardLatentCodec(nn.Module):
             return [{"y_hat": self.embed(yh)} for yh in y_hat_]
         return [{"y_hat": self.embed(yh), "y_rec": self.embed(yr)} for yh, yr in zip(y_hat_, y_rec_)]
 
-    def forward(self, y: Tensor, side_params: Tensor):
-        raise NotImplementedError("training-time likelihoods are outside the entropy-coding path")
+    def _check_mask(self) -> None:
+        """forward()'s condition on context_prediction: a 5x5 convolution whose ``mask`` buffer is the checkerboard pattern.  Looked
+        at once per mask (its address and version): the comparison reads the device back"""
+        cp = self.context_prediction
+        w, mask = getattr(cp, "weight", None), getattr(cp, "mask", None)
+        if w is None or mask is None or w.dim() != 4 or tuple(w.shape[2:]) != (5, 5) or tuple(mask.shape) != tuple(w.shape):
+            raise ValueError("forward() needs context_prediction to be a 5x5 convolution with a `mask` buffer of its weight's shape "
+                             "(the reference's CheckerboardMaskedConv2d)")
+        key = (mask.data_ptr(), mask._version, tuple(mask.shape))
+        if getattr(self, "_mask_ok", None) == key:
+            return
+        keep = torch.zeros(25, dtype=torch.bool, device=mask.device)
+        keep[1::2] = True  # the kernel positions (i, j) with i + j odd
+        flat = mask.detach().reshape(mask.shape[0], mask.shape[1], 25)
+        if not bool(((flat == 1) == keep).all()) or not bool(((flat == 0) == ~keep).all()):
+            raise ValueError("context_prediction.mask is not the checkerboard pattern (1 at the kernel positions (i, j) with i + j odd, 0 elsewhere)")
+        self._mask_ok = key
+
+    def forward(self, y: Tensor, side_params: Tensor) -> Dict[str, Any]:
+        """The reference's one-pass training forward (``_forward_onepass``, checkerboard.py:154-171; the only forward method the GMM
+        models use, models/ckbd_gmm.py:125), any batch size: ``y_hat = y + U(-0.5, 0.5)`` in training, ``round(y)`` otherwise
+        (:414-417); ``y_ctx`` = the context convolution of ``y_hat`` kept at the non-anchors, zeros at the anchors;
+        ``params = entropy_parameters(merge(y_ctx, side_params))``; ``latent_codec["y"](y, params)`` ->
+        ``{"likelihoods": {"y": ...}, "y_hat": y_hat}`` with this codec's own ``y_hat``, as the reference returns.
+
+        ``fuse_context=False``: ``context_prediction`` runs as the torch module it is.  ``fuse_context=True``: a checkerboard-masked
+        filter at a non-anchor reads only anchors, so ``y_ctx = embed([0, checkerboard_context(unembed(y_hat)[0], weight * mask,
+        bias)])`` - the library's operator under autograd (header sections 5b, 5c: one fixed summation order forward and backward), the
+        module's own ``forward`` never runs.  Its bits differ from MIOpen's: a model meant to be coded with ``fuse_context`` sees it in
+        training.  ``context_prediction`` must carry a ``mask`` buffer equal to the checkerboard pattern (``ValueError`` otherwise).  A
+        documented difference from the reference: the gradient of ``context_prediction.weight`` is that of ``weight * mask`` - +0 at
+        the 13 dropped taps - where the reference, zeroing ``weight.data`` in place and differentiating a plain convolution
+        (compressai/layers/layers.py:141-144), leaves non-zero values there that enter a global gradient-norm clip.
+
+        ``fuse_head``, ``rdo_lambda`` / ``rdo_channel_skip`` and the inner codec's ``param_dtype`` are choices of the coding path and
+        do not apply here.  The two-pass forward methods are not provided (the reference does not support them for GMM either)."""
+        if self.forward_method != "onepass":
+            raise NotImplementedError(f"forward_method {self.forward_method!r}: only \"onepass\" is provided, the one forward method the GMM models "
+                                      "use (compressai/models/ckbd_gmm.py:125)")
+        self._check_mask()
+        if self.training:
+            y_hat = y + torch.empty_like(y).uniform_(-0.5, 0.5)
+        else:
+            y_hat = torch.round(y)
+        if self.fuse_context:
+            cp = self.context_prediction
+            ctx1 = checkerboard_context(self.unembed(y_hat)[0], cp.weight * cp.mask, getattr(cp, "bias", None), self.anchor_parity)
+            y_ctx = self.embed(torch.stack([torch.zeros_like(ctx1), ctx1]))
+        else:
+            y_ctx = self.context_prediction(y_hat)
+            keep = torch.zeros((1, 1) + tuple(y_ctx.shape[2:]), dtype=torch.bool, device=y_ctx.device)
+            s = int(self.anchor_parity == "odd")  # non-anchors: (even row, odd column) and (odd row, even column) for "even"
+            keep[..., 0::2, 1 - s::2] = True
+            keep[..., 1::2, s::2] = True
+            y_ctx = torch.where(keep, y_ctx, torch.zeros_like(y_ctx))  # _keep_only(., "non_anchor")
+        params = self.entropy_parameters(self.merge(y_ctx, side_params))
+        y_out = self.latent_codec["y"](y, params)
+        return {"likelihoods": {"y": y_out["likelihoods"]["y"]}, "y_hat": y_hat}
 
 
 class ChannelGroupsLatentCodec(nn.Module):
@@ -703,8 +760,19 @@ class ChannelGroupsLatentCodec(nn.Module):
             return {"y_hat": y_hat, "y_rec": self.merge_y(*(r["y_rec"] for r in results))}
         return {"y_hat": y_hat}
 
-    def forward(self, y: Tensor, side_params: Tensor):
-        raise NotImplementedError("training-time likelihoods are outside the entropy-coding path")
+    def forward(self, y: Tensor, side_params: Tensor) -> Dict[str, Any]:
+        """As the reference's (channel_groups.py:89-109): group k's codec is called with its slice of ``y`` and the parameters
+        ``_get_ctx_params`` builds from the side parameters and the ``y_hat`` of groups 0 .. k-1; likelihoods and ``y_hat`` are
+        concatenated along the channels."""
+        y_ = torch.split(y, self.groups, dim=1)
+        y_hat_: List[Tensor] = []
+        y_likelihoods_: List[Tensor] = []
+        for k in range(len(self.groups)):
+            params = self._get_ctx_params(k, side_params, tuple(y_hat_))
+            y_out = self.latent_codec[f"y{k}"](y_[k], params)
+            y_hat_.append(y_out["y_hat"])
+            y_likelihoods_.append(y_out["likelihoods"]["y"])
+        return {"likelihoods": {"y": torch.cat(y_likelihoods_, dim=1)}, "y_hat": torch.cat(y_hat_, dim=1)}
 
 
 class HyperLatentCodec(nn.Module):
@@ -781,5 +849,9 @@ class HyperpriorLatentCodec(nn.Module):
         y_out = self.latent_codec["y"].decompress(y_strings_, shape["y"], hyper_out["params"])
         return {"y_hat": y_out["y_hat"]}
 
-    def forward(self, y: Tensor):
-        raise NotImplementedError("training-time likelihoods are outside the entropy-coding path")
+    def forward(self, y: Tensor) -> Dict[str, Any]:
+        """As the reference's (hyperprior.py:109-118): the hyper codec's ``forward`` gives the ``z`` likelihoods and the parameters the
+        ``y`` codec's ``forward`` runs under -> ``{"likelihoods": {"y": ..., "z": ...}, "y_hat": ...}``."""
+        hyper_out = self.latent_codec["hyper"](y)
+        y_out = self.latent_codec["y"](y, hyper_out["params"])
+        return {"likelihoods": {"y": y_out["likelihoods"]["y"], "z": hyper_out["likelihoods"]["z"]}, "y_hat": y_out["y_hat"]}

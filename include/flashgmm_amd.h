@@ -1068,6 +1068,56 @@ void fgmm_ckbd_ctx_destroy(fgmm_ckbd_context *cc);
 int fgmm_ckbd_ctx_apply(fgmm_ctx *ctx, void *stream, const fgmm_ckbd_context *cc, const float *anchors, float *out, int n, int64_t h,
                         int64_t w, int anchor_odd);
 
+/* ---- section 5c. The context convolution's GRADIENTS on the matrix cores, in one fixed order; caller-owned packed weights -------------
+ * What CheckerboardLatentCodec._forward_onepass (compressai/latent_codecs/checkerboard.py:154-171) needs under autograd: there the
+ * convolution's output is kept at the non-anchor positions only, where a checkerboard-masked filter reads only anchors - the forward
+ * is exactly section 5b's operator on unembed(y_hat)[0].  Notation as 5b; g [n, C_out, h, w/2] is the gradient with respect to the
+ * compact non-anchor context, hw = h * w/2, TAPS[t] = (i, j) the 12 kept kernel positions.
+ *   DATA GRADIENT  dA[n][c][p], p the anchor at full-size (r, col): the chain  acc = +0; for u = 0 .. 11 ascending, for o = 0 ..
+ *          C_out-1 ascending:  acc = fmaf(W[o][c][tap 11-u], gamma(u, o), acc), gamma(u, o) = g[n][o] at the non-anchor at full-size
+ *          (r + i_u - 2, col + j_u - 2), (i_u, j_u) = TAPS[u]; +0 outside the image.  That is 5b's chain with the filters
+ *          W'[c][o][i][j] = W[o][c][4-i][4-j], no bias, anchor_odd ^ 1, and M and C_out exchanged: fgmm_ckbd_ctx_pack(transposed = 1),
+ *          then fgmm_ckbd_ctx_apply_packed(packed, C_out, M, g, dA, n, h, w, anchor_odd ^ 1).
+ *   WEIGHT GRADIENT  the reduction runs over the positions of ALL items, concatenated: s = n hw + q, P = n_items hw, in slices whose
+ *          number and length are a function of P alone (never of the device, the grid or the kernel variant):
+ *              S0 = min(FGMM_CKBD_WGRAD_SLICES_MAX, ceil(P / FGMM_CKBD_WGRAD_SLICE_MIN)),  L = 32 ceil(P / (32 S0)),  S = ceil(P / L)
+ *          slice k is s in [k L, min((k+1) L, P)) and may cross item boundaries (P = 1: S = 1, L = 32; 405: 2, 224; 4097: 15, 288 - a
+ *          sixteenth slice would be empty; 4352: 16, 288, the last slice 32 long).
+ *              partial_k[o][t M + c] = the chain  acc = +0; for s ascending in slice k:  acc = fmaf(g(s)[o], x(s)(t, c), acc)
+ *              dW[o][c][tap t]       = ((partial_0 + partial_1) + partial_2) + ...   in binary32, ascending
+ *          x(s)(t, c) is what tap t of channel c reads at the non-anchor s (5b; +0 outside the image, which takes part).  The 13
+ *          dropped taps of every filter are written +0.  dbias[o]: the same slices in the same order with x = 1.
+ *          On v_mfma_f32_32x32x2_f32 bit for bit - signs of zero, infinities and NaN included; no float atomics.
+ *   A DIFFERENCE FROM THE REFERENCE  CheckerboardMaskedConv2d zeroes weight.data in place before every forward (compressai/layers/
+ *          layers.py:141-144) and then differentiates a plain convolution: its dropped taps receive non-zero gradients, which never
+ *          influence a forward value but do enter a global gradient-norm clip.  Here the gradient is that of weight * mask: +0 at the
+ *          dropped taps. */
+#define FGMM_HAS_CKBD_CONTEXT_GRAD 1 /* section 5c (added without a bump, as 3b - 5b) */
+#define FGMM_CKBD_WGRAD_SLICE_MIN 256 /* positions a slice holds before the weight gradient's reduction is cut into more slices */
+#define FGMM_CKBD_WGRAD_SLICES_MAX 16 /* slices at the most: the workspace holds as many partial copies of [C_out, 12 M + 1] */
+/* Packed weights in CALLER-OWNED device memory (a training step repacks every time; fgmm_ckbd_ctx_create allocates, waits and reads a
+ * flag back).  All five calls are STREAM-ORDERED like section 5's: enqueued on `stream`, no context lock, no host wait; a refused call
+ * launches nothing and writes nothing.
+ * fgmm_ckbd_ctx_packed_floats: float32 elements of `packed` for a convolution from M to C_out channels (0 for sizes that are refused).
+ * fgmm_ckbd_ctx_pack: weight device float32 [C_out, M, 5, 5], the EFFECTIVE weight - the 13 dropped taps are not looked at (create keeps
+ *   its refusal); transposed = 0 writes the layout create builds, into packed[fgmm_ckbd_ctx_packed_floats(M, C_out)]; transposed = 1
+ *   writes W' above - a convolution from C_out to M channels, packed[fgmm_ckbd_ctx_packed_floats(C_out, M)], to be applied with the
+ *   sizes exchanged - and takes no bias (a bias with it is refused).
+ * fgmm_ckbd_ctx_apply_packed: fgmm_ckbd_ctx_apply on such a buffer; M, C_out are the PACKED convolution's.  Refusals as apply's. */
+size_t fgmm_ckbd_ctx_packed_floats(int M, int C_out);
+int fgmm_ckbd_ctx_pack(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int C_out, int transposed, float *packed);
+int fgmm_ckbd_ctx_apply_packed(fgmm_ctx *ctx, void *stream, const float *packed, int M, int C_out, const float *anchors, float *out, int n,
+                               int64_t h, int64_t w, int anchor_odd);
+/* fgmm_ckbd_ctx_wgrad: anchors device float32 [n, M, h, w/2] (may be NULL when dweight is), g device float32 [n, C_out, h, w/2];
+ * dweight device float32 [C_out, M, 5, 5] or NULL, dbias device float32 [C_out] or NULL: only what is asked for is computed.
+ * workspace: device memory of at least fgmm_ckbd_ctx_wgrad_workspace(...) BYTES (S partial copies of [C_out, 12 M + 1] float32; 0 for
+ * sizes that are refused or n == 0), aligned to 16 bytes, the call's own until the work enqueued by it has run.  Refused: what
+ * fgmm_ckbd_ctx_apply refuses, n * h * w/2 beyond 2^31, a workspace that is null, smaller than that or misaligned, and both outputs NULL
+ * with n > 0.  n == 0: success, no launch. */
+size_t fgmm_ckbd_ctx_wgrad_workspace(int M, int C_out, int n, int64_t h, int64_t w);
+int fgmm_ckbd_ctx_wgrad(fgmm_ctx *ctx, void *stream, const float *anchors, const float *g, int M, int C_out, int n, int64_t h, int64_t w,
+                        int anchor_odd, float *dweight, float *dbias, void *workspace, size_t workspace_bytes);
+
 /* compressai._CXX.pmf_to_quantized_cdf (compressai/cpp_exts/ops/ops.cpp:40-109): cdf_out has n + 1 entries */
 int fgmm_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *cdf_out);
 
