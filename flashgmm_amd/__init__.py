@@ -9,7 +9,7 @@
 All floating-point work runs in hand-written HIP kernels (flashgmm_amd/csrc); there is no CPU fallback.
 """
 from . import _lib  # noqa: F401
-from .entropy_models import BudgetQuantized, RdCurve, CheckpointedBytes, CompressedBatch, EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead, RateEstimate, RdoQuantized, RdoSkipQuantized  # noqa: F401
+from .entropy_models import BudgetQuantized, RdCurve, CheckpointedBytes, CompressedBatch, EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead, RateEstimate, RdoQuantized, RdoSkipQuantized, aux_loss, update_entropy_models  # noqa: F401
 from .ops import CheckerboardContext, checkerboard_context  # noqa: F401
 from . import ans  # noqa: F401
 

@@ -155,6 +155,7 @@ LIKE_GRAD_ITEM_DTYPE = _item_dtype(fgmm_like_grad_item)
 CENTROID_ITEM_DTYPE = _item_dtype(fgmm_centroid_item)
 FGMM_EB_PARAMS = 58  # float32 values per channel of section 3j's theta
 FGMM_EB_SLICE = 1024  # section 3j: elements of a channel one workgroup walks
+FGMM_EB_SEARCH_CAP = 256  # section 3k: bisection steps of one quantile search at the most
 FGMM_LIKE_Q = 32  # unit of the likelihood call's bits_q: 2^-32 bit
 FGMM_RATE_Q = 24  # unit of the size estimate's costs: 2^-24 bit
 
@@ -239,6 +240,10 @@ SIGNATURES = {
     "fgmm_gmc_centroid_batch": (_i, [_p, _p, C.POINTER(fgmm_centroid_item), _i, C.c_float, C.c_float]),
     "fgmm_eb_likelihood": (_i, [_p, _p, C.POINTER(fgmm_eb_call), _i, C.c_float]),
     "fgmm_eb_likelihood_backward": (_i, [_p, _p, C.POINTER(fgmm_eb_grad_call), _i, C.c_float]),
+    # section 3k: (ctx, stream, theta, C, targets[3], search_radius, q_out); (ctx, stream, theta, start, length, C, stride, pmf_out, cdf_out,
+    # failed_channel_out)
+    "fgmm_eb_quantiles": (_i, [_p, _p, _p, _i, C.POINTER(C.c_float), C.c_float, _p]),
+    "fgmm_eb_tables": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, C.POINTER(_i32)]),
     "fgmm_build_tab_hip": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i32, _i, _p, _p, _p, C.c_uint64, _p, C.POINTER(_i32)]),
     "fgmm_ctx_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fgmm_ctx_get_option": (_i, [_p, C.c_char_p, C.POINTER(_i64)]),

@@ -16,7 +16,8 @@
 # gradients on the encode frame, in the same entry-point shell, without the census: not part of the fake-device build either);
 # fgmm_centroid.cpp over fgmm_centroid.hip (centroid reconstruction of decoded latents, section 3i of the header: like_kernel's forward with one
 # more sum, in the same shell: not part of the fake-device build either); fgmm_eb.cpp over fgmm_eb.hip (the entropy bottleneck's forward(),
-# section 3j: the factorized density of the hyper-latent, its rate and gradients: not part of the fake-device build either); fgmm_ckbd_ctx.cpp over fgmm_ckbd_ctx.hip
+# section 3j: the factorized density of the hyper-latent, its rate and gradients, and its update(), section 3k: the quantile search and the
+# masses of the coding tables: not part of the fake-device build either); fgmm_ckbd_ctx.cpp over fgmm_ckbd_ctx.hip
 # (the checkerboard context convolution on the matrix cores, section 5b: a weights handle and a stream-ordered apply, on fgmm_headframe.h's
 # placement and bias helpers: not part of the fake-device build either; fgmm_ckbd_ctx_grad.hip: its weight and bias gradients, section 5c,
 # behind the same fgmm_ckbd_ctx.cpp).

@@ -1,7 +1,8 @@
 // fgmm_eb.cpp — the entropy bottleneck's forward(): the likelihood of the hyper-latent under its factorized density, its rate, and the
 // gradients of either (include/flashgmm_amd.h section 3j).  Orchestration over fgmm_eb.hip behind two entry points, in the shell of the
 // likelihood calls (fgmm_ctx.h: latent_call).  Forward: one memset of the items' sums, one launch, one small copy back.  Backward: at most
-// one small upload (the items' g_bits), two launches - the partial rows [C][S][59] live in the context's workspace.  A file of its own:
+// one small upload (the items' g_bits), two launches - the partial rows [C][S][59] live in the context's workspace.  update() (section
+// 3k): the quantile search, one launch and nothing else; the tables, one launch, the rows back and the integer quantiser.  A file of its own:
 // the host sources that build against the fake device reference no launcher of these.
 #include "fgmm_ctx.h"
 
@@ -79,9 +80,83 @@ int eb_backward(fgmm_ctx *ctx, dev::Stream stream, fgmm_eb_grad_call *call, int 
   return FGMM_OK;
 }
 
+// ---- section 3k: update() ------------------------------------------------------------------------------------------------------------
+// the shell of latent_call for a call without items: the context's lock and device around `body(stream)`; a failure drains the stream
+template <class Body> int eb_update_call(fgmm_ctx *ctx, void *stream, Body body) {
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
+  const int rc = body((dev::Stream)stream);
+  if (rc != FGMM_OK) (void)dev::stream_sync((dev::Stream)stream);
+  return rc;
+}
+
+// One launch into the workspace, the rows and the lengths back, the integer quantiser per channel on the host; the caller's arrays are
+// written last, once every channel has passed.
+int eb_tables(fgmm_ctx *ctx, dev::Stream stream, const float *theta, const float *start, const int32_t *length, int C, int stride, float *pmf_out,
+              int32_t *cdf_out, int32_t *failed) {
+  Arena ar;
+  const size_t n = (size_t)C * (size_t)stride;
+  const size_t o_pmf = ar.take(sizeof(float) * n), o_len = ar.take(sizeof(int32_t) * (size_t)C), end = ar.off;
+  int rc;
+  if ((rc = ctx->ensure_device(end)) || (rc = ctx->ensure_host(end)) || (rc = ctx->ensure_events(1))) return rc;
+  float *d_pmf = ws<float>(ctx->d_ws, o_pmf);
+  LAUNCH_TRY(launch_eb_pmf(theta, start, length, C, stride, d_pmf, stream));
+  DEV_TRY(dev::copy_async(ctx->h_ws + o_pmf, d_pmf, sizeof(float) * n, dev::kD2H, stream));
+  DEV_TRY(dev::copy_async(ctx->h_ws + o_len, length, sizeof(int32_t) * (size_t)C, dev::kD2H, stream));
+  DEV_TRY(dev::event_record(ctx->events[0], stream));
+  DEV_TRY(dev::event_sync(ctx->events[0]));
+  const float *pmf = ws<const float>(ctx->h_ws, o_pmf);
+  const int32_t *len = ws<const int32_t>(ctx->h_ws, o_len);
+  std::vector<int32_t> cdf((size_t)C * ((size_t)stride + 1), 0);
+  for (int c = 0; c < C; ++c) {
+    const float *row = pmf + (size_t)c * (size_t)stride;
+    if (failed) *failed = c;
+    if (len[c] < 1 || (int64_t)len[c] + 1 > stride) return fail(FGMM_ERR_INVALID, "channel %d: length = %d does not fit a row of %d entries with its tail", c, len[c], stride);
+    for (int i = 0; i <= len[c]; ++i)
+      if (!(row[i] >= 0.0f) || !(row[i] < INFINITY))
+        return fail(FGMM_ERR_INVALID, "channel %d: the mass of entry %d of %d is %g", c, i, len[c] + 1, (double)row[i]);
+    if (len[c] + 1 > 65536) return fail(FGMM_ERR_INVALID, "channel %d: %d symbols (its support and the tail) exceed 2^16 counts", c, len[c] + 1);
+    if (pmf_to_quantized_cdf(row, len[c] + 1, 16, reinterpret_cast<uint32_t *>(cdf.data() + (size_t)c * ((size_t)stride + 1))) != FGMM_OK)
+      return fail(FGMM_ERR_INVALID, "channel %d: every mass rounds to zero", c);
+  }
+  if (failed) *failed = -1;
+  if (pmf_out) { // (the workspace is the next call's: the copy has completed before this one returns)
+    DEV_TRY(dev::copy_async(pmf_out, d_pmf, sizeof(float) * n, dev::kD2D, stream));
+    DEV_TRY(dev::event_record(ctx->events[0], stream));
+    DEV_TRY(dev::event_sync(ctx->events[0]));
+  }
+  memcpy(cdf_out, cdf.data(), sizeof(int32_t) * cdf.size());
+  return FGMM_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int fgmm_eb_quantiles(fgmm_ctx *ctx, void *stream, const float *theta, int C, const float *targets, float search_radius, float *q_out) {
+  if (!ctx || !theta || !targets || !q_out) return fail(FGMM_ERR_INVALID, "null ctx, theta, targets or q_out");
+  if (C < 1) return fail(FGMM_ERR_INVALID, "C = %d: must be at least 1", C);
+  if (!(search_radius > 0.0f) || !(search_radius < INFINITY)) return fail(FGMM_ERR_INVALID, "search_radius = %g: must be finite and > 0", (double)search_radius);
+  EbTargets t;
+  for (int k = 0; k < 3; ++k) {
+    if (targets[k] != targets[k]) return fail(FGMM_ERR_INVALID, "targets[%d] is NaN", k);
+    t.t[k] = targets[k];
+  }
+  return eb_update_call(ctx, stream, [&](dev::Stream s) {
+    LAUNCH_TRY(launch_eb_quantiles(theta, C, t, search_radius, q_out, s));
+    return (int)FGMM_OK;
+  });
+}
+
+int fgmm_eb_tables(fgmm_ctx *ctx, void *stream, const float *theta, const float *start, const int32_t *length, int C, int stride, float *pmf_out,
+                   int32_t *cdf_out, int32_t *failed_channel_out) {
+  if (!ctx || !theta || !start || !length || !cdf_out) return fail(FGMM_ERR_INVALID, "null ctx, theta, start, length or cdf_out");
+  if (C < 1 || stride < 2) return fail(FGMM_ERR_INVALID, "C = %d, stride = %d: at least 1 channel and 2 entries (one mass and the tail)", C, stride);
+  if ((int64_t)C * stride > 0x7FFFFFFFll) return fail(FGMM_ERR_INVALID, "C * stride = %lld exceeds 2^31 - 1", (long long)C * stride);
+  if (failed_channel_out) *failed_channel_out = -1;
+  return eb_update_call(ctx, stream, [&](dev::Stream s) { return eb_tables(ctx, s, theta, start, length, C, stride, pmf_out, cdf_out, failed_channel_out); });
+}
 
 int fgmm_eb_likelihood(fgmm_ctx *ctx, void *stream, fgmm_eb_call *call, int mode, float likelihood_bound) {
   if (!ctx || !call) return fail(FGMM_ERR_INVALID, "bad argument");

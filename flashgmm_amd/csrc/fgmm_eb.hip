@@ -4,6 +4,8 @@
 //   eb_kernel          (x, theta, med) -> the bounded likelihood per element (optional map), v (optional), every item's bit count
 //   eb_bwd_kernel      (x | v, theta, med, g | g_bits) -> dx (optional) and one partial row of dH | db | dt | sum dv per workgroup
 //   eb_finish_kernel   a channel's rows, in index order -> dtheta (the dM / df step applied once per channel), dmed
+//   eb_quantile_kernel (theta, three targets) -> the channel's quantiles: chain(q) = target, bisected          (section 3k: update())
+//   eb_pmf_kernel      (theta, start, length) -> the masses of a channel's integer support and its tail mass   (section 3k)
 //
 // A workgroup works inside ONE channel: it derives the channel's 58 values (softplus of the matrices, tanh of the factors) once, into
 // LDS, where every lane reads them (one address per read), and walks FGMM_EB_SLICE of the channel's B * hw elements.  What torch eager does with
@@ -329,9 +331,78 @@ __global__ __launch_bounds__(64) void eb_finish_kernel(const float *__restrict__
   dtheta[(int64_t)c * kEbP + i] = (float)t;
 }
 
+// ---- update() (header section 3k): the quantiles and the masses of the coding tables, on eb_params, eb_chain and eb_sig as they are --------
+// One 64-lane workgroup per channel: 58 lanes derive the channel's values, lanes 0 - 2 each bisect chain(q) = targets[lane] on
+// [-radius, radius].  A search sees its own channel and target only.  The start is the reference's non-strict one (a target that is not
+// bracketed collapses the interval onto the bound it lies beyond); a step ends the search when the midpoint equals one of the ends in
+// binary32, or after kEbSearchCap steps; a NaN anywhere among the chain values of a search makes its result NaN.
+__global__ __launch_bounds__(64) void eb_quantile_kernel(const float *__restrict__ theta, const EbTargets tg, float radius, float *__restrict__ q) {
+  __shared__ float s_par[64];
+  const int c = blockIdx.x, lane = threadIdx.x;
+  eb_params(theta, c, s_par);
+  if (lane >= 3) return;
+  const float *P = s_par;
+  const float t = lane == 0 ? tg.t[0] : (lane == 1 ? tg.t[1] : tg.t[2]);
+  float h[4][3], th[4][3];
+  float lo = -radius, hi = radius;
+  float f = eb_chain(P, hi, h, th);
+  bool nan = __builtin_isnan(f);
+  lo = t <= f ? lo : hi;
+  f = eb_chain(P, lo, h, th);
+  nan = nan || __builtin_isnan(f);
+  hi = f <= t ? hi : lo;
+#pragma unroll 1
+  for (int it = 0; it < kEbSearchCap && !nan; ++it) {
+    const float mid = (lo + hi) / 2.0f;
+    if (mid == lo || mid == hi) break;
+    f = eb_chain(P, mid, h, th);
+    nan = __builtin_isnan(f);
+    lo = f <= t ? mid : lo;
+    hi = f >= t ? mid : hi;
+  }
+  ((FGMM_GLOBAL float *)q)[(int64_t)c * 3 + lane] = nan ? __builtin_nanf("") : (lo + hi) / 2.0f;
+}
+
+// One lane per entry of a channel's row of `stride` floats, nb workgroups per channel.  Entry i < length: eb_kernel's L (mode 0, no
+// bound) of s = start + (float)i; entry length: the tail, both of its chains evaluated by the lane that writes it; the rest: +0.
+__global__ __launch_bounds__(kBlock) void eb_pmf_kernel(const float *__restrict__ theta, const float *__restrict__ start, const int32_t *__restrict__ length,
+                                                        int stride, int nb, float *__restrict__ pmf) {
+  __shared__ float s_par[64];
+  const int c = (int)(blockIdx.x / (unsigned)nb);
+  const int i = (int)(blockIdx.x - (unsigned)c * (unsigned)nb) * kBlock + (int)threadIdx.x;
+  eb_params(theta, c, s_par);
+  if (i >= stride) return;
+  const float *P = s_par;
+  const float s0 = eb_uniform(((const FGMM_GLOBAL float *)start)[c]);
+  const int len = __builtin_amdgcn_readfirstlane(((const FGMM_GLOBAL int32_t *)length)[c]);
+  float out = 0.0f;
+  float h[4][3], th[4][3];
+  if (i < len) {
+    const float v = s0 + (float)i;
+    const float lo = eb_chain(P, v - 0.5f, h, th), up = eb_chain(P, v + 0.5f, h, th);
+    const bool flip = (lo + up) > 0.0f;
+    out = eb_sig(flip ? -lo : up) - eb_sig(flip ? -up : lo);
+  } else if (i == len) {
+    const float lo = eb_chain(P, s0 - 0.5f, h, th), up = eb_chain(P, (s0 + (float)(len - 1)) + 0.5f, h, th);
+    out = eb_sig(lo) + eb_sig(-up);
+  }
+  ((FGMM_GLOBAL float *)pmf)[(int64_t)c * stride + i] = out;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------
+int launch_eb_quantiles(const float *theta, int C, const EbTargets &targets, float radius, float *q_out, void *stream) {
+  hipLaunchKernelGGL(eb_quantile_kernel, dim3((unsigned)C), dim3(64), 0, (hipStream_t)stream, theta, targets, radius, q_out);
+  return (int)hipGetLastError();
+}
+int launch_eb_pmf(const float *theta, const float *start, const int32_t *length, int C, int stride, float *pmf, void *stream) {
+  const int64_t nb = ((int64_t)stride + kBlock - 1) / kBlock, blocks = nb * C;
+  if (C < 1 || stride < 1 || blocks > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(eb_pmf_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, theta, start, length, stride, (int)nb, pmf);
+  return (int)hipGetLastError();
+}
+
 static bool eb_grid(const EbArgs &a, unsigned &blocks) {
   const int64_t g = (int64_t)a.C * a.S;
   blocks = (unsigned)g;

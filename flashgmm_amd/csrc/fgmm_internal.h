@@ -454,6 +454,15 @@ int launch_eb(const EbArgs &a, int vec, void *stream);
 int launch_eb_bwd(const EbArgs &a, void *stream);
 // sums a channel's S rows in index order, applies the dM / df step -> dtheta [C][58] (may be null), dmed [C] (may be null)
 int launch_eb_finish(const float *theta, const double *rows, float *dtheta, float *dmed, int C, int S, int mode, void *stream);
+// ---- its update(): quantiles and the masses of the coding tables (fgmm_eb.hip, fgmm_eb.cpp; header section 3k) ----------------------
+constexpr int kEbSearchCap = FGMM_EB_SEARCH_CAP; // bisection steps of one search at the most
+struct EbTargets { float t[3]; };
+// one 64-lane workgroup per channel -> q_out device [C][3]
+int launch_eb_quantiles(const float *theta, int C, const EbTargets &targets, float radius, float *q_out, void *stream);
+// start, length: device [C]; pmf: device [C][stride]: one lane per entry, ceil(stride / kBlock) workgroups per channel
+int launch_eb_pmf(const float *theta, const float *start, const int32_t *length, int C, int stride, float *pmf, void *stream);
+// compressai._CXX.pmf_to_quantized_cdf on the host (fgmm_rans.cpp): cdf has n + 1 entries
+int pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *cdf);
 
 // ---- host rANS (fgmm_rans.cpp), integer only --------------------------------------------------------------
 // Where a finished bitstream goes.  Default: a malloc'ed buffer (fgmm_free).  With a sink (include/flashgmm_amd.h: fgmm_sink) the

@@ -18,6 +18,7 @@ CPU, entropy_models.py:905-908, and lets the caller's assignment copy it back).
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -28,7 +29,7 @@ from torch import Tensor
 
 from . import _boundary, _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneck", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneck", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve", "update_entropy_models", "aux_loss"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -1316,8 +1317,10 @@ class EntropyBottleneck(nn.Module):
     same parameters (``_matrix{i}``, ``_bias{i}``, ``_factor{i}``, ``quantiles``), buffers and initialisation, so that a reference
     checkpoint loads with ``strict=True``; ``forward`` / ``rate_bits`` run the fused kernels of include/flashgmm_amd.h section 3j, which
     form the likelihood in the mirrored form (the reference's written form is rounding noise in the upper tail in float32).  The kernels
-    are bound to ``filters=(3, 3, 3, 3)``, the reference's default and what both GMM models construct.  ``update()`` - building the
-    tables - is not here: tables define the bitstream and come with the checkpoint; ``coder()`` codes on them."""
+    are bound to ``filters=(3, 3, 3, 3)``, the reference's default and what both GMM models construct.  ``update()`` builds the tables
+    (header section 3k): the support from the quantiles as the reference does, the masses by the kernels in ``forward``'s own arithmetic,
+    so that a model trained here is coded here; ``update_quantiles=True`` bisects the quantiles first, every channel on its own.  Tables
+    define the bitstream: a decoder uses the ones its encoder used, which is why they travel in the state dict.  ``coder()`` codes on them."""
 
     FILTERS = (3, 3, 3, 3)
     _TABLES = ("_offset", "_quantized_cdf", "_cdf_length")
@@ -1336,8 +1339,9 @@ class EntropyBottleneck(nn.Module):
         self.use_likelihood_bound = self.likelihood_bound > 0
         if self.use_likelihood_bound:
             self.likelihood_lower_bound = _EbBound(self.likelihood_bound)
-        for name in self._TABLES:  # filled by a checkpoint of an updated model
+        for name in self._TABLES:  # filled by update(), or by a checkpoint of an updated model
             self.register_buffer(name, torch.IntTensor())
+        self.update_report = None  # update(): {"pmf_length": [C], "tail_mass": [C]}
         width = (1,) + self.filters + (1,)
         scale = self.init_scale ** (1 / (len(self.filters) + 1))
         for i in range(len(self.filters) + 1):  # :360-385
@@ -1430,11 +1434,86 @@ class EntropyBottleneck(nn.Module):
         return (outputs, bits, nonfinite) if return_nonfinite else (outputs, bits)
 
     # ------------------------------------------------------------------------------------------------
+    def _update_device(self) -> torch.device:
+        dev = self.quantiles.device
+        if dev.type != "cuda":
+            raise RuntimeError("EntropyBottleneck.update runs on the GPU: the module must be on a CUDA/HIP device (there is no CPU path)")
+        return dev
+
+    def _search_quantiles(self, search_radius: float = 1e5) -> Tensor:
+        """-> ``[C, 1, 3]`` float32: per channel and target the bisected solution of ``chain(q) = target`` on ``[-search_radius,
+        search_radius]`` (``fgmm_eb_quantiles``, header section 3k; NaN where the chain of a search gave NaN)"""
+        dev = self._update_device()
+        theta = self._theta().detach().to(torch.float32).contiguous()
+        q = torch.empty((self.channels, 3), dtype=torch.float32, device=dev)
+        targets = (C.c_float * 3)(*self.target.detach().to("cpu", torch.float32).tolist())
+        _lib.check(_lib.lib().fgmm_eb_quantiles(*_ctx_stream(dev), theta.data_ptr(), self.channels, targets, float(search_radius), q.data_ptr()),
+                   "EntropyBottleneck._update_quantiles")
+        return q.reshape(self.channels, 1, 3)
+
+    @torch.no_grad()
+    def _update_quantiles(self, search_radius: float = 1e5) -> None:
+        """the reference's fast quantile update (:572-603) as one kernel: every channel's three searches run to the end on their own,
+        where the reference stops all channels once all pass ``isclose(rtol=1e-4, atol=1e-3)``"""
+        self.quantiles.copy_(self._search_quantiles(search_radius))
+
+    @torch.no_grad()
+    def update(self, force: bool = False, update_quantiles: bool = False) -> bool:
+        """As the reference's (:391-427): builds ``_offset``, ``_quantized_cdf`` ``[C, max_length + 2]`` and ``_cdf_length`` (int32, on the
+        module's device) from the quantiles, after bisecting those anew with ``update_quantiles``; -> False, nothing done, when the tables
+        are there and ``force`` is not set.  The support is the reference's float32 / int32 arithmetic in torch; the masses are the
+        kernels' (``fgmm_eb_tables``, header section 3k: the mirrored form, bit for bit ``forward``'s unbounded likelihood of the
+        same points; each channel's tail at its own last sample), the integer quantiser the host's.  The module changes only once the call has
+        succeeded: a channel whose quantiles are not finite, whose support exceeds 2^16 counts or whose masses are invalid raises
+        ``ValueError`` naming it.  ``update_report``: per channel ``pmf_length`` and ``tail_mass`` (the mass the tail entry holds);
+        a tail above ``10 * tail_mass`` - quantiles that do not bracket the density, as untrained ones do not - is warned about."""
+        if self._offset.numel() > 0 and not force:
+            return False
+        dev = self._update_device()
+        q = (self._search_quantiles() if update_quantiles else self.quantiles.detach()).to(torch.float32)
+        bad = (~torch.isfinite(q)).reshape(self.channels, -1).any(1).nonzero()
+        if bad.numel():
+            raise ValueError(f"EntropyBottleneck.update: channel {int(bad[0])}: its quantiles {q[int(bad[0]), 0].tolist()} are not finite")
+        medians = q[:, 0, 1]
+        span = torch.clamp(torch.ceil(medians - q[:, 0, 0]).double(), min=0) + torch.clamp(torch.ceil(q[:, 0, 2] - medians).double(), min=0) + 2
+        bad = (span > 65536).nonzero()
+        if bad.numel():
+            raise ValueError(f"EntropyBottleneck.update: channel {int(bad[0])}: {int(span[int(bad[0])])} symbols (its support and the tail) "
+                             "exceed 2^16 counts")
+        minima = torch.clamp(torch.ceil(medians - q[:, 0, 0]).int(), min=0)
+        maxima = torch.clamp(torch.ceil(q[:, 0, 2] - medians).int(), min=0)
+        pmf_start = (medians - minima).contiguous()
+        pmf_length = (maxima + minima + 1).contiguous()
+        stride = int(pmf_length.max().item()) + 1
+        theta = self._theta().detach().to(torch.float32).contiguous()
+        pmf = torch.empty((self.channels, stride), dtype=torch.float32, device=dev)
+        cdf = np.zeros((self.channels, stride + 1), np.int32)
+        failed = C.c_int32(-1)
+        rc = _lib.lib().fgmm_eb_tables(*_ctx_stream(dev), theta.data_ptr(), pmf_start.data_ptr(), pmf_length.data_ptr(), self.channels, stride,
+                                       pmf.data_ptr(), cdf.ctypes.data, C.byref(failed))
+        if rc == 1 and failed.value >= 0:  # FGMM_ERR_INVALID with a channel named: a property of the model, not of the call
+            raise ValueError("EntropyBottleneck.update: " + _lib.lib().fgmm_last_error().decode(errors="replace"))
+        _lib.check(rc, "EntropyBottleneck.update")
+        tail = pmf.gather(1, pmf_length.long().reshape(-1, 1)).reshape(-1).cpu()
+        if update_quantiles:
+            self.quantiles.copy_(q)
+        self._offset = -minima
+        self._quantized_cdf = torch.from_numpy(cdf).to(dev)
+        self._cdf_length = pmf_length + 2
+        self.__dict__.pop("_coder_cache", None)
+        self.update_report = {"pmf_length": pmf_length.cpu().tolist(), "tail_mass": tail.tolist()}
+        over = (tail > 10 * self.tail_mass).nonzero().reshape(-1).tolist()
+        if over:
+            warnings.warn(f"EntropyBottleneck.update: the tail entry of {len(over)} of {self.channels} channels holds more than 10 * tail_mass "
+                          f"(channel {over[0]}: {float(tail[over[0]]):.3g}): the quantiles do not bracket the density; "
+                          "update(force=True, update_quantiles=True) bisects them first", stacklevel=3)
+        return True
+
     def coder(self) -> "EntropyBottleneckCoder":
         """the coding half on this module's table buffers (built once per state of tables and medians)"""
         if any(getattr(self, n).numel() == 0 for n in self._TABLES):
-            raise RuntimeError("the table buffers are empty: load the checkpoint of an updated model (update() is not part of this class)")
-        key = tuple(getattr(self, n)._version for n in self._TABLES) + (self.quantiles._version, self.quantiles.data_ptr())
+            raise RuntimeError("the table buffers are empty: load the checkpoint of an updated model, or run update()")
+        key = tuple(k for n in self._TABLES for k in (getattr(self, n)._version, getattr(self, n).data_ptr())) + (self.quantiles._version, self.quantiles.data_ptr())
         cached = self.__dict__.get("_coder_cache")
         if cached is None or cached[0] != key:
             cached = (key, EntropyBottleneckCoder.from_entropy_bottleneck(self))
@@ -1446,3 +1525,19 @@ class EntropyBottleneck(nn.Module):
 
     def decompress(self, strings, size) -> Tensor:
         return self.coder().decompress(strings, size)
+
+
+def update_entropy_models(module: nn.Module, force: bool = False, update_quantiles: bool = False) -> bool:
+    """``CompressionModel.update`` (compressai/models/base.py:117-141) for any module tree: ``update()`` of every ``EntropyBottleneck``
+    in it (``module`` itself included) -> whether at least one was updated.  (The GMM path has no scale table to update.)"""
+    updated = False
+    for m in module.modules():
+        if isinstance(m, EntropyBottleneck):
+            updated |= m.update(force=force, update_quantiles=update_quantiles)
+    return updated
+
+
+def aux_loss(module: nn.Module) -> Tensor:
+    """``CompressionModel.aux_loss`` (base.py:143-172): the sum of the quantile losses of every ``EntropyBottleneck`` of the tree (the
+    integer 0 for a tree without one, as the reference's ``sum``)"""
+    return sum(m.loss() for m in module.modules() if isinstance(m, EntropyBottleneck))

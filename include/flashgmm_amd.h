@@ -57,6 +57,8 @@ extern "C" {
 #define FGMM_HAS_CENTROID 1  /* section 3i: fgmm_gmc_centroid_batch (added without a bump, as 3b - 3h) */
 #define FGMM_HAS_EB 1        /* section 3j: fgmm_eb_likelihood, fgmm_eb_likelihood_backward (added without a bump, as 3b - 3i) */
 #define FGMM_HAS_CKBD_CONTEXT 1 /* section 5b: fgmm_ckbd_ctx_create, fgmm_ckbd_ctx_destroy, fgmm_ckbd_ctx_apply (added without a bump, as 3b - 3j) */
+#define FGMM_HAS_EB_UPDATE 1 /* section 3k: fgmm_eb_quantiles, fgmm_eb_tables (added without a bump, as 3b - 3j) */
+#define FGMM_EB_SEARCH_CAP 256 /* section 3k: bisection steps of one quantile search at the most */
 #define FGMM_EB_PARAMS 58    /* float32 values per channel of section 3j's theta */
 #define FGMM_EB_SLICE 1024   /* section 3j: elements of a channel one workgroup walks; the backward's partial rows per channel are
                                 ceil(B*hw / FGMM_EB_SLICE) */
@@ -983,6 +985,46 @@ typedef struct {
   int32_t status, pad_;    /* out */
 } fgmm_eb_grad_call;
 int fgmm_eb_likelihood_backward(fgmm_ctx *ctx, void *stream, fgmm_eb_grad_call *call, int mode, float likelihood_bound);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 3k. The ENTROPY BOTTLENECK's update(): the quantiles of the factorized density and the coding tables of the z hyper-latent
+ *    (entropy_models.py:391-427, 573-603), the step between training on 3j and coding on section 4.  Once per checkpoint, no hot
+ *    path; on the GPU because the masses that become the tables must be the ones 3j assigns to the same points: H_i, t_i, chain
+ *    and sig are 3j's, theta [C][58] is 3j's, binary32 throughout, the same device code.
+ *    QUANTILES.  Per channel c and k = 0, 1, 2, an independent search for chain_c(q) = targets[k] (the reference searches all
+ *    channels together and stops when ALL pass isclose(rtol 1e-4, atol 1e-3): a channel's result there depends on the others):
+ *      lo = -search_radius, hi = search_radius
+ *      lo = targets[k] <= chain(hi) ? lo : hi;   then   hi = chain(lo) <= targets[k] ? hi : lo      (the reference's non-strict start: a
+ *                                                        target that is not bracketed collapses the interval onto the bound it lies beyond)
+ *      at most FGMM_EB_SEARCH_CAP times:  mid = (lo + hi) / 2;  stop if mid == lo or mid == hi;  f = chain(mid);
+ *                                         lo = f <= targets[k] ? mid : lo;   hi = f >= targets[k] ? mid : hi
+ *      q[c][k] = (lo + hi) / 2
+ *    The search ends where binary32 cannot split the interval (about 190 steps on [-1e5, 1e5] at the most, the cap is never the
+ *    reason with finite values).  IF ANY chain VALUE OF A SEARCH IS NaN (NaN parameters; infinite ones where inf - inf arises) THE
+ *    SEARCH STOPS AND q[c][k] IS NaN - the reference's loop does not end then.  Infinite chain values compare as they are.
+ *    One 64-lane workgroup per channel.  Stream-ordered: the call returns once the kernel is queued on `stream`; q_out is DEVICE
+ *    float32 [C][3].  targets: HOST float[3].  Refused (FGMM_ERR_INVALID, nothing queued): a null ctx, theta, targets or q_out;
+ *    C < 1; a NaN target; a search_radius that is not finite and > 0.
+ *    TABLES.  start[c] (float32) and length[c] (int32) describe channel c's integer support s_i = start + (float)i, i < length
+ *    (the reference's pmf_start and pmf_length).  Row c of the masses, `stride` floats:
+ *      entry i < length:   lo = chain(s_i - 0.5f), up = chain(s_i + 0.5f);  3j's L (the mirrored form, NO bound: update() applies
+ *                          none): bit for bit what fgmm_eb_likelihood writes for x = s_i in mode 0 with likelihood_bound 0
+ *      entry length:       the tail mass  sig(chain(s_0 - 0.5f)) + sig(-chain(s_{length-1} + 0.5f))      (entropy_models.py:422; the
+ *                          reference takes the upper term at the LONGEST channel's last sample for every channel, which is the
+ *                          channel's own wherever all lengths are equal and below its own tail otherwise)
+ *      entries after it:   +0
+ *    The rows come to the host, where compressai._CXX.pmf_to_quantized_cdf (fgmm_pmf_to_quantized_cdf, section 4; precision 16)
+ *    runs on the length + 1 entries of every channel: cdf_out, HOST int32 [C][stride + 1], row c = its length + 2 cumulative
+ *    counts, then zeros (entropy_models.py:206-214).  The call returns when cdf_out is complete.  pmf_out: NULL, or DEVICE float32
+ *    [C][stride], the rows as the quantiser saw them.  failed_channel_out: NULL, or HOST int32[1]: -1, or the channel refused.
+ *    start, length, theta: DEVICE.  Refused with FGMM_ERR_INVALID, cdf_out and pmf_out left as they were: a null ctx, theta, start,
+ *    length or cdf_out; C < 1; stride < 2; C * stride beyond 2^31 - 1; and, found after the kernel has run, the first channel with
+ *    length < 1 or length + 1 > stride, with a mass that is negative or not finite, with masses that all round to zero, or with
+ *    more symbols (length + 1) than 2^16 counts - *failed_channel_out names it.
+ * ---------------------------------------------------------------------------------------------------------- */
+int fgmm_eb_quantiles(fgmm_ctx *ctx, void *stream, const float *theta, int C, const float *targets, float search_radius, float *q_out);
+int fgmm_eb_tables(fgmm_ctx *ctx, void *stream, const float *theta, const float *start, const int32_t *length, int C, int stride,
+                   float *pmf_out, int32_t *cdf_out, int32_t *failed_channel_out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 4. Table path — the `z` hyper-latent coder: CompressAI's original table rANS, the other
