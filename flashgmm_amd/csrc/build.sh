@@ -7,6 +7,8 @@
 #                                               pairing moves: measured 1-6 % (symtab) / 12 % (cdftab count) slower with them
 # Sources: the kernels (*.hip; fgmm_encframe.h is the frame fgmm_kernels.hip, fgmm_rate.hip, fgmm_rdoq.hip and fgmm_rdcurve.hip share,
 # fgmm_headframe.h the one fgmm_head.hip and fgmm_head16.hip share: placement, rank prologue, epilogues, launch geometry and ladder,
+# fgmm_mfma32.h the binary32 matrix-core tile of fgmm_head.hip and fgmm_ckbd_ctx.hip - pitches, fragments, staging, the fenced K loop -
+# whose fragments fgmm_ckbd_ctx_grad.hip reads too, fgmm_ckbd_geom.h the checkerboard's taps and positions and the rule for a block's row tiles,
 # fgmm_decframe.h the one of the decode-side kernels of fgmm_tab.hip: a latent's parameters, window, pair of edges, trimming, ladder), the device layer over HIP (fgmm_device_hip.cpp), and the host side, which sees the device only
 # through fgmm_device.h (fgmm_capi / fgmm_encode / fgmm_decode / fgmm_decode_gpu / fgmm_rans: plain C++, also built without a GPU
 # toolchain against tests/fake/fake_device.cpp by scripts/tsan_host.sh); fgmm_rate_host.cpp (the coded size of a table, integer only) and

@@ -6,31 +6,30 @@
 // data movements, of which the mask keeps 12 taps and the codec half of the outputs.  Here: the compact anchors half in, the compact
 // non-anchor context out, one launch, the 12 kept taps at the non-anchor positions only - a quarter of the multiply-adds.
 //
-// Arithmetic: a non-anchor at full-size (r, c) reads, for tap t = 0 .. 11 = kernel position (i, j) = ((2 t + 1) / 5, (2 t + 1) % 5) (the
-// positions with i + j odd, row-major), the full-size position (r + i - 2, c + j - 2): inside the image always an anchor (read from the
-// anchors half at its compact place), outside +0.  Then, on v_mfma_f32_32x32x2_f32, bit for bit the chain
+// Arithmetic: a non-anchor at full-size (r, c) reads, for tap t = 0 .. 11 (fgmm_ckbd_geom.h: the kernel positions (i, j) with i + j odd,
+// row-major), the full-size position (r + i - 2, c + j - 2): inside the image always an anchor (read from the anchors half at its
+// compact place), outside +0.  Then, on v_mfma_f32_32x32x2_f32, bit for bit the chain
 //     acc = bias[o] (+0 without);  for t ascending, for c = 0 .. M - 1 ascending:  acc = fmaf(W[o][c][tap t], x(t, c), acc)
-// - head_kernel's chain (fgmm_head.hip) over c_in = 12 M gathered features, and its tiling: 256 threads = 4 waves, two blocks per CU,
-//   block  = T row tiles of 32 output channels (T x 16 accumulator registers per lane) x 128 compact positions (a wave: 32)
-//   K loop = tiles of 32 input channels of ONE tap through LDS: the gather offset of a position is constant over a tile.  Weights from a
-//            PRE-PACKED copy [row tile][K tile][32 rows][32 columns] (column h * 16 + s = channel 2 s + h of the tile), features by
-//            masked element loads of A[c][neighbour(q, t)].
+// - head_kernel's chain (fgmm_head.hip) over c_in = 12 M gathered features, on the same tile (fgmm_mfma32.h), two blocks per CU,
+//   block  = T row tiles of 32 output channels x 128 compact positions
+//   K loop = mfma32_k_loop over tiles of 32 input channels of ONE tap: the gather offset of a position is constant over a tile.  Weights
+//            from a PRE-PACKED copy [row tile][K tile][32 rows][32 columns], features by masked element loads of A[c][neighbour(q, t)].
 //   T      = 6 (head_kernel's block: 192 rows) where that still gives every CU a block, else 2, else 1: ONE Kodak image is 6 position
 //            tiles - at T = 6 and C_out = 384 twelve blocks on 256 CUs, each walking the whole K loop with six products per step; at
 //            T = 1, 72 blocks with one.  An output's chain does not depend on T: the same bits from every instantiation.
 // Padding (channels up to a K tile, positions up to 128, rows up to a row tile - and row tiles up to six): weights +0, features -0:
 // +0 * -0 = -0 leaves every accumulator's bits alone, -0 included.  A tap outside the image is +0 and takes part in the chain as the
 // definition says.
+#include "fgmm_ckbd_geom.h"
 #include "fgmm_headframe.h"
 
 namespace fgmm {
 namespace {
 
 constexpr int kBK = kCkbdCtxBK;     // input channels per LDS tile
-constexpr int kTileW = 32 * kBK;    // floats of one packed tile: 32 rows x 32 columns
-constexpr int kPB = 128;            // compact positions per block (4 waves x 32)
-constexpr int kALd = kBK + 4;       // LDS row pitches as in fgmm_head.hip
-constexpr int kBLd = kPB + 32;
+constexpr int kTileW = kMfma32TileW; // floats of one packed tile: 32 rows x 32 columns
+constexpr int kPB = kMfma32PB;      // compact positions per block
+constexpr int kALd = kMfma32ALd, kBLd = kMfma32BLd; // LDS row pitches
 
 // packs the 12 kept taps, and flags a dropped tap that is not +-0 (*bad = 1; zeroed by the host; null: not looked for).  M, c_out: the
 // PACKED convolution's input and output channels.  TRANSPOSED (the data gradient's filters, section 5c): w is [M, c_out, 5, 5] - the
@@ -49,10 +48,10 @@ __global__ __launch_bounds__(256) void ckbd_ctx_pack_kernel(const float *__restr
     }
     const int q = (int)(i % kBK), r = (int)((i / kBK) % 32);
     const int kt = (int)((i / kTileW) % n_kt), rt = (int)(i / ((int64_t)kTileW * n_kt));
-    const int t = kt / mt, c = (kt - t * mt) * kBK + 2 * (q & 15) + (q >> 4);
+    const int t = kt / mt, c = (kt - t * mt) * kBK + mfma32_pack_col(q);
     const int64_t o = (int64_t)rt * 32 + r;
-    if (TRANSPOSED) wp[i] = (o < c_out && c < M) ? w[((int64_t)c * c_out + o) * 25 + 23 - 2 * t] : 0.0f;
-    else wp[i] = (o < c_out && c < M) ? w[(o * M + c) * 25 + 2 * t + 1] : 0.0f;
+    if (TRANSPOSED) wp[i] = (o < c_out && c < M) ? w[((int64_t)c * c_out + o) * 25 + ckbd_tap_flat(11 - t)] : 0.0f;
+    else wp[i] = (o < c_out && c < M) ? w[(o * M + c) * 25 + ckbd_tap_flat(t)] : 0.0f;
   }
   if (!bad) return;
   bool any = false;
@@ -80,8 +79,8 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_r
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int q = P0 + 4 * (tid & 31) + e;
-    const int r = q / w2, j = q - r * w2;
-    pr[e] = r, pc[e] = 2 * j + 1 - ((r + a.odd) & 1);
+    const CkbdAt at = ckbd_nonanchor(q, w2, a.odd);
+    pr[e] = at.r, pc[e] = at.c;
     p_ok |= (q < hw ? 1u : 0u) << e;
   }
   // ---- accumulators start at the bias
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_r
 #pragma unroll
     for (int tl = 0; tl < kTiles; ++tl) head_bias_tile(bp, tl, h, acc[tl]);
   }
-  // ---- K loop (fgmm_head.hip's: one basic block, the loads of tile i + 1 in flight under the products of tile i)
+  // ---- K loop (mfma32_k_loop): tile kt = K tile kt - t * mt of tap t = kt / mt
   const int n_kt = a.n_kt, mt = a.mt;
   const float *wp = a.wp + (int64_t)rg * kTiles * n_kt * kTileW; // row tile rg * T + j, K tile kt: at ((rg * T + j) * n_kt + kt) * kTileW
   // Staging, branch-free: a load that would fall outside the anchors (channels past M in a tap's last tile, positions past hw, a tap
@@ -102,18 +101,17 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_r
   unsigned rb_ch = 0; // bit j: the channel of rb[j] is one of the M
   auto load_tile = [&](int kt) {
     rb_ok = 0, rb_ch = 0;
-    const FGMM_GLOBAL float4_t *src = (const FGMM_GLOBAL float4_t *)(wp + (int64_t)kt * kTileW);
 #pragma unroll
-    for (int j = 0; j < kTiles; ++j) ra[j] = src[tid + (int64_t)j * n_kt * (kTileW / 4)]; // (256 threads x 16 bytes: one packed tile)
+    for (int j = 0; j < kTiles; ++j) ra[j] = mfma32_load_a(wp + (int64_t)kt * kTileW, (int64_t)j * n_kt * (kTileW / 4));
     const int t = kt / mt, c0 = (kt - t * mt) * kBK;
-    const int di = (2 * t + 1) / 5 - 2, dj = (2 * t + 1) % 5 - 2;
+    const CkbdTap tap = ckbd_tap(t);
     int off[4];
     unsigned in = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int rr = pr[e] + di, cc = pc[e] + dj;
-      const bool ok = ((p_ok >> e) & 1u) && (unsigned)rr < (unsigned)hgt && (unsigned)cc < (unsigned)wid;
-      off[e] = ok ? rr * w2 + (cc >> 1) : 0; // the anchor at full-size (rr, cc) is compact (rr, cc >> 1)
+      const int rr = pr[e] + tap.di, cc = pc[e] + tap.dj;
+      const bool ok = ((p_ok >> e) & 1u) && ckbd_inside(rr, cc, hgt, wid);
+      off[e] = ok ? ckbd_anchor_at(rr, cc, w2) : 0;
       in |= (ok ? 1u : 0u) << e;
     }
 #pragma unroll
@@ -129,69 +127,9 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_r
       rb_ch |= (k_ok ? 1u : 0u) << j;
     }
   };
-  auto store_tile = [&]() {
-#pragma unroll
-    for (int j = 0; j < kTiles; ++j) {
-      const int f = tid + 256 * j;
-      *reinterpret_cast<float4_t *>(&sA[(f >> 3) * kALd + (f & 7) * 4]) = ra[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int f = tid + 256 * j;
-      const float fill = (rb_ch >> j) & 1u ? 0.0f : -0.0f;
-      float4_t v = rb[j];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (rb_ok >> (4 * j + e)) & 1u ? v[e] : fill;
-      *reinterpret_cast<float4_t *>(&sB[(f >> 5) * kBLd + (f & 31) * 4]) = v;
-    }
-  };
-  struct Frag {
-    float4_t a[kTiles];
-    float b[4];
-  };
-  auto read_frag = [&](Frag &f, int s4) {
-    const float *a_base = sA + col * kALd + h * 16 + s4 * 4;
-    const float *b_base = sB + h * kBLd + wave * 32 + col + 8 * s4 * kBLd;
-#pragma unroll
-    for (int tl = 0; tl < kTiles; ++tl) f.a[tl] = *reinterpret_cast<const float4_t *>(a_base + tl * 32 * kALd);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) f.b[e] = b_base[2 * e * kBLd];
-  };
-  auto multiply = [&](const Frag &f) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int tl = 0; tl < kTiles; ++tl) acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tl][e], f.b[e], acc[tl], 0, 0, 0);
-  };
-#define FGMM_FENCE() __builtin_amdgcn_sched_barrier(0)
-  load_tile(0);
-  store_tile();
-  __syncthreads();
-  Frag f0, f1;
-  read_frag(f0, 0);
-  for (int kt = 0; kt < n_kt; ++kt) {
-    FGMM_FENCE();
-    load_tile(kt + 1 < n_kt ? kt + 1 : kt); // (the last tile loads itself again: harmless)
-    read_frag(f1, 1);
-    FGMM_FENCE();
-    multiply(f0);
-    FGMM_FENCE();
-    read_frag(f0, 2);
-    FGMM_FENCE();
-    multiply(f1);
-    FGMM_FENCE();
-    read_frag(f1, 3);
-    FGMM_FENCE();
-    multiply(f0);
-    multiply(f1);
-    FGMM_FENCE();
-    __syncthreads(); // every wave has read the tile
-    store_tile();
-    __syncthreads();
-    read_frag(f0, 0); // (after the last tile: a read that nobody uses)
-  }
-#undef FGMM_FENCE
-  // ---- epilogue: register reg of row tile tl is output channel (rg * T + tl) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 h at the lane's position
+  mfma32_k_loop(acc, sA, sB, n_kt, wave, h, col, load_tile,
+                [&]() { mfma32_store_tile(sA, sB, ra, rb, rb_ok, [&](int j) { return (rb_ch >> j) & 1u ? 0.0f : -0.0f; }); });
+  // ---- epilogue: register reg of row tile tl is output channel (rg * T + tl) * 32 + mfma32_row(reg, h) at the lane's position
   const int p = P0 + wave * 32 + col;
   if (p < hw) {
     float *out = a.out + (int64_t)item * a.c_out * hw + p;
@@ -199,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_r
     for (int tl = 0; tl < kTiles; ++tl)
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int o = rg * kRows + tl * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        const int o = rg * kRows + tl * 32 + mfma32_row(reg, h);
         if (o < a.c_out) stg<float>(out + (int64_t)o * hw, acc[tl][reg]);
       }
   }
@@ -217,14 +155,6 @@ int launch_ckbd_ctx_pack(const float *w, const float *bias, int M, int c_out, bo
   return (int)hipGetLastError();
 }
 
-// T: the most row tiles per block (6, 2, 1) at which the launch still has a block for every CU; 1 when none has
-int ckbd_ctx_tiles(int64_t n, int64_t pt, int c_out) {
-  const int64_t n_rt = (c_out + 31) / 32;
-  for (int T : {6, 2})
-    if (n * pt * ((n_rt + T - 1) / T) >= kCkbdCtxFill) return T;
-  return 1;
-}
-
 template <int T> static int ckbd_ctx_go(const CkbdCtxArgs &a, int64_t n, hipStream_t st) {
   const int n_rg = ((a.c_out + 31) / 32 + T - 1) / T;
   const int64_t total = n * a.pt * n_rg;
@@ -235,12 +165,12 @@ template <int T> static int ckbd_ctx_go(const CkbdCtxArgs &a, int64_t n, hipStre
   return (int)hipGetLastError();
 }
 
+// T: the most row tiles per block (6, 2, 1) at which the launch still has a block for every CU; 1 when none has
+int ckbd_ctx_tiles(int64_t n, int64_t pt, int c_out) {
+  return ckbd_row_tiles_go<6, 2, 1>(n * pt, c_out, [](auto T) { return (int)T; });
+}
 int launch_ckbd_ctx(const CkbdCtxArgs &args, int64_t n, void *stream) {
-  switch (ckbd_ctx_tiles(n, args.pt, args.c_out)) {
-  case 6: return ckbd_ctx_go<6>(args, n, (hipStream_t)stream);
-  case 2: return ckbd_ctx_go<2>(args, n, (hipStream_t)stream);
-  }
-  return ckbd_ctx_go<1>(args, n, (hipStream_t)stream);
+  return ckbd_row_tiles_go<6, 2, 1>(n * args.pt, args.c_out, [&](auto T) { return ckbd_ctx_go<T>(args, n, (hipStream_t)stream); });
 }
 
 } // namespace fgmm

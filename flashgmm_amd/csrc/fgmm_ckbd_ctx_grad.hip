@@ -12,19 +12,21 @@
 //   block  = 256 threads = 4 waves: T row tiles of 32 output channels (T x 16 accumulator registers per lane) x 4 column tiles (one per
 //            wave: 32 input channels of ONE tap, so a position's gather offset is constant over the tile; or the bias' column) x ONE slice
 //   K loop = chunks of 32 positions through LDS (a slice is a multiple of 32 long but for the last): the instruction's k is a PAIR of
-//            positions, 2 i + (lane >> 5) in step i - head_kernel's layout with positions where it has input channels.  g rows are
-//            contiguous along positions: 32 lanes load 32 consecutive positions of a row; the features likewise, one channel a time
+//            positions - the tile of fgmm_mfma32.h with positions where it has input channels, its fragments and products, in a plain
+//            loop.  g rows are contiguous along positions: 32 lanes load 32 consecutive positions of a row; the features likewise
 //   T      = 4, 2 or 1 by the number of blocks of the launch, as ckbd_ctx_kernel picks among 6, 2 and 1 (six row tiles beside the staging
 //            registers of a chunk spill here); an output's chain does not depend on it
 // Padding: positions past the slice's end are g = +0, x = -0 (+0 * -0 = -0 leaves every accumulator's bits alone); rows past C_out and
 // channels past M read valid addresses and their accumulators are never stored.
+#include "fgmm_ckbd_geom.h"
 #include "fgmm_headframe.h"
 
 namespace fgmm {
 namespace {
 
 constexpr int kCh = 32;        // positions per chunk
-constexpr int kGLd = kCh + 4;  // LDS row pitch of the g tile (fgmm_head.hip's weights pitch)
+constexpr int kGLd = kMfma32ALd; // LDS row pitch of the g tile: the A tile's, its fragments are read by mfma32_read_frag
+static_assert(kCh == kMfma32BK, "a chunk is one K tile");
 constexpr int kXLd = kCh + 1;  // ... of a wave's feature tile [position][channel]
 
 template <int T> // row tiles per block
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_wgrad_kernel(CkbdWgradArgs a,
   const int jl = cg * 4 + wave, jt = a.col0 + jl;
   const bool active = jl < a.n_col, is_bias = jt == kCkbdCtxTaps * a.mt;
   const int t = is_bias ? 0 : jt / a.mt, c0 = is_bias ? 0 : (jt - t * a.mt) * 32;
-  const int di = (2 * t + 1) / 5 - 2, dj = (2 * t + 1) % 5 - 2;
+  const CkbdTap tap = ckbd_tap(t);
   f16_t acc[T];
 #pragma unroll
   for (int tl = 0; tl < T; ++tl)
@@ -69,10 +71,10 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_wgrad_kernel(CkbdWgradArgs a,
       for (int i = 0; i < 16; ++i) rx[i] = in ? 1.0f : -0.0f;
       return;
     }
-    const int r = q / w2, j2 = q - r * w2;
-    const int rr = r + di, cc = 2 * j2 + 1 - ((r + a.odd) & 1) + dj;
-    const bool ok = in && (unsigned)rr < (unsigned)hgt && (unsigned)cc < (unsigned)wid;
-    const int off = ok ? rr * w2 + (cc >> 1) : 0; // the anchor at full-size (rr, cc) is compact (rr, cc >> 1)
+    const CkbdAt at = ckbd_nonanchor(q, w2, a.odd);
+    const int rr = at.r + tap.di, cc = at.c + tap.dj;
+    const bool ok = in && ckbd_inside(rr, cc, hgt, wid);
+    const int off = ok ? ckbd_anchor_at(rr, cc, w2) : 0;
     const float fill = in ? 0.0f : -0.0f;
     const FGMM_GLOBAL float *xp = (const FGMM_GLOBAL float *)(a.anchors + (int64_t)item * M * hw + off);
 #pragma unroll
@@ -95,16 +97,9 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_wgrad_kernel(CkbdWgradArgs a,
     const float *b_base = sX + (wave * kCh + h) * kXLd + col;
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) {
-      float4_t fa[T];
-      float fb[4];
-#pragma unroll
-      for (int tl = 0; tl < T; ++tl) fa[tl] = *reinterpret_cast<const float4_t *>(a_base + tl * 32 * kGLd + s4 * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) fb[e] = b_base[2 * (4 * s4 + e) * kXLd];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int tl = 0; tl < T; ++tl) acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[tl][e], fb[e], acc[tl], 0, 0, 0);
+      Mfma32Frag<T> f;
+      mfma32_read_frag(f, a_base + s4 * 4, b_base + 8 * s4 * kXLd, kXLd);
+      mfma32_multiply(acc, f);
     }
   };
   load_chunk(0);
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_wgrad_kernel(CkbdWgradArgs a,
     if (more) store_chunk();
     __syncthreads();
   }
-  // ---- epilogue: register reg of row tile tl is output channel rg * 32 T + tl * 32 + (reg & 3) + 8 * (reg >> 2) + 4 h, the lane's column
+  // ---- epilogue: register reg of row tile tl is output channel rg * 32 T + tl * 32 + mfma32_row(reg, h), the lane's column
   if (!active) return;
   const int64_t n_col = (int64_t)kCkbdCtxTaps * M + 1; // ckbd_wgrad_cols
   int64_t column = -1;
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_wgrad_kernel(CkbdWgradArgs a,
   for (int tl = 0; tl < T; ++tl)
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int o = rg * kRows + tl * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+      const int o = rg * kRows + tl * 32 + mfma32_row(reg, h);
       if (o < c_out) stg<float>(out + (int64_t)o * n_col, acc[tl][reg]);
     }
 }
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(256) void ckbd_ctx_wgrad_finish_kernel(const float 
     int64_t at; // of partial_0
     if (i < n_w) {
       const int f = (int)(i % 25);
-      if (!(f & 1)) {
+      if (f != ckbd_tap_flat(f >> 1)) { // a dropped tap
         dw[i] = 0.0f;
         continue;
       }
@@ -174,18 +169,10 @@ template <int T> int ckbd_wgrad_go(const CkbdWgradArgs &a, hipStream_t st) {
 
 // T: the most row tiles per block (4, 2, 1) at which the launch still has a block for every CU; 1 when none has
 int ckbd_wgrad_tiles(int64_t S, int n_col, int c_out) {
-  const int64_t n_rt = (c_out + 31) / 32, n_cgrp = (n_col + 3) / 4;
-  for (int T : {4, 2})
-    if (S * n_cgrp * ((n_rt + T - 1) / T) >= kCkbdCtxFill) return T;
-  return 1;
+  return ckbd_row_tiles_go<4, 2, 1>(S * ((n_col + 3) / 4), c_out, [](auto T) { return (int)T; });
 }
-
 int launch_ckbd_wgrad(const CkbdWgradArgs &args, void *stream) {
-  switch (ckbd_wgrad_tiles(args.S, args.n_col, args.c_out)) {
-  case 4: return ckbd_wgrad_go<4>(args, (hipStream_t)stream);
-  case 2: return ckbd_wgrad_go<2>(args, (hipStream_t)stream);
-  }
-  return ckbd_wgrad_go<1>(args, (hipStream_t)stream);
+  return ckbd_row_tiles_go<4, 2, 1>((int64_t)args.S * ((args.n_col + 3) / 4), args.c_out, [&](auto T) { return ckbd_wgrad_go<T>(args, (hipStream_t)stream); });
 }
 
 int launch_ckbd_wgrad_finish(const float *partial, int M, int c_out, int S, float *dw, float *db, void *stream) {

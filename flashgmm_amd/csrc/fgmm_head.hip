@@ -16,13 +16,10 @@
 // Tiling (wave64, 256 threads = 4 waves, TWO blocks per CU - a wave holds 96 accumulator registers and at most 256 in all):
 //   block  = 16 latent channels (their 3*K = 12 parameters each: 192 rows of W) x 128 positions
 //   wave   = all 192 rows x 32 positions = 6 row tiles of 32x32 accumulators
-//   K loop = tiles of 32 input channels staged through LDS (W tile 192 x 32 from a PRE-PACKED copy of the weights: one contiguous 24 KB
-//            read per block and tile; x tile 32 x 128): the global loads of tile i + 1 are in flight while tile i is multiplied, the
-//            operand fragments are read from LDS one group of four k-pairs ahead of the products that use them.  One LDS buffer,
-//            two barriers per tile: the CU's OTHER block multiplies meanwhile (two blocks drift out of phase by themselves - a block's
-//            prologue, barriers and epilogue fall under the other's products; one block per CU with twice the tile: 0.67 of the roof)
+//   K loop = mfma32_k_loop (fgmm_mfma32.h) over tiles of 32 input channels: W tile 192 x 32 from a PRE-PACKED copy of the weights
+//            (one contiguous 24 KB read per block and tile), x tile 32 x 128
 //   rows   : row tile (g, t), g = which 8 of the 16 channels, t = scales | means | logits; row 4 * cl + k within it = parameter
-//            (t, k) of channel 8 g + cl.  The 32x32 accumulator map (row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), column = lane & 31)
+//            (t, k) of channel 8 g + cl.  The 32x32 accumulator map (row = mfma32_row(reg, lane >> 5), column = lane & 31)
 //            then gives every lane, for ITS position, registers 4 j + k = parameter (t, k) of channel 8 g + 2 j + (lane >> 5): a lane
 //            owns all twelve parameters of its latents - the epilogue needs no lane movement and no LDS.
 //   blocks that share an x tile (the channel groups of one position tile) get consecutive slots on ONE XCD: its L2 holds the tile.
@@ -34,9 +31,8 @@ namespace {
 constexpr int kCG = kHeadCG;          // latent channels per block
 constexpr int kRows = 12 * kCG;       // rows of W per block (192)
 constexpr int kBK = kHeadBK;          // input channels per LDS tile
-constexpr int kPB = 128;              // positions per block (4 waves x 32)
-constexpr int kALd = kBK + 4;         // LDS row pitch of the W tile (floats): 16-byte reads of 64 lanes hit 64 different banks
-constexpr int kBLd = kPB + 32;        // ... of the x tile: the two lane halves read rows k, k + 1 -> banks 32 apart
+constexpr int kPB = kMfma32PB;        // positions per block
+constexpr int kALd = kMfma32ALd, kBLd = kMfma32BLd; // LDS row pitches
 constexpr int kTiles = kRows / 32;    // 6 row tiles
 
 // packed weights: [channel group][K tile][192 rows][32 columns]; column h * 16 + s of a tile = input channel tile * 32 + 2 s + h
@@ -54,7 +50,7 @@ __global__ __launch_bounds__(256) void head_pack_kernel(const float *__restrict_
     if (is_bias) {
       bp[e] = (c < M && bias) ? bias[o] : 0.0f;
     } else {
-      const int kin = kt * kBK + 2 * (q & 15) + (q >> 4);
+      const int kin = kt * kBK + mfma32_pack_col(q);
       wp[e] = (c < M && kin < c_in) ? w[o * c_in + kin] : 0.0f;
     }
   }
@@ -102,18 +98,15 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
   // ---- K loop
   const int n_kt = hw_.n_kt, c_in = hw_.c_in;
   const float *wp = static_cast<const float *>(hw_.wp) + (int64_t)cg * n_kt * (kRows * kBK);
-  // Staging, branch-free (the K loop is ONE basic block, so that the instruction order below is the order issued): a load that would
-  // fall outside the features (input channels past c_in in the last tile, positions past hw in the last position tile) reads a valid
-  // address instead and is replaced by -0; the packed weights are +0 there.  +0 * -0 = -0 adds nothing to any accumulator, -0
-  // included (+0 + -0 = +0 would turn a chain that ends at -0 into +0): the padded channels leave the chain's bits as they are.
-  float4_t ra[6], rb[4];
-  unsigned rb_ok = 0; // bit 4 j + e: element e of rb[j] lies inside the features (applied when the tile is WRITTEN: a select right after
-                      // the load would wait for it, and the loads are there to be in flight under a tile's products)
+  // Staging, branch-free: a load that would fall outside the features (input channels past c_in in the last tile, positions past hw
+  // in the last position tile) reads a valid address instead and is replaced by -0 when the tile is written (mfma32_store_tile); the
+  // packed weights are +0 there: the padded channels leave the chain's bits as they are.
+  float4_t ra[kTiles], rb[4];
+  unsigned rb_ok = 0; // bit 4 j + e: element e of rb[j] lies inside the features
   auto load_tile = [&](int kt) {
     rb_ok = 0;
-    const float4_t *src = reinterpret_cast<const float4_t *>(wp + (int64_t)kt * (kRows * kBK));
 #pragma unroll
-    for (int j = 0; j < 6; ++j) ra[j] = src[tid + 256 * j];
+    for (int j = 0; j < kTiles; ++j) ra[j] = mfma32_load_a(wp + (int64_t)kt * (kRows * kBK), 256 * j);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int f = tid + 256 * j, kk = f >> 5, p4 = f & 31;
@@ -135,73 +128,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(const EncDesc *__restrict_
       rb[j] = v;
     }
   };
-  auto store_tile = [&]() {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int f = tid + 256 * j;
-      *reinterpret_cast<float4_t *>(&sA[(f >> 3) * kALd + (f & 7) * 4]) = ra[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int f = tid + 256 * j;
-      float4_t v = rb[j];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (rb_ok >> (4 * j + e)) & 1u ? v[e] : -0.0f;
-      *reinterpret_cast<float4_t *>(&sB[(f >> 5) * kBLd + (f & 31) * 4]) = v;
-    }
-  };
-  // the fragments of four k-pairs (one 16-byte read per row tile, one 4-byte read per k-pair): read one group AHEAD of the products
-  // that use them
-  struct Frag {
-    float4_t a[kTiles];
-    float b[4];
-  };
-  auto read_frag = [&](Frag &f, int s4) {
-    const float *a_base = sA + col * kALd + h * 16 + s4 * 4;
-    const float *b_base = sB + h * kBLd + wave * 32 + col + 8 * s4 * kBLd;
-#pragma unroll
-    for (int tl = 0; tl < kTiles; ++tl) f.a[tl] = *reinterpret_cast<const float4_t *>(a_base + tl * 32 * kALd);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) f.b[e] = b_base[2 * e * kBLd];
-  };
-  auto multiply = [&](const Frag &f) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int tl = 0; tl < kTiles; ++tl) acc[tl] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tl][e], f.b[e], acc[tl], 0, 0, 0);
-  };
-  // __builtin_amdgcn_sched_barrier(0): nothing is scheduled across it.  Left to itself the scheduler sinks every LDS read to just before
-  // its first use and the global loads to just before the LDS writes - each then waited for with the matrix pipe idle.
-#define FGMM_FENCE() __builtin_amdgcn_sched_barrier(0)
-  load_tile(0);
-  store_tile();
-  __syncthreads();
-  Frag f0, f1;
-  read_frag(f0, 0);
-  for (int kt = 0; kt < n_kt; ++kt) {
-    // 96 products per wave and tile in four groups of 24; before a group, what a LATER step needs is issued: the global loads of the
-    // next tile (the last tile loads itself again: harmless) and the fragments of the next group
-    FGMM_FENCE();
-    load_tile(kt + 1 < n_kt ? kt + 1 : kt);
-    read_frag(f1, 1);
-    FGMM_FENCE();
-    multiply(f0);
-    FGMM_FENCE();
-    read_frag(f0, 2);
-    FGMM_FENCE();
-    multiply(f1);
-    FGMM_FENCE();
-    read_frag(f1, 3);
-    FGMM_FENCE();
-    multiply(f0);
-    multiply(f1);
-    FGMM_FENCE();
-    __syncthreads(); // every wave has read the tile
-    store_tile();
-    __syncthreads();
-    read_frag(f0, 0); // (after the last tile: a read that nobody uses)
-  }
-#undef FGMM_FENCE
+  mfma32_k_loop(acc, sA, sB, n_kt, wave, h, col, load_tile, [&]() { mfma32_store_tile(sA, sB, ra, rb, rb_ok, [](int) { return -0.0f; }); });
   // ---- epilogue: the lane's 8 latents (2 channel halves x 4 channels at its position), all twelve parameters in registers
   if constexpr (FUSED) {
     const EncDesc &d = edescs[item];

@@ -5,11 +5,9 @@
 // A kernel adds its tiling, its staging and its K loop: the table entry one arithmetic writes is the entry the other writes because
 // they run this text, not a copy of it.
 #pragma once
-#include "fgmm_dev.h"
+#include "fgmm_mfma32.h"
 
 namespace fgmm {
-
-typedef float f16_t __attribute__((ext_vector_type(16))); // one 32x32 accumulator tile: row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), column = lane & 31
 
 // placement.  Blocks are dealt to the 8 XCDs round robin: the blocks that share an x tile (the channel groups of one position tile) get
 // consecutive logical slots L on ONE XCD, whose L2 then holds the tile.  PB: positions per block
@@ -96,7 +94,7 @@ template <int THREADS> __device__ __forceinline__ bool head_ranks(const EncDesc 
 // the accumulators of row tile `tile` of the block's 192 rows start at the bias (bp: the channel group's)
 __device__ __forceinline__ void head_bias_tile(const float *bp, int tile, int h, f16_t &acc) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = bp[tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
+  for (int r = 0; r < 16; ++r) acc[r] = bp[tile * 32 + mfma32_row(r, h)];
 }
 
 // epilogues.  A lane owns all twelve parameters of its latents: registers 4 j + k of the scales | means | logits tiles of a channel

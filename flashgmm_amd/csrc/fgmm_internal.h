@@ -86,7 +86,8 @@ struct DecDesc {
 
 // ---- the parameter head's last layer on the matrix cores (fgmm_head.hip) ----------------------------------------
 constexpr int kHeadCG = 16; // latent channels per block: the packed weights are laid out in groups of this many
-constexpr int kHeadBK = 32; // input channels per LDS tile
+constexpr int kMfma32BK = 32;       // the K tile of the binary32 matrix-core loop (fgmm_mfma32.h)
+constexpr int kHeadBK = kMfma32BK; // input channels per LDS tile
 struct HeadW {              // the PACKED weights of a head (device): see head_pack_kernel / head16_pack_kernel
   const void *wp;           // exact form: float [n_cg][n_kt][12 * kHeadCG][kHeadBK]; bf16x6: bf16 [n_cg][n_kt][3][12 * kHeadCG][kHeadBK]
   const float *bp;          // [n_cg][12 * kHeadCG]
@@ -136,7 +137,7 @@ int launch_head_planes(const HeadDesc *d_descs, const HeadPair &head, int count,
 int launch_head_entries(const EncDesc *d_descs, const HeadPair &head, int count, int M_max, int64_t hw_max, int mode, bool clamped, bool vec, void *stream);
 
 // ---- the checkerboard context convolution on the matrix cores (fgmm_ckbd_ctx.hip; header section 5b) --------------
-constexpr int kCkbdCtxBK = 32;    // input channels of one tap per LDS tile
+constexpr int kCkbdCtxBK = kMfma32BK; // input channels of one tap per LDS tile
 constexpr int kCkbdCtxTaps = 12;  // the kernel positions (i, j) of the 5x5 with i + j odd, row-major: flat index 2 t + 1
 constexpr int kCkbdCtxFill = 256; // blocks a launch wants before it takes more row tiles per block (one per CU)
 static inline int ckbd_ctx_row_tiles(int c_out) { return (c_out + 31) / 32 + 5 - ((c_out + 31) / 32 + 5) % 6; } // of 32 rows, padded to a multiple of 6

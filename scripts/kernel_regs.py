@@ -7,8 +7,9 @@
 For every kernel of OLD: its VGPRs, SGPRs, scratch bytes, LDS bytes and occupancy in both sets, and whether its instructions are the
 SAME TEXT (labels renumbered: inserting instantiations shifts the function numbers in .LBB<n>_<m>).  A kernel with matrix instructions
 gets a second verdict for the span from its first to its last v_mfma - the K loop of the parameter head (profiles/head_frame_refactor.md):
-"same mfma span" says that a change around the loop left the loop's own schedule alone.  Kernels only NEW has are summarised per
-template.  Needs no GPU."""
+"same mfma span" says that a change around the loop left the loop's own schedule alone; "same mfma span, masked" that the spans are
+equal once block labels and register numbers are masked - the same opcodes and waits in the same order, other registers
+(profiles/mfma32_tile_refactor.md).  Kernels only NEW has are summarised per template.  Needs no GPU."""
 import hashlib
 import re
 import subprocess
@@ -25,13 +26,14 @@ def demangle(names):
 
 
 LABEL = re.compile(r"\.L(BB|tmp|func_begin|func_end)\d+(_\d+)?")
+MASK = re.compile(rb"\.LBB_\d+|\b[vsa](\d+|\[\d+:\d+\])")  # block labels and register numbers, for the span's third verdict
 FIELDS = {"next_free_vgpr": "vgpr", "next_free_sgpr": "sgpr", "private_segment_fixed_size": "scratch", "group_segment_fixed_size": "lds"}
 
 
 def kernels(d):
-    """name -> dict(vgpr, sgpr, scratch, lds, occ, sha, span) for every kernel of the directory's .s files (one pass over the lines);
-    span: the hash of the lines from the first to the last v_mfma, None without one"""
-    res, sha, span, occ = {}, {}, {}, {}
+    """name -> dict(vgpr, sgpr, scratch, lds, occ, sha, span, masked) for every kernel of the directory's .s files (one pass over the
+    lines); span: the hash of the lines from the first to the last v_mfma, None without one; masked: the same with MASK applied"""
+    res, sha, span, masked, occ = {}, {}, {}, {}, {}
     for f in sorted(Path(d).glob("*.s")):
         cur = text = last = desc = pending = None
         with open(f) as fh:
@@ -51,6 +53,7 @@ def kernels(d):
                     if t.startswith(".Lfunc_end"):
                         mf = [i for i, ln in enumerate(text) if ln.startswith(b"v_mfma")]
                         span[cur] = hashlib.sha1(b"".join(text[mf[0]:mf[-1] + 1])).hexdigest()[:12] if mf else None
+                        masked[cur] = hashlib.sha1(MASK.sub(b"#", b"".join(text[mf[0]:mf[-1] + 1]))).hexdigest()[:12] if mf else None
                         sha[cur], last, cur = hashlib.sha1(b"".join(text)).hexdigest()[:12], cur, None
                     elif t and not t.startswith((";", ".loc", ".file", ".cfi")):
                         text.append(LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) or ""), t.split(";")[0].rstrip()).encode() + b"\n")
@@ -62,7 +65,7 @@ def kernels(d):
                     occ[last] = int(t.split()[-1])
                     last = None
     for name, r in res.items():
-        r["sha"], r["span"], r["occ"] = sha.get(name, "?"), span.get(name), occ.get(name)
+        r["sha"], r["span"], r["masked"], r["occ"] = sha.get(name, "?"), span.get(name), masked.get(name), occ.get(name)
     return res
 
 
@@ -72,7 +75,7 @@ def main():
     old, new = kernels(args[0]), kernels(args[1])
     dm = demangle(sorted(set(old) | set(new)))
     keys = ("vgpr", "sgpr", "scratch", "lds", "occ")
-    differ, regs_differ, n_mfma, span_differ = [], 0, 0, 0
+    differ, regs_differ, n_mfma, span_differ, masked_differ = [], 0, 0, 0, 0
     for name in sorted(old):
         if name not in new:
             differ.append((name, "missing in NEW"))
@@ -85,12 +88,14 @@ def main():
         if o["span"]:
             n_mfma += 1
             span_differ += o["span"] != n["span"]
+            masked_differ += o["masked"] != n["masked"]
         if show_all:
-            verdict = "same mfma span" if o["span"] == n["span"] else "MFMA SPAN DIFFERS"
+            verdict = "same mfma span" if o["span"] == n["span"] else "same mfma span, masked" if o["masked"] == n["masked"] else "MFMA SPAN DIFFERS"
             print(f"{dm[name][:150]:150s} " + " ".join(f"{k}={o.get(k)}" for k in keys) + (" same text" if o["sha"] == n["sha"] else " TEXT DIFFERS")
                   + (f" {verdict}" if o["span"] else ""))
     print(f"{len(old)} kernels in OLD, {len(new)} in NEW; of OLD's: {len(old) - len(differ)} with the same instructions, registers, scratch, LDS and occupancy; "
-          f"{len(differ)} that differ, {regs_differ} of them in {list(keys)}; {n_mfma} with matrix instructions, {span_differ} whose first-to-last v_mfma span differs")
+          f"{len(differ)} that differ, {regs_differ} of them in {list(keys)}; {n_mfma} with matrix instructions, {span_differ} whose first-to-last v_mfma span differs, "
+          f"{masked_differ} of them with labels and register numbers masked too")
     for name, why in differ:
         print("  DIFFERS", dm[name], why)
     # the kernels only NEW has: each bfloat16 instantiation (DF16b in the mangled name) beside its float16 sibling (DF16_)
