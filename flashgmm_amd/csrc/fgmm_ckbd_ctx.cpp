@@ -1,6 +1,7 @@
 // fgmm_ckbd_ctx.cpp — the checkerboard context convolution's entry points (include/flashgmm_amd.h section 5b) over fgmm_ckbd_ctx.hip: a
 // handle that owns the packed weights (immutable once made, like a parameter head's), and a STREAM-ORDERED apply - validation, one
-// launch, no workspace, no lock, no wait; and section 5c over fgmm_ckbd_ctx_grad.hip: the same with caller-owned packed weights (a
+// launch, no workspace, no lock, no wait (a FGMM_CKBD_CTX_BF16X6 handle, over fgmm_ckbd_ctx16.hip: both packings, and an apply with
+// the caller's workspace - the split, the bf16x6 kernel, the exact kernel for the items outside the domain); and section 5c over fgmm_ckbd_ctx_grad.hip: the same with caller-owned packed weights (a
 // training step repacks every time), the transposed packing the data gradient runs on, and the weight and bias gradients.  A file of
 // its own: the host sources that build against the fake device reference no launcher of these.
 #include "fgmm_ctx.h"
@@ -10,15 +11,23 @@ using namespace fgmm;
 struct fgmm_ckbd_context {
   int device = 0;
   int M = 0, c_out = 0;
-  float *packed = nullptr; // [wp | bp]
+  float *packed = nullptr;  // [wp | bp]
+  void *packed16 = nullptr; // FGMM_CKBD_CTX_BF16X6: the three bf16 parts of the weights (fgmm_ckbd_ctx16.hip) - the handle holds both packings
 };
 
 extern "C" {
 
 int fgmm_ckbd_ctx_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int c_out, fgmm_ckbd_context **out) {
+  return fgmm_ckbd_ctx_create_ex(ctx, stream, weight, bias, M, c_out, 0, out);
+}
+
+int fgmm_ckbd_ctx_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int c_out, int flags, fgmm_ckbd_context **out) {
   if (!out) return fail(FGMM_ERR_INVALID, "out == NULL");
   *out = nullptr;
   if (!ctx || !weight || M <= 0 || c_out <= 0 || M > (1 << 20) || c_out > (1 << 20)) return fail(FGMM_ERR_INVALID, "context convolution: bad argument");
+  if (flags & ~FGMM_CKBD_CTX_BF16X6) return fail(FGMM_ERR_INVALID, "context convolution: unknown flags 0x%x", (unsigned)flags);
+  const bool b16 = (flags & FGMM_CKBD_CTX_BF16X6) != 0;
+  if (b16 && ckbd_ctx16_mt(M) > 65535) return fail(FGMM_ERR_INVALID, "context convolution: bf16x6 takes at most %d input channels", 65535 * kHead16BK);
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
@@ -27,21 +36,29 @@ int fgmm_ckbd_ctx_create(fgmm_ctx *ctx, void *stream, const float *weight, const
   c->device = ctx->device, c->M = M, c->c_out = c_out;
   const size_t floats = ckbd_ctx_packed_floats(M, c_out), bias_floats = (size_t)ckbd_ctx_row_tiles(c_out) * 32;
   void *p = nullptr;
-  if (dev::malloc_device(&p, (floats + 4) * sizeof(float)) != 0) { // (+ the word the pack kernel flags a dropped tap in)
+  if (dev::malloc_device(&p, (floats + 4) * sizeof(float)) != 0) { // (+ the words the pack kernels flag a dropped tap and a weight outside the domain in)
     delete c;
     return fail(FGMM_ERR_NOMEM, "%zu bytes of device memory for the packed weights", floats * sizeof(float));
   }
   c->packed = static_cast<float *>(p);
-  uint32_t *d_bad = reinterpret_cast<uint32_t *>(c->packed + floats);
-  uint32_t bad = 0;
-  int e = dev::memset_async(d_bad, 0, sizeof(uint32_t), (dev::Stream)stream);
-  if (!e) e = launch_ckbd_ctx_pack(weight, bias, M, c_out, false, c->packed, c->packed + (floats - bias_floats), d_bad, stream);
-  if (!e) e = dev::stream_sync((dev::Stream)stream); // (the caller may free or overwrite its weights on return)
-  if (!e) e = dev::copy_sync(&bad, d_bad, sizeof(uint32_t), dev::kD2H);
-  if (e || bad) {
+  if (b16 && dev::malloc_device(&c->packed16, ckbd_ctx16_packed_bytes(M, c_out)) != 0) {
     (void)dev::free_device(p);
     delete c;
-    if (bad) return fail(FGMM_ERR_INVALID, "context convolution: a dropped tap (kernel position (i, j) with i + j even) of the weights is not zero");
+    return fail(FGMM_ERR_NOMEM, "%zu bytes of device memory for the packed bf16x6 weights", ckbd_ctx16_packed_bytes(M, c_out));
+  }
+  uint32_t *d_bad = reinterpret_cast<uint32_t *>(c->packed + floats); // [0]: a dropped tap is not zero; [1]: a kept tap outside the bf16x6 domain
+  uint32_t bad[2] = {0, 0};
+  int e = dev::memset_async(d_bad, 0, sizeof bad, (dev::Stream)stream);
+  if (!e) e = launch_ckbd_ctx_pack(weight, bias, M, c_out, false, c->packed, c->packed + (floats - bias_floats), d_bad, stream);
+  if (!e && b16) e = launch_ckbd_ctx16_pack(weight, M, c_out, c->packed16, d_bad + 1, stream);
+  if (!e) e = dev::stream_sync((dev::Stream)stream); // (the caller may free or overwrite its weights on return)
+  if (!e) e = dev::copy_sync(bad, d_bad, sizeof bad, dev::kD2H);
+  if (e || bad[0] || bad[1]) {
+    (void)dev::free_device(p);
+    if (c->packed16) (void)dev::free_device(c->packed16);
+    delete c;
+    if (bad[0]) return fail(FGMM_ERR_INVALID, "context convolution: a dropped tap (kernel position (i, j) with i + j even) of the weights is not zero");
+    if (bad[1]) return fail(FGMM_ERR_INVALID, "context convolution: a weight is outside the bf16x6 domain (finite, |w| < 0x1.FFp127)");
     return fail(FGMM_ERR_HIP, "packing the context convolution's weights: %s", dev::error_string(e));
   }
   *out = c;
@@ -53,13 +70,22 @@ void fgmm_ckbd_ctx_destroy(fgmm_ckbd_context *c) {
   {
     DeviceGuard g(c->device);
     (void)dev::free_device(c->packed);
+    if (c->packed16) (void)dev::free_device(c->packed16);
   }
   delete c;
 }
 
-// the checks apply and apply_packed share, then the one launch
+// bf16x6: bytes of one item's split copy with its domain word (0: the sizes overflow), the whole workspace being n of them
+static size_t ckbd_ctx16_item_bytes(int M, int n, int64_t hw) {
+  const int64_t per_pos = (int64_t)ckbd_ctx16_mt(M) * 3 * kHead16BK * (int64_t)sizeof(uint16_t);
+  if (n <= 0 || hw <= 0 || per_pos > (INT64_MAX / 4 - 64) / hw / n) return 0;
+  return (size_t)(per_pos * hw) + kHead16FlagElems * sizeof(uint16_t);
+}
+
+// the checks the applies share, then the launches: one, or - c16, a bf16x6 handle - the split, the bf16x6 kernel and the exact kernel
+// for the items the split flagged
 static int ckbd_ctx_run(fgmm_ctx *ctx, void *stream, const float *packed, int M, int c_out, const float *anchors, float *out, int n, int64_t h, int64_t w,
-                        int anchor_odd) {
+                        int anchor_odd, const fgmm_ckbd_context *c16 = nullptr, void *workspace = nullptr, size_t workspace_bytes = 0) {
   if (n < 0 || h < 1 || w < 2 || (w & 1) || (anchor_odd & ~1))
     return fail(FGMM_ERR_INVALID, "context convolution: bad argument (n >= 0, h >= 1, w even and >= 2)");
   if (n == 0) return FGMM_OK;
@@ -72,6 +98,15 @@ static int ckbd_ctx_run(fgmm_ctx *ctx, void *stream, const float *packed, int M,
   const int64_t hw = h * w2, pt = (hw + 127) / 128, n_rt = (c_out + 31) / 32; // (at most a block per row tile of 32)
   if (pt * n_rt > (1ll << 30) / n) return fail(FGMM_ERR_INVALID, "context convolution: %d x %lld x %lld workgroups exceed a grid", n, (long long)pt, (long long)n_rt);
   if (hw > INT64_MAX / 4 / n / std::max(M, c_out)) return fail(FGMM_ERR_INVALID, "context convolution: n * channels * h * w/2 overflows");
+  size_t item_bytes = 0;
+  if (c16) {
+    item_bytes = ckbd_ctx16_item_bytes(M, n, hw);
+    if (!item_bytes) return fail(FGMM_ERR_INVALID, "context convolution: n * channels * h * w/2 overflows");
+    const size_t need = item_bytes * (size_t)n;
+    if (!workspace || workspace_bytes < need)
+      return fail(FGMM_ERR_INVALID, "context convolution: a workspace of %zu bytes, %zu needed (fgmm_ckbd_ctx_workspace_bytes)", workspace ? workspace_bytes : (size_t)0, need);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(FGMM_ERR_INVALID, "context convolution: the workspace (%zu bytes needed) is not aligned to 16 bytes", need);
+  }
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select HIP device %d", ctx->device);
   CkbdCtxArgs a;
@@ -81,6 +116,19 @@ static int ckbd_ctx_run(fgmm_ctx *ctx, void *stream, const float *packed, int M,
   a.wp = packed, a.bp = packed + (ckbd_ctx_packed_floats(M, c_out) - (size_t)ckbd_ctx_row_tiles(c_out) * 32);
   a.M = M, a.c_out = c_out, a.h = (int32_t)h, a.w2 = (int32_t)w2, a.odd = anchor_odd;
   a.mt = mt, a.n_kt = kCkbdCtxTaps * mt, a.pt = (int32_t)pt;
+  if (c16) {
+    const int64_t xs_stride = (int64_t)(item_bytes / sizeof(uint16_t));
+    for (int i0 = 0; i0 < n; i0 += 65535) // (a grid's third dimension)
+      LAUNCH_TRY(launch_head16_split(anchors + (int64_t)i0 * M * hw, static_cast<uint16_t *>(workspace) + i0 * xs_stride, hw, M, std::min(n - i0, 65535), (int64_t)M * hw,
+                                     xs_stride, stream));
+    CkbdCtx16Args b;
+    memset(&b, 0, sizeof b);
+    b.xs = static_cast<const uint16_t *>(workspace), b.xs_stride = xs_stride, b.out = out, b.wp16 = c16->packed16, b.bp = a.bp;
+    b.M = M, b.c_out = c_out, b.h = a.h, b.w2 = a.w2, b.odd = anchor_odd;
+    b.mt = ckbd_ctx16_mt(M), b.n_kt = kCkbdCtxTaps * b.mt, b.pt = a.pt;
+    LAUNCH_TRY(launch_ckbd_ctx16(b, n, stream));
+    a.only = head16_oob_word(workspace, M, hw), a.only_stride = xs_stride / 2; // (in 32-bit words)
+  }
   LAUNCH_TRY(launch_ckbd_ctx(a, n, stream));
   return FGMM_OK;
 }
@@ -90,7 +138,22 @@ int fgmm_ckbd_ctx_apply(fgmm_ctx *ctx, void *stream, const fgmm_ckbd_context *c,
   if (!ctx || !c) return fail(FGMM_ERR_INVALID, "context convolution: bad argument (n >= 0, h >= 1, w even and >= 2)");
   if (n >= 0 && h >= 1 && w >= 2 && !(w & 1) && !(anchor_odd & ~1) && c->device != ctx->device)
     return fail(FGMM_ERR_INVALID, "context convolution: made for device %d, context on %d", c->device, ctx->device);
+  if (c->packed16) return fail(FGMM_ERR_INVALID, "context convolution: a bf16x6 handle needs a workspace: call fgmm_ckbd_ctx_apply_ws");
   return ckbd_ctx_run(ctx, stream, c->packed, c->M, c->c_out, anchors, out, n, h, w, anchor_odd);
+}
+
+size_t fgmm_ckbd_ctx_workspace_bytes(const fgmm_ckbd_context *c, int n, int64_t h, int64_t w) {
+  if (!c || !c->packed16 || n <= 0 || h < 1 || w < 2 || (w & 1) || h > (INT32_MAX - 256) / (w / 2)) return 0;
+  return ckbd_ctx16_item_bytes(c->M, n, h * (w / 2)) * (size_t)n;
+}
+
+int fgmm_ckbd_ctx_apply_ws(fgmm_ctx *ctx, void *stream, const fgmm_ckbd_context *c, const float *anchors, float *out, int n, int64_t h, int64_t w,
+                           int anchor_odd, void *workspace, size_t workspace_bytes) {
+  if (c && !c->packed16) return fgmm_ckbd_ctx_apply(ctx, stream, c, anchors, out, n, h, w, anchor_odd);
+  if (!ctx || !c) return fail(FGMM_ERR_INVALID, "context convolution: bad argument (n >= 0, h >= 1, w even and >= 2)");
+  if (n >= 0 && h >= 1 && w >= 2 && !(w & 1) && !(anchor_odd & ~1) && c->device != ctx->device)
+    return fail(FGMM_ERR_INVALID, "context convolution: made for device %d, context on %d", c->device, ctx->device);
+  return ckbd_ctx_run(ctx, stream, c->packed, c->M, c->c_out, anchors, out, n, h, w, anchor_odd, c, workspace, workspace_bytes);
 }
 
 // ---- section 5c: caller-owned packed weights, and the gradients ---------------------------------------------------

@@ -20,6 +20,8 @@
 // Padding (channels up to a K tile, positions up to 128, rows up to a row tile - and row tiles up to six): weights +0, features -0:
 // +0 * -0 = -0 leaves every accumulator's bits alone, -0 included.  A tap outside the image is +0 and takes part in the chain as the
 // definition says.
+// A bf16x6 call (fgmm_ckbd_ctx16.hip) launches this kernel after its own with per-item domain words (CkbdCtxArgs::only): the blocks of an
+// item inside the domain return at once, a flagged item gets the chain above.  Null - every other caller - means every item.
 #include "fgmm_ckbd_geom.h"
 #include "fgmm_headframe.h"
 
@@ -69,6 +71,7 @@ __global__ __launch_bounds__(256, 2) void ckbd_ctx_kernel(CkbdCtxArgs a, int n_r
   if (L >= total) return;
   const int per_item = a.pt * n_rg;
   const int item = L / per_item, rem = L - item * per_item, pt = rem / n_rg, rg = rem - pt * n_rg;
+  if (a.only && !a.only[(int64_t)item * a.only_stride]) return; // a bf16x6 call (fgmm_ckbd_ctx16.hip), and the item is inside its domain
   const int M = a.M, hgt = a.h, w2 = a.w2, wid = 2 * a.w2, hw = a.h * a.w2, P0 = pt * kPB;
   const float *x = a.anchors + (int64_t)item * M * hw;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;

@@ -20,6 +20,7 @@
 // of 24 bf16 (48 bytes) in LDS: the 16-byte reads and writes of 16 consecutive lanes fall on 64 different banks.  Block placement, rank
 // prologue and epilogues are fgmm_head.hip's: fgmm_headframe.h.
 #include "fgmm_headframe.h"
+#include "fgmm_split3.h"
 
 namespace fgmm {
 namespace {
@@ -30,25 +31,7 @@ constexpr int kA16 = 3 * kRows * kPitch, kB16 = 3 * kPB * kPitch;    // bf16 ele
 constexpr int kBuf16 = kA16 + kB16;                                  // one staged (W tile, x tile) pair: 64 512 bytes
 constexpr size_t kLds16 = 2 * sizeof(uint16_t) * (size_t)kBuf16;     // two of them: 129 024 bytes
 
-typedef __bf16 bf8_t __attribute__((ext_vector_type(8)));
-typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
-
-struct Split3 {
-  uint16_t p[3];
-};
-__device__ __forceinline__ uint16_t bf_bits(__bf16 b) { return __builtin_bit_cast(uint16_t, b); }
-__device__ __forceinline__ Split3 split3(float v) {
-  const __bf16 a = (__bf16)v; // round to nearest even (v_cvt_pk_bf16_f32)
-  const float r1 = v - (float)a;
-  const __bf16 b = (__bf16)r1;
-  const float r2 = r1 - (float)b;
-  const __bf16 c = (__bf16)r2;
-  return Split3{{bf_bits(a), bf_bits(b), bf_bits(c)}};
-}
-
-// the operands whose three bfloat16 parts carry them: finite, and not rounding to an infinite first part (|v| < 0x1.FFp127; NaN fails
-// the test).  Beyond, split3 gives (+-inf, NaN, NaN), and the six part products turn an infinite or a finite exact result into NaN.
-__device__ __forceinline__ bool in_domain(float v) { return __builtin_fabsf(v) < 0x1.FFp127f; }
+// (split3, in_domain and the sixteen-byte operand types: fgmm_split3.h, shared with fgmm_ckbd_ctx16.hip)
 
 // packed weights: bf16 [channel group][K tile of 16][part 3][192 rows][16 input channels in natural order]; bias as in fgmm_head.hip
 __global__ __launch_bounds__(256) void head16_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, int M, int c_in, int n_cg, int n_kt,

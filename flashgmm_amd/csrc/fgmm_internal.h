@@ -152,6 +152,10 @@ struct CkbdCtxArgs {    // one launch, by value: items of one size
   int32_t M, c_out, h, w2, odd;
   int32_t mt, n_kt; // K tiles per tap, in all (12 * mt)
   int32_t pt;       // position tiles of 128 per item
+  // null: every item is the kernel's.  Else a bf16x6 call's domain words (fgmm_ckbd_ctx16.hip), item i's at only[i * only_stride]: the
+  // kernel computes the items whose word is not 0 - those with an anchor outside the bf16x6 domain - and leaves the others alone
+  const uint32_t *only;
+  int64_t only_stride;
 };
 // w: device [c_out, M, 5, 5]; *bad (device, zeroed by the caller; may be null: the dropped taps are then not looked at) becomes 1 when a
 // dropped tap (i + j even) of w is not +-0.  transposed: packs W'[c][o][i][j] = w[o][c][4 - i][4 - j] instead - a convolution from c_out to
@@ -160,6 +164,28 @@ int launch_ckbd_ctx_pack(const float *w, const float *bias_or_null, int M, int c
 // row tiles per block the launch of n items takes (6, 2 or 1); blocks = n * pt * ceil(ceil(c_out / 32) / that)
 int ckbd_ctx_tiles(int64_t n, int64_t pt, int c_out);
 int launch_ckbd_ctx(const CkbdCtxArgs &args, int64_t n, void *stream);
+
+// ---- the same convolution in bf16x6 on the BF16 matrix cores (fgmm_ckbd_ctx16.hip; FGMM_CKBD_CTX_BF16X6) ------------
+// packed weights: bf16 [n_rt row tiles of 32][12 * mt K tiles: tap, then tile of 16 channels][part 3][k half 2][32 rows][8 channels] -
+// 3072 contiguous bytes per row tile and K tile; n_rt = ckbd_ctx_row_tiles(c_out).  The bias is the f32 packing's (bp)
+static inline int ckbd_ctx16_mt(int M) { return (M + kHead16BK - 1) / kHead16BK; }
+static inline size_t ckbd_ctx16_packed_bytes(int M, int c_out) {
+  return (size_t)ckbd_ctx_row_tiles(c_out) * kCkbdCtxTaps * (size_t)ckbd_ctx16_mt(M) * 3 * 32 * kHead16BK * sizeof(uint16_t);
+}
+// *bad (device, zeroed by the caller) becomes 1 when a kept tap of w is outside the bf16x6 domain (|w| >= 0x1.FFp127, inf, NaN)
+int launch_ckbd_ctx16_pack(const float *w, int M, int c_out, void *wp16, uint32_t *bad, void *stream);
+struct CkbdCtx16Args {  // one launch, by value: items of one size
+  const uint16_t *xs;   // the anchors' split copies (launch_head16_split with c_in = M, hw = h * w2), item i's at xs + i * xs_stride, each
+  int64_t xs_stride;    // followed by its domain word (head16_oob_word): an item whose word is not 0 is left to ckbd_ctx_kernel
+  float *out;           // device [n, c_out, h, w2]
+  const void *wp16;     // the packed parts of the weights
+  const float *bp;      // the packed bias
+  int32_t M, c_out, h, w2, odd;
+  int32_t mt, n_kt; // K tiles of 16 channels per tap, in all (12 * mt)
+  int32_t pt;       // position tiles of 128 per item
+};
+// the row tiles per block are launch_ckbd_ctx's (ckbd_ctx_tiles)
+int launch_ckbd_ctx16(const CkbdCtx16Args &args, int64_t n, void *stream);
 
 // ---- its weight and bias gradients (fgmm_ckbd_ctx_grad.hip; header section 5c) ------------------------------------
 constexpr int kCkbdWgradSliceMin = 256; // positions a slice holds before the reduction is cut into more slices (FGMM_CKBD_WGRAD_SLICE_MIN)

@@ -347,7 +347,7 @@ class CheckerboardLatentCodec(nn.Module):
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None, entropy_parameters: Optional[nn.Module] = None,
                  context_prediction: Optional[nn.Module] = None, anchor_parity: str = "even", forward_method: str = "twopass",
-                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, fuse_context: bool = False, **kwargs: Any):
+                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, fuse_context=False, **kwargs: Any):
         super().__init__()
         # fuse_context: context_prediction - a 5x5 CheckerboardMaskedConv2d(M, C_out, padding=2) - runs inside the library
         # (flashgmm_amd.ops.CheckerboardContext, header section 5b: compact anchors in, compact non-anchor context out, one launch on the
@@ -355,7 +355,12 @@ class CheckerboardLatentCodec(nn.Module):
         # fuse_head it changes the last bits of the parameters: the streams are self-consistent on any ROCm / MIOpen version, but they are
         # not the un-fused path's streams - encoder and decoder must agree on this switch.  Works alone and together with fuse_head.
         # In compress / decompress the weights are detached; forward() runs the same operator under autograd (section 5c).
+        # fuse_context: True / "f32" (the exact form) or "bf16x6" (CheckerboardContext's faster arithmetic in compress / decompress:
+        # MI355X on both sides; forward() stays the f32 operator)
+        if fuse_context not in (False, True, "f32", "bf16x6"):
+            raise ValueError(f"fuse_context {fuse_context!r}")
         self.fuse_context = bool(fuse_context)
+        self._context_arith = "bf16x6" if fuse_context == "bf16x6" else "f32"
         self._context: Optional[CheckerboardContext] = None
         self._context_key = None
         # rdo_channel_skip: channel skipping (section 3f) in the halves' quantisation at THIS codec's rdo_lambda - with rdo_lambda > 0 it
@@ -425,9 +430,9 @@ class CheckerboardLatentCodec(nn.Module):
         """the CheckerboardContext of context_prediction: packed once, again when its weights have changed (the key of _head_parts)"""
         cp = self.context_prediction
         bias = getattr(cp, "bias", None)
-        key = (cp.weight.data_ptr(), cp.weight._version, None if bias is None else (bias.data_ptr(), bias._version))
+        key = (cp.weight.data_ptr(), cp.weight._version, None if bias is None else (bias.data_ptr(), bias._version), self._context_arith)
         if self._context is None or self._context_key != key:
-            self._context, self._context_key = CheckerboardContext(cp, self.anchor_parity), key
+            self._context, self._context_key = CheckerboardContext(cp, self.anchor_parity, self._context_arith), key
         return self._context
 
     def _ctx(self, y_hat_: Tensor, i: int) -> Tensor:

@@ -104,7 +104,20 @@ def ckbd_embed(y_, anchor_parity: str = "even"):
     return _ckbd_maybe_grad(y_, anchor_parity, True)
 
 
-class CheckerboardContext:
+class _TakesArithmetic(type):
+    """``CheckerboardContext(conv, anchor_parity="even", arithmetic="f32")``: the class's call takes the arithmetic and sets it on the
+    new object before ``__init__(conv, anchor_parity)`` runs - ``__init__`` keeps the two parameters it has had since section 5b"""
+
+    def __call__(cls, conv, anchor_parity: str = "even", arithmetic: str = "f32"):
+        if arithmetic not in ("f32", "bf16x6"):
+            raise ValueError(f"arithmetic {arithmetic!r}")
+        self = cls.__new__(cls)
+        self.arithmetic = arithmetic
+        self.__init__(conv, anchor_parity)
+        return self
+
+
+class CheckerboardContext(metaclass=_TakesArithmetic):
     """The context convolution of the checkerboard codec - ``unembed(context_prediction(embed([anchors, 0])))[1]`` with
     ``context_prediction`` a 5x5 ``CheckerboardMaskedConv2d(M, C_out, padding=2)`` (compressai/latent_codecs/checkerboard.py:281-284) -
     on the matrix cores in ONE fixed summation order (include/flashgmm_amd.h section 5b: bit for bit an ``fmaf`` chain over the 12 kept
@@ -117,10 +130,18 @@ class CheckerboardContext:
     read.  Inference only: the weights are detached and packed once, here.  The result differs from MIOpen's convolution in its last
     bits, so encoder and decoder must both use it.
 
+    ``arithmetic="bf16x6"`` (``FGMM_CKBD_CTX_BF16X6``, fgmm_ckbd_ctx16.hip) evaluates the same sum on the BF16 matrix cores as
+    ``ParameterHead(arithmetic="bf16x6")`` evaluates its own: three bfloat16 parts per operand, six part products per product,
+    accumulated in binary32 - binary32 accuracy (the header states the bound), not the ``fmaf`` chain and not restatable on a CPU, but
+    the same bits from every launch on gfx950 whatever the batch: encoder and decoder must both use it, on MI355X.  An item with a
+    non-finite (or, in magnitude, >= 0x1.FFp127) anchor is computed by the exact form.
+
     Training: ``checkerboard_context(anchors, weight * mask, bias, anchor_parity)`` is the same operator under autograd (header section
     5c).  One documented difference from the reference: its ``CheckerboardMaskedConv2d`` zeroes ``weight.data`` in place and then
     differentiates a plain convolution (compressai/layers/layers.py:141-144), so its dropped taps receive non-zero gradients (which
     never change a forward value but enter a global gradient-norm clip); here the gradient is that of ``weight * mask``: +0 there."""
+
+    arithmetic = "f32"
 
     def __init__(self, conv, anchor_parity: str = "even"):
         import torch
@@ -148,8 +169,9 @@ class CheckerboardContext:
         b = None if getattr(conv, "bias", None) is None else conv.bias.detach().to(torch.float32).contiguous()
         out = C.c_void_p()
         stream = torch.cuda.current_stream(w.device).cuda_stream
-        _lib.check(_lib.lib().fgmm_ckbd_ctx_create(_lib.ctx(self._dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, self.M,
-                                                   self.C_out, C.byref(out)), "CheckerboardContext")
+        _lib.check(_lib.lib().fgmm_ckbd_ctx_create_ex(_lib.ctx(self._dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, self.M,
+                                                      self.C_out, _lib.FGMM_CKBD_CTX_BF16X6 if self.arithmetic == "bf16x6" else 0, C.byref(out)),
+                   "CheckerboardContext")
         self._h = out
 
     def __del__(self):
@@ -171,8 +193,15 @@ class CheckerboardContext:
         N, _, h, w2 = a.shape
         out = torch.empty((N, self.C_out, h, w2), dtype=torch.float32, device=a.device)
         if N and h and w2:
-            _lib.check(_lib.lib().fgmm_ckbd_ctx_apply(_lib.ctx(self._dev), torch.cuda.current_stream(a.device).cuda_stream, self._h, a.data_ptr(),
-                                                      out.data_ptr(), N, h, 2 * w2, int(self.anchor_parity == "odd")), "CheckerboardContext.non_anchor")
+            L, stream, odd = _lib.lib(), torch.cuda.current_stream(a.device).cuda_stream, int(self.anchor_parity == "odd")
+            if self.arithmetic == "bf16x6":  # the anchors' split copy: torch's allocator hands it out and takes it back in stream order
+                with torch.cuda.device(a.device):
+                    ws = torch.empty((int(L.fgmm_ckbd_ctx_workspace_bytes(self._h, N, h, 2 * w2)),), dtype=torch.uint8, device=a.device)
+                _lib.check(L.fgmm_ckbd_ctx_apply_ws(_lib.ctx(self._dev), stream, self._h, a.data_ptr(), out.data_ptr(), N, h, 2 * w2, odd, ws.data_ptr(),
+                                                    ws.numel()), "CheckerboardContext.non_anchor")
+            else:
+                _lib.check(L.fgmm_ckbd_ctx_apply(_lib.ctx(self._dev), stream, self._h, a.data_ptr(), out.data_ptr(), N, h, 2 * w2, odd),
+                           "CheckerboardContext.non_anchor")
         return out
 
 

@@ -1109,6 +1109,31 @@ void fgmm_ckbd_ctx_destroy(fgmm_ckbd_context *cc);
  * h < 1, n < 0, a null tensor with n > 0, sizes whose grid would overflow.  n == 0: success, no launch. */
 int fgmm_ckbd_ctx_apply(fgmm_ctx *ctx, void *stream, const fgmm_ckbd_context *cc, const float *anchors, float *out, int n, int64_t h,
                         int64_t w, int anchor_odd);
+/* ... with flags.  FGMM_CKBD_CTX_BF16X6: the same sum on the BF16 matrix cores with binary32 accuracy, evaluated as FGMM_HEAD_BF16X6
+ * evaluates the head's (section 2b; fgmm_ckbd_ctx16.hip): every weight and every anchor split into three bfloat16 parts, a product =
+ * the six part products (w1,x3) (w3,x1) (w2,x2) (w1,x2) (w2,x1) (w1,x1), smallest first, each one v_mfma_f32_32x32x16_bf16 over 16
+ * input channels OF ONE TAP, accumulated in binary32 from the bias; K tiles ascend by tap, then by channel tile: n16 = 12 ceil(M / 16)
+ * matrix steps (not ceil(12 M / 16): a tap's last tile is padded, with zeros in all three parts).  Bound, per output, over the 12 M
+ * gathered terms (w = weight[o][c][tap t], x = x(t, c)):
+ *     |out - exact| <= R (sum |w x| + |b|) + 2^-133 (sum |w| + sum |x|) + 6 n16 2^-150,   R = 2^-23 (1 + 2^-6) + 6 n16 2^-24 (1 + 2^-7)
+ * NOT the fmaf chain and not restatable bit for bit on a CPU, but THE SAME BITS FROM EVERY LAUNCH on gfx950: an output's bits do not
+ * depend on n, on the item's place in a batch, on the block shape the launch takes or on the caller - an encoder's batch and a
+ * decoder's single image agree; encoder and decoder must both use it, on MI355X.  Domain: finite operands with |v| < 0x1.FFp127.
+ * Weights outside it are refused here (FGMM_ERR_INVALID); an ITEM with an anchor outside it is computed by the exact form instead, bit
+ * for bit the chain above - the handle holds both packings.  flags == 0: fgmm_ckbd_ctx_create. */
+#define FGMM_CKBD_CTX_BF16X6 1
+int fgmm_ckbd_ctx_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int M, int C_out, int flags,
+                            fgmm_ckbd_context **out);
+/* A bf16x6 handle's apply needs room for the anchors' split copy - three bfloat16 parts, channels padded to 16 - and a domain word per
+ * item: this many bytes, the caller's, 16-byte aligned, used on `stream` only until the call's work is done.  0: an exact handle, or
+ * sizes fgmm_ckbd_ctx_apply_ws refuses (and n == 0). */
+size_t fgmm_ckbd_ctx_workspace_bytes(const fgmm_ckbd_context *cc, int n, int64_t h, int64_t w);
+/* fgmm_ckbd_ctx_apply with a workspace: STREAM-ORDERED, no lock, no wait; three launches (the split, the bf16x6 kernel, the exact
+ * kernel for the items outside the domain).  Refused like fgmm_ckbd_ctx_apply, and for a workspace that is NULL, shorter than
+ * fgmm_ckbd_ctx_workspace_bytes or not 16-byte aligned (the message says how many bytes are needed).  An exact handle ignores the
+ * workspace: the call is fgmm_ckbd_ctx_apply.  fgmm_ckbd_ctx_apply itself refuses a bf16x6 handle. */
+int fgmm_ckbd_ctx_apply_ws(fgmm_ctx *ctx, void *stream, const fgmm_ckbd_context *cc, const float *anchors, float *out, int n, int64_t h,
+                           int64_t w, int anchor_odd, void *workspace, size_t workspace_bytes);
 
 /* ---- section 5c. The context convolution's GRADIENTS on the matrix cores, in one fixed order; caller-owned packed weights -------------
  * What CheckerboardLatentCodec._forward_onepass (compressai/latent_codecs/checkerboard.py:154-171) needs under autograd: there the

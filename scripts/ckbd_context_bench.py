@@ -7,7 +7,11 @@ GPU time by device events on the current stream: a sample is `inner` back-to-bac
 call of N = 1 is tens of microseconds: near the resolution of an event pair); the two paths alternate sample by sample in one process;
 the median and the minimum of `samples` samples after `warm` warm-up samples of each.  The fraction of the f32 MFMA roof (157.3 TF, as
 profiles/r06_head_kernel.md) counts the multiply-adds the definition needs, 2 * C_out * 12 M per compact position.
-usage: python scripts/ckbd_context_bench.py [samples=30] [inner=10] [warm=5]"""
+arithmetic "bf16x6" (profiles/ckbd_context_bf16x6.md) adds CheckerboardContext(arithmetic="bf16x6") as a fourth path beside the f32
+kernel - "kernel16", the whole call: the split, the bf16x6 kernel, the exact kernel's launch for flagged items (its blocks return at
+once here) - alternating with it; the launches one by one come from a kernel trace of this script, a run of its own.  Its roof is the
+BF16 pipe's at six part products per product, 6 x 32 cycles per 16 channels against the f32 pipe's 8 x 64: 8 / 3 of the f32 roof.
+usage: python scripts/ckbd_context_bench.py [samples=30] [inner=10] [warm=5] [arithmetic=f32|bf16x6]"""
 import json
 import os
 import sys
@@ -22,6 +26,9 @@ from flashgmm_amd.ops import CheckerboardContext, ckbd_embed, ckbd_unembed  # no
 samples = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 inner = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+arithmetic = sys.argv[4] if len(sys.argv) > 4 else "f32"
+if arithmetic not in ("f32", "bf16x6"):
+    raise SystemExit(f"arithmetic {arithmetic!r}: f32 or bf16x6")
 M, C_out, h, w = 192, 384, 32, 48
 ROOF_TF = 157.3
 dev = "cuda:0"
@@ -33,6 +40,7 @@ mask.view(C_out, M, 25)[:, :, 1::2] = 1  # the kernel positions (i, j) with i + 
 with torch.no_grad():
     conv.weight.mul_(mask)
 op = CheckerboardContext(conv, "even")
+op16 = CheckerboardContext(conv, "even", arithmetic="bf16x6") if arithmetic == "bf16x6" else None
 
 
 def sample(fn):
@@ -60,6 +68,8 @@ for N in (1, 24):
             return conv(full)
 
     paths = {"kernel": lambda: op.non_anchor(anchors), "torch": torch_path, "torch_conv_alone": conv_only}
+    if op16 is not None:
+        paths["kernel16"] = lambda: op16.non_anchor(anchors)
     for _ in range(warm):
         for fn in paths.values():
             sample(fn)
@@ -76,5 +86,11 @@ for N in (1, 24):
     res["gflop_needed"] = round(flop / 1e9, 3)
     res["kernel_over_torch"] = round(km / res["torch"]["median_ms"], 4)
     res["max_abs_diff_to_torch"] = float((ref - got).abs().max())
+    if op16 is not None:
+        k16 = res["kernel16"]["median_ms"]
+        res["kernel16"]["tflops"] = round(flop / k16 / 1e9, 2)
+        res["kernel16"]["frac_of_bf16x6_roof"] = round(flop / k16 / 1e9 / (ROOF_TF * 8 / 3), 4)
+        res["kernel16_over_kernel"] = round(k16 / km, 4)
+        res["max_abs_diff_kernel16_to_kernel"] = float((op16.non_anchor(anchors) - got).abs().max())
     out[f"N={N}"] = res
 print(json.dumps(out))
