@@ -262,6 +262,10 @@ SIGNATURES = {
     "fgmm_decstream_destroy": (None, [_p]),
     "fgmm_decstream_decode": (_i, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
     "fgmm_pmf_to_quantized_cdf": (_i, [_p, _i, _i, _p]),
+    # section 2c: (ctx, stream, weight, bias, c_out, c_a, c_b, act, slope, out); (handle); (ctx, stream, handle, xa, xb, out, n, hw)
+    "fgmm_hidden_create": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _pp]),
+    "fgmm_hidden_destroy": (None, [_p]),
+    "fgmm_hidden_apply": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64]),
     "fgmm_ckbd_unembed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
     "fgmm_ckbd_embed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
     "fgmm_ckbd_ctx_create": (_i, [_p, _p, _p, _p, _i, _i, _pp]),
@@ -279,6 +283,7 @@ SIGNATURES = {
     "fgmm_ckbd_ctx_wgrad_workspace": (_sz, [_i, _i, _i, _i64, _i64]),
     "fgmm_ckbd_ctx_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i64, _i64, _i, _p, _p, _p, _sz]),
 }
+FGMM_ACT_NONE, FGMM_ACT_LEAKY, FGMM_ACT_RELU = 0, 1, 2  # section 2c: fgmm_hidden_create's activations
 FGMM_CKBD_CTX_BF16X6 = 1  # section 5b: fgmm_ckbd_ctx_create_ex's flag
 FGMM_CKBD_WGRAD_SLICE_MIN, FGMM_CKBD_WGRAD_SLICES_MAX = 256, 16  # section 5c: the weight gradient's slice rule
 

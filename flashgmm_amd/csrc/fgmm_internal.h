@@ -136,6 +136,35 @@ int launch_head_symtab(const EncDesc *d_descs, const HeadW &w, int count, int M_
 int launch_head_planes(const HeadDesc *d_descs, const HeadPair &head, int count, int64_t hw_max, bool vec, void *stream);
 int launch_head_entries(const EncDesc *d_descs, const HeadPair &head, int count, int M_max, int64_t hw_max, int mode, bool clamped, bool vec, void *stream);
 
+// ---- the hidden layers of the parameter network on the matrix cores (fgmm_hidden.hip; header section 2c) -----------
+// row tiles of 32 the packed weights hold: enough for the last block of every height of the ladder (5, 2, 1) to read its own
+static inline int hidden_row_tiles(int c_out) {
+  const int n = (c_out + 31) / 32, by5 = (n + 4) / 5 * 5, by2 = (n + 1) / 2 * 2;
+  return by5 > by2 ? by5 : by2;
+}
+static inline size_t hidden_packed_floats(int c_out, int c_a, int c_b) { // [n_rt][kta + ktb][32][32] weights, then [n_rt][32] bias
+  const size_t n_rt = (size_t)hidden_row_tiles(c_out), n_kt = ((size_t)c_a + kMfma32BK - 1) / kMfma32BK + ((size_t)c_b + kMfma32BK - 1) / kMfma32BK;
+  return n_rt * n_kt * 32 * kMfma32BK + n_rt * 32;
+}
+struct HiddenArgs {     // one launch, by value: items of one size
+  const float *xa, *xb; // device [n, c_a, hw] (null: absent - then kta == 0), [n, c_b, hw]
+  float *out;           // device [n, c_out, hw]
+  const float *wp, *bp; // the packed weights - of the FIRST K tile of the chain: past source a's tiles when it is absent - and bias
+  int64_t hw;
+  int64_t rt_words;     // 16-byte words between the packed weights of two row tiles (all K tiles, an absent source's included)
+  int32_t c_a, c_b, c_out;
+  int32_t kta, n_kt;    // K tiles of source a in the chain (0: absent or c_a == 0), in all
+  int32_t pt;           // position tiles of 128 per item
+  int32_t act;          // FGMM_ACT_*
+  float slope;
+};
+// w: device [c_out, c_a + c_b] row-major
+int launch_hidden_pack(const float *w, const float *bias_or_null, int c_out, int c_a, int c_b, float *wp, float *bp, void *stream);
+int hidden_device_cus(int device, int *cus); // the device's compute units
+// row tiles per block the launch of n items takes (5, 2 or 1) on a device of `cus` compute units; blocks = n * pt * ceil(ceil(c_out / 32) / that)
+int hidden_tiles(int64_t n, int64_t pt, int c_out, int cus);
+int launch_hidden(const HiddenArgs &args, int64_t n, int cus, bool vec, void *stream);
+
 // ---- the checkerboard context convolution on the matrix cores (fgmm_ckbd_ctx.hip; header section 5b) --------------
 constexpr int kCkbdCtxBK = kMfma32BK; // input channels of one tap per LDS tile
 constexpr int kCkbdCtxTaps = 12;  // the kernel positions (i, j) of the 5x5 with i + j odd, row-major: flat index 2 t + 1

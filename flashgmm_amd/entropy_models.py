@@ -29,7 +29,7 @@ from torch import Tensor
 
 from . import _boundary, _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneck", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve", "update_entropy_models", "aux_loss"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneck", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterBody", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve", "update_entropy_models", "aux_loss"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -479,6 +479,96 @@ class ParameterHead:
             _lib.check(_lib.lib().fgmm_head_params_batch(_lib.ctx(self._dev), torch.cuda.current_stream(x.device).cuda_stream, self._h, xs, os_, hws, N),
                        "ParameterHead.params")
         return tuple(out.chunk(3, 1))
+
+
+class ParameterBody:
+    """Everything of the reference's ``entropy_parameters`` BEFORE its last layer - ``Conv2d(768, 640, 1), LeakyReLU, Conv2d(640, 640, 1),
+    LeakyReLU`` (compressai/models/ckbd_gmm.py:115-121; ELIC's parameter aggregation: the same with ReLU) - on the matrix cores in ONE
+    fixed summation order (include/flashgmm_amd.h section 2c: bit for bit an ``fmaf`` chain, then the library's own activation
+    sequence), one launch per layer, with the ``torch.cat`` of context and side parameters folded into the first layer:
+
+        body = ParameterBody(entropy_parameters[:-1], c_ctx)    # 1x1 nn.Conv2d [+ nn.LeakyReLU | nn.ReLU] ..., on the GPU
+        x = body.features(ctx, side)                            # [N, c_ctx, h, w] or None, [N, c_side, h, w] -> [N, c_out, h, w]
+        scales, means, logits = ParameterHead(entropy_parameters[-1]).params(x)
+
+    ``ctx=None`` is the ABSENT context of the checkerboard anchors: the first ``c_ctx`` input channels of the first layer take no part in
+    the sum - for finite weights what a context of zeros gives (section 2c states the two differences), at half the multiply-adds and
+    without the zeros.  The weights are packed once, here."""
+
+    @staticmethod
+    def check(modules):
+        """-> [(conv, FGMM_ACT_*, slope)], one per layer; ValueError naming the first module that does not fit the pattern"""
+        layers = []
+        bare = False  # the last layer has no activation yet
+        for m in modules:
+            if isinstance(m, nn.Conv2d):
+                if m.kernel_size != (1, 1) or m.stride != (1, 1) or m.groups != 1 or m.padding not in ((0, 0), "valid") or m.dilation != (1, 1):
+                    raise ValueError(f"ParameterBody: not a plain 1x1 convolution: {m}")
+                layers.append((m, _lib.FGMM_ACT_NONE, 0.0))
+                bare = True
+            elif isinstance(m, (nn.LeakyReLU, nn.ReLU)) and bare:
+                slope = float(getattr(m, "negative_slope", 0.0))
+                if slope != slope or slope in (float("inf"), float("-inf")):
+                    raise ValueError(f"ParameterBody: the slope is not finite: {m}")
+                layers[-1] = (layers[-1][0], _lib.FGMM_ACT_LEAKY if isinstance(m, nn.LeakyReLU) else _lib.FGMM_ACT_RELU, slope)
+                bare = False
+            else:
+                raise ValueError(f"ParameterBody: expected a 1x1 nn.Conv2d optionally followed by nn.LeakyReLU or nn.ReLU, got {m}")
+        if not layers:
+            raise ValueError("ParameterBody: no convolution")
+        for a, b in zip(layers, layers[1:]):
+            if b[0].in_channels != a[0].out_channels:
+                raise ValueError(f"ParameterBody: {b[0]} does not take the {a[0].out_channels} channels of the layer before it")
+        return layers
+
+    def __init__(self, modules, c_ctx: int):
+        layers = self.check(list(modules))
+        self.c_ctx = int(c_ctx)
+        if self.c_ctx < 0 or layers[0][0].in_channels <= self.c_ctx:
+            raise ValueError(f"ParameterBody: the first layer has {layers[0][0].in_channels} input channels, not more than c_ctx = {self.c_ctx}")
+        w0 = layers[0][0].weight
+        if not w0.is_cuda:
+            raise RuntimeError("ParameterBody: expected modules on a HIP device (there is no CPU implementation)")
+        self.device = w0.device
+        self._dev = w0.device.index if w0.device.index is not None else -1
+        self.c_side = layers[0][0].in_channels - self.c_ctx
+        self.c_out = layers[-1][0].out_channels
+        self._h: List[Tuple[C.c_void_p, int]] = []  # (handle, its output channels)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        for j, (conv, act, slope) in enumerate(layers):
+            w = conv.weight.detach()
+            w2 = w.reshape(w.shape[0], w.shape[1]).to(torch.float32).contiguous()
+            b = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
+            c_a = self.c_ctx if j == 0 else 0
+            out = C.c_void_p()
+            _lib.check(_lib.lib().fgmm_hidden_create(_lib.ctx(self._dev), stream, w2.data_ptr(), b.data_ptr() if b is not None else None, conv.out_channels,
+                                                     c_a, conv.in_channels - c_a, act, slope, C.byref(out)), "ParameterBody")
+            self._h.append((out, conv.out_channels))
+
+    def __del__(self):
+        hs, self._h = getattr(self, "_h", None) or [], []
+        for h, _ in hs:
+            try:
+                _lib.lib().fgmm_hidden_destroy(h)
+            except Exception:  # pragma: no cover - interpreter shutdown
+                pass
+
+    def features(self, ctx: Optional[Tensor], side: Tensor) -> Tensor:
+        """-> ``[N, c_out, h, w]`` float32: what ``entropy_parameters[:-1](torch.cat((ctx, side), 1))`` gives, in the library's order;
+        ``ctx=None``: the absent context.  The layers run back to back on the current stream."""
+        if side.dim() != 4 or side.shape[1] != self.c_side or side.device != self.device:
+            raise RuntimeError(f"side must be [N, {self.c_side}, h, w] on {self.device}; got {tuple(side.shape)} on {side.device}")
+        N, _, h, w = side.shape
+        if ctx is not None and (tuple(ctx.shape) != (N, self.c_ctx, h, w) or ctx.device != self.device or self.c_ctx == 0):
+            raise RuntimeError(f"ctx must be None or [{N}, {self.c_ctx}, {h}, {w}] on {self.device} (c_ctx > 0); got {tuple(ctx.shape)} on {ctx.device}")
+        xa = None if ctx is None else ctx.to(torch.float32).contiguous()
+        x = side.to(torch.float32).contiguous()
+        L, cx, stream = _lib.lib(), _lib.ctx(self._dev), torch.cuda.current_stream(self.device).cuda_stream
+        for hd, c_out in self._h:
+            out = torch.empty((N, c_out, h, w), dtype=torch.float32, device=self.device)
+            _lib.check(L.fgmm_hidden_apply(cx, stream, hd, None if xa is None else xa.data_ptr(), x.data_ptr(), out.data_ptr(), N, h * w), "ParameterBody.features")
+            xa, x = None, out
+        return x
 
 
 def _like_forward(gmc, x, scales, means, weights, rnd: bool, want_map: bool, logits: bool):

@@ -31,7 +31,7 @@ from torch import Tensor
 
 from itertools import accumulate
 
-from .entropy_models import EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterHead
+from .entropy_models import EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterBody, ParameterHead
 from .ops import CheckerboardContext, checkerboard_context, ckbd_embed, ckbd_unembed
 
 __all__ = ["GaussianMixtureConditionalLatentCodec", "CheckerboardLatentCodec", "ChannelGroupsLatentCodec", "HyperLatentCodec",
@@ -347,8 +347,25 @@ class CheckerboardLatentCodec(nn.Module):
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None, entropy_parameters: Optional[nn.Module] = None,
                  context_prediction: Optional[nn.Module] = None, anchor_parity: str = "even", forward_method: str = "twopass",
-                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, fuse_context=False, **kwargs: Any):
+                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, fuse_context=False, fuse_body: bool = False,
+                 **kwargs: Any):
         super().__init__()
+        # fuse_body: everything of entropy_parameters BEFORE its last layer - 1x1 convolutions with LeakyReLU / ReLU, models/ckbd_gmm.py:
+        # 115-121 - runs inside the library (flashgmm_amd.ParameterBody, header section 2c: one launch per layer on the matrix cores in ONE
+        # fixed summation order, the merge of context and side parameters folded into the first layer; the anchors' context is ABSENT:
+        # no zeros tensor, half the first layer's sum).  Like fuse_head and fuse_context it changes the last bits of the parameters:
+        # encoder and decoder must agree on this switch.  Works alone and with fuse_head / fuse_context in any combination; with all three
+        # every float between the decoded anchors and the table entry is computed in the library's order.  compress / decompress /
+        # estimate only: forward() runs the torch modules (these layers' gradients are not the library's).  Its reason is the fixed
+        # order, not speed: measured at the reference's widths (profiles/param_body.md) the two layers are 2 % SLOWER than torch's for 24
+        # non-anchor halves (0.374 against 0.368 ms), faster for the anchors (0.283 against 0.368) and for a single image (0.052 against 0.074).
+        self.fuse_body = bool(fuse_body)
+        self._body: Optional[ParameterBody] = None
+        self._body_key = None
+        if self.fuse_body:
+            if not isinstance(entropy_parameters, nn.Sequential) or len(entropy_parameters) < 2:
+                raise ValueError("fuse_body needs entropy_parameters to be an nn.Sequential of hidden layers and a last layer")
+            ParameterBody.check(entropy_parameters[:-1])
         # fuse_context: context_prediction - a 5x5 CheckerboardMaskedConv2d(M, C_out, padding=2) - runs inside the library
         # (flashgmm_amd.ops.CheckerboardContext, header section 5b: compact anchors in, compact non-anchor context out, one launch on the
         # matrix cores in ONE fixed summation order; the anchors' context is zeros and costs no convolution).  Like fuse_softmax and
@@ -426,6 +443,25 @@ class CheckerboardLatentCodec(nn.Module):
             self._head, self._head_key = ParameterHead(last, K=self.latent_codec["y"].K, arithmetic=self._head_arith), key
         return body, self._head
 
+    def _ep_features(self, y_hat_: Tensor, i: int, side_i: Tensor) -> Tensor:
+        """what the LAST layer of entropy_parameters reads for half i: everything before it, applied to merge(context, side)"""
+        ep = self.entropy_parameters
+        if not self.fuse_body:
+            body = ep[:-1] if isinstance(ep, nn.Sequential) else nn.Identity()
+            return body(self.merge(self._ctx(y_hat_, i), side_i))
+        first = ep[0]
+        params = [p for m in ep[:-1] for p in (getattr(m, "weight", None), getattr(m, "bias", None)) if p is not None]
+        key = (first.in_channels - side_i.shape[1],) + tuple((p.data_ptr(), p._version) for p in params)  # (the key of _head_parts, every layer's)
+        if self._body is None or self._body_key != key:
+            self._body, self._body_key = ParameterBody(ep[:-1], key[0]), key
+        return self._body.features(None if i == 0 else self._ctx(y_hat_, i), side_i)  # the anchors' context: absent
+
+    def _ep_params(self, y_hat_: Tensor, i: int, side_i: Tensor) -> Tensor:
+        """entropy_parameters(merge(context, side)) for half i"""
+        if not self.fuse_body:
+            return self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_i))
+        return self.entropy_parameters[-1](self._ep_features(y_hat_, i, side_i))
+
     def _context_op(self) -> CheckerboardContext:
         """the CheckerboardContext of context_prediction: packed once, again when its weights have changed (the key of _head_parts)"""
         cp = self.context_prediction
@@ -469,14 +505,13 @@ class CheckerboardLatentCodec(nn.Module):
         side_params_ = self.unembed(side_params)
         y_ = self.unembed(y)
         prepared = []
-        body = self._head_parts()[0] if self.fuse_head else None
         for i in range(2):
             if self.fuse_head:  # (y, the features the head's last layer reads): the parameters are the encode kernel's business
                 if codec.rdo_lambda > 0:
                     raise RuntimeError("rdo_lambda > 0 together with fuse_head is not supported")
-                prepared.append((y_[i], body(self.merge(self._ctx(y_hat_, i), side_params_[i]))))
+                prepared.append((y_[i], self._ep_features(y_hat_, i, side_params_[i])))
             else:
-                params_i = self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_params_[i]))
+                params_i = self._ep_params(y_hat_, i, side_params_[i])
                 # (rdo_lambda = 0: the latent codec's own entry point, with its own setting - today's path)
                 prepared.append(codec.coder_inputs_rdo(y_[i], params_i, self.rdo_lambda, imp_[i], self.rdo_channel_skip) if self.rdo_lambda > 0
                                 else codec.coder_inputs(y_[i], params_i, imp_[i]) if imp_[i] is not None else codec.coder_inputs(y_[i], params_i))
@@ -519,11 +554,10 @@ class CheckerboardLatentCodec(nn.Module):
         side_params_ = self.unembed(side_params)
         for i in range(2):  # sequential by construction: the non-anchor parameters need the decoded anchors
             if self.fuse_head:
-                body, head = self._head_parts()
-                feat_i = body(self.merge(self._ctx(y_hat_, i), side_params_[i]))
-                out = codec.decompress_many_head([[strings[i]]], (h, w // 2), [feat_i], head)[0]
+                feat_i = self._ep_features(y_hat_, i, side_params_[i])
+                out = codec.decompress_many_head([[strings[i]]], (h, w // 2), [feat_i], self._head_parts()[1])[0]
             else:
-                params_i = self.entropy_parameters(self.merge(self._ctx(y_hat_, i), side_params_[i]))
+                params_i = self._ep_params(y_hat_, i, side_params_[i])
                 out = codec.decompress([strings[i]], (h, w // 2), params_i)
             y_hat_[i] = out["y_hat"]
             if "y_rec" in out:
@@ -544,11 +578,10 @@ class CheckerboardLatentCodec(nn.Module):
         side_ = [self.unembed(sp) for sp in side_params]
         for i in range(2):
             if self.fuse_head:
-                body, head = self._head_parts()
-                feats = [body(self.merge(self._ctx(yh, i), sd[i])) for yh, sd in zip(y_hat_, side_)]
-                outs = codec.decompress_many_head([[st[i]] for st in strings], (h, w // 2), feats, head)
+                feats = [self._ep_features(yh, i, sd[i]) for yh, sd in zip(y_hat_, side_)]
+                outs = codec.decompress_many_head([[st[i]] for st in strings], (h, w // 2), feats, self._head_parts()[1])
             else:
-                params = [self.entropy_parameters(self.merge(self._ctx(yh, i), sd[i])) for yh, sd in zip(y_hat_, side_)]
+                params = [self._ep_params(yh, i, sd[i]) for yh, sd in zip(y_hat_, side_)]
                 outs = codec.decompress_many([[st[i]] for st in strings], (h, w // 2), params)
             for yh, o in zip(y_hat_, outs):
                 yh[i] = o["y_hat"]

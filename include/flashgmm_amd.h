@@ -58,6 +58,7 @@ extern "C" {
 #define FGMM_HAS_EB 1        /* section 3j: fgmm_eb_likelihood, fgmm_eb_likelihood_backward (added without a bump, as 3b - 3i) */
 #define FGMM_HAS_CKBD_CONTEXT 1 /* section 5b: fgmm_ckbd_ctx_create, fgmm_ckbd_ctx_destroy, fgmm_ckbd_ctx_apply (added without a bump, as 3b - 3j) */
 #define FGMM_HAS_EB_UPDATE 1 /* section 3k: fgmm_eb_quantiles, fgmm_eb_tables (added without a bump, as 3b - 3j) */
+#define FGMM_HAS_HIDDEN 1    /* section 2c: fgmm_hidden_create, fgmm_hidden_destroy, fgmm_hidden_apply (added without a bump, as 3b - 5c) */
 #define FGMM_EB_SEARCH_CAP 256 /* section 3k: bisection steps of one quantile search at the most */
 #define FGMM_EB_PARAMS 58    /* float32 values per channel of section 3j's theta */
 #define FGMM_EB_SLICE 1024   /* section 3j: elements of a channel one workgroup walks; the backward's partial rows per channel are
@@ -375,6 +376,54 @@ int fgmm_gmc_compress_head_batch(fgmm_ctx *ctx, void *stream, fgmm_item *items, 
 /* ... with the bitstreams written into the caller's storage (fgmm_sink, section 2) */
 int fgmm_gmc_compress_head_batch_to(fgmm_ctx *ctx, void *stream, fgmm_item *items, const float *const *x, int count,
                                     const fgmm_head *head, int mode, int clamp_scales, const fgmm_sink *sink);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2c. The parameter network's HIDDEN layers, on the matrix cores, in one fixed order.
+ *    Replaces: entropy_parameters[:-1] - Conv2d(768, 640, 1), LeakyReLU, Conv2d(640, 640, 1), LeakyReLU in
+ *    compressai/models/ckbd_gmm.py:115-121; ELIC's parameter aggregation has the same shape with ReLU - and the torch.cat in front
+ *    of it: a layer reads its input as TWO sources, xa (the context, c_a channels) and xb (the side parameters, c_b channels); the
+ *    merged tensor never exists.  With section 5b before it and section 2b after it, every float between the decoded anchors and the
+ *    table entry is computed in this library's order, for the reason of section 2b.
+ *    One layer, per item i of n and position p of hw, on v_mfma_f32_32x32x2_f32, bit for bit - signs of zero, infinities and NaN
+ *    included - the chain
+ *        acc = bias[o] (+0 without a bias)
+ *        for k = 0 .. c_a-1 ascending: acc = fmaf(weight[o][k],       xa[i][k][p], acc)     (skipped ENTIRELY when xa is NULL)
+ *        for k = 0 .. c_b-1 ascending: acc = fmaf(weight[o][c_a + k], xb[i][k][p], acc)
+ *        out[i][o][p] = act(acc)
+ *    with the activation one of the library's own sequences, in binary32:
+ *        FGMM_ACT_NONE   acc
+ *        FGMM_ACT_LEAKY  acc > 0 ? acc : acc * slope          (one multiply; NaN stays NaN; -0 gives -0 * slope)
+ *        FGMM_ACT_RELU   acc > 0 ? acc : (acc != acc ? acc : +0)
+ *    An ABSENT first source (xa == NULL on a layer made with c_a > 0: the checkerboard anchors, whose context is zeros) means that
+ *    those c_a columns of the weight are not part of the chain: half the K range, and no zeros tensor.  This is NOT multiplying by
+ *    zeros in two places: a non-finite weight[o][k], k < c_a, gives NaN against explicit zeros (inf * 0) and takes no part in the
+ *    absent form; and a chain that sits at -0 (a -0 bias) stays -0 in the absent form where explicit +0 features turn it into +0
+ *    at the first weight[o][k], k < c_a, whose sign bit is clear (+w * +0 = +0, and -0 + +0 = +0).  Everywhere else - finite weights,
+ *    a chain not at -0 - the two agree bit for bit.  Encoder and decoder both run the absent form for the anchors, so they agree.
+ *    The result is NOT MIOpen's in its last bits: both sides must use it.
+ *    Block heights: a workgroup computes T tiles of 32 output channels x 128 positions, T from the ladder 5, 2, 1.  The rule, with
+ *    B(T) = n * ceil(hw / 128) * ceil(ceil(c_out / 32) / T) workgroups and CU the device's compute units (256 on MI355X): the first T
+ *    of 5, 2, 1 with B(T) >= CU; T = 1 when none has.  Every height gives the same bits: an output's chain does not depend on T, on n
+ *    or on the item's place in a batch - an encoder's batch and a decoder's single image agree.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FGMM_ACT_NONE 0
+#define FGMM_ACT_LEAKY 1
+#define FGMM_ACT_RELU 2
+typedef struct fgmm_hidden fgmm_hidden; /* one layer's weights, packed for the kernel, on the context's device.  Immutable once created:
+                                         * usable from any context on its device, from several at the same time */
+/* weight: device float32 [c_out, c_a + c_b] row-major (Conv2d.weight [c_out, c_a + c_b, 1, 1] applied to cat(xa, xb)); bias: device
+ * float32 [c_out] or NULL.  A single-source layer: c_a == 0.  The weights are copied (packed) before the call returns.  Refused
+ * (FGMM_ERR_INVALID): c_out < 1, c_b < 1, c_a < 0, an act that is none of the three, a slope that is not finite. */
+int fgmm_hidden_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_a, int c_b, int act,
+                       float slope, fgmm_hidden **out);
+void fgmm_hidden_destroy(fgmm_hidden *hidden);
+/* xa: device float32 [n, c_a, hw] or NULL (absent, above; a layer with c_a == 0 takes NULL only); xb: device float32 [n, c_b, hw];
+ * out: device float32 [n, c_out, hw] - what the next layer's xb, or x[i] of fgmm_head_params_batch and fgmm_gmc_compress_head_batch,
+ * is.  STREAM-ORDERED, like fgmm_ckbd_ctx_apply (section 5b): ONE kernel enqueued on `stream`, no workspace, no context lock, no host
+ * wait; the same rules for the sources and `out` as there.  Refused, launching and writing nothing: n < 0, hw < 0, a NULL xb or out,
+ * xa given to a layer with c_a == 0, sizes whose grid would exceed 2^30 workgroups.  n == 0 or hw == 0: success, no launch. */
+int fgmm_hidden_apply(fgmm_ctx *ctx, void *stream, const fgmm_hidden *hidden, const float *xa, const float *xb, float *out, int n,
+                      int64_t hw);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Building blocks ("same tables => same bytes" surfaces; also what the parity tests probe).
