@@ -266,6 +266,10 @@ SIGNATURES = {
     "fgmm_hidden_create": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _pp]),
     "fgmm_hidden_destroy": (None, [_p]),
     "fgmm_hidden_apply": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64]),
+    # FGMM_HIDDEN_BF16X6: (.. create's .., flags, out); (handle, has_xa, n, hw); (.. apply's .., workspace, workspace_bytes)
+    "fgmm_hidden_create_ex": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _pp]),
+    "fgmm_hidden_workspace_bytes": (_sz, [_p, _i, _i, _i64]),
+    "fgmm_hidden_apply_ws": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _p, _sz]),
     "fgmm_ckbd_unembed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
     "fgmm_ckbd_embed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
     "fgmm_ckbd_ctx_create": (_i, [_p, _p, _p, _p, _i, _i, _pp]),
@@ -284,6 +288,7 @@ SIGNATURES = {
     "fgmm_ckbd_ctx_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i64, _i64, _i, _p, _p, _p, _sz]),
 }
 FGMM_ACT_NONE, FGMM_ACT_LEAKY, FGMM_ACT_RELU = 0, 1, 2  # section 2c: fgmm_hidden_create's activations
+FGMM_HIDDEN_BF16X6 = 1  # section 2c: fgmm_hidden_create_ex's flag
 FGMM_CKBD_CTX_BF16X6 = 1  # section 5b: fgmm_ckbd_ctx_create_ex's flag
 FGMM_CKBD_WGRAD_SLICE_MIN, FGMM_CKBD_WGRAD_SLICES_MAX = 256, 16  # section 5c: the weight gradient's slice rule
 

@@ -23,7 +23,11 @@
 //   epilogue: the activation in registers (the sequences of header section 2c), plane stores out[i][o][p] - what the next hidden
 //            layer, or the head, reads as its features.
 // No atomics, no workspace.
+// A bf16x6 call (fgmm_hidden16.hip) launches this kernel after its own with the per-item domain words of its split copies (HiddenArgs::
+// only, only_b): the blocks of an item inside the domain return at once, a flagged item gets the chain above.  Null - every other caller
+// - means every item.
 #include "fgmm_headframe.h"
+#include "fgmm_hidden_act.h"
 
 namespace fgmm {
 namespace {
@@ -56,9 +60,7 @@ __global__ __launch_bounds__(256) void hidden_pack_kernel(const float *__restric
   }
 }
 
-// the library's activations (header section 2c), one binary32 operation each
-__device__ __forceinline__ float act_leaky(float v, float s) { return v > 0.0f ? v : v * s; }
-__device__ __forceinline__ float act_relu(float v) { return v > 0.0f ? v : (v != v ? v : 0.0f); }
+// (the library's activations, header section 2c: fgmm_hidden_act.h, shared with fgmm_hidden16.hip)
 
 template <int T, bool VEC> // row tiles per block; 16-byte feature loads
 __global__ __launch_bounds__(256, 2) void hidden_kernel(HiddenArgs a, int n_rg, int total) {
@@ -70,6 +72,8 @@ __global__ __launch_bounds__(256, 2) void hidden_kernel(HiddenArgs a, int n_rg, 
   // the row groups of one position tile are consecutive slots of one XCD: its L2 holds the feature tile
   const int per_item = a.pt * n_rg;
   const int item = L / per_item, rem = L - item * per_item, pt = rem / n_rg, rg = rem - pt * n_rg;
+  // a bf16x6 call (fgmm_hidden16.hip), and every present source of the item is inside its domain: hidden16_kernel has written it
+  if (a.only && !(a.only[(int64_t)item * a.only_stride] | a.only_b[(int64_t)item * a.only_stride])) return;
   const int64_t hw = a.hw, P0 = (int64_t)pt * kPB;
   const int c_a = a.c_a, c_b = a.c_b, kta = a.kta;
   const float *xa = a.xa ? a.xa + (int64_t)item * c_a * hw : a.xb; // (absent: kta == 0 and no tile reads it)
@@ -133,10 +137,7 @@ __global__ __launch_bounds__(256, 2) void hidden_kernel(HiddenArgs a, int n_rg, 
         if (o < a.c_out) stg<float>(out + (int64_t)o * hw, act(acc[tl][reg]));
       }
   };
-  const float slope = a.slope;
-  if (a.act == FGMM_ACT_LEAKY) store([slope](float v) { return act_leaky(v, slope); });
-  else if (a.act == FGMM_ACT_RELU) store([](float v) { return act_relu(v); });
-  else store([](float v) { return v; });
+  with_activation(a.act, a.slope, store);
 }
 
 template <int T> static int hidden_go(const HiddenArgs &a, int64_t n, bool vec, hipStream_t st) {

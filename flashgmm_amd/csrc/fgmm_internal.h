@@ -157,6 +157,11 @@ struct HiddenArgs {     // one launch, by value: items of one size
   int32_t pt;           // position tiles of 128 per item
   int32_t act;          // FGMM_ACT_*
   float slope;
+  // null: every item is the kernel's.  Else a bf16x6 call's domain words (fgmm_hidden16.hip), item i's at only[i * only_stride] (source
+  // a's split copy) and only_b[i * only_stride] (source b's; the same word twice when xa is absent): the kernel computes the items with
+  // a word that is not 0 - a feature outside the bf16x6 domain - and leaves the others alone
+  const uint32_t *only, *only_b;
+  int64_t only_stride;
 };
 // w: device [c_out, c_a + c_b] row-major
 int launch_hidden_pack(const float *w, const float *bias_or_null, int c_out, int c_a, int c_b, float *wp, float *bp, void *stream);
@@ -164,6 +169,33 @@ int hidden_device_cus(int device, int *cus); // the device's compute units
 // row tiles per block the launch of n items takes (5, 2 or 1) on a device of `cus` compute units; blocks = n * pt * ceil(ceil(c_out / 32) / that)
 int hidden_tiles(int64_t n, int64_t pt, int c_out, int cus);
 int launch_hidden(const HiddenArgs &args, int64_t n, int cus, bool vec, void *stream);
+
+// ---- the same layer in bf16x6 on the BF16 matrix cores (fgmm_hidden16.hip; FGMM_HIDDEN_BF16X6) ---------------------
+// packed weights: bf16 [n_rt row tiles of 32][kta + ktb K tiles of 16 channels: source a's, then source b's][part 3][k half 2][32 rows]
+// [8 channels] - 3072 contiguous bytes per row tile and K tile; n_rt = hidden_row_tiles(c_out).  The bias is the f32 packing's (bp)
+static inline int hidden16_kt(int c) { return (c + kHead16BK - 1) / kHead16BK; }
+static inline size_t hidden16_packed_bytes(int c_out, int c_a, int c_b) {
+  return (size_t)hidden_row_tiles(c_out) * ((size_t)hidden16_kt(c_a) + hidden16_kt(c_b)) * 3 * 32 * kHead16BK * sizeof(uint16_t);
+}
+// *bad (device, zeroed by the caller) becomes 1 when a weight is outside the bf16x6 domain (|w| >= 0x1.FFp127, inf, NaN)
+int launch_hidden16_pack(const float *w, int c_out, int c_a, int c_b, void *wp16, uint32_t *bad, void *stream);
+struct Hidden16Args {       // one launch, by value: items of one size
+  const uint16_t *xsa, *xsb; // the sources' split copies (launch_head16_split with c_in = c_a / c_b), item i's at + i * xs_stride, each
+  int64_t xs_stride;         // followed by its domain word (head16_oob_word): an item with a word that is not 0 is left to hidden_kernel.
+                             // xa absent: kta == 0 and xsa is not read
+  float *out;                // device [n, c_out, hw]
+  const void *wp16;          // the packed parts of the weights
+  const float *bp;           // the packed bias
+  int64_t hw;
+  int32_t c_a, c_b, c_out;
+  int32_t kta, n_kt;         // K tiles of source a in the sum (0: absent or c_a == 0), in all
+  int32_t kt0, kt_all;       // the packed K tile the sum starts at (past source a's when it is absent); packed K tiles per row tile
+  int32_t pt;                // position tiles of 128 per item
+  int32_t act;               // FGMM_ACT_*
+  float slope;
+};
+// the row tiles per block are launch_hidden's (hidden_tiles)
+int launch_hidden16(const Hidden16Args &args, int64_t n, int cus, void *stream);
 
 // ---- the checkerboard context convolution on the matrix cores (fgmm_ckbd_ctx.hip; header section 5b) --------------
 constexpr int kCkbdCtxBK = kMfma32BK; // input channels of one tap per LDS tile

@@ -493,7 +493,13 @@ class ParameterBody:
 
     ``ctx=None`` is the ABSENT context of the checkerboard anchors: the first ``c_ctx`` input channels of the first layer take no part in
     the sum - for finite weights what a context of zeros gives (section 2c states the two differences), at half the multiply-adds and
-    without the zeros.  The weights are packed once, here."""
+    without the zeros.  The weights are packed once, here.
+
+    ``arithmetic="bf16x6"`` (``FGMM_HIDDEN_BF16X6``, fgmm_hidden16.hip) evaluates every layer's sum on the BF16 matrix cores as
+    ``ParameterHead(arithmetic="bf16x6")`` evaluates its own: three bfloat16 parts per operand, six part products per product,
+    accumulated in binary32 from the bias, then the same activation - binary32 accuracy (the header states the bound), not the ``fmaf``
+    chain and not restatable on a CPU, but the same bits from every launch shape on MI355X: encoder and decoder must both use it there.
+    Weights outside its domain (finite, ``|w| < 0x1.FFp127``) raise here; an item with such a feature is computed by the exact kernel."""
 
     @staticmethod
     def check(modules):
@@ -521,7 +527,10 @@ class ParameterBody:
                 raise ValueError(f"ParameterBody: {b[0]} does not take the {a[0].out_channels} channels of the layer before it")
         return layers
 
-    def __init__(self, modules, c_ctx: int):
+    def __init__(self, modules, c_ctx: int, arithmetic: str = "f32"):
+        if arithmetic not in ("f32", "bf16x6"):
+            raise ValueError(f"ParameterBody: arithmetic {arithmetic!r} (\"f32\" or \"bf16x6\")")
+        self.arithmetic = arithmetic
         layers = self.check(list(modules))
         self.c_ctx = int(c_ctx)
         if self.c_ctx < 0 or layers[0][0].in_channels <= self.c_ctx:
@@ -541,8 +550,9 @@ class ParameterBody:
             b = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
             c_a = self.c_ctx if j == 0 else 0
             out = C.c_void_p()
-            _lib.check(_lib.lib().fgmm_hidden_create(_lib.ctx(self._dev), stream, w2.data_ptr(), b.data_ptr() if b is not None else None, conv.out_channels,
-                                                     c_a, conv.in_channels - c_a, act, slope, C.byref(out)), "ParameterBody")
+            _lib.check(_lib.lib().fgmm_hidden_create_ex(_lib.ctx(self._dev), stream, w2.data_ptr(), b.data_ptr() if b is not None else None, conv.out_channels,
+                                                        c_a, conv.in_channels - c_a, act, slope, _lib.FGMM_HIDDEN_BF16X6 if arithmetic == "bf16x6" else 0,
+                                                        C.byref(out)), "ParameterBody")
             self._h.append((out, conv.out_channels))
 
     def __del__(self):
@@ -564,9 +574,15 @@ class ParameterBody:
         xa = None if ctx is None else ctx.to(torch.float32).contiguous()
         x = side.to(torch.float32).contiguous()
         L, cx, stream = _lib.lib(), _lib.ctx(self._dev), torch.cuda.current_stream(self.device).cuda_stream
+        # bf16x6: ONE workspace for the split copies, sized for the largest layer and reused layer to layer (the layers are ordered on
+        # the stream); torch's allocator hands it out and takes it back in stream order.  An exact body's is empty and ignored
+        need = max(int(L.fgmm_hidden_workspace_bytes(hd, int(j == 0 and xa is not None), N, h * w)) for j, (hd, _) in enumerate(self._h))
+        with torch.cuda.device(self.device):
+            ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         for hd, c_out in self._h:
             out = torch.empty((N, c_out, h, w), dtype=torch.float32, device=self.device)
-            _lib.check(L.fgmm_hidden_apply(cx, stream, hd, None if xa is None else xa.data_ptr(), x.data_ptr(), out.data_ptr(), N, h * w), "ParameterBody.features")
+            _lib.check(L.fgmm_hidden_apply_ws(cx, stream, hd, None if xa is None else xa.data_ptr(), x.data_ptr(), out.data_ptr(), N, h * w,
+                                              ws.data_ptr() if need else None, need), "ParameterBody.features")
             xa, x = None, out
         return x
 

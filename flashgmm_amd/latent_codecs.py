@@ -347,7 +347,7 @@ class CheckerboardLatentCodec(nn.Module):
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None, entropy_parameters: Optional[nn.Module] = None,
                  context_prediction: Optional[nn.Module] = None, anchor_parity: str = "even", forward_method: str = "twopass",
-                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, fuse_context=False, fuse_body: bool = False,
+                 fuse_head=False, rdo_lambda: float = 0.0, rdo_channel_skip: bool = False, fuse_context=False, fuse_body=False,
                  **kwargs: Any):
         super().__init__()
         # fuse_body: everything of entropy_parameters BEFORE its last layer - 1x1 convolutions with LeakyReLU / ReLU, models/ckbd_gmm.py:
@@ -359,7 +359,15 @@ class CheckerboardLatentCodec(nn.Module):
         # estimate only: forward() runs the torch modules (these layers' gradients are not the library's).  Its reason is the fixed
         # order, not speed: measured at the reference's widths (profiles/param_body.md) the two layers are 2 % SLOWER than torch's for 24
         # non-anchor halves (0.374 against 0.368 ms), faster for the anchors (0.283 against 0.368) and for a single image (0.052 against 0.074).
+        # fuse_body: True / "f32" (the exact form) or "bf16x6" (ParameterBody's arithmetic on the BF16 matrix cores, fgmm_hidden16.hip: binary32
+        # accuracy, not the fmaf chain, the same bits from every launch shape - MI355X on both sides; part of the body's cache key).
+        # Measured (profiles/param_body_bf16x6.md), the splits of the features included: 24 non-anchor halves 0.304 ms against the f32
+        # form's 0.371 and torch's 0.369 in the same process - 1.22 times the f32 form; the anchors 0.226 against 0.282; a single image
+        # 0.062 against the f32 form's 0.052 - SLOWER there (two more launches per layer), still ahead of torch's 0.078.
+        if fuse_body not in (False, True, "f32", "bf16x6"):
+            raise ValueError(f"fuse_body {fuse_body!r}")
         self.fuse_body = bool(fuse_body)
+        self._body_arith = "bf16x6" if fuse_body == "bf16x6" else "f32"
         self._body: Optional[ParameterBody] = None
         self._body_key = None
         if self.fuse_body:
@@ -451,9 +459,9 @@ class CheckerboardLatentCodec(nn.Module):
             return body(self.merge(self._ctx(y_hat_, i), side_i))
         first = ep[0]
         params = [p for m in ep[:-1] for p in (getattr(m, "weight", None), getattr(m, "bias", None)) if p is not None]
-        key = (first.in_channels - side_i.shape[1],) + tuple((p.data_ptr(), p._version) for p in params)  # (the key of _head_parts, every layer's)
+        key = (first.in_channels - side_i.shape[1], self._body_arith) + tuple((p.data_ptr(), p._version) for p in params)  # (the key of _head_parts, every layer's)
         if self._body is None or self._body_key != key:
-            self._body, self._body_key = ParameterBody(ep[:-1], key[0]), key
+            self._body, self._body_key = ParameterBody(ep[:-1], key[0], self._body_arith), key
         return self._body.features(None if i == 0 else self._ctx(y_hat_, i), side_i)  # the anchors' context: absent
 
     def _ep_params(self, y_hat_: Tensor, i: int, side_i: Tensor) -> Tensor:

@@ -59,6 +59,7 @@ extern "C" {
 #define FGMM_HAS_CKBD_CONTEXT 1 /* section 5b: fgmm_ckbd_ctx_create, fgmm_ckbd_ctx_destroy, fgmm_ckbd_ctx_apply (added without a bump, as 3b - 3j) */
 #define FGMM_HAS_EB_UPDATE 1 /* section 3k: fgmm_eb_quantiles, fgmm_eb_tables (added without a bump, as 3b - 3j) */
 #define FGMM_HAS_HIDDEN 1    /* section 2c: fgmm_hidden_create, fgmm_hidden_destroy, fgmm_hidden_apply (added without a bump, as 3b - 5c) */
+#define FGMM_HAS_HIDDEN_BF16X6 1 /* section 2c: FGMM_HIDDEN_BF16X6, fgmm_hidden_create_ex, fgmm_hidden_workspace_bytes, fgmm_hidden_apply_ws (added without a bump) */
 #define FGMM_EB_SEARCH_CAP 256 /* section 3k: bisection steps of one quantile search at the most */
 #define FGMM_EB_PARAMS 58    /* float32 values per channel of section 3j's theta */
 #define FGMM_EB_SLICE 1024   /* section 3j: elements of a channel one workgroup walks; the backward's partial rows per channel are
@@ -424,6 +425,45 @@ void fgmm_hidden_destroy(fgmm_hidden *hidden);
  * xa given to a layer with c_a == 0, sizes whose grid would exceed 2^30 workgroups.  n == 0 or hw == 0: success, no launch. */
 int fgmm_hidden_apply(fgmm_ctx *ctx, void *stream, const fgmm_hidden *hidden, const float *xa, const float *xb, float *out, int n,
                       int64_t hw);
+/* FGMM_HIDDEN_BF16X6: the same layer on the BF16 matrix cores with binary32 accuracy ("bf16x6"), as FGMM_HEAD_BF16X6 (section 2b) and
+ * FGMM_CKBD_CTX_BF16X6 (section 5b) evaluate their sums.
+ *   The sum: every weight and every feature v is three bfloat16 parts, v1 = bf16(v), v2 = bf16(v - v1), v3 = bf16(v - v1 - v2) (round to
+ *   nearest even; the subtractions exact in binary32).  A product w x is the six part products (w1,x3) (w3,x1) (w2,x2) (w1,x2) (w2,x1)
+ *   (w1,x1), in that order, smallest first; each is one v_mfma_f32_32x32x16_bf16 over 16 input channels of ONE source, accumulated in
+ *   binary32 starting from the bias (+0 without).  Tiles of 16 channels ascend through xa, then xb; each source is padded to a multiple of
+ *   16 channels on its own with zeros: n16 = ceil(c_a / 16) + ceil(c_b / 16) matrix steps of six products.  With xa NULL its tiles are
+ *   not multiplied (section 2c's absent source, carried over): n16 = ceil(c_b / 16).  Then the activation of section 2c, unchanged, on
+ *   the binary32 accumulator.
+ *   The bound, for operands in the domain, with S = sum |w x| + |bias| over the channels that take part and exact = bias + sum w x:
+ *       |pre - exact| <= E = R S + 2^-133 (sum |w| + sum |x|) + 6 n16 2^-150,   R = 2^-23 (1 + 2^-6) + 6 n16 2^-24 (1 + 2^-7)
+ *       |out - act(exact)| <= max(1, |slope|) E + 2^-24 |act(exact)| + 2^-150
+ *   - the head's bound with this n16 through an activation of Lipschitz constant max(1, |slope|) (1 for FGMM_ACT_NONE and FGMM_ACT_RELU),
+ *   and the one rounding of LeakyReLU's multiply.
+ *   The domain: finite operands with |v| < 0x1.FFp127 (beyond, the first part rounds to an infinity).  A WEIGHT outside is refused by
+ *   fgmm_hidden_create_ex (FGMM_ERR_INVALID, *out NULL).  An ITEM with a feature outside in any PRESENT source is computed whole by the
+ *   exact kernel instead, launched right after on the same stream: that item is bit for bit section 2c's fmaf chain; the other items of
+ *   the call keep their bf16x6 bits.  A layer's own output leaving the domain needs nothing: the next layer's call sees it as a feature.
+ *   What it is NOT: the fmaf chain above, or a sequence a CPU can restate bit for bit (the matrix instruction's internal order is not
+ *   documented).  What it is: the SAME BITS FROM EVERY LAUNCH on MI355X - an output's bits depend on its weight row, its bias and the
+ *   features at its position, not on the block height, on n, on the item's place in a batch or on its neighbours.  Encoder and decoder
+ *   must BOTH use it, on MI355X.  The block heights are those of the paragraph above, by the same rule.
+ * A bf16x6 handle holds both packings (the exact kernel serves the items outside the domain).  Unknown flags are refused; also refused
+ * with FGMM_HIDDEN_BF16X6: a source of more than 65535 * 16 channels (the split's grid holds a tile of 16 channels per block row). */
+#define FGMM_HIDDEN_BF16X6 1
+int fgmm_hidden_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_a, int c_b, int act,
+                          float slope, int flags, fgmm_hidden **out);
+/* bytes of the workspace fgmm_hidden_apply_ws needs for n items of hw positions, with (has_xa != 0) or without a first source: per item
+ * and present source the three bfloat16 parts of its features, channels padded to 16, and 16 bytes.  0: an exact handle, a NULL handle,
+ * n == 0 or hw == 0, or sizes the apply refuses. */
+size_t fgmm_hidden_workspace_bytes(const fgmm_hidden *hidden, int has_xa, int n, int64_t hw);
+/* fgmm_hidden_apply with a caller-owned workspace: device memory, 16-byte aligned, at least fgmm_hidden_workspace_bytes(hidden, xa !=
+ * NULL, n, hw) bytes, the call's until the work enqueued here has run.  STREAM-ORDERED as fgmm_hidden_apply: on a bf16x6 handle the split of
+ * each present source, the bf16x6 kernel and the exact kernel for the items outside the domain are enqueued on `stream` - no context
+ * lock, no host wait.  Refused, launching and writing nothing: what fgmm_hidden_apply refuses; a workspace that is NULL, too small (the
+ * message names the bytes needed) or not 16-byte aligned.  An exact handle ignores the workspace.  fgmm_hidden_apply on a bf16x6 handle
+ * is refused (the message names this call). */
+int fgmm_hidden_apply_ws(fgmm_ctx *ctx, void *stream, const fgmm_hidden *hidden, const float *xa, const float *xb, float *out, int n,
+                         int64_t hw, void *workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Building blocks ("same tables => same bytes" surfaces; also what the parity tests probe).
