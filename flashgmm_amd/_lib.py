@@ -270,6 +270,15 @@ SIGNATURES = {
     "fgmm_hidden_create_ex": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _pp]),
     "fgmm_hidden_workspace_bytes": (_sz, [_p, _i, _i, _i64]),
     "fgmm_hidden_apply_ws": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _p, _sz]),
+    # section 2d: (c_out, c_a, c_b); (ctx, stream, weight, bias, c_out, c_a, c_b, transposed, packed); (ctx, stream, packed, c_out, c_a, c_b, act,
+    # slope, xa, xb, out, n, hw); (ctx, stream, packed_t, c_out, c_a, c_b, act, slope, gy, out, dxa, dxb, n, hw); (c_out, c_a, c_b, has_xa, n, hw);
+    # (ctx, stream, xa, xb, gy, out, c_out, c_a, c_b, act, slope, n, hw, dweight, dbias, workspace, workspace_bytes)
+    "fgmm_hidden_packed_floats": (_sz, [_i, _i, _i]),
+    "fgmm_hidden_pack": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fgmm_hidden_apply_packed": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_float, _p, _p, _p, _i, _i64]),
+    "fgmm_hidden_dgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_float, _p, _p, _p, _p, _i, _i64]),
+    "fgmm_hidden_wgrad_workspace": (_sz, [_i, _i, _i, _i, _i, _i64]),
+    "fgmm_hidden_wgrad": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _i64, _p, _p, _p, _sz]),
     "fgmm_ckbd_unembed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
     "fgmm_ckbd_embed": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _i]),
     "fgmm_ckbd_ctx_create": (_i, [_p, _p, _p, _p, _i, _i, _pp]),

@@ -179,4 +179,35 @@ int fgmm_hidden_apply_ws(fgmm_ctx *ctx, void *stream, const fgmm_hidden *h, cons
   return hidden_run(ctx, stream, h, xa, xb, out, n, hw, h && h->packed16, workspace, workspace_bytes);
 }
 
+// ---- section 2d: caller-owned packed weights (the gradients themselves: fgmm_hidden_grad.cpp) ---------------------------------------
+static bool hidden_sizes_ok(int c_out, int c_a, int c_b) { return c_out >= 1 && c_b >= 1 && c_a >= 0 && c_out <= (1 << 20) && c_a <= (1 << 20) && c_b <= (1 << 20); }
+
+size_t fgmm_hidden_packed_floats(int c_out, int c_a, int c_b) { return hidden_sizes_ok(c_out, c_a, c_b) ? hidden_packed_floats(c_out, c_a, c_b) : 0; }
+
+int fgmm_hidden_pack(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_a, int c_b, int transposed, float *packed) {
+  if (!ctx || !weight || !packed || !hidden_sizes_ok(c_out, c_a, c_b) || (transposed & ~1) || (transposed && bias))
+    return fail(FGMM_ERR_INVALID, "hidden layer: bad argument to pack (null tensor, sizes, a bias with the transposed form)");
+  if ((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(packed)) % sizeof(float))
+    return fail(FGMM_ERR_INVALID, "hidden layer: misaligned tensor");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select HIP device %d", ctx->device);
+  if (transposed) LAUNCH_TRY(launch_hidden_pack_t(weight, c_out, c_a, c_b, packed, stream));
+  else LAUNCH_TRY(launch_hidden_pack(weight, bias, c_out, c_a, c_b, packed, packed + (hidden_packed_floats(c_out, c_a, c_b) - (size_t)hidden_row_tiles(c_out) * 32), stream));
+  return FGMM_OK;
+}
+
+int fgmm_hidden_apply_packed(fgmm_ctx *ctx, void *stream, const float *packed, int c_out, int c_a, int c_b, int act, float slope, const float *xa,
+                             const float *xb, float *out, int n, int64_t hw) {
+  if (!ctx || !hidden_sizes_ok(c_out, c_a, c_b)) return fail(FGMM_ERR_INVALID, "hidden layer: bad argument (context, channel counts)");
+  if (act != FGMM_ACT_NONE && act != FGMM_ACT_LEAKY && act != FGMM_ACT_RELU) return fail(FGMM_ERR_INVALID, "hidden layer: unknown activation %d", act);
+  if (!std::isfinite(slope)) return fail(FGMM_ERR_INVALID, "hidden layer: the slope is not finite");
+  if (!packed || reinterpret_cast<uintptr_t>(packed) % 16) return fail(FGMM_ERR_INVALID, "hidden layer: null packed weights, or not aligned to 16 bytes");
+  fgmm_hidden h; // the handle's view of the caller's buffer: nothing here is owned
+  h.device = ctx->device, h.c_out = c_out, h.c_a = c_a, h.c_b = c_b, h.act = act, h.slope = slope;
+  h.packed = const_cast<float *>(packed);
+  const int e = hidden_device_cus(ctx->device, &h.cus);
+  if (e || h.cus < 1) return fail(FGMM_ERR_HIP, "hidden layer: the device's compute units: %s", dev::error_string(e));
+  return hidden_run(ctx, stream, &h, xa, xb, out, n, hw, false, nullptr, 0);
+}
+
 } // extern "C"

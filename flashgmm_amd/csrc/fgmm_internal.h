@@ -272,6 +272,42 @@ int ckbd_wgrad_tiles(int64_t S, int n_col, int c_out);
 int launch_ckbd_wgrad(const CkbdWgradArgs &args, void *stream);
 int launch_ckbd_wgrad_finish(const float *partial, int M, int c_out, int S, float *dweight_or_null, float *dbias_or_null, void *stream);
 
+// ---- the hidden layers' gradients (fgmm_hidden_grad.hip; header section 2d) ---------------------------------------
+// the transposed packing the data gradient runs on: hidden_pack_kernel's layout of the layer W'[r][o] = w[o][r] - c_a + c_b rows, one
+// source of c_out channels, a bias of +0: hidden_packed_floats(c_a + c_b, 0, c_out) floats at wp
+int launch_hidden_pack_t(const float *w, int c_out, int c_a, int c_b, float *wp, void *stream);
+struct HiddenDgradArgs {  // one launch, by value: items of one size
+  const float *gy, *out;  // device [n, c_out, hw]: the gradient of the layer's output, the saved output (not read with FGMM_ACT_NONE)
+  float *dxa, *dxb;       // device [n, c_a, hw], [n, c_b, hw]; null: not asked for
+  const float *wp;        // the transposed packing
+  int64_t hw;
+  int32_t c_a, c_b, c_out;
+  int32_t r0, r1;         // the asked rows of [0, c_a + c_b): r0 = 0 with dxa, else c_a; r1 = c_a + c_b with dxb, else c_a
+  int32_t n_kt;           // K tiles: ceil(c_out / 32)
+  int32_t pt;             // position tiles of 128 per item
+  int32_t act;            // FGMM_ACT_*
+  float slope;
+};
+// row tiles per block the launch takes (5, 2 or 1): section 2c's rule over the blocks of T tiles, aligned at multiples of T, that hold an
+// asked row
+int hidden_dgrad_tiles(int64_t n, int64_t pt, int r0, int r1, int cus);
+int launch_hidden_dgrad(const HiddenDgradArgs &args, int64_t n, int cus, bool vec, void *stream);
+struct HiddenWgradArgs {
+  const float *xa, *xb;   // device [n, c_a, hw] (null: absent, or dweight not asked for), [n, c_b, hw] (null: dweight not asked for)
+  const float *gy, *out;  // device [n, c_out, hw]
+  float *partial;         // device [S][c_out][c_a + c_b + 1]
+  int32_t c_a, c_b, c_out, hw;
+  int32_t mta, mtb;       // channel tiles of 32 of the two sources
+  int32_t col0, n_col;    // the column tiles the launch computes: of [0, mta + mtb] (mta + mtb: the bias')
+  int32_t P, L, S;        // ckbd_wgrad_slices(P = n * hw)
+  int32_t act;
+  float slope;
+};
+// row tiles per block the launch takes (4, 2 or 1): ckbd_wgrad_tiles' rule; blocks = S * ceil(n_col / 4) * ceil(ceil(c_out / 32) / that)
+int hidden_wgrad_tiles(int64_t S, int n_col, int c_out);
+int launch_hidden_wgrad(const HiddenWgradArgs &args, void *stream);
+int launch_hidden_wgrad_finish(const float *partial, int c_a, int c_b, int c_out, bool has_xa, int S, float *dweight_or_null, float *dbias_or_null, void *stream);
+
 // ---- GPU-side decode of CHECKPOINTED bitstreams (segdec_kernel): one wave per segment ---------------------------
 struct SegDesc {
   const void *scales, *means, *weights; // float32, float16 or bfloat16 planes

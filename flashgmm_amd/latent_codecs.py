@@ -32,7 +32,8 @@ from torch import Tensor
 from itertools import accumulate
 
 from .entropy_models import EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterBody, ParameterHead
-from .ops import CheckerboardContext, checkerboard_context, ckbd_embed, ckbd_unembed
+from . import _lib
+from .ops import CheckerboardContext, checkerboard_context, ckbd_embed, ckbd_unembed, pointwise_layer
 
 __all__ = ["GaussianMixtureConditionalLatentCodec", "CheckerboardLatentCodec", "ChannelGroupsLatentCodec", "HyperLatentCodec",
            "HyperpriorLatentCodec"]
@@ -355,8 +356,9 @@ class CheckerboardLatentCodec(nn.Module):
         # fixed summation order, the merge of context and side parameters folded into the first layer; the anchors' context is ABSENT:
         # no zeros tensor, half the first layer's sum).  Like fuse_head and fuse_context it changes the last bits of the parameters:
         # encoder and decoder must agree on this switch.  Works alone and with fuse_head / fuse_context in any combination; with all three
-        # every float between the decoded anchors and the table entry is computed in the library's order.  compress / decompress /
-        # estimate only: forward() runs the torch modules (these layers' gradients are not the library's).  Its reason is the fixed
+        # every float between the decoded anchors and the table entry is computed in the library's order.  forward() runs the exact
+        # form's layers through ops.pointwise_layer (header section 2d: the same chain, and the gradients in one fixed order), with
+        # fuse_head in its exact form the last layer too; a "bf16x6" body or head keeps the torch modules there.  Its reason is the fixed
         # order, not speed: measured at the reference's widths (profiles/param_body.md) the two layers are 2 % SLOWER than torch's for 24
         # non-anchor halves (0.374 against 0.368 ms), faster for the anchors (0.283 against 0.368) and for a single image (0.052 against 0.074).
         # fuse_body: True / "f32" (the exact form) or "bf16x6" (ParameterBody's arithmetic on the BF16 matrix cores, fgmm_hidden16.hip: binary32
@@ -619,6 +621,22 @@ class CheckerboardLatentCodec(nn.Module):
             raise ValueError("context_prediction.mask is not the checkerboard pattern (1 at the kernel positions (i, j) with i + j odd, 0 elsewhere)")
         self._mask_ok = key
 
+    def _forward_params(self, y_ctx: Tensor, side_params: Tensor) -> Tensor:
+        """forward()'s ``entropy_parameters(merge(y_ctx, side_params))`` with the exact fused body: the layers ``ParameterBody.check``
+        accepts through ``pointwise_layer`` (header section 2d), the first one on the two sources - the merge is never made; the last
+        layer too with the exact fused head (``activation="none"``: the head's own chain), else as the torch module it is"""
+        ep = self.entropy_parameters
+        layers = ParameterBody.check(ep[:-1])
+        head = self.fuse_head and self._head_arith == "f32"
+        if head:
+            layers.append((ep[-1], _lib.FGMM_ACT_NONE, 0.0))
+        names = {_lib.FGMM_ACT_NONE: "none", _lib.FGMM_ACT_LEAKY: "leaky_relu", _lib.FGMM_ACT_RELU: "relu"}
+        ctx, x = y_ctx, side_params
+        for conv, act, slope in layers:
+            x = pointwise_layer(ctx, x, conv.weight, conv.bias, names[act], slope)
+            ctx = None  # (every later layer has one source: c_ctx == 0)
+        return x if head else ep[-1](x)
+
     def forward(self, y: Tensor, side_params: Tensor) -> Dict[str, Any]:
         """The reference's one-pass training forward (``_forward_onepass``, checkerboard.py:154-171; the only forward method the GMM
         models use, models/ckbd_gmm.py:125), any batch size: ``y_hat = y + U(-0.5, 0.5)`` in training, ``round(y)`` otherwise
@@ -635,7 +653,14 @@ class CheckerboardLatentCodec(nn.Module):
         the 13 dropped taps - where the reference, zeroing ``weight.data`` in place and differentiating a plain convolution
         (compressai/layers/layers.py:141-144), leaves non-zero values there that enter a global gradient-norm clip.
 
-        ``fuse_head``, ``rdo_lambda`` / ``rdo_channel_skip`` and the inner codec's ``param_dtype`` are choices of the coding path and
+        ``fuse_body`` in ``(True, "f32")``: the layers of ``entropy_parameters`` before its last run through ``ops.pointwise_layer``
+        (header section 2d: section 2c's chain forward, data, weight and bias gradients on the matrix cores in one fixed order), the
+        first one on ``(y_ctx, side_params)`` as its two sources - the merge is never made, the modules' own ``forward`` never runs.
+        With ``fuse_head`` in ``(True, "f32")`` as well the last layer runs through it too (``activation="none"``: the head's own
+        chain).  ``fuse_body="bf16x6"``, ``fuse_head="bf16x6"`` and the defaults keep the torch modules.  A LeakyReLU with a negative
+        slope is refused there (``ValueError``).
+
+        ``rdo_lambda`` / ``rdo_channel_skip`` and the inner codec's ``param_dtype`` are choices of the coding path and
         do not apply here.  The two-pass forward methods are not provided (the reference does not support them for GMM either)."""
         if self.forward_method != "onepass":
             raise NotImplementedError(f"forward_method {self.forward_method!r}: only \"onepass\" is provided, the one forward method the GMM models "
@@ -656,7 +681,10 @@ class CheckerboardLatentCodec(nn.Module):
             keep[..., 0::2, 1 - s::2] = True
             keep[..., 1::2, s::2] = True
             y_ctx = torch.where(keep, y_ctx, torch.zeros_like(y_ctx))  # _keep_only(., "non_anchor")
-        params = self.entropy_parameters(self.merge(y_ctx, side_params))
+        if self.fuse_body and self._body_arith == "f32":
+            params = self._forward_params(y_ctx, side_params)
+        else:
+            params = self.entropy_parameters(self.merge(y_ctx, side_params))
         y_out = self.latent_codec["y"](y, params)
         return {"likelihoods": {"y": y_out["likelihoods"]["y"]}, "y_hat": y_hat}
 

@@ -11,6 +11,9 @@ summation order (include/flashgmm_amd.h section 5b).
 over the transposed filters, its weight and bias gradients one matrix-core kernel in a summation order that is a function of the shape
 alone.  ``ckbd_unembed`` / ``ckbd_embed`` are differentiable as well: each one's backward is the other.
 
+``pointwise_layer`` — one 1x1 layer of the parameter network over two sources, with its activation, as a DIFFERENTIABLE operator
+(header sections 2c and 2d): forward, data gradients and weight and bias gradients on the matrix cores, each in one fixed order.
+
 ``pmf_to_quantized_cdf`` — mirror of ``compressai._CXX.pmf_to_quantized_cdf`` (compressai/cpp_exts/ops/ops.cpp:40-109),
 the table builder behind ``EntropyBottleneck.update()`` / ``GaussianConditional.update()`` (the `z` hyper-latent path).
 Runs once per model; host code in libflashgmm_amd.so."""
@@ -23,7 +26,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["pmf_to_quantized_cdf", "ckbd_unembed", "ckbd_embed", "CheckerboardContext", "checkerboard_context"]
+__all__ = ["pmf_to_quantized_cdf", "ckbd_unembed", "ckbd_embed", "CheckerboardContext", "checkerboard_context", "pointwise_layer"]
 
 
 def _ckbd(t, anchor_parity: str, embed: bool):
@@ -308,6 +311,129 @@ def checkerboard_context(anchors, weight, bias=None, anchor_parity: str = "even"
     that never change a forward value but do enter a global gradient-norm clip."""
     _ctx_check(anchors, weight, bias, anchor_parity)
     return _ctx_function().apply(anchors, weight, bias, anchor_parity)
+
+
+_ACTIVATIONS = {"none": _lib.FGMM_ACT_NONE, "leaky_relu": _lib.FGMM_ACT_LEAKY, "relu": _lib.FGMM_ACT_RELU}
+
+
+def _pw_check(ctx, side, weight, bias, activation, negative_slope):
+    """the refusals of ``pointwise_layer``: activation, slope, device, dtype, shape -> (c_ctx, c_side, c_out)"""
+    import torch
+
+    if activation not in _ACTIVATIONS:
+        raise ValueError(f"activation {activation!r} (\"none\", \"leaky_relu\" or \"relu\")")
+    slope = float(negative_slope)
+    if slope != slope or slope in (float("inf"), float("-inf")) or (activation == "leaky_relu" and slope < 0):
+        raise ValueError(f"negative_slope {negative_slope!r}: finite, and not negative with \"leaky_relu\" (the saved output's sign is then not the pre-activation's)")
+    if not (torch.is_tensor(side) and torch.is_tensor(weight)) or not (ctx is None or torch.is_tensor(ctx)) or not (bias is None or torch.is_tensor(bias)):
+        raise TypeError("ctx, side, weight and bias must be tensors (ctx and bias may be None)")
+    if weight.dim() not in (2, 4) or tuple(weight.shape[2:]) not in ((), (1, 1)) or weight.dtype != torch.float32:
+        raise RuntimeError(f"weight must be float32 [c_out, c_ctx + c_side] or [c_out, c_ctx + c_side, 1, 1]; got {weight.dtype} {tuple(weight.shape)}")
+    if not weight.is_cuda:
+        raise RuntimeError("flashgmm_amd operators run on the GPU only: the layer's weights must be on a HIP device")
+    c_out, c_in = int(weight.shape[0]), int(weight.shape[1])
+    if side.dim() != 4 or not 0 < side.shape[1] <= c_in or side.device != weight.device or side.dtype != torch.float32:
+        raise RuntimeError(f"side must be float32 [N, c_side <= {c_in}, h, w] on {weight.device}; got {side.dtype} {tuple(side.shape)} on {side.device}")
+    c_side = int(side.shape[1])
+    c_ctx = c_in - c_side
+    want = (side.shape[0], c_ctx) + tuple(side.shape[2:])
+    if ctx is not None and (c_ctx == 0 or tuple(ctx.shape) != want or ctx.device != weight.device or ctx.dtype != torch.float32):
+        raise RuntimeError(f"ctx must be None or float32 {want} on {weight.device} (c_ctx > 0); got {ctx.dtype} {tuple(ctx.shape)} on {ctx.device}")
+    if c_out < 1 or (bias is not None and (tuple(bias.shape) != (c_out,) or bias.device != weight.device or bias.dtype != torch.float32)):
+        raise RuntimeError(f"bias must be float32 [{c_out}] on {weight.device}")
+    return c_ctx, c_side, c_out
+
+
+def _pw_pack(dev, stream, w, b, transposed, c_out, c_a, c_b):
+    """section 2d's packing of w [c_out, c_a + c_b] in torch-allocated memory, on ``stream``"""
+    import torch
+
+    L = _lib.lib()
+    floats = L.fgmm_hidden_packed_floats(c_a + c_b, 0, c_out) if transposed else L.fgmm_hidden_packed_floats(c_out, c_a, c_b)
+    packed = torch.empty((int(floats),), dtype=torch.float32, device=w.device)
+    _lib.check(L.fgmm_hidden_pack(_lib.ctx(dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, c_out, c_a, c_b, int(transposed),
+                                  packed.data_ptr()), "pointwise_layer: pack")
+    return packed
+
+
+_pw_fn = []
+
+
+def _pw_function():
+    if not _pw_fn:
+        import torch
+
+        class PointwiseLayerFn(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, xa, xb, weight, bias, activation, negative_slope):
+                c_a, c_b, c_out = _pw_check(xa, xb, weight, bias, activation, negative_slope)
+                a = None if xa is None else xa.detach().contiguous()
+                x, w = xb.detach().contiguous(), weight.detach().reshape(c_out, c_a + c_b).contiguous()
+                b = None if bias is None else bias.detach().contiguous()
+                dev = w.device.index if w.device.index is not None else -1
+                act, slope = _ACTIVATIONS[activation], float(negative_slope)
+                N, _, h, wd = x.shape
+                out = torch.empty((N, c_out, h, wd), dtype=torch.float32, device=w.device)
+                with torch.cuda.device(w.device):
+                    stream = torch.cuda.current_stream(w.device).cuda_stream
+                    if N and h and wd:
+                        packed = _pw_pack(dev, stream, w, b, False, c_out, c_a, c_b)
+                        _lib.check(_lib.lib().fgmm_hidden_apply_packed(_lib.ctx(dev), stream, packed.data_ptr(), c_out, c_a, c_b, act, slope,
+                                                                       None if a is None else a.data_ptr(), x.data_ptr(), out.data_ptr(), N, h * wd),
+                                   "pointwise_layer: apply")
+                ctx.save_for_backward(a, x, w, out)
+                ctx.geom = (dev, act, slope, c_a, c_b, c_out, bias is not None, weight.shape)
+                return out
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable
+            def backward(ctx, gy):
+                a, x, w, out = ctx.saved_tensors
+                dev, act, slope, c_a, c_b, c_out, has_bias, w_shape = ctx.geom
+                N, _, h, wd = x.shape
+                gy = gy.to(torch.float32).contiguous()
+                need_a, need_x, need_w = a is not None and ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+                need_b = has_bias and ctx.needs_input_grad[3]
+                L, empty = _lib.lib(), not (N and h and wd)
+                new = torch.zeros if empty else torch.empty  # (an empty batch: zero gradients)
+                with torch.cuda.device(w.device):
+                    stream = torch.cuda.current_stream(w.device).cuda_stream
+                    da = new(a.shape, dtype=torch.float32, device=w.device) if need_a else None
+                    dx = new(x.shape, dtype=torch.float32, device=w.device) if need_x else None
+                    dw = new((c_out, c_a + c_b), dtype=torch.float32, device=w.device) if need_w else None
+                    db = new((c_out,), dtype=torch.float32, device=w.device) if need_b else None
+                    if (need_a or need_x) and not empty:
+                        packed_t = _pw_pack(dev, stream, w, None, True, c_out, c_a, c_b)
+                        _lib.check(L.fgmm_hidden_dgrad(_lib.ctx(dev), stream, packed_t.data_ptr(), c_out, c_a, c_b, act, slope, gy.data_ptr(), out.data_ptr(),
+                                                       da.data_ptr() if need_a else None, dx.data_ptr() if need_x else None, N, h * wd),
+                                   "pointwise_layer: dgrad")
+                    if (need_w or need_b) and not empty:
+                        nbytes = int(L.fgmm_hidden_wgrad_workspace(c_out, c_a, c_b, int(a is not None), N, h * wd))
+                        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=w.device)
+                        _lib.check(L.fgmm_hidden_wgrad(_lib.ctx(dev), stream, None if a is None else a.data_ptr(), x.data_ptr(), gy.data_ptr(), out.data_ptr(),
+                                                       c_out, c_a, c_b, act, slope, N, h * wd, dw.data_ptr() if need_w else None,
+                                                       db.data_ptr() if need_b else None, ws.data_ptr(), nbytes), "pointwise_layer: wgrad")
+                return da, dx, None if dw is None else dw.reshape(w_shape), db, None, None
+
+        _pw_fn.append(PointwiseLayerFn)
+    return _pw_fn[0]
+
+
+def pointwise_layer(ctx, side, weight, bias=None, activation: str = "none", negative_slope: float = 0.01):
+    """One layer of the parameter network as a differentiable operator (include/flashgmm_amd.h sections 2c and 2d): ``ctx``
+    ``[N, c_ctx, h, w]`` float32 or None (ABSENT: the first ``c_ctx`` columns of ``weight`` take no part), ``side`` ``[N, c_side, h, w]``,
+    ``weight`` ``[c_out, c_ctx + c_side]`` (or the convolution's ``[.., .., 1, 1]``), ``bias`` ``[c_out]`` or None ->
+    ``act(conv2d(cat(ctx, side), weight, bias))`` ``[N, c_out, h, w]``, bit for bit section 2c's ``fmaf`` chain and activation
+    (``"none"``, ``"leaky_relu"`` with ``negative_slope >= 0``, ``"relu"``); the concatenation never exists.  The weights are packed
+    at every call (a training step changes them), into torch-allocated memory on the current stream.
+
+    Backward (once differentiable, only what is asked for): the activation's derivative is taken from the saved OUTPUT (nothing else
+    is kept); the gradients of ``ctx`` and ``side`` are one matrix-core kernel over the transposed weights, those of ``weight`` and
+    ``bias`` one kernel over a torch-allocated workspace, in a summation order that depends on the shape alone - the same bits on every
+    run, device and launch geometry.  With ``ctx=None`` the first ``c_ctx`` columns of the weight's gradient are +0.  An empty batch gives
+    zero gradients."""
+    _pw_check(ctx, side, weight, bias, activation, negative_slope)
+    return _pw_function().apply(ctx, side, weight, bias, activation, float(negative_slope))
 
 
 def pmf_to_quantized_cdf(pmf: Sequence[float], precision: int = 16) -> List[int]:

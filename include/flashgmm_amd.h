@@ -466,6 +466,62 @@ int fgmm_hidden_apply_ws(fgmm_ctx *ctx, void *stream, const fgmm_hidden *hidden,
                          int64_t hw, void *workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * 2d. The hidden layer of 2c as a DIFFERENTIABLE operator: the forward over caller-owned packed weights and three gradients, on the
+ *    matrix cores, in one fixed order.  What CheckerboardLatentCodec.forward() needs of entropy_parameters under autograd (a model
+ *    that is coded with section 2c's kernels sees their bits while it trains, for the reason of section 2b), exact binary32 only.
+ *    Notation as 2c.  `out` [n, c_out, hw] is the layer's saved OUTPUT (the next layer keeps it as its input anyway: the pre-activation
+ *    is never stored), gy [n, c_out, hw] the gradient with respect to it.
+ *    ACTIVATION DERIVATIVE, formed on the fly, one binary32 operation - the library's own sequence; torch's rule wherever the output
+ *    is not NaN:
+ *        FGMM_ACT_NONE   gz = gy                              (`out` is not read and may be NULL)
+ *        FGMM_ACT_LEAKY  gz = out > 0 ? gy : gy * slope       (out > 0 exactly where acc > 0 only for slope >= 0: a negative slope is
+ *                                                              refused by the two gradient calls)
+ *        FGMM_ACT_RELU   gz = out > 0 ? gy : +0
+ *    A NaN output takes the second branch.
+ *    DATA GRADIENTS, only those asked for, on v_mfma_f32_32x32x2_f32 bit for bit - signs of zero, infinities and NaN included:
+ *        dxa[i][k][p] = the chain  acc = +0; for o = 0 .. c_out-1 ascending: acc = fmaf(weight[o][k],       gz[i][o][p], acc)
+ *        dxb[i][k][p] = the chain  acc = +0; for o = 0 .. c_out-1 ascending: acc = fmaf(weight[o][c_a + k], gz[i][o][p], acc)
+ *    Block heights: 2c's ladder 5, 2, 1 and rule, with B(T) = n * ceil(hw / 128) * G(T), G(T) the groups of T row tiles of 32 input
+ *    channels, counted from channel 0, that hold an asked channel of cat(xa, xb).  Every height gives the same bits.
+ *    WEIGHT AND BIAS GRADIENTS  the reduction runs over the positions of all items, concatenated: s = i hw + p, P = n hw, cut by
+ *    section 5c's slice rule with 5c's constants (S slices of L positions, a function of P alone; slices may cross item boundaries):
+ *        partial_k[o][c] = the chain  acc = +0; for s ascending in slice k: acc = fmaf(gz(s)[o], x(s)[c], acc),   x = cat(xa, xb)
+ *        dweight[o][c]   = ((partial_0 + partial_1) + partial_2) + ...   in binary32, ascending
+ *        dbias[o]        = the same with x = 1
+ *    With xa absent (NULL on a layer with c_a > 0) columns [0, c_a) of dweight are written +0.  No float atomics: every partial has one
+ *    writer.  Block heights 4, 2, 1 by 5c's rule; every height gives the same bits.
+ * All six calls are STREAM-ORDERED like section 2c's apply: enqueued on `stream`, no context lock, no host wait, caller-owned memory; a
+ * refused call launches nothing and writes nothing.
+ * fgmm_hidden_packed_floats: float32 elements of a packing of a layer (0 for sizes that are refused).
+ * fgmm_hidden_pack: weight device float32 [c_out, c_a + c_b], bias [c_out] or NULL.  transposed = 0 writes the layout a handle holds,
+ *   into packed[fgmm_hidden_packed_floats(c_out, c_a, c_b)]; transposed = 1 writes the layer W'[r][o] = weight[o][r] - c_a + c_b output
+ *   channels, ONE source of c_out channels - into packed[fgmm_hidden_packed_floats(c_a + c_b, 0, c_out)], what fgmm_hidden_dgrad runs on;
+ *   it takes no bias (a bias with it is refused).  `packed` is aligned to 16 bytes where it is used.
+ * fgmm_hidden_apply_packed: fgmm_hidden_apply on such a buffer (transposed = 0) - the same bits as a handle made of the same weights.
+ *   Refusals as fgmm_hidden_create's and fgmm_hidden_apply's.
+ * fgmm_hidden_dgrad: packed_t from fgmm_hidden_pack(transposed = 1); dxa device float32 [n, c_a, hw] or NULL, dxb [n, c_b, hw] or NULL.
+ * fgmm_hidden_wgrad: xa [n, c_a, hw] or NULL (absent), xb [n, c_b, hw] (may be NULL when dweight is); dweight device float32
+ *   [c_out, c_a + c_b] or NULL, dbias [c_out] or NULL.  workspace: device memory of at least fgmm_hidden_wgrad_workspace(...) BYTES (S
+ *   partial copies of [c_out, c_a + c_b + 1] float32; 0 for sizes that are refused, n == 0 or hw == 0), aligned to 16 bytes, the call's
+ *   own until the work enqueued by it has run.
+ * The gradient calls refuse what fgmm_hidden_apply refuses, and: n * hw beyond 2^31; both outputs NULL with n > 0; dxa (or, in wgrad,
+ * xa) for a layer with c_a == 0; a workspace that is NULL, too small or not 16-byte aligned; FGMM_ACT_LEAKY with slope < 0.  n == 0 or
+ * hw == 0: success, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FGMM_HAS_HIDDEN_GRAD 1 /* section 2d (added without a bump, as 3b - 5c) */
+size_t fgmm_hidden_packed_floats(int c_out, int c_a, int c_b);
+int fgmm_hidden_pack(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_a, int c_b, int transposed,
+                     float *packed);
+int fgmm_hidden_apply_packed(fgmm_ctx *ctx, void *stream, const float *packed, int c_out, int c_a, int c_b, int act, float slope,
+                             const float *xa, const float *xb, float *out, int n, int64_t hw);
+int fgmm_hidden_dgrad(fgmm_ctx *ctx, void *stream, const float *packed_t, int c_out, int c_a, int c_b, int act, float slope, const float *gy,
+                      const float *out, float *dxa, float *dxb, int n, int64_t hw);
+size_t fgmm_hidden_wgrad_workspace(int c_out, int c_a, int c_b, int has_xa, int n, int64_t hw);
+int fgmm_hidden_wgrad(fgmm_ctx *ctx, void *stream, const float *xa, const float *xb, const float *gy, const float *out, int c_out, int c_a,
+                      int c_b, int act, float slope, int n, int64_t hw, float *dweight, float *dbias, void *workspace,
+                      size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------------------
  * 3. Building blocks ("same tables => same bytes" surfaces; also what the parity tests probe).
  *    SURVEY.md section 8(b) also lists fgmm_build_symtab_host / fgmm_build_cdftab_host: they do not exist on purpose —
  *    this library has no CPU implementation of the float work; the GPU builders below are the only ones.
