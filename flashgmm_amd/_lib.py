@@ -295,6 +295,10 @@ SIGNATURES = {
     "fgmm_ckbd_ctx_apply_packed": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i64, _i64, _i]),
     "fgmm_ckbd_ctx_wgrad_workspace": (_sz, [_i, _i, _i, _i64, _i64]),
     "fgmm_ckbd_ctx_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i64, _i64, _i, _p, _p, _p, _sz]),
+    # section 5d: (ctx, stream, weight, bias, c_out, c_in, k, act, slope, shuffle, out); (handle); (ctx, stream, handle, x, x_item_stride, out, n, h, w)
+    "fgmm_conv_create": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _pp]),
+    "fgmm_conv_destroy": (None, [_p]),
+    "fgmm_conv_apply": (_i, [_p, _p, _p, _p, _i64, _p, _i, _i, _i]),
 }
 FGMM_ACT_NONE, FGMM_ACT_LEAKY, FGMM_ACT_RELU = 0, 1, 2  # section 2c: fgmm_hidden_create's activations
 FGMM_HIDDEN_BF16X6 = 1  # section 2c: fgmm_hidden_create_ex's flag

@@ -308,6 +308,31 @@ int hidden_wgrad_tiles(int64_t S, int n_col, int c_out);
 int launch_hidden_wgrad(const HiddenWgradArgs &args, void *stream);
 int launch_hidden_wgrad_finish(const float *partial, int c_a, int c_b, int c_out, bool has_xa, int S, float *dweight_or_null, float *dbias_or_null, void *stream);
 
+// ---- dense 3x3 / 5x5 convolutions on the matrix cores (fgmm_conv.hip; header section 5d) --------------------------
+constexpr int kConvCB = 8;                // input channels per chunk of the K loop: 8 k^2 K entries, whole groups of four k-pairs
+constexpr int kConvPR = 8, kConvPC = 16;  // a block's 128 positions: a patch of 8 rows x 16 columns
+static inline int conv_row_tiles(int c_out) { return ((c_out + 31) / 32 + 3) / 4 * 4; } // of 32 rows, padded to the tallest block (4)
+static inline int conv_chunks(int c_in) { return (c_in + kConvCB - 1) / kConvCB; }
+static inline size_t conv_packed_floats(int c_out, int c_in, int k) { // [n_rt][chunks][32][8 k^2] weights, then [n_rt][32] bias
+  const size_t n_rt = (size_t)conv_row_tiles(c_out);
+  return n_rt * (size_t)conv_chunks(c_in) * 32 * kConvCB * k * k + n_rt * 32;
+}
+struct ConvArgs {       // one launch, by value: items of one size
+  const float *x;       // device: item i's [c_in, h, w] at x + i * x_item_stride
+  float *out;           // device [n, c_out, h, w], or - shuffle 2 - [n, c_out / 4, 2 h, 2 w]
+  const float *wp, *bp; // the packed weights and bias
+  int64_t x_item_stride;
+  int32_t c_in, c_out, h, w;
+  int32_t n_ch;         // chunks of kConvCB input channels
+  int32_t ph, pw;       // patches per item: ceil(h / 8) x ceil(w / 16)
+  int32_t act, shuffle; // FGMM_ACT_*; 1 | 2
+  float slope;
+};
+// w: device [c_out, c_in, k, k], k = 3 | 5
+int launch_conv_pack(const float *w, const float *bias_or_null, int c_out, int c_in, int k, float *wp, float *bp, void *stream);
+// the row tiles per block: 4, 2 or 1 by ckbd_row_tiles_go's rule; blocks = n * patches * ceil(ceil(c_out / 32) / that)
+int launch_conv(const ConvArgs &args, int k, int64_t n, void *stream);
+
 // ---- GPU-side decode of CHECKPOINTED bitstreams (segdec_kernel): one wave per segment ---------------------------
 struct SegDesc {
   const void *scales, *means, *weights; // float32, float16 or bfloat16 planes

@@ -29,7 +29,7 @@ from torch import Tensor
 
 from . import _boundary, _lib
 
-__all__ = ["GaussianMixtureConditional", "EntropyBottleneck", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ParameterBody", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve", "update_entropy_models", "aux_loss"]
+__all__ = ["GaussianMixtureConditional", "EntropyBottleneck", "EntropyBottleneckCoder", "CheckpointedBytes", "CompressedBatch", "ConvStack", "ParameterBody", "ParameterHead", "RateEstimate", "RdoQuantized", "RdoSkipQuantized", "BudgetQuantized", "RdCurve", "update_entropy_models", "aux_loss"]
 
 CKPT_DTYPE = np.dtype([("x", "<u8"), ("pos", "<u8")])  # fgmm_ckpt
 
@@ -584,6 +584,99 @@ class ParameterBody:
             _lib.check(L.fgmm_hidden_apply_ws(cx, stream, hd, None if xa is None else xa.data_ptr(), x.data_ptr(), out.data_ptr(), N, h * w,
                                               ws.data_ptr() if need else None, need), "ParameterBody.features")
             xa, x = None, out
+        return x
+
+
+class ConvStack:
+    """A stack of dense 3x3 / 5x5 convolution layers - the reference's hyper-synthesis ``h_s`` of the checkerboard GMM model
+    (compressai/models/ckbd_gmm.py:97-107) or one module of ELIC's channel context (models/elic_gmm.py:151-164) - on the matrix cores in
+    ONE fixed summation order (include/flashgmm_amd.h section 5d: bit for bit an ``fmaf`` chain, channel outer, tap inner, then the
+    library's own activation sequence), one launch per layer with activation and ``PixelShuffle(2)`` folded into its store:
+
+        stack = ConvStack(h_s)                 # Conv2d | Sequential(Conv2d, PixelShuffle(2)) [+ LeakyReLU | ReLU] ..., on the GPU
+        params = stack(z_hat)                  # [N, c_in, h, w] -> [N, c_out, h', w'] float32
+        ctx = ConvStack(channel_context_k)(y_hat, channels=c_k)    # the first c_k channels of y_hat, without a slice's copy
+
+    The weights are packed once, here.  Not MIOpen's last bits: encoder and decoder must both use it.  No gradients."""
+
+    @staticmethod
+    def check(modules):
+        """-> [(conv, FGMM_ACT_*, slope, shuffle)], one per layer; ValueError naming the first module that does not fit the pattern"""
+        layers = []
+        bare = False  # the last layer has no activation yet
+        for m in modules:
+            conv, shuffle = m, 1
+            if isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[0], nn.Conv2d) and isinstance(m[1], nn.PixelShuffle):
+                if m[1].upscale_factor != 2:
+                    raise ValueError(f"ConvStack: only PixelShuffle(2) is taken: {m}")
+                conv, shuffle = m[0], 2
+            if isinstance(conv, nn.Conv2d):
+                k = conv.kernel_size[0]
+                if (conv.kernel_size not in ((3, 3), (5, 5)) or conv.stride != (1, 1) or conv.padding != (k // 2, k // 2) or conv.dilation != (1, 1)
+                        or conv.groups != 1 or conv.padding_mode != "zeros"):
+                    raise ValueError(f"ConvStack: not a plain 3x3 or 5x5 convolution with stride 1 and padding k // 2: {conv}")
+                if shuffle == 2 and conv.out_channels % 4:
+                    raise ValueError(f"ConvStack: PixelShuffle(2) needs a multiple of 4 output channels: {m}")
+                layers.append((conv, _lib.FGMM_ACT_NONE, 0.0, shuffle))
+                bare = True
+            elif isinstance(m, (nn.LeakyReLU, nn.ReLU)) and bare:
+                slope = float(getattr(m, "negative_slope", 0.0))
+                if slope != slope or slope in (float("inf"), float("-inf")):
+                    raise ValueError(f"ConvStack: the slope is not finite: {m}")
+                layers[-1] = (layers[-1][0], _lib.FGMM_ACT_LEAKY if isinstance(m, nn.LeakyReLU) else _lib.FGMM_ACT_RELU, slope, layers[-1][3])
+                bare = False
+            else:
+                raise ValueError("ConvStack: expected a 3x3 / 5x5 nn.Conv2d or nn.Sequential(nn.Conv2d, nn.PixelShuffle(2)), optionally followed by "
+                                 f"nn.LeakyReLU or nn.ReLU, got {m}")
+        if not layers:
+            raise ValueError("ConvStack: no convolution")
+        for a, b in zip(layers, layers[1:]):
+            if b[0].in_channels * a[3] ** 2 != a[0].out_channels:
+                raise ValueError(f"ConvStack: {b[0]} does not take the {a[0].out_channels // a[3] ** 2} channels of the layer before it")
+        return layers
+
+    def __init__(self, modules):
+        layers = self.check(list(modules))
+        w0 = layers[0][0].weight
+        if not w0.is_cuda:
+            raise RuntimeError("ConvStack: expected modules on a HIP device (there is no CPU implementation)")
+        self.device = w0.device
+        self._dev = w0.device.index if w0.device.index is not None else -1
+        self.c_in = layers[0][0].in_channels
+        self._h: List[Tuple[C.c_void_p, int, int, int]] = []  # (handle, the layer's input channels, output channels, shuffle)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        for conv, act, slope, shuffle in layers:
+            w = conv.weight.detach().to(torch.float32).contiguous()
+            b = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
+            out = C.c_void_p()
+            _lib.check(_lib.lib().fgmm_conv_create(_lib.ctx(self._dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, conv.out_channels,
+                                                   conv.in_channels, conv.kernel_size[0], act, slope, shuffle, C.byref(out)), "ConvStack")
+            self._h.append((out, conv.in_channels, conv.out_channels, shuffle))
+
+    def __del__(self):
+        hs, self._h = getattr(self, "_h", None) or [], []
+        for h, *_ in hs:
+            try:
+                _lib.lib().fgmm_conv_destroy(h)
+            except Exception:  # pragma: no cover - interpreter shutdown
+                pass
+
+    def __call__(self, x: Tensor, channels: Optional[int] = None) -> Tensor:
+        """-> what the modules give for ``x`` (``channels``: for ``x[:, :channels]``, read in place through the item stride), float32, in
+        the library's order.  The layers run back to back on the current stream."""
+        c = x.shape[1] if channels is None and x.dim() == 4 else channels
+        if x.dim() != 4 or c != self.c_in or x.shape[1] < c or x.device != self.device:
+            raise RuntimeError(f"x must be [N, >= {self.c_in}, h, w] on {self.device} with channels = {self.c_in}; got {tuple(x.shape)}, channels = {c} on {x.device}")
+        x = x.to(torch.float32).contiguous()
+        N, C_all, h, w = x.shape
+        L, cx, stream = _lib.lib(), _lib.ctx(self._dev), torch.cuda.current_stream(self.device).cuda_stream
+        stride = C_all * h * w
+        for hd, _, c_out, shuffle in self._h:
+            out = torch.empty((N, c_out // shuffle ** 2, h * shuffle, w * shuffle), dtype=torch.float32, device=self.device)
+            if N and h * w:
+                _lib.check(L.fgmm_conv_apply(cx, stream, hd, x.data_ptr(), stride, out.data_ptr(), N, h, w), "ConvStack")
+            x, (_, C_all, h, w) = out, out.shape
+            stride = C_all * h * w
         return x
 
 

@@ -31,7 +31,7 @@ from torch import Tensor
 
 from itertools import accumulate
 
-from .entropy_models import EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterBody, ParameterHead
+from .entropy_models import ConvStack, EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterBody, ParameterHead
 from . import _lib
 from .ops import CheckerboardContext, checkerboard_context, ckbd_embed, ckbd_unembed, pointwise_layer
 
@@ -689,17 +689,34 @@ class CheckerboardLatentCodec(nn.Module):
         return {"likelihoods": {"y": y_out["likelihoods"]["y"]}, "y_hat": y_hat}
 
 
+def _cached_stack(cache: Dict[int, Tuple[Any, ConvStack]], slot: int, modules: nn.Module) -> ConvStack:
+    """the ConvStack of ``modules``, packed once and again when a weight or bias has changed (``_head_parts``' key, every layer's)"""
+    key = tuple((p.data_ptr(), p._version) for p in modules.parameters())
+    if slot not in cache or cache[slot][0] != key:
+        cache[slot] = (key, ConvStack(modules))
+    return cache[slot][1]
+
+
 class ChannelGroupsLatentCodec(nn.Module):
     """Channel groups coded one after the other, each conditioned on the previous ones (channel_groups.py:111-158);
     ``latent_codec[f"y{k}"]`` is typically a ``CheckerboardLatentCodec`` (models/elic_gmm.py:198-219)."""
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None,
-                 channel_context: Optional[Dict[str, nn.Module]] = None, *, groups: List[int], **kwargs: Any):
+                 channel_context: Optional[Dict[str, nn.Module]] = None, *, groups: List[int], fuse_channel_context: bool = False, **kwargs: Any):
         super().__init__()
         self.groups = list(groups)
         self.groups_acc = list(accumulate(self.groups, initial=0))
         self.channel_context = nn.ModuleDict(channel_context)
         self.latent_codec = nn.ModuleDict(latent_codec)
+        # fuse_channel_context: group k's channel_context module - three 5x5 convolutions with ReLU, models/elic_gmm.py:151-164 - runs inside
+        # the library (flashgmm_amd.ConvStack, header section 5d: one launch per layer on the matrix cores in ONE summation order) over the
+        # first groups_acc[k] channels of the one full-size y_hat tensor compress / decompress hold: no merge_y.  It changes the last bits
+        # of the parameters: encoder and decoder must agree on this switch.  forward() keeps the torch modules (no gradients).
+        self.fuse_channel_context = bool(fuse_channel_context)
+        self._cc_stacks: Dict[int, Tuple[Any, ConvStack]] = {}
+        if self.fuse_channel_context:
+            for m in self.channel_context.values():
+                ConvStack.check(m)
 
     def __getitem__(self, key: str) -> nn.Module:
         return self.latent_codec[key]
@@ -710,11 +727,14 @@ class ChannelGroupsLatentCodec(nn.Module):
     def merge_params(self, *args: Tensor) -> Tensor:
         return torch.cat(args, dim=1)
 
-    def _get_ctx_params(self, k: int, side_params: Tensor, y_hat_: Tuple[Tensor, ...]) -> Tensor:
+    def _get_ctx_params(self, k: int, side_params: Tensor, y_hat_: Tuple[Tensor, ...], y_hat: Optional[Tensor] = None) -> Tensor:
         """parameters group k is coded under: the side parameters, preceded (k > 0) by the channel context computed
-        from the reconstructions of groups 0..k-1 (channel_groups.py:166-173)"""
+        from the reconstructions of groups 0..k-1 (channel_groups.py:166-173).  ``y_hat``: the full-size tensor ``y_hat_`` are the
+        views of - with ``fuse_channel_context`` the context is the library's, read from its first ``groups_acc[k]`` channels"""
         if k == 0:
             return side_params
+        if self.fuse_channel_context and y_hat is not None:
+            return self.merge_params(_cached_stack(self._cc_stacks, k, self.channel_context[f"y{k}"])(y_hat, channels=self.groups_acc[k]), side_params)
         return self.merge_params(self.channel_context[f"y{k}"](self.merge_y(*y_hat_[:k])), side_params)
 
     def _run(self, y_hat: Tensor, side_params: Tensor, code_group):
@@ -723,7 +743,7 @@ class ChannelGroupsLatentCodec(nn.Module):
         views = y_hat.split(self.groups, dim=1)
         results = []
         for k in range(len(self.groups)):
-            res = code_group(k, self._get_ctx_params(k, side_params, views))
+            res = code_group(k, self._get_ctx_params(k, side_params, views, y_hat))
             views[k].copy_(res["y_hat"])
             results.append(res)
         return results
@@ -752,7 +772,7 @@ class ChannelGroupsLatentCodec(nn.Module):
             views = y_hat.split(self.groups, dim=1)
             prepared, hats = [], []
             for k, c in enumerate(codecs):
-                pk, hk = c.prepare(parts[k], self._get_ctx_params(k, side_params, views))
+                pk, hk = c.prepare(parts[k], self._get_ctx_params(k, side_params, views, y_hat))
                 views[k].copy_(hk)
                 prepared.append(pk)
                 hats.append(hk)
@@ -781,7 +801,7 @@ class ChannelGroupsLatentCodec(nn.Module):
             views = y_hat.split(self.groups, dim=1)
             prepared, hats = [], []
             for k, c in enumerate(codecs):
-                pk, hk = c.prepare(parts[k], self._get_ctx_params(k, sp, views))
+                pk, hk = c.prepare(parts[k], self._get_ctx_params(k, sp, views, y_hat))
                 views[k].copy_(hk)
                 prepared.append(pk)
                 hats.append(hk)
@@ -809,7 +829,7 @@ class ChannelGroupsLatentCodec(nn.Module):
         recs = []  # per group, per image: the group codec's "y_rec" or None
         for k in range(len(self.groups)):
             codec = self.latent_codec[f"y{k}"]
-            params = [self._get_ctx_params(k, sp, v) for sp, v in zip(side_params, views)]
+            params = [self._get_ctx_params(k, sp, v, yh) for sp, v, yh in zip(side_params, views, y_hats)]
             sub = [st[per_group * k: per_group * (k + 1)] for st in strings]
             if hasattr(codec, "decompress_many"):
                 outs = codec.decompress_many(sub, shape[k], params)
@@ -856,13 +876,23 @@ class HyperLatentCodec(nn.Module):
     ``flashgmm_amd.EntropyBottleneckCoder`` (built from the tables of a trained ``EntropyBottleneck``), or the reference's own class."""
 
     def __init__(self, entropy_bottleneck=None, h_a: Optional[nn.Module] = None, h_s: Optional[nn.Module] = None,
-                 quantizer: str = "noise", **kwargs: Any):
+                 quantizer: str = "noise", fuse_h_s: bool = False, **kwargs: Any):
         super().__init__()
         assert entropy_bottleneck is not None
         self.entropy_bottleneck = entropy_bottleneck
         self.h_a = h_a or nn.Identity()
         self.h_s = h_s or nn.Identity()
         self.quantizer = quantizer
+        # fuse_h_s: compress() and decompress() compute the side parameters inside the library (flashgmm_amd.ConvStack, header section
+        # 5d: the 3x3 layers of models/ckbd_gmm.py:97-107, PixelShuffle(2) folded into the store, in ONE summation order).  It changes
+        # the last bits of the parameters: encoder and decoder must agree on this switch.  ELIC's h_s (transposed convolutions) is refused.
+        self.fuse_h_s = bool(fuse_h_s)
+        self._h_s_stack: Dict[int, Tuple[Any, ConvStack]] = {}
+        if self.fuse_h_s:
+            ConvStack.check(self.h_s)
+
+    def _side_params(self, z_hat: Tensor) -> Tensor:
+        return _cached_stack(self._h_s_stack, 0, self.h_s)(z_hat) if self.fuse_h_s else self.h_s(z_hat)
 
     def compress(self, y: Tensor) -> Dict[str, Any]:  # hyper.py:94-100
         z = self.h_a(y)
@@ -877,16 +907,17 @@ class HyperLatentCodec(nn.Module):
         else:  # any other entropy bottleneck with the reference's contract
             z_strings = eb.compress(z)
             z_hat = eb.decompress(z_strings, shape)
-        return {"strings": [z_strings], "shape": shape, "params": self.h_s(z_hat)}
+        return {"strings": [z_strings], "shape": shape, "params": self._side_params(z_hat)}
 
     def decompress(self, strings: List[List[bytes]], shape: Tuple[int, int], **kwargs: Any) -> Dict[str, Any]:  # hyper.py:102-108
         (z_strings,) = strings
         z_hat = self.entropy_bottleneck.decompress(z_strings, shape)
-        return {"params": self.h_s(z_hat)}
+        return {"params": self._side_params(z_hat)}
 
     def forward(self, y: Tensor) -> Dict[str, Any]:  # hyper.py:87-94
         """-> ``{"likelihoods": {"z": ...}, "params": h_s(z_hat)}``; ``entropy_bottleneck`` is ``flashgmm_amd.EntropyBottleneck`` (its
-        density on the GPU, include/flashgmm_amd.h section 3j) or anything callable as the reference's class"""
+        density on the GPU, include/flashgmm_amd.h section 3j) or anything callable as the reference's class.  ``h_s`` is the torch
+        module here whatever ``fuse_h_s`` says: the library's convolution has no gradients"""
         z = self.h_a(y)
         z_hat, z_likelihoods = self.entropy_bottleneck(z)
         if self.quantizer == "ste":

@@ -1330,6 +1330,49 @@ size_t fgmm_ckbd_ctx_wgrad_workspace(int M, int C_out, int n, int64_t h, int64_t
 int fgmm_ckbd_ctx_wgrad(fgmm_ctx *ctx, void *stream, const float *anchors, const float *g, int M, int C_out, int n, int64_t h, int64_t w,
                         int anchor_odd, float *dweight, float *dbias, void *workspace, size_t workspace_bytes);
 
+/* ---- section 5d. DENSE 3x3 / 5x5 CONVOLUTIONS on the matrix cores, in one fixed order -------------------------------------------------
+ *    The convolutions the decode-side parameter path still took from MIOpen: the hyper-synthesis h_s of the checkerboard GMM model
+ *    (compressai/models/ckbd_gmm.py:97-107: five 3x3 layers, two of them followed by PixelShuffle(2)), whose output is the side
+ *    parameters, and ELIC's channel context (models/elic_gmm.py:151-164: three 5x5 layers with ReLU), which runs over the decoded groups.
+ *    A last-bit difference in either changes scales / means / weights, the tables and the decoded symbols - the reason of section 2b.
+ *    Strided and transposed convolutions (ELIC's own h_s, h_a) are not covered.
+ *    One layer is Conv2d(c_in, c_out, k, stride=1, padding=k/2), k = 3 | 5, an activation of section 2c, and a plain or PixelShuffle(2)
+ *    store.  Per item i of n, output channel o and position (r, q) of h x w, on v_mfma_f32_32x32x2_f32, bit for bit - signs of zero,
+ *    infinities and NaN included - the chain
+ *        acc = bias[o] (+0 without a bias)
+ *        for c = 0 .. c_in-1 ascending:
+ *          for t = 0 .. k*k-1 ascending (the taps row-major, t = a*k + b):
+ *            x = input[i][c][r + a - k/2][q + b - k/2] inside the image, else +0
+ *            acc = fmaf(weight[o][c][a][b], x, acc)
+ *        v = act(acc)                                                     (FGMM_ACT_*, the sequences of section 2c)
+ *        shuffle 1:  out[i][o][r][q] = v
+ *        shuffle 2:  out[i][o >> 2][2r + ((o >> 1) & 1)][2q + (o & 1)] = v      (PixelShuffle(2); c_out % 4 == 0)
+ *    The K order is weight.reshape(c_out, c_in*k*k) as torch stores it - channel outer, tap inner: NOT section 5b's tap-major order.  A
+ *    tap outside the image is a +0 TERM of the chain (as in 5b): an infinite weight there gives NaN.  An activation after the shuffle is
+ *    element-wise, so Sequential(Conv2d, PixelShuffle(2)) followed by LeakyReLU is one layer.  The result is NOT MIOpen's in its last bits.
+ *    Block heights: a workgroup computes T tiles of 32 output channels x an 8 x 16 patch of positions, T from the ladder 4, 2, 1.  The
+ *    rule, with B(T) = n * ceil(h / 8) * ceil(w / 16) * ceil(ceil(c_out / 32) / T) workgroups: the first T of 4, 2, 1 with B(T) >= 256;
+ *    T = 1 when none has.  Every height gives the same bits: an output's chain depends on neither T, nor n, nor the item's place in a
+ *    batch, nor the patch it falls in - an encoder's batch and a decoder's single image agree.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FGMM_HAS_CONV 1 /* section 5d: fgmm_conv_create, fgmm_conv_destroy, fgmm_conv_apply (added without a bump, as 3b - 5c) */
+typedef struct fgmm_conv fgmm_conv; /* one layer's weights, packed for the kernel, on the context's device.  Immutable once created: usable
+                                     * from any context on its device, from several at the same time */
+/* weight: device float32 [c_out, c_in, k, k]; bias: device float32 [c_out] or NULL.  The weights are copied (packed) before the call
+ * returns.  Refused (FGMM_ERR_INVALID, *out NULL): k not 3 or 5, c_out < 1, c_in < 1, an act that is none of the three, a slope that is
+ * not finite, shuffle not 1 or 2, shuffle 2 with c_out % 4 != 0. */
+int fgmm_conv_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_in, int k, int act, float slope,
+                     int shuffle, fgmm_conv **out);
+void fgmm_conv_destroy(fgmm_conv *conv);
+/* x: device float32, item i's [c_in, h, w] at x + i * x_item_stride (floats; >= c_in*h*w - more when the input is the first c_in
+ * channels of a larger [n, C, h, w] tensor: the channels beyond are never read); out: device float32, dense - [n, c_out, h, w], or
+ * [n, c_out/4, 2h, 2w] with shuffle 2.  STREAM-ORDERED, like fgmm_hidden_apply (section 2c): ONE kernel enqueued on `stream`, no
+ * workspace, no context lock, no host wait; the same rules for x and `out` as there.  Refused, launching and writing nothing: n, h or w
+ * negative, a NULL x or out, a stride below c_in*h*w, h*w beyond 2^29, sizes whose grid would exceed 2^30 workgroups.  n*h*w == 0:
+ * success, no launch. */
+int fgmm_conv_apply(fgmm_ctx *ctx, void *stream, const fgmm_conv *conv, const float *x, int64_t x_item_stride, float *out, int n, int h,
+                    int w);
+
 /* compressai._CXX.pmf_to_quantized_cdf (compressai/cpp_exts/ops/ops.cpp:40-109): cdf_out has n + 1 entries */
 int fgmm_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *cdf_out);
 

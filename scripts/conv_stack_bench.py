@@ -1,0 +1,84 @@
+"""The dense convolution layers of header section 5d, measured (profiles/conv_stack.md): ConvStack (fgmm_conv.hip: one launch per layer,
+activation and PixelShuffle(2) folded into the store) against the torch modules it replaces (MIOpen, warmed) on
+  - the checkerboard GMM model's h_s (N = 192, M = 320: five 3x3 layers, two with PixelShuffle(2)) on z_hat [24, 192, 8, 12] and [1, 192, 8, 12];
+  - ELIC's last channel-context module (three 5x5 layers, 128 -> 224 -> 128 -> 384, ReLU) on [1, 128, 135, 240].
+
+GPU time by device events on the current stream: a sample is `inner` back-to-back calls between two events, divided by `inner`; the two
+paths alternate sample by sample in one process; the median and the minimum of `samples` samples after `warm` warm-up samples of each.
+The share of the f32 MFMA roof (157.3 TF, as profiles/r06_head_kernel.md) counts the multiply-adds the definition needs,
+2 * c_out * c_in * k^2 per position and layer.  Needs a GPU: fails without one.
+usage: python scripts/conv_stack_bench.py [samples=20] [inner=5] [warm=3]"""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+from torch import nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from flashgmm_amd import ConvStack  # noqa: E402
+
+samples = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+inner = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+warm = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+ROOF_TF = 157.3
+assert torch.cuda.is_available(), "scripts/conv_stack_bench.py needs a GPU"
+dev = "cuda:0"
+torch.manual_seed(1)
+conv3, conv5 = lambda i, o: nn.Conv2d(i, o, 3, padding=1), lambda i, o: nn.Conv2d(i, o, 5, padding=2)
+subpel = lambda i, o: nn.Sequential(nn.Conv2d(i, o * 4, 3, padding=1), nn.PixelShuffle(2))
+N_, M_ = 192, 320
+h_s = nn.Sequential(conv3(N_, M_), nn.LeakyReLU(), subpel(M_, M_), nn.LeakyReLU(), conv3(M_, M_ * 3 // 2), nn.LeakyReLU(), subpel(M_ * 3 // 2, M_ * 3 // 2),
+                    nn.LeakyReLU(), conv3(M_ * 3 // 2, M_ * 2)).to(dev)
+cc = nn.Sequential(conv5(128, 224), nn.ReLU(), conv5(224, 128), nn.ReLU(), conv5(128, 384)).to(dev)
+
+
+def sample(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        r = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / inner, r
+
+
+def flops(net, x):
+    """multiply-adds x 2 of every convolution of net on x, by the shapes"""
+    total, hooks = [0.0], []
+    for m in net.modules():
+        if isinstance(m, nn.Conv2d):
+            hooks.append(m.register_forward_hook(lambda m, i, o: total.__setitem__(0, total[0] + 2.0 * o.numel() * m.in_channels * m.kernel_size[0] ** 2)))
+    with torch.no_grad():
+        net(x)
+    for hk in hooks:
+        hk.remove()
+    return total[0]
+
+
+out = {"compute_units": torch.cuda.get_device_properties(0).multi_processor_count, "samples": samples, "calls_per_sample": inner, "warmup_samples": warm,
+       "roof_tf": ROOF_TF}
+for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1, N_, 8, 12)), ("channel_context", cc, (1, 128, 135, 240))):
+    x, op = torch.randn(shape, device=dev), ConvStack(net)
+
+    def torch_path():
+        with torch.no_grad():
+            return net(x)
+
+    paths = {"kernel": lambda: op(x), "torch": torch_path}
+    for _ in range(warm):
+        for fn in paths.values():
+            sample(fn)
+    t = {k: [] for k in paths}
+    for _ in range(samples):
+        for k, fn in paths.items():
+            t[k].append(sample(fn)[0])
+    res = {k: {"median_ms": round(float(np.median(v)), 5), "min_ms": round(float(np.min(v)), 5)} for k, v in t.items()}
+    res["gflop"] = round(flops(net, x) / 1e9, 3)
+    res["kernel"]["frac_of_roof"] = round(res["gflop"] / res["kernel"]["median_ms"] / ROOF_TF, 4)
+    res["kernel_over_torch"] = round(res["kernel"]["median_ms"] / res["torch"]["median_ms"], 4)
+    res["max_abs_diff_to_torch"] = float((torch_path() - op(x)).abs().max())
+    out[name] = res
+print(json.dumps(out))
