@@ -299,6 +299,8 @@ SIGNATURES = {
     "fgmm_conv_create": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _pp]),
     "fgmm_conv_destroy": (None, [_p]),
     "fgmm_conv_apply": (_i, [_p, _p, _p, _p, _i64, _p, _i, _i, _i]),
+    # section 5e: (ctx, stream, weight, bias, c_in, c_out, k, stride, act, slope, out) -> a handle of section 5d's
+    "fgmm_conv_create_transposed": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _pp]),
 }
 FGMM_ACT_NONE, FGMM_ACT_LEAKY, FGMM_ACT_RELU = 0, 1, 2  # section 2c: fgmm_hidden_create's activations
 FGMM_HIDDEN_BF16X6 = 1  # section 2c: fgmm_hidden_create_ex's flag

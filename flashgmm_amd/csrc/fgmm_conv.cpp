@@ -1,7 +1,8 @@
 // fgmm_conv.cpp — the entry points of the dense 3x3 / 5x5 convolution layers (include/flashgmm_amd.h section 5d) over fgmm_conv.hip: a
 // handle that owns one layer's packed weights (immutable once made, like a hidden layer's) and a STREAM-ORDERED apply - validation, one
 // launch, no workspace, no lock, no wait.  A file of its own: the host sources that build against the fake device reference no launcher
-// of these.
+// of these.  The transposed layers of section 5e (fgmm_conv_create_transposed) are the same handle: stride 1 on fgmm_conv.hip's kernel
+// over the flipped pack, stride 2 on fgmm_deconv.hip; apply dispatches on the handle.
 #include "fgmm_ctx.h"
 
 using namespace fgmm;
@@ -9,14 +10,14 @@ using namespace fgmm;
 struct fgmm_conv {
   int device = 0;
   int c_out = 0, c_in = 0, k = 0, act = 0, shuffle = 1;
+  int stride = 0; // 0: a Conv2d layer (section 5d); 1 | 2: a ConvTranspose2d layer of that stride (section 5e)
   float slope = 0.0f;
   float *packed = nullptr; // [wp | bp]
 };
 
-extern "C" {
-
-int fgmm_conv_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_in, int k, int act, float slope, int shuffle,
-                     fgmm_conv **out) {
+// both create calls: stride 0 = Conv2d, weight [c_out, c_in, k, k]; 1 | 2 = ConvTranspose2d, weight [c_in, c_out, k, k]
+static int conv_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_in, int k, int stride, int act, float slope,
+                       int shuffle, fgmm_conv **out) {
   if (!out) return fail(FGMM_ERR_INVALID, "out == NULL");
   *out = nullptr;
   if (!ctx || !weight) return fail(FGMM_ERR_INVALID, "convolution: null context or weights");
@@ -33,7 +34,7 @@ int fgmm_conv_create(fgmm_ctx *ctx, void *stream, const float *weight, const flo
   if (!g.ok) return fail(FGMM_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   fgmm_conv *c = new (std::nothrow) fgmm_conv;
   if (!c) return fail(FGMM_ERR_NOMEM, "convolution");
-  c->device = ctx->device, c->c_out = c_out, c->c_in = c_in, c->k = k, c->act = act, c->slope = slope, c->shuffle = shuffle;
+  c->device = ctx->device, c->c_out = c_out, c->c_in = c_in, c->k = k, c->act = act, c->slope = slope, c->shuffle = shuffle, c->stride = stride;
   const size_t floats = conv_packed_floats(c_out, c_in, k), bias_floats = (size_t)conv_row_tiles(c_out) * 32;
   void *p = nullptr;
   if (dev::malloc_device(&p, floats * sizeof(float)) != 0) {
@@ -41,7 +42,9 @@ int fgmm_conv_create(fgmm_ctx *ctx, void *stream, const float *weight, const flo
     return fail(FGMM_ERR_NOMEM, "%zu bytes of device memory for the packed weights", floats * sizeof(float));
   }
   c->packed = static_cast<float *>(p);
-  int e = launch_conv_pack(weight, bias, c_out, c_in, k, c->packed, c->packed + (floats - bias_floats), stream);
+  float *bp = c->packed + (floats - bias_floats);
+  int e = stride == 2 ? launch_deconv_pack(weight, bias, c_out, c_in, k, c->packed, bp, stream)
+                      : launch_conv_pack(weight, bias, c_out, c_in, k, stride == 1, c->packed, bp, stream);
   if (!e) e = dev::stream_sync((dev::Stream)stream); // (the caller may free or overwrite its weights on return)
   if (e) {
     (void)dev::free_device(p);
@@ -50,6 +53,20 @@ int fgmm_conv_create(fgmm_ctx *ctx, void *stream, const float *weight, const flo
   }
   *out = c;
   return FGMM_OK;
+}
+
+extern "C" {
+
+int fgmm_conv_create(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_in, int k, int act, float slope, int shuffle,
+                     fgmm_conv **out) {
+  return conv_create(ctx, stream, weight, bias, c_out, c_in, k, 0, act, slope, shuffle, out);
+}
+
+int fgmm_conv_create_transposed(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_in, int c_out, int k, int stride, int act,
+                                float slope, fgmm_conv **out) {
+  if (out) *out = nullptr;
+  if (stride != 1 && stride != 2) return fail(FGMM_ERR_INVALID, "transposed convolution: stride = %d (1 or 2)", stride);
+  return conv_create(ctx, stream, weight, bias, c_out, c_in, k, stride, act, slope, 1, out);
 }
 
 void fgmm_conv_destroy(fgmm_conv *c) {
@@ -85,6 +102,10 @@ int fgmm_conv_apply(fgmm_ctx *ctx, void *stream, const fgmm_conv *c, const float
   a.wp = c->packed, a.bp = c->packed + (conv_packed_floats(c->c_out, c->c_in, c->k) - (size_t)conv_row_tiles(c->c_out) * 32);
   a.c_in = c->c_in, a.c_out = c->c_out, a.h = h, a.w = w, a.n_ch = conv_chunks(c->c_in), a.ph = (int32_t)ph, a.pw = (int32_t)pw;
   a.act = c->act, a.shuffle = c->shuffle, a.slope = c->slope;
+  if (c->stride == 2) { // out [n, c_out, 2 h, 2 w]: its plane's 4 h w positions are within the limit above
+    LAUNCH_TRY(launch_deconv(a, c->k, n, stream));
+    return FGMM_OK;
+  }
   LAUNCH_TRY(launch_conv(a, c->k, n, stream));
   return FGMM_OK;
 }

@@ -61,8 +61,9 @@ template <int K> struct ConvGeom {
 
 // packed weights: [n_rt row tiles][n_ch chunks][32 rows][KC columns], then the bias [n_rt][32].  Column 8 g + 4 h + e of a row holds K
 // entry kappa = 8 g + 2 e + h of the chunk - mfma32_pack_col's order within a group of four k-pairs: a lane's 16-byte read is its half's
-// four.  kappa = c k^2 + t: channel CB ch + c, tap t.  Padding (rows past c_out, channels past c_in): +0
-template <int K>
+// four.  kappa = c k^2 + t: channel CB ch + c, tap t.  Padding (rows past c_out, channels past c_in): +0.  TR (section 5e, stride 1): w is
+// a ConvTranspose2d's [c_in, c_out, k, k], and tap t of the chain is its flipped tap k^2 - 1 - t = (k - 1 - a, k - 1 - b)
+template <int K, bool TR>
 __global__ __launch_bounds__(256) void conv_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, int c_out, int c_in, int n_rt, int n_ch,
                                                         float *__restrict__ wp, float *__restrict__ bp) {
   using G = ConvGeom<K>;
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float *__restrict_
     const int kappa = (q & ~7) + 2 * (q & 3) + ((q >> 2) & 1);
     const int c = ch * kCB + kappa / G::KK, t = kappa % G::KK;
     const int64_t o = (int64_t)rt * 32 + r;
-    wp[i] = (o < c_out && c < c_in) ? w[(o * c_in + c) * G::KK + t] : 0.0f;
+    wp[i] = (o < c_out && c < c_in) ? (TR ? w[((int64_t)c * c_out + o) * G::KK + (G::KK - 1 - t)] : w[(o * c_in + c) * G::KK + t]) : 0.0f;
   }
 }
 
@@ -228,18 +229,19 @@ template <int K, int T> static int conv_go(const ConvArgs &a, int64_t n, hipStre
   return (int)hipGetLastError();
 }
 
-template <int K> static int conv_pack_go(const float *w, const float *bias, int c_out, int c_in, float *wp, float *bp, hipStream_t st) {
+template <int K, bool TR> static int conv_pack_go(const float *w, const float *bias, int c_out, int c_in, float *wp, float *bp, hipStream_t st) {
   const int64_t total = (int64_t)conv_packed_floats(c_out, c_in, K);
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(conv_pack_kernel<K>, dim3(grid), dim3(256), 0, st, w, bias, c_out, c_in, conv_row_tiles(c_out), conv_chunks(c_in), wp, bp);
+  hipLaunchKernelGGL((conv_pack_kernel<K, TR>), dim3(grid), dim3(256), 0, st, w, bias, c_out, c_in, conv_row_tiles(c_out), conv_chunks(c_in), wp, bp);
   return (int)hipGetLastError();
 }
 
 } // namespace
 
-int launch_conv_pack(const float *w, const float *bias, int c_out, int c_in, int k, float *wp, float *bp, void *stream) {
-  if (k == 3) return conv_pack_go<3>(w, bias, c_out, c_in, wp, bp, (hipStream_t)stream);
-  return conv_pack_go<5>(w, bias, c_out, c_in, wp, bp, (hipStream_t)stream);
+int launch_conv_pack(const float *w, const float *bias, int c_out, int c_in, int k, bool transposed, float *wp, float *bp, void *stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  if (transposed) return k == 3 ? conv_pack_go<3, true>(w, bias, c_out, c_in, wp, bp, st) : conv_pack_go<5, true>(w, bias, c_out, c_in, wp, bp, st);
+  return k == 3 ? conv_pack_go<3, false>(w, bias, c_out, c_in, wp, bp, st) : conv_pack_go<5, false>(w, bias, c_out, c_in, wp, bp, st);
 }
 
 // T: the most row tiles per block (4, 2, 1) at which the launch - n * patches blocks per group of T row tiles - still has a block for

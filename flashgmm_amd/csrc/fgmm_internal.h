@@ -328,10 +328,23 @@ struct ConvArgs {       // one launch, by value: items of one size
   int32_t act, shuffle; // FGMM_ACT_*; 1 | 2
   float slope;
 };
-// w: device [c_out, c_in, k, k], k = 3 | 5
-int launch_conv_pack(const float *w, const float *bias_or_null, int c_out, int c_in, int k, float *wp, float *bp, void *stream);
+// w: device [c_out, c_in, k, k], k = 3 | 5; transposed (section 5e, stride 1): device [c_in, c_out, k, k] as a ConvTranspose2d holds it,
+// packed as W'[o][c][a][b] = w[c][o][k - 1 - a][k - 1 - b]
+int launch_conv_pack(const float *w, const float *bias_or_null, int c_out, int c_in, int k, bool transposed, float *wp, float *bp, void *stream);
 // the row tiles per block: 4, 2 or 1 by ckbd_row_tiles_go's rule; blocks = n * patches * ceil(ceil(c_out / 32) / that)
 int launch_conv(const ConvArgs &args, int k, int64_t n, void *stream);
+
+// ---- stride-2 transposed 3x3 / 5x5 convolutions on the matrix cores (fgmm_deconv.hip; header section 5e) ----------
+// the launch form for `outer` = n * patches (of 8 x 16 INPUT positions) blocks per row group: 1 = four phases per block, two row tiles;
+// 2 = four phases, one row tile; 3 = one phase and one row tile per block.  The first of 1, 2 with at least kCkbdCtxFill blocks, else 3
+static inline int deconv_form(int64_t outer, int c_out) {
+  const int64_t n_rt = (c_out + 31) / 32;
+  return outer * ((n_rt + 1) / 2) >= kCkbdCtxFill ? 1 : outer * n_rt >= kCkbdCtxFill ? 2 : 3;
+}
+// w: device [c_in, c_out, k, k], k = 3 | 5 -> [n_rt][chunks][phase][32][8 taps(phase)] (conv_packed_floats' size), then the bias
+int launch_deconv_pack(const float *w, const float *bias_or_null, int c_out, int c_in, int k, float *wp, float *bp, void *stream);
+// ConvArgs as for launch_conv (h, w, ph, pw: the INPUT's; shuffle unused); out [n, c_out, 2 h, 2 w]
+int launch_deconv(const ConvArgs &args, int k, int64_t n, void *stream);
 
 // ---- GPU-side decode of CHECKPOINTED bitstreams (segdec_kernel): one wave per segment ---------------------------
 struct SegDesc {

@@ -597,11 +597,27 @@ class ConvStack:
         params = stack(z_hat)                  # [N, c_in, h, w] -> [N, c_out, h', w'] float32
         ctx = ConvStack(channel_context_k)(y_hat, channels=c_k)    # the first c_k channels of y_hat, without a slice's copy
 
+    ``transposed=True`` also takes ``nn.ConvTranspose2d`` layers of kernel 3 | 5 and stride 1 | 2 with ``padding = k // 2`` and
+    ``output_padding = stride - 1`` - ELIC's own ``h_s`` (models/elic_gmm.py:142-148) - in the order of header section 5e, mixed freely
+    with the layers above.
+
     The weights are packed once, here.  Not MIOpen's last bits: encoder and decoder must both use it.  No gradients."""
 
     @staticmethod
-    def check(modules):
-        """-> [(conv, FGMM_ACT_*, slope, shuffle)], one per layer; ValueError naming the first module that does not fit the pattern"""
+    def _check_transposed(m):
+        """ValueError naming the condition of header section 5e that the ``nn.ConvTranspose2d`` ``m`` fails"""
+        k, s = m.kernel_size[0], m.stride[0]
+        for ok, what in ((m.kernel_size in ((3, 3), (5, 5)), "a square kernel of 3 or 5"), (m.stride in ((1, 1), (2, 2)), "a stride of (1, 1) or (2, 2)"),
+                         (m.padding == (k // 2, k // 2), "padding == k // 2"), (m.output_padding == (s - 1, s - 1), "output_padding == stride - 1"),
+                         (m.dilation == (1, 1), "dilation 1"), (m.groups == 1, "groups 1"), (m.padding_mode == "zeros", 'padding_mode "zeros"')):
+            if not ok:
+                raise ValueError(f"ConvStack: a transposed layer needs {what}: {m}")
+
+    @staticmethod
+    def check(modules, transposed=False):
+        """-> [(conv, FGMM_ACT_*, slope, up)], one per layer, ``up`` the PixelShuffle factor of a ``Conv2d`` (1 | 2; for an
+        ``nn.ConvTranspose2d``, taken with ``transposed`` only: 1, its stride is its own); ValueError naming the first module that does
+        not fit the pattern"""
         layers = []
         bare = False  # the last layer has no activation yet
         for m in modules:
@@ -619,6 +635,10 @@ class ConvStack:
                     raise ValueError(f"ConvStack: PixelShuffle(2) needs a multiple of 4 output channels: {m}")
                 layers.append((conv, _lib.FGMM_ACT_NONE, 0.0, shuffle))
                 bare = True
+            elif transposed and isinstance(m, nn.ConvTranspose2d):
+                ConvStack._check_transposed(m)
+                layers.append((m, _lib.FGMM_ACT_NONE, 0.0, 1))
+                bare = True
             elif isinstance(m, (nn.LeakyReLU, nn.ReLU)) and bare:
                 slope = float(getattr(m, "negative_slope", 0.0))
                 if slope != slope or slope in (float("inf"), float("-inf")):
@@ -635,23 +655,28 @@ class ConvStack:
                 raise ValueError(f"ConvStack: {b[0]} does not take the {a[0].out_channels // a[3] ** 2} channels of the layer before it")
         return layers
 
-    def __init__(self, modules):
-        layers = self.check(list(modules))
+    def __init__(self, modules, transposed=False):
+        layers = self.check(list(modules), transposed)
         w0 = layers[0][0].weight
         if not w0.is_cuda:
             raise RuntimeError("ConvStack: expected modules on a HIP device (there is no CPU implementation)")
         self.device = w0.device
         self._dev = w0.device.index if w0.device.index is not None else -1
         self.c_in = layers[0][0].in_channels
-        self._h: List[Tuple[C.c_void_p, int, int, int]] = []  # (handle, the layer's input channels, output channels, shuffle)
+        self._h: List[Tuple[C.c_void_p, int, int, int]] = []  # (handle, the layer's input channels, the output's channels, its scale: 1 | 2)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         for conv, act, slope, shuffle in layers:
             w = conv.weight.detach().to(torch.float32).contiguous()
             b = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
             out = C.c_void_p()
+            if isinstance(conv, nn.ConvTranspose2d):
+                _lib.check(_lib.lib().fgmm_conv_create_transposed(_lib.ctx(self._dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, conv.in_channels,
+                                                                  conv.out_channels, conv.kernel_size[0], conv.stride[0], act, slope, C.byref(out)), "ConvStack")
+                self._h.append((out, conv.in_channels, conv.out_channels, conv.stride[0]))
+                continue
             _lib.check(_lib.lib().fgmm_conv_create(_lib.ctx(self._dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, conv.out_channels,
                                                    conv.in_channels, conv.kernel_size[0], act, slope, shuffle, C.byref(out)), "ConvStack")
-            self._h.append((out, conv.in_channels, conv.out_channels, shuffle))
+            self._h.append((out, conv.in_channels, conv.out_channels // shuffle ** 2, shuffle))
 
     def __del__(self):
         hs, self._h = getattr(self, "_h", None) or [], []
@@ -671,8 +696,8 @@ class ConvStack:
         N, C_all, h, w = x.shape
         L, cx, stream = _lib.lib(), _lib.ctx(self._dev), torch.cuda.current_stream(self.device).cuda_stream
         stride = C_all * h * w
-        for hd, _, c_out, shuffle in self._h:
-            out = torch.empty((N, c_out // shuffle ** 2, h * shuffle, w * shuffle), dtype=torch.float32, device=self.device)
+        for hd, _, c_out, up in self._h:
+            out = torch.empty((N, c_out, h * up, w * up), dtype=torch.float32, device=self.device)
             if N and h * w:
                 _lib.check(L.fgmm_conv_apply(cx, stream, hd, x.data_ptr(), stride, out.data_ptr(), N, h, w), "ConvStack")
             x, (_, C_all, h, w) = out, out.shape

@@ -23,7 +23,7 @@ holds (checkerboard.py:282-288), so nothing has to wait for the anchors' bitstre
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -689,11 +689,11 @@ class CheckerboardLatentCodec(nn.Module):
         return {"likelihoods": {"y": y_out["likelihoods"]["y"]}, "y_hat": y_hat}
 
 
-def _cached_stack(cache: Dict[int, Tuple[Any, ConvStack]], slot: int, modules: nn.Module) -> ConvStack:
+def _cached_stack(cache: Dict[int, Tuple[Any, ConvStack]], slot: int, modules: nn.Module, transposed: bool = False) -> ConvStack:
     """the ConvStack of ``modules``, packed once and again when a weight or bias has changed (``_head_parts``' key, every layer's)"""
     key = tuple((p.data_ptr(), p._version) for p in modules.parameters())
     if slot not in cache or cache[slot][0] != key:
-        cache[slot] = (key, ConvStack(modules))
+        cache[slot] = (key, ConvStack(modules, transposed))
     return cache[slot][1]
 
 
@@ -876,7 +876,7 @@ class HyperLatentCodec(nn.Module):
     ``flashgmm_amd.EntropyBottleneckCoder`` (built from the tables of a trained ``EntropyBottleneck``), or the reference's own class."""
 
     def __init__(self, entropy_bottleneck=None, h_a: Optional[nn.Module] = None, h_s: Optional[nn.Module] = None,
-                 quantizer: str = "noise", fuse_h_s: bool = False, **kwargs: Any):
+                 quantizer: str = "noise", fuse_h_s: Union[bool, str] = False, **kwargs: Any):
         super().__init__()
         assert entropy_bottleneck is not None
         self.entropy_bottleneck = entropy_bottleneck
@@ -885,14 +885,19 @@ class HyperLatentCodec(nn.Module):
         self.quantizer = quantizer
         # fuse_h_s: compress() and decompress() compute the side parameters inside the library (flashgmm_amd.ConvStack, header section
         # 5d: the 3x3 layers of models/ckbd_gmm.py:97-107, PixelShuffle(2) folded into the store, in ONE summation order).  It changes
-        # the last bits of the parameters: encoder and decoder must agree on this switch.  ELIC's h_s (transposed convolutions) is refused.
+        # the last bits of the parameters: encoder and decoder must agree on this switch.  True refuses ELIC's h_s (transposed
+        # convolutions); fuse_h_s="transposed" takes it too (ConvStack(h_s, transposed=True), header section 5e: the stride-2 layers of
+        # models/elic_gmm.py:142-148 as four sub-pixel phases of real terms only).
+        if isinstance(fuse_h_s, str) and fuse_h_s != "transposed":
+            raise ValueError(f'fuse_h_s: False, True or "transposed", got {fuse_h_s!r}')
         self.fuse_h_s = bool(fuse_h_s)
+        self._h_s_transposed = fuse_h_s == "transposed"
         self._h_s_stack: Dict[int, Tuple[Any, ConvStack]] = {}
         if self.fuse_h_s:
-            ConvStack.check(self.h_s)
+            ConvStack.check(self.h_s, self._h_s_transposed)
 
     def _side_params(self, z_hat: Tensor) -> Tensor:
-        return _cached_stack(self._h_s_stack, 0, self.h_s)(z_hat) if self.fuse_h_s else self.h_s(z_hat)
+        return _cached_stack(self._h_s_stack, 0, self.h_s, self._h_s_transposed)(z_hat) if self.fuse_h_s else self.h_s(z_hat)
 
     def compress(self, y: Tensor) -> Dict[str, Any]:  # hyper.py:94-100
         z = self.h_a(y)

@@ -1335,7 +1335,7 @@ int fgmm_ckbd_ctx_wgrad(fgmm_ctx *ctx, void *stream, const float *anchors, const
  *    (compressai/models/ckbd_gmm.py:97-107: five 3x3 layers, two of them followed by PixelShuffle(2)), whose output is the side
  *    parameters, and ELIC's channel context (models/elic_gmm.py:151-164: three 5x5 layers with ReLU), which runs over the decoded groups.
  *    A last-bit difference in either changes scales / means / weights, the tables and the decoded symbols - the reason of section 2b.
- *    Strided and transposed convolutions (ELIC's own h_s, h_a) are not covered.
+ *    Strided convolutions (ELIC's h_a, encoder only) are not covered; the transposed ones of ELIC's h_s are section 5e's.
  *    One layer is Conv2d(c_in, c_out, k, stride=1, padding=k/2), k = 3 | 5, an activation of section 2c, and a plain or PixelShuffle(2)
  *    store.  Per item i of n, output channel o and position (r, q) of h x w, on v_mfma_f32_32x32x2_f32, bit for bit - signs of zero,
  *    infinities and NaN included - the chain
@@ -1372,6 +1372,40 @@ void fgmm_conv_destroy(fgmm_conv *conv);
  * success, no launch. */
 int fgmm_conv_apply(fgmm_ctx *ctx, void *stream, const fgmm_conv *conv, const float *x, int64_t x_item_stride, float *out, int n, int h,
                     int w);
+
+/* ---- section 5e. TRANSPOSED 3x3 / 5x5 CONVOLUTIONS of stride 1 | 2 on the matrix cores, in one fixed order ----------------------------
+ *    ELIC's own hyper-synthesis h_s (compressai/models/elic_gmm.py:142-148, deconv in models/utils.py:160-168): two
+ *    ConvTranspose2d(.., 5, stride=2, padding=2, output_padding=1) with ReLU and one ConvTranspose2d(.., 3, stride=1, padding=1), whose
+ *    output is the side parameters - the reason of sections 2b and 5d.
+ *    One layer is ConvTranspose2d(c_in, c_out, k, stride=s, padding=k/2, output_padding=s-1), k = 3 | 5, s = 1 | 2, then an activation of
+ *    section 2c; the output is [n, c_out, s*h, s*w].  Per item i, output channel o and OUTPUT position (R, Q), on
+ *    v_mfma_f32_32x32x2_f32, bit for bit - signs of zero, infinities and NaN included - the chain
+ *        acc = bias[o] (+0 without a bias)
+ *        for c = 0 .. c_in-1 ascending:
+ *          for a' = 0 .. k-1 ascending, for b' = 0 .. k-1 ascending:
+ *            u = R + a' - k/2;  v = Q + b' - k/2
+ *            if u % s != 0 or v % s != 0: no term              (a structural zero is NOT part of the chain)
+ *            x = input[i][c][u/s][v/s] inside the h x w image, else +0        (a +0 TERM, as in 5b and 5d)
+ *            acc = fmaf(weight[c][o][k-1-a'][k-1-b'], x, acc)
+ *        out[i][o][R][Q] = act(acc)
+ *    weight is [c_in, c_out, k, k] as torch stores a ConvTranspose2d.  Terms per input channel at output parity (R&1, Q&1), s = 2:
+ *    k = 5: 9 | 6 | 6 | 4, k = 3: 1 | 2 | 2 | 4 - 25 | 9 over the four, not the 36 of a zero-padded 3x3 to 4*c_out channels with
+ *    PixelShuffle(2), whose planted zeros would be terms: 0 * inf = NaN, and a -0 accumulator turned +0, at outputs whose sum never
+ *    touches that input.  s = 1 is section 5d's chain over W'[o][c][a'][b'] = weight[c][o][k-1-a'][k-1-b'] on its kernel.
+ *    Launch forms (s = 2): a workgroup computes an 8 x 16 patch of INPUT positions - 16 x 32 outputs a channel - in one of three forms:
+ *    1. all four output parities, two tiles of 32 output channels;  2. all four, one tile;  3. ONE parity and one tile (four times the
+ *    workgroups).  The rule, with P = n * ceil(h / 8) * ceil(w / 16) and R = ceil(c_out / 32): form 1 if P * ceil(R / 2) >= 256, else
+ *    form 2 if P * R >= 256, else form 3.  Every form gives the same bits: an output's chain depends on neither the form, nor n, nor the
+ *    item's place in a batch, nor the patch it falls in.  s = 1: section 5d's block heights.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FGMM_HAS_CONV_TRANSPOSED 1 /* section 5e: fgmm_conv_create_transposed (added without a bump, as 3b - 5d) */
+/* weight: device float32 [c_in, c_out, k, k]; bias: device float32 [c_out] or NULL.  -> a handle of section 5d's type: fgmm_conv_destroy
+ * and fgmm_conv_apply take it as they take fgmm_conv_create's (apply: x [c_in, h, w] per item through x_item_stride, out dense
+ * [n, c_out, stride*h, stride*w]; stream-ordered, ONE kernel, no workspace, no lock, no host wait; the same refusals - h*w beyond 2^29
+ * keeps the output plane's 4*h*w positions in 32 bits).  Refused (FGMM_ERR_INVALID, *out NULL): k not 3 or 5, stride not 1 or 2,
+ * c_in < 1, c_out < 1, an act that is none of the three, a slope that is not finite. */
+int fgmm_conv_create_transposed(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_in, int c_out, int k, int stride,
+                                int act, float slope, fgmm_conv **out);
 
 /* compressai._CXX.pmf_to_quantized_cdf (compressai/cpp_exts/ops/ops.cpp:40-109): cdf_out has n + 1 entries */
 int fgmm_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *cdf_out);

@@ -1,7 +1,12 @@
-"""The dense convolution layers of header section 5d, measured (profiles/conv_stack.md): ConvStack (fgmm_conv.hip: one launch per layer,
+"""The dense convolution layers of header section 5d and the transposed ones of 5e, measured (profiles/conv_stack.md,
+profiles/conv_transposed.md): ConvStack (fgmm_conv.hip: one launch per layer,
 activation and PixelShuffle(2) folded into the store) against the torch modules it replaces (MIOpen, warmed) on
   - the checkerboard GMM model's h_s (N = 192, M = 320: five 3x3 layers, two with PixelShuffle(2)) on z_hat [24, 192, 8, 12] and [1, 192, 8, 12];
-  - ELIC's last channel-context module (three 5x5 layers, 128 -> 224 -> 128 -> 384, ReLU) on [1, 128, 135, 240].
+  - ELIC's last channel-context module (three 5x5 layers, 128 -> 224 -> 128 -> 384, ReLU) on [1, 128, 135, 240];
+  - ELIC's h_s (N = 192: ConvTranspose2d 5x5 stride 2, 192 -> 192 -> 288, ReLU, then 3x3 stride 1 to 384; ConvStack(transposed=True),
+    fgmm_deconv.hip) on z_hat [1, 192, 34, 60] (ELIC-4K) and [16, 192, 34, 60] - and, for its two stride-2 layers alone, the third path
+    "emulation": the same layers as a dense 3x3 to 4 c_out channels with zero-padded sub-kernels and the PixelShuffle(2) store on
+    section 5d's kernel, the 36 products per channel the phase split's 25 have to beat.
 
 GPU time by device events on the current stream: a sample is `inner` back-to-back calls between two events, divided by `inner`; the two
 paths alternate sample by sample in one process; the median and the minimum of `samples` samples after `warm` warm-up samples of each.
@@ -33,6 +38,30 @@ N_, M_ = 192, 320
 h_s = nn.Sequential(conv3(N_, M_), nn.LeakyReLU(), subpel(M_, M_), nn.LeakyReLU(), conv3(M_, M_ * 3 // 2), nn.LeakyReLU(), subpel(M_ * 3 // 2, M_ * 3 // 2),
                     nn.LeakyReLU(), conv3(M_ * 3 // 2, M_ * 2)).to(dev)
 cc = nn.Sequential(conv5(128, 224), nn.ReLU(), conv5(224, 128), nn.ReLU(), conv5(128, 384)).to(dev)
+deconv = lambda i, o, k, s: nn.ConvTranspose2d(i, o, k, stride=s, padding=k // 2, output_padding=s - 1)
+elic_h_s = nn.Sequential(deconv(N_, N_, 5, 2), nn.ReLU(), deconv(N_, N_ * 3 // 2, 5, 2), nn.ReLU(), deconv(N_ * 3 // 2, N_ * 2, 3, 1)).to(dev)
+
+
+def emulation(net):
+    """the stride-2 5x5 transposed layers of net as Conv2d(c_in, 4 c_out, 3, padding=1) + PixelShuffle(2): output channel 4 o + 2 pr + pc
+    holds phase (pr, pc)'s taps at their input offsets, zeros elsewhere"""
+    taps = lambda par: [(a, (par + a - 2) // 2) for a in range(5) if (par + a) % 2 == 0]
+    mods = []
+    for m in net:
+        if not isinstance(m, nn.ConvTranspose2d):
+            mods.append(m)
+            continue
+        conv = nn.Conv2d(m.in_channels, 4 * m.out_channels, 3, padding=1).to(dev)
+        with torch.no_grad():
+            conv.weight.zero_()
+            conv.bias.copy_(m.bias.repeat_interleave(4))
+            for pr in (0, 1):
+                for pc in (0, 1):
+                    for a, dr in taps(pr):
+                        for b, dc in taps(pc):
+                            conv.weight[2 * pr + pc::4, :, dr + 1, dc + 1] = m.weight[:, :, 4 - a, 4 - b].t()
+        mods.append(nn.Sequential(conv, nn.PixelShuffle(2)))
+    return nn.Sequential(*mods)
 
 
 def sample(fn):
@@ -51,6 +80,8 @@ def flops(net, x):
     for m in net.modules():
         if isinstance(m, nn.Conv2d):
             hooks.append(m.register_forward_hook(lambda m, i, o: total.__setitem__(0, total[0] + 2.0 * o.numel() * m.in_channels * m.kernel_size[0] ** 2)))
+        if isinstance(m, nn.ConvTranspose2d):  # k^2 products per input position and channel pair
+            hooks.append(m.register_forward_hook(lambda m, i, o: total.__setitem__(0, total[0] + 2.0 * i[0].numel() * m.out_channels * m.kernel_size[0] ** 2)))
     with torch.no_grad():
         net(x)
     for hk in hooks:
@@ -60,14 +91,19 @@ def flops(net, x):
 
 out = {"compute_units": torch.cuda.get_device_properties(0).multi_processor_count, "samples": samples, "calls_per_sample": inner, "warmup_samples": warm,
        "roof_tf": ROOF_TF}
-for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1, N_, 8, 12)), ("channel_context", cc, (1, 128, 135, 240))):
-    x, op = torch.randn(shape, device=dev), ConvStack(net)
+for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1, N_, 8, 12)), ("channel_context", cc, (1, 128, 135, 240)),
+                         ("elic_h_s N=1", elic_h_s, (1, N_, 34, 60)), ("elic_h_s N=16", elic_h_s, (16, N_, 34, 60)),
+                         ("elic_h_s stride-2 layers N=1", elic_h_s[:4], (1, N_, 34, 60)), ("elic_h_s stride-2 layers N=16", elic_h_s[:4], (16, N_, 34, 60))):
+    x, op = torch.randn(shape, device=dev), ConvStack(net, transposed=True)
 
     def torch_path():
         with torch.no_grad():
             return net(x)
 
     paths = {"kernel": lambda: op(x), "torch": torch_path}
+    if "stride-2" in name:
+        emu = ConvStack(emulation(net))
+        paths["emulation"] = lambda: emu(x)
     for _ in range(warm):
         for fn in paths.values():
             sample(fn)
@@ -80,5 +116,8 @@ for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1
     res["kernel"]["frac_of_roof"] = round(res["gflop"] / res["kernel"]["median_ms"] / ROOF_TF, 4)
     res["kernel_over_torch"] = round(res["kernel"]["median_ms"] / res["torch"]["median_ms"], 4)
     res["max_abs_diff_to_torch"] = float((torch_path() - op(x)).abs().max())
+    if "emulation" in paths:
+        res["kernel_over_emulation"] = round(res["kernel"]["median_ms"] / res["emulation"]["median_ms"], 4)
+        res["emulation_max_abs_diff_to_torch"] = float((torch_path() - emu(x)).abs().max())
     out[name] = res
 print(json.dumps(out))
