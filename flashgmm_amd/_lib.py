@@ -299,12 +299,17 @@ SIGNATURES = {
     "fgmm_conv_create": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _pp]),
     "fgmm_conv_destroy": (None, [_p]),
     "fgmm_conv_apply": (_i, [_p, _p, _p, _p, _i64, _p, _i, _i, _i]),
+    # FGMM_CONV_BF16X6: (.. create's .., flags, out); (handle, n, hw); (.. apply's .., workspace, workspace_bytes)
+    "fgmm_conv_create_ex": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _i, _pp]),
+    "fgmm_conv_workspace_bytes": (_sz, [_p, _i, _i64]),
+    "fgmm_conv_apply_ws": (_i, [_p, _p, _p, _p, _i64, _p, _i, _i, _i, _p, _sz]),
     # section 5e: (ctx, stream, weight, bias, c_in, c_out, k, stride, act, slope, out) -> a handle of section 5d's
     "fgmm_conv_create_transposed": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _pp]),
 }
 FGMM_ACT_NONE, FGMM_ACT_LEAKY, FGMM_ACT_RELU = 0, 1, 2  # section 2c: fgmm_hidden_create's activations
 FGMM_HIDDEN_BF16X6 = 1  # section 2c: fgmm_hidden_create_ex's flag
 FGMM_CKBD_CTX_BF16X6 = 1  # section 5b: fgmm_ckbd_ctx_create_ex's flag
+FGMM_CONV_BF16X6 = 1  # section 5d: fgmm_conv_create_ex's flag
 FGMM_CKBD_WGRAD_SLICE_MIN, FGMM_CKBD_WGRAD_SLICES_MAX = 256, 16  # section 5c: the weight gradient's slice rule
 
 _lib = None

@@ -37,6 +37,8 @@
 //   epilogue: the activation on the accumulators, then out[i][o][r][q] or - shuffle 2, PixelShuffle(2) by index arithmetic -
 //             out[i][o >> 2][2 r + ((o >> 1) & 1)][2 q + (o & 1)].  Lanes outside the image and rows past c_out store nothing.
 // No atomics, no workspace.
+// A bf16x6 call (fgmm_conv16.hip) launches conv_kernel after its own with per-item domain words (ConvArgs::only): the blocks of an item
+// inside the domain return at once, a flagged item gets the chain above.  Null - every other caller - means every item.
 #include "fgmm_ckbd_geom.h"
 #include "fgmm_headframe.h"
 #include "fgmm_hidden_act.h"
@@ -94,6 +96,7 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int tot
   // the row groups of one patch are consecutive slots of one XCD: its L2 holds the patch's planes
   const int per_item = a.ph * a.pw * n_rg;
   const int item = L / per_item, rem = L - item * per_item, patch = rem / n_rg, rg = rem - patch * n_rg;
+  if (a.only && !a.only[(int64_t)item * a.only_stride]) return; // a bf16x6 call (fgmm_conv16.hip), and the item is inside its domain
   const int py = patch / a.pw, r0 = py * kPR, q0 = (patch - py * a.pw) * kPC;
   const int hgt = a.h, wid = a.w, c_in = a.c_in;
   const int64_t hw = (int64_t)hgt * wid;

@@ -327,12 +327,40 @@ struct ConvArgs {       // one launch, by value: items of one size
   int32_t ph, pw;       // patches per item: ceil(h / 8) x ceil(w / 16)
   int32_t act, shuffle; // FGMM_ACT_*; 1 | 2
   float slope;
+  // null: every item is the kernel's.  Else a bf16x6 call's domain words (fgmm_conv16.hip), item i's at only[i * only_stride]: conv_kernel
+  // computes the items whose word is not 0 - those with an input outside the bf16x6 domain - and leaves the others alone
+  const uint32_t *only;
+  int64_t only_stride;
 };
 // w: device [c_out, c_in, k, k], k = 3 | 5; transposed (section 5e, stride 1): device [c_in, c_out, k, k] as a ConvTranspose2d holds it,
 // packed as W'[o][c][a][b] = w[c][o][k - 1 - a][k - 1 - b]
 int launch_conv_pack(const float *w, const float *bias_or_null, int c_out, int c_in, int k, bool transposed, float *wp, float *bp, void *stream);
 // the row tiles per block: 4, 2 or 1 by ckbd_row_tiles_go's rule; blocks = n * patches * ceil(ceil(c_out / 32) / that)
 int launch_conv(const ConvArgs &args, int k, int64_t n, void *stream);
+
+// ---- the same layer in bf16x6 on the BF16 matrix cores (fgmm_conv16.hip; FGMM_CONV_BF16X6) ------------------------
+// packed weights: bf16 [n_rt row tiles of 32][channel tiles of 16][k^2 taps][part 3][k half 2][32 rows][8 channels] - 3072 contiguous
+// bytes per row tile and matrix step; n_rt = conv_row_tiles(c_out).  The bias is the f32 packing's (bp)
+static inline int conv16_tiles(int c_in) { return (c_in + kHead16BK - 1) / kHead16BK; }
+static inline size_t conv16_packed_bytes(int c_out, int c_in, int k) {
+  return (size_t)conv_row_tiles(c_out) * (size_t)conv16_tiles(c_in) * k * k * 3 * 32 * kHead16BK * sizeof(uint16_t);
+}
+// *bad (device, zeroed by the caller) becomes 1 when a weight is outside the bf16x6 domain (|w| >= 0x1.FFp127, inf, NaN)
+int launch_conv16_pack(const float *w, int c_out, int c_in, int k, void *wp16, uint32_t *bad, void *stream);
+struct Conv16Args {     // one launch, by value: items of one size
+  const uint16_t *xs;   // the inputs' split copies (launch_head16_split with c_in, hw = h * w), item i's at xs + i * xs_stride, each
+  int64_t xs_stride;    // followed by its domain word (head16_oob_word): an item whose word is not 0 is left to conv_kernel
+  float *out;           // device [n, c_out, h, w], or - shuffle 2 - [n, c_out / 4, 2 h, 2 w]
+  const void *wp16;     // the packed parts of the weights
+  const float *bp;      // the packed bias
+  int32_t c_in, c_out, h, w;
+  int32_t n_ct;         // channel tiles of 16: k^2 matrix steps each
+  int32_t ph, pw;       // patches per item: ceil(h / 8) x ceil(w / 16)
+  int32_t act, shuffle; // FGMM_ACT_*; 1 | 2
+  float slope;
+};
+// the row tiles per block are launch_conv's (4, 2 or 1 by ckbd_row_tiles_go's rule)
+int launch_conv16(const Conv16Args &args, int k, int64_t n, void *stream);
 
 // ---- stride-2 transposed 3x3 / 5x5 convolutions on the matrix cores (fgmm_deconv.hip; header section 5e) ----------
 // the launch form for `outer` = n * patches (of 8 x 16 INPUT positions) blocks per row group: 1 = four phases per block, two row tiles;

@@ -601,6 +601,13 @@ class ConvStack:
     ``output_padding = stride - 1`` - ELIC's own ``h_s`` (models/elic_gmm.py:142-148) - in the order of header section 5e, mixed freely
     with the layers above.
 
+    ``arithmetic="bf16x6"`` (``FGMM_CONV_BF16X6``, fgmm_conv16.hip) evaluates every ``Conv2d`` layer's sum on the BF16 matrix cores as
+    ``ParameterBody(arithmetic="bf16x6")`` evaluates its own: three bfloat16 parts per operand, six part products per product,
+    accumulated in binary32 from the bias, then the same activation and store - binary32 accuracy (the header states the bound), not
+    the ``fmaf`` chain and not restatable on a CPU, but the same bits from every launch shape on MI355X: encoder and decoder must both
+    use it there.  Weights outside its domain (finite, ``|w| < 0x1.FFp127``) raise here; an item with such an input is computed by the
+    exact kernel.  Transposed layers have the exact form only: a stack that holds one is refused.
+
     The weights are packed once, here.  Not MIOpen's last bits: encoder and decoder must both use it.  No gradients."""
 
     @staticmethod
@@ -655,8 +662,14 @@ class ConvStack:
                 raise ValueError(f"ConvStack: {b[0]} does not take the {a[0].out_channels // a[3] ** 2} channels of the layer before it")
         return layers
 
-    def __init__(self, modules, transposed=False):
+    def __init__(self, modules, transposed=False, arithmetic: str = "f32"):
+        if arithmetic not in ("f32", "bf16x6"):
+            raise ValueError(f"ConvStack: arithmetic {arithmetic!r} (\"f32\" or \"bf16x6\")")
+        self.arithmetic = arithmetic
         layers = self.check(list(modules), transposed)
+        for conv, *_ in layers:
+            if arithmetic == "bf16x6" and isinstance(conv, nn.ConvTranspose2d):
+                raise ValueError(f"ConvStack: arithmetic \"bf16x6\" takes nn.Conv2d layers only, got {conv}")
         w0 = layers[0][0].weight
         if not w0.is_cuda:
             raise RuntimeError("ConvStack: expected modules on a HIP device (there is no CPU implementation)")
@@ -674,8 +687,9 @@ class ConvStack:
                                                                   conv.out_channels, conv.kernel_size[0], conv.stride[0], act, slope, C.byref(out)), "ConvStack")
                 self._h.append((out, conv.in_channels, conv.out_channels, conv.stride[0]))
                 continue
-            _lib.check(_lib.lib().fgmm_conv_create(_lib.ctx(self._dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, conv.out_channels,
-                                                   conv.in_channels, conv.kernel_size[0], act, slope, shuffle, C.byref(out)), "ConvStack")
+            _lib.check(_lib.lib().fgmm_conv_create_ex(_lib.ctx(self._dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, conv.out_channels,
+                                                      conv.in_channels, conv.kernel_size[0], act, slope, shuffle,
+                                                      _lib.FGMM_CONV_BF16X6 if arithmetic == "bf16x6" else 0, C.byref(out)), "ConvStack")
             self._h.append((out, conv.in_channels, conv.out_channels // shuffle ** 2, shuffle))
 
     def __del__(self):
@@ -696,10 +710,17 @@ class ConvStack:
         N, C_all, h, w = x.shape
         L, cx, stream = _lib.lib(), _lib.ctx(self._dev), torch.cuda.current_stream(self.device).cuda_stream
         stride = C_all * h * w
+        # bf16x6: ONE workspace for the split copies, sized for the largest layer and reused layer to layer (the layers are ordered on
+        # the stream); torch's allocator hands it out and takes it back in stream order.  An exact stack's is empty and ignored
+        need, hw = 0, h * w
+        for hd, _, _, up in self._h:
+            need, hw = max(need, int(L.fgmm_conv_workspace_bytes(hd, N, hw))), hw * up * up
+        with torch.cuda.device(self.device):
+            ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         for hd, _, c_out, up in self._h:
             out = torch.empty((N, c_out, h * up, w * up), dtype=torch.float32, device=self.device)
             if N and h * w:
-                _lib.check(L.fgmm_conv_apply(cx, stream, hd, x.data_ptr(), stride, out.data_ptr(), N, h, w), "ConvStack")
+                _lib.check(L.fgmm_conv_apply_ws(cx, stream, hd, x.data_ptr(), stride, out.data_ptr(), N, h, w, ws.data_ptr() if need else None, need), "ConvStack")
             x, (_, C_all, h, w) = out, out.shape
             stride = C_all * h * w
         return x

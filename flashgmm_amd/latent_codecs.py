@@ -689,11 +689,11 @@ class CheckerboardLatentCodec(nn.Module):
         return {"likelihoods": {"y": y_out["likelihoods"]["y"]}, "y_hat": y_hat}
 
 
-def _cached_stack(cache: Dict[int, Tuple[Any, ConvStack]], slot: int, modules: nn.Module, transposed: bool = False) -> ConvStack:
+def _cached_stack(cache: Dict[int, Tuple[Any, ConvStack]], slot: int, modules: nn.Module, transposed: bool = False, arithmetic: str = "f32") -> ConvStack:
     """the ConvStack of ``modules``, packed once and again when a weight or bias has changed (``_head_parts``' key, every layer's)"""
-    key = tuple((p.data_ptr(), p._version) for p in modules.parameters())
+    key = (arithmetic,) + tuple((p.data_ptr(), p._version) for p in modules.parameters())
     if slot not in cache or cache[slot][0] != key:
-        cache[slot] = (key, ConvStack(modules, transposed))
+        cache[slot] = (key, ConvStack(modules, transposed, arithmetic))
     return cache[slot][1]
 
 
@@ -702,7 +702,7 @@ class ChannelGroupsLatentCodec(nn.Module):
     ``latent_codec[f"y{k}"]`` is typically a ``CheckerboardLatentCodec`` (models/elic_gmm.py:198-219)."""
 
     def __init__(self, latent_codec: Optional[Dict[str, nn.Module]] = None,
-                 channel_context: Optional[Dict[str, nn.Module]] = None, *, groups: List[int], fuse_channel_context: bool = False, **kwargs: Any):
+                 channel_context: Optional[Dict[str, nn.Module]] = None, *, groups: List[int], fuse_channel_context: Union[bool, str] = False, **kwargs: Any):
         super().__init__()
         self.groups = list(groups)
         self.groups_acc = list(accumulate(self.groups, initial=0))
@@ -712,7 +712,11 @@ class ChannelGroupsLatentCodec(nn.Module):
         # the library (flashgmm_amd.ConvStack, header section 5d: one launch per layer on the matrix cores in ONE summation order) over the
         # first groups_acc[k] channels of the one full-size y_hat tensor compress / decompress hold: no merge_y.  It changes the last bits
         # of the parameters: encoder and decoder must agree on this switch.  forward() keeps the torch modules (no gradients).
+        # fuse_channel_context="bf16x6": the same with ConvStack(arithmetic="bf16x6") (FGMM_CONV_BF16X6: the BF16 matrix cores, MI355X's bits).
+        if isinstance(fuse_channel_context, str) and fuse_channel_context != "bf16x6":
+            raise ValueError(f'fuse_channel_context: False, True or "bf16x6", got {fuse_channel_context!r}')
         self.fuse_channel_context = bool(fuse_channel_context)
+        self._cc_arith = "bf16x6" if fuse_channel_context == "bf16x6" else "f32"
         self._cc_stacks: Dict[int, Tuple[Any, ConvStack]] = {}
         if self.fuse_channel_context:
             for m in self.channel_context.values():
@@ -734,7 +738,7 @@ class ChannelGroupsLatentCodec(nn.Module):
         if k == 0:
             return side_params
         if self.fuse_channel_context and y_hat is not None:
-            return self.merge_params(_cached_stack(self._cc_stacks, k, self.channel_context[f"y{k}"])(y_hat, channels=self.groups_acc[k]), side_params)
+            return self.merge_params(_cached_stack(self._cc_stacks, k, self.channel_context[f"y{k}"], False, self._cc_arith)(y_hat, channels=self.groups_acc[k]), side_params)
         return self.merge_params(self.channel_context[f"y{k}"](self.merge_y(*y_hat_[:k])), side_params)
 
     def _run(self, y_hat: Tensor, side_params: Tensor, code_group):
@@ -887,17 +891,19 @@ class HyperLatentCodec(nn.Module):
         # 5d: the 3x3 layers of models/ckbd_gmm.py:97-107, PixelShuffle(2) folded into the store, in ONE summation order).  It changes
         # the last bits of the parameters: encoder and decoder must agree on this switch.  True refuses ELIC's h_s (transposed
         # convolutions); fuse_h_s="transposed" takes it too (ConvStack(h_s, transposed=True), header section 5e: the stride-2 layers of
-        # models/elic_gmm.py:142-148 as four sub-pixel phases of real terms only).
-        if isinstance(fuse_h_s, str) and fuse_h_s != "transposed":
-            raise ValueError(f'fuse_h_s: False, True or "transposed", got {fuse_h_s!r}')
+        # models/elic_gmm.py:142-148 as four sub-pixel phases of real terms only); fuse_h_s="bf16x6" is True with
+        # ConvStack(arithmetic="bf16x6") (FGMM_CONV_BF16X6: the BF16 matrix cores, MI355X's bits; Conv2d layers only).
+        if isinstance(fuse_h_s, str) and fuse_h_s not in ("transposed", "bf16x6"):
+            raise ValueError(f'fuse_h_s: False, True, "transposed" or "bf16x6", got {fuse_h_s!r}')
         self.fuse_h_s = bool(fuse_h_s)
         self._h_s_transposed = fuse_h_s == "transposed"
+        self._h_s_arith = "bf16x6" if fuse_h_s == "bf16x6" else "f32"
         self._h_s_stack: Dict[int, Tuple[Any, ConvStack]] = {}
         if self.fuse_h_s:
             ConvStack.check(self.h_s, self._h_s_transposed)
 
     def _side_params(self, z_hat: Tensor) -> Tensor:
-        return _cached_stack(self._h_s_stack, 0, self.h_s, self._h_s_transposed)(z_hat) if self.fuse_h_s else self.h_s(z_hat)
+        return _cached_stack(self._h_s_stack, 0, self.h_s, self._h_s_transposed, self._h_s_arith)(z_hat) if self.fuse_h_s else self.h_s(z_hat)
 
     def compress(self, y: Tensor) -> Dict[str, Any]:  # hyper.py:94-100
         z = self.h_a(y)

@@ -1372,6 +1372,44 @@ void fgmm_conv_destroy(fgmm_conv *conv);
  * success, no launch. */
 int fgmm_conv_apply(fgmm_ctx *ctx, void *stream, const fgmm_conv *conv, const float *x, int64_t x_item_stride, float *out, int n, int h,
                     int w);
+/* FGMM_CONV_BF16X6: the same layer on the BF16 matrix cores with binary32 accuracy ("bf16x6"), as FGMM_HEAD_BF16X6 (section 2b),
+ * FGMM_HIDDEN_BF16X6 (section 2c) and FGMM_CKBD_CTX_BF16X6 (section 5b) evaluate their sums.
+ *   The sum: every weight and every input v is three bfloat16 parts, v1 = bf16(v), v2 = bf16(v - v1), v3 = bf16(v - v1 - v2) (round to
+ *   nearest even; the subtractions exact in binary32).  A product w x is the six part products (w1,x3) (w3,x1) (w2,x2) (w1,x2) (w2,x1)
+ *   (w1,x1), in that order, smallest first; each is one v_mfma_f32_32x32x16_bf16 over 16 input channels of ONE tap, accumulated in
+ *   binary32 starting from the bias (+0 without).  The K tiles ascend with the channel tile of 16 outer and the tap (row-major, a*k + b)
+ *   inner: n16 = k*k * ceil(c_in / 16) matrix steps of six products.  A tap outside the image, and a channel past c_in, are zero in all
+ *   three parts, in every launch shape alike.  Then the activation of section 2c, unchanged, on the binary32 accumulator, and the plain
+ *   or PixelShuffle(2) store above.
+ *   The bound, for operands in the domain, with S = sum |w x| + |bias| over channels and taps and exact = bias + sum w x:
+ *       |pre - exact| <= E = R S + 2^-133 (sum |w| + sum |x|) + 6 n16 2^-150,   R = 2^-23 (1 + 2^-6) + 6 n16 2^-24 (1 + 2^-7)
+ *       |out - act(exact)| <= max(1, |slope|) E + 2^-24 |act(exact)| + 2^-150
+ *   - section 2c's bound with this n16.
+ *   The domain: finite operands with |v| < 0x1.FFp127.  A WEIGHT outside is refused by fgmm_conv_create_ex (FGMM_ERR_INVALID, *out
+ *   NULL).  An ITEM with an input outside (among its c_in channels) is computed whole by the exact kernel instead, launched right after
+ *   on the same stream: that item is bit for bit the fmaf chain above; the other items of the call keep their bf16x6 bits.
+ *   What it is NOT: the fmaf chain above, or a sequence a CPU can restate bit for bit (the matrix instruction's internal order is not
+ *   documented).  What it is: the SAME BITS FROM EVERY LAUNCH on MI355X - an output's bits depend on its weight row, its bias and the
+ *   inputs its taps read, not on the block height, on n, on the item's place in a batch or in its patch.  Encoder and decoder must BOTH
+ *   use it, on MI355X.  The block heights are those of the paragraph above, by the same rule.
+ * flags == 0 is fgmm_conv_create.  A bf16x6 handle holds both packings (the exact kernel serves the items outside the domain).  Unknown
+ * flags are refused; also refused with FGMM_CONV_BF16X6: more than 65535 * 16 input channels (the split's grid holds a tile of 16
+ * channels per block row).  Transposed layers (section 5e) have the exact form only. */
+#define FGMM_HAS_CONV_BF16X6 1 /* FGMM_CONV_BF16X6, fgmm_conv_create_ex, fgmm_conv_workspace_bytes, fgmm_conv_apply_ws (added without a bump) */
+#define FGMM_CONV_BF16X6 1
+int fgmm_conv_create_ex(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_in, int k, int act,
+                        float slope, int shuffle, int flags, fgmm_conv **out);
+/* bytes of the workspace fgmm_conv_apply_ws needs for n items of hw = h * w positions: per item the three bfloat16 parts of its input,
+ * channels padded to 16, and 16 bytes.  0: an exact handle, a NULL handle, n == 0 or hw == 0, or sizes the apply refuses. */
+size_t fgmm_conv_workspace_bytes(const fgmm_conv *conv, int n, int64_t hw);
+/* fgmm_conv_apply with a caller-owned workspace: device memory, 16-byte aligned, at least fgmm_conv_workspace_bytes(conv, n, h * w)
+ * bytes, the call's until the work enqueued here has run.  STREAM-ORDERED as fgmm_conv_apply: on a bf16x6 handle the split of the input,
+ * the bf16x6 kernel and the exact kernel for the items outside the domain are enqueued on `stream` - no context lock, no host wait.
+ * Refused, launching and writing nothing: what fgmm_conv_apply refuses; a workspace that is NULL, too small (the message names the
+ * bytes needed) or not 16-byte aligned.  An exact handle ignores the workspace.  fgmm_conv_apply on a bf16x6 handle is refused (the
+ * message names this call). */
+int fgmm_conv_apply_ws(fgmm_ctx *ctx, void *stream, const fgmm_conv *conv, const float *x, int64_t x_item_stride, float *out, int n,
+                       int h, int w, void *workspace, size_t workspace_bytes);
 
 /* ---- section 5e. TRANSPOSED 3x3 / 5x5 CONVOLUTIONS of stride 1 | 2 on the matrix cores, in one fixed order ----------------------------
  *    ELIC's own hyper-synthesis h_s (compressai/models/elic_gmm.py:142-148, deconv in models/utils.py:160-168): two

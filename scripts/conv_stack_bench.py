@@ -12,7 +12,11 @@ GPU time by device events on the current stream: a sample is `inner` back-to-bac
 paths alternate sample by sample in one process; the median and the minimum of `samples` samples after `warm` warm-up samples of each.
 The share of the f32 MFMA roof (157.3 TF, as profiles/r06_head_kernel.md) counts the multiply-adds the definition needs,
 2 * c_out * c_in * k^2 per position and layer.  Needs a GPU: fails without one.
-usage: python scripts/conv_stack_bench.py [samples=20] [inner=5] [warm=3]"""
+With `--arithmetic bf16x6` the bf16x6 form (fgmm_conv16.hip; profiles/conv_bf16x6.md) joins the alternation on the workloads of Conv2d
+layers: the whole call - per layer the split, conv16_kernel and the flagged-items launch - against the exact handle and torch in the same
+process, and conv16_kernel alone (the device durations torch's profiler records for it over `samples` calls, summed per call) as a share
+of the BF16 roof (419.5 TF of six part products per product, as profiles/ckbd_context_bf16x6.md).
+usage: python scripts/conv_stack_bench.py [samples=20] [inner=5] [warm=3] [--arithmetic bf16x6]"""
 import json
 import os
 import sys
@@ -25,10 +29,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from flashgmm_amd import ConvStack  # noqa: E402
 
+ARITH = "f32"
+if "--arithmetic" in sys.argv:
+    at = sys.argv.index("--arithmetic")
+    ARITH = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
+assert ARITH in ("f32", "bf16x6"), ARITH
 samples = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 inner = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 3
-ROOF_TF = 157.3
+ROOF_TF, ROOF16_TF = 157.3, 419.5
 assert torch.cuda.is_available(), "scripts/conv_stack_bench.py needs a GPU"
 dev = "cuda:0"
 torch.manual_seed(1)
@@ -74,6 +84,19 @@ def sample(fn):
     return a.elapsed_time(b) / inner, r
 
 
+def kernel_alone_ms(fn, name, calls):
+    """the device time of the kernels whose name holds `name`, per call of fn, from torch's profiler (None: it recorded none)"""
+    from torch.profiler import ProfilerActivity, profile
+
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(calls):
+            fn()
+        torch.cuda.synchronize()
+    us = [float(getattr(e, "device_time_total", 0) or getattr(e, "cuda_time_total", 0)) for e in prof.key_averages() if name in e.key]
+    return round(sum(us) / calls / 1e3, 5) if us and sum(us) > 0 else None
+
+
 def flops(net, x):
     """multiply-adds x 2 of every convolution of net on x, by the shapes"""
     total, hooks = [0.0], []
@@ -104,6 +127,10 @@ for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1
     if "stride-2" in name:
         emu = ConvStack(emulation(net))
         paths["emulation"] = lambda: emu(x)
+    b16 = ARITH == "bf16x6" and not any(isinstance(m, nn.ConvTranspose2d) for m in net)
+    if b16:
+        op16 = ConvStack(net, arithmetic="bf16x6")
+        paths["bf16x6"] = lambda: op16(x)
     for _ in range(warm):
         for fn in paths.values():
             sample(fn)
@@ -116,6 +143,14 @@ for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1
     res["kernel"]["frac_of_roof"] = round(res["gflop"] / res["kernel"]["median_ms"] / ROOF_TF, 4)
     res["kernel_over_torch"] = round(res["kernel"]["median_ms"] / res["torch"]["median_ms"], 4)
     res["max_abs_diff_to_torch"] = float((torch_path() - op(x)).abs().max())
+    if b16:
+        res["bf16x6"]["tflops"] = round(res["gflop"] / res["bf16x6"]["median_ms"], 2)
+        res["bf16x6"]["frac_of_bf16_roof"] = round(res["gflop"] / res["bf16x6"]["median_ms"] / ROOF16_TF, 4)
+        res["kernel_over_bf16x6"] = round(res["kernel"]["median_ms"] / res["bf16x6"]["median_ms"], 4)
+        res["bf16x6_over_torch"] = round(res["bf16x6"]["median_ms"] / res["torch"]["median_ms"], 4)
+        res["max_abs_diff_bf16x6_to_kernel"] = float((op16(x) - op(x)).abs().max())
+        alone = kernel_alone_ms(lambda: op16(x), "conv16_kernel", samples)
+        res["conv16_kernel_alone"] = {"ms": alone, "frac_of_bf16_roof": alone and round(res["gflop"] / alone / ROOF16_TF, 4)}
     if "emulation" in paths:
         res["kernel_over_emulation"] = round(res["kernel"]["median_ms"] / res["emulation"]["median_ms"], 4)
         res["emulation_max_abs_diff_to_torch"] = float((torch_path() - emu(x)).abs().max())
