@@ -10,7 +10,7 @@ All floating-point work runs in hand-written HIP kernels (flashgmm_amd/csrc); th
 """
 from . import _lib  # noqa: F401
 from .entropy_models import BudgetQuantized, RdCurve, CheckpointedBytes, CompressedBatch, ConvStack, EntropyBottleneck, EntropyBottleneckCoder, GaussianMixtureConditional, ParameterBody, ParameterHead, RateEstimate, RdoQuantized, RdoSkipQuantized, aux_loss, update_entropy_models  # noqa: F401
-from .ops import CheckerboardContext, checkerboard_context, pointwise_layer  # noqa: F401
+from .ops import CheckerboardContext, checkerboard_context, conv_layer, pointwise_layer  # noqa: F401
 from . import ans  # noqa: F401
 
 __version__ = "0.1.0"

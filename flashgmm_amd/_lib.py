@@ -305,6 +305,16 @@ SIGNATURES = {
     "fgmm_conv_apply_ws": (_i, [_p, _p, _p, _p, _i64, _p, _i, _i, _i, _p, _sz]),
     # section 5e: (ctx, stream, weight, bias, c_in, c_out, k, stride, act, slope, out) -> a handle of section 5d's
     "fgmm_conv_create_transposed": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _pp]),
+    # section 5f: (c_out, c_in, k); (ctx, stream, weight, bias, c_out, c_in, k, transposed, packed);
+    # (ctx, stream, packed, c_out, c_in, k, act, slope, shuffle, x, x_item_stride, out, n, h, w);
+    # (ctx, stream, packed_t, c_out, c_in, k, act, slope, shuffle, gy, out, dx, n, h, w); (c_out, c_in, k, n, h, w);
+    # (ctx, stream, x, x_item_stride, gy, out, c_out, c_in, k, act, slope, shuffle, n, h, w, workspace, dweight, dbias)
+    "fgmm_conv_packed_floats": (_sz, [_i, _i, _i]),
+    "fgmm_conv_pack": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fgmm_conv_apply_packed": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _p, _i64, _p, _i, _i, _i]),
+    "fgmm_conv_dgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _i, _i, _i]),
+    "fgmm_conv_wgrad_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "fgmm_conv_wgrad": (_i, [_p, _p, _p, _i64, _p, _p, _i, _i, _i, _i, C.c_float, _i, _i, _i, _i, _p, _p, _p]),
 }
 FGMM_ACT_NONE, FGMM_ACT_LEAKY, FGMM_ACT_RELU = 0, 1, 2  # section 2c: fgmm_hidden_create's activations
 FGMM_HIDDEN_BF16X6 = 1  # section 2c: fgmm_hidden_create_ex's flag

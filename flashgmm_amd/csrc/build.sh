@@ -34,14 +34,16 @@
 # fgmm_deconv.hip: the stride-2 transposed 3x3 / 5x5 layers of section 5e - four output parities as four small convolutions over one LDS-staged
 # patch - behind the same fgmm_conv.cpp, compiled like fgmm_conv.hip; fgmm_conv16.hip: the dense layers in bf16x6 on the BF16 matrix cores,
 # FGMM_CONV_BF16X6, behind the same fgmm_conv.cpp too - a halo staged once per tile of 16 channels for all k^2 taps, on fgmm_split3.h and
-# fgmm_head16.hip's split kernel, compiled like fgmm_conv.hip).
+# fgmm_head16.hip's split kernel, compiled like fgmm_conv.hip; fgmm_conv_grad.hip: the layer's weight and bias gradients, section 5f - the
+# halo staged once per patch for every (channel, tap) column, the positions as the matrix instruction's k - behind the same fgmm_conv.cpp, which
+# also runs fgmm_conv.hip's kernel with a gradient staging as the data gradient; compiled like fgmm_conv.hip).
 set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OUT=${OUT:-../libflashgmm_amd.so}
 COMMON="-O3 -fPIC -std=c++17 -Wall -Wextra -Wno-unused-parameter -ffp-contract=off -fno-fast-math"
 DEVICE="--offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-rdc -Xarch_device -fno-slp-vectorize -march=x86-64-v3"
-# fgmm_hidden.hip, fgmm_hidden16.hip, fgmm_hidden_grad.hip, fgmm_conv.hip, fgmm_conv16.hip and fgmm_deconv.hip are compiled on their own, with the packed fp32 instructions off altogether (their activations
+# fgmm_hidden.hip, fgmm_hidden16.hip, fgmm_hidden_grad.hip, fgmm_conv.hip, fgmm_conv_grad.hip, fgmm_conv16.hip and fgmm_deconv.hip are compiled on their own, with the packed fp32 instructions off altogether (their activations
 # are scalar binary32 sequences, header section 2c); their objects live in a temporary directory and go into the one link below
 OBJ=$(mktemp -d)
 trap 'rm -rf "$OBJ"' EXIT
@@ -49,9 +51,10 @@ $HIPCC $COMMON $DEVICE -Xclang -target-feature -Xclang -packed-fp32-ops -c fgmm_
 $HIPCC $COMMON $DEVICE -Xclang -target-feature -Xclang -packed-fp32-ops -c fgmm_hidden16.hip -o "$OBJ/fgmm_hidden16.o"
 $HIPCC $COMMON $DEVICE -Xclang -target-feature -Xclang -packed-fp32-ops -c fgmm_hidden_grad.hip -o "$OBJ/fgmm_hidden_grad.o"
 $HIPCC $COMMON $DEVICE -Xclang -target-feature -Xclang -packed-fp32-ops -c fgmm_conv.hip -o "$OBJ/fgmm_conv.o"
+$HIPCC $COMMON $DEVICE -Xclang -target-feature -Xclang -packed-fp32-ops -c fgmm_conv_grad.hip -o "$OBJ/fgmm_conv_grad.o"
 $HIPCC $COMMON $DEVICE -Xclang -target-feature -Xclang -packed-fp32-ops -c fgmm_conv16.hip -o "$OBJ/fgmm_conv16.o"
 $HIPCC $COMMON $DEVICE -Xclang -target-feature -Xclang -packed-fp32-ops -c fgmm_deconv.hip -o "$OBJ/fgmm_deconv.o"
-$HIPCC $COMMON $DEVICE -shared -o $OUT "$OBJ/fgmm_hidden.o" "$OBJ/fgmm_hidden16.o" "$OBJ/fgmm_hidden_grad.o" "$OBJ/fgmm_conv.o" "$OBJ/fgmm_conv16.o" "$OBJ/fgmm_deconv.o" fgmm_kernels.hip fgmm_tab.hip fgmm_head.hip fgmm_head16.hip fgmm_rate.hip fgmm_rdoq.hip fgmm_rdcurve.hip fgmm_like.hip fgmm_centroid.hip fgmm_eb.hip fgmm_ckbd_ctx.hip fgmm_ckbd_ctx16.hip fgmm_ckbd_ctx_grad.hip fgmm_device_hip.cpp fgmm_rans.cpp fgmm_rate_host.cpp fgmm_capi.cpp \
+$HIPCC $COMMON $DEVICE -shared -o $OUT "$OBJ/fgmm_hidden.o" "$OBJ/fgmm_hidden16.o" "$OBJ/fgmm_hidden_grad.o" "$OBJ/fgmm_conv.o" "$OBJ/fgmm_conv_grad.o" "$OBJ/fgmm_conv16.o" "$OBJ/fgmm_deconv.o" fgmm_kernels.hip fgmm_tab.hip fgmm_head.hip fgmm_head16.hip fgmm_rate.hip fgmm_rdoq.hip fgmm_rdcurve.hip fgmm_like.hip fgmm_centroid.hip fgmm_eb.hip fgmm_ckbd_ctx.hip fgmm_ckbd_ctx16.hip fgmm_ckbd_ctx_grad.hip fgmm_device_hip.cpp fgmm_rans.cpp fgmm_rate_host.cpp fgmm_capi.cpp \
     fgmm_encode.cpp fgmm_decode.cpp fgmm_decode_gpu.cpp fgmm_estimate.cpp fgmm_rdoq.cpp fgmm_rdcurve.cpp fgmm_like.cpp fgmm_centroid.cpp fgmm_eb.cpp fgmm_ckbd_ctx.cpp fgmm_hidden.cpp fgmm_hidden_grad.cpp fgmm_conv.cpp -lpthread "$@"
 echo "built $(realpath $OUT)"
 # The compiled Python boundary over the C ABI (fgmm_pybind.cpp -> flashgmm_amd/_native.*.so): plain C++ against the Python and pybind11

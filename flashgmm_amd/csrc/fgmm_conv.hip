@@ -85,7 +85,10 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float *__restrict_
   }
 }
 
-template <int K, int T> // kernel size; row tiles per block
+// GRAD (header section 5f, the data gradient): 0 - the layer.  1 | 2 - x is gy, the gradient of a layer's stored output, and what is staged
+// is gz: gy itself (1: FGMM_ACT_NONE, the saved output is never loaded) or grad_act(gy, saved output) (2), both read through the
+// un-shuffle of the epilogue's store when g_shuffle is 2.  Everything past the staging is the layer's text
+template <int K, int T, int GRAD = 0> // kernel size; row tiles per block
 __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int total) {
   using G = ConvGeom<K>;
   constexpr int kRows = 32 * T;
@@ -101,6 +104,10 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int tot
   const int hgt = a.h, wid = a.w, c_in = a.c_in;
   const int64_t hw = (int64_t)hgt * wid;
   const float *x = a.x + (int64_t)item * a.x_item_stride;
+  // GRAD: gy's plane [c_in / 4, 2 h, 2 w] holds channel c at (c >> 2, 2 r + ((c >> 1) & 1), 2 q + (c & 1)) - the epilogue's store, inverted
+  const bool g_sh = GRAD && a.g_shuffle == 2;
+  const float *g_out = GRAD == 2 ? a.g_out + (int64_t)item * a.x_item_stride : nullptr;
+  auto g_plane = [&](int c) { return g_sh ? (int64_t)(c >> 2) * 4 * hw + ((c >> 1) & 1) * 2 * wid + (c & 1) : (int64_t)c * hw; };
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
   // the thread's halo elements e = tid + 256 j = (channel of the chunk, halo row, halo column): where they lie in a plane of the
   // image - the same for every chunk
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int tot
     const int e = tid + 256 * j;
     const int r = r0 + (e / G::HW) % G::HR - K / 2, q = q0 + e % G::HW - K / 2;
     const bool in = e < G::HALO_N && ckbd_inside(r, q, hgt, wid);
-    goff[j] = in ? r * wid + q : 0;
+    goff[j] = in ? (g_sh ? 4 * r * wid + 2 * q : r * wid + q) : 0;
     g_in |= (in ? 1u : 0u) << j;
   }
   // ---- accumulators start at the bias
@@ -128,6 +135,7 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int tot
   const float *wp = a.wp + (int64_t)rg * T * rt_words * 4;          // row tile rg * T + tl, chunk ch: at wp + (tl * rt_words + ch * A_W) * 4
   float4_t ra[T][G::A_J];
   float rb[G::HALO_J];
+  [[maybe_unused]] float ro[GRAD == 2 ? G::HALO_J : 1]; // GRAD 2: the saved output beside gy
   unsigned rb_ok = 0, rb_ch = 0; // bit j: rb[j] is an element inside the image of a channel below c_in; its channel is below c_in
   auto load_chunk = [&](int ch) {
     rb_ok = 0, rb_ch = 0;
@@ -143,7 +151,13 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int tot
     for (int j = 0; j < G::HALO_J; ++j) {
       const int c = ch * kCB + (tid + 256 * j) / (G::HR * G::HW);
       const bool k_ok = c < c_in;
-      rb[j] = ((const FGMM_GLOBAL float *)(x + (int64_t)(k_ok ? c : c_in - 1) * hw))[goff[j]];
+      if constexpr (GRAD) {
+        const int64_t at = g_plane(k_ok ? c : c_in - 1) + goff[j];
+        rb[j] = ((const FGMM_GLOBAL float *)x)[at];
+        if constexpr (GRAD == 2) ro[j] = ((const FGMM_GLOBAL float *)g_out)[at];
+      } else {
+        rb[j] = ((const FGMM_GLOBAL float *)(x + (int64_t)(k_ok ? c : c_in - 1) * hw))[goff[j]];
+      }
       rb_ok |= (k_ok ? (g_in >> j) & 1u : 0u) << j;
       rb_ch |= (k_ok ? 1u : 0u) << j;
     }
@@ -159,7 +173,9 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int tot
 #pragma unroll
     for (int j = 0; j < G::HALO_J; ++j) {
       const int e = tid + 256 * j;
-      const float v = (rb_ok >> j) & 1u ? rb[j] : ((rb_ch >> j) & 1u ? 0.0f : -0.0f);
+      float v = rb[j];
+      if constexpr (GRAD == 2) v = grad_act(v, ro[j], a.g_act == FGMM_ACT_RELU, a.g_slope); // the select: here, where the loads have landed
+      v = (rb_ok >> j) & 1u ? v : ((rb_ch >> j) & 1u ? 0.0f : -0.0f);
       if (e < G::HALO_N) sH[(e / (G::HR * G::HW)) * G::PLANE + ((e / G::HW) % G::HR) * G::PITCH + e % G::HW] = v;
     }
   };
@@ -222,13 +238,13 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int n_rg, int tot
   with_activation(a.act, a.slope, store);
 }
 
-template <int K, int T> static int conv_go(const ConvArgs &a, int64_t n, hipStream_t st) {
+template <int K, int T, int GRAD = 0> static int conv_go(const ConvArgs &a, int64_t n, hipStream_t st) {
   const int n_rg = ((a.c_out + 31) / 32 + T - 1) / T;
   const int64_t total = n * a.ph * a.pw * n_rg;
   if (total <= 0) return 0;
   if (total > (1ll << 30)) return (int)hipErrorInvalidValue;
   const unsigned blocks = (unsigned)((total + 7) / 8 * 8); // every XCD gets as many slots (head_slot)
-  hipLaunchKernelGGL((conv_kernel<K, T>), dim3(blocks), dim3(256), 0, st, a, n_rg, (int)total);
+  hipLaunchKernelGGL((conv_kernel<K, T, GRAD>), dim3(blocks), dim3(256), 0, st, a, n_rg, (int)total);
   return (int)hipGetLastError();
 }
 
@@ -252,6 +268,15 @@ int launch_conv_pack(const float *w, const float *bias, int c_out, int c_in, int
 int launch_conv(const ConvArgs &args, int k, int64_t n, void *stream) {
   return ckbd_row_tiles_go<4, 2, 1>(n * args.ph * args.pw, args.c_out, [&](auto T) {
     return k == 3 ? conv_go<3, T>(args, n, (hipStream_t)stream) : conv_go<5, T>(args, n, (hipStream_t)stream);
+  });
+}
+
+// the data gradient (section 5f): the same kernel, block heights by the same rule over its output's rows (the layer's c_in)
+int launch_conv_dgrad(const ConvArgs &args, int k, int64_t n, void *stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  return ckbd_row_tiles_go<4, 2, 1>(n * args.ph * args.pw, args.c_out, [&](auto T) {
+    if (args.g_act == FGMM_ACT_NONE) return k == 3 ? conv_go<3, T, 1>(args, n, st) : conv_go<5, T, 1>(args, n, st);
+    return k == 3 ? conv_go<3, T, 2>(args, n, st) : conv_go<5, T, 2>(args, n, st);
   });
 }
 

@@ -16,4 +16,12 @@ template <typename F> __device__ __forceinline__ void with_activation(int act, f
   else f([](float v) { return v; });
 }
 
+// the activation's derivative (header sections 2d and 5f): gz from (gy, out), the saved OUTPUT.  leaky, relu are the call's activation
+// (both false: gz = gy, and `out` is whatever the caller passes); a NaN output takes the second branch
+__device__ __forceinline__ float grad_act(float gy, float out, bool relu, float slope) {
+  const float scaled = gy * slope;
+  const float off = relu ? 0.0f : scaled;
+  return out > 0.0f ? gy : off;
+}
+
 } // namespace fgmm

@@ -26,6 +26,7 @@
 // No atomics: every partial has one writer.
 #include "fgmm_ckbd_geom.h"
 #include "fgmm_headframe.h"
+#include "fgmm_hidden_act.h" // grad_act: gz from (gy, out)
 
 namespace fgmm {
 namespace {
@@ -34,13 +35,6 @@ constexpr int kBK = kMfma32BK;
 constexpr int kTileW = kMfma32TileW;
 constexpr int kPB = kMfma32PB;
 constexpr int kALd = kMfma32ALd, kBLd = kMfma32BLd;
-
-// gz from (gy, out): leaky, relu are the call's activation (both false: gz = gy, and `out` is whatever the caller passes)
-__device__ __forceinline__ float grad_act(float gy, float out, bool relu, float slope) {
-  const float scaled = gy * slope;
-  const float off = relu ? 0.0f : scaled;
-  return out > 0.0f ? gy : off;
-}
 
 // the transposed packing: hidden_pack_kernel's layout (fgmm_hidden.hip) of the layer  W'[r][o] = w[o][r]  - c_a + c_b rows, ONE source of
 // c_out channels, no bias: [n_rt row tiles][n_kt K tiles][32 rows][32 columns], then [n_rt][32] of +0.  Padding: +0

@@ -331,12 +331,49 @@ struct ConvArgs {       // one launch, by value: items of one size
   // computes the items whose word is not 0 - those with an input outside the bf16x6 domain - and leaves the others alone
   const uint32_t *only;
   int64_t only_stride;
+  // the data gradient's launch alone (launch_conv_dgrad; section 5f): x is gy - the gradient of the LAYER's stored output, [n, c_in of this
+  // launch, h, w] or, g_shuffle 2, [n, c_in / 4, 2 h, 2 w] - and the staging forms gz from it and the saved output g_out (same shape; not
+  // read with g_act == FGMM_ACT_NONE).  act above is FGMM_ACT_NONE, shuffle 1: dx is stored plainly
+  const float *g_out;
+  int32_t g_act, g_shuffle;
+  float g_slope;
 };
 // w: device [c_out, c_in, k, k], k = 3 | 5; transposed (section 5e, stride 1): device [c_in, c_out, k, k] as a ConvTranspose2d holds it,
 // packed as W'[o][c][a][b] = w[c][o][k - 1 - a][k - 1 - b]
 int launch_conv_pack(const float *w, const float *bias_or_null, int c_out, int c_in, int k, bool transposed, float *wp, float *bp, void *stream);
 // the row tiles per block: 4, 2 or 1 by ckbd_row_tiles_go's rule; blocks = n * patches * ceil(ceil(c_out / 32) / that)
 int launch_conv(const ConvArgs &args, int k, int64_t n, void *stream);
+
+// ---- its gradients (fgmm_conv.hip's kernel with a gradient staging; fgmm_conv_grad.hip; header section 5f) --------
+// the data gradient: conv_kernel over the packing launch_conv_pack(transposed) makes of the layer's own weight, with the g_* fields set;
+// args.c_in = the LAYER's c_out (gz's channels), args.c_out = the layer's c_in (dx's).  Block heights: launch_conv's rule over args.c_out
+int launch_conv_dgrad(const ConvArgs &args, int k, int64_t n, void *stream);
+constexpr int kConvWgradSliceMin = 256; // positions the reduction holds before it is cut into more slices (FGMM_CONV_WGRAD_SLICE_MIN)
+constexpr int kConvWgradSliceMax = 16;  // slices at the most (FGMM_CONV_WGRAD_SLICES_MAX)
+struct ConvWgradSlices { int64_t S, B; }; // S slices of B bands (the last one fewer); a band: 8 image rows of one item
+static inline ConvWgradSlices conv_wgrad_slices(int64_t n, int64_t h, int64_t w) {
+  const int64_t nb = n * ((h + kConvPR - 1) / kConvPR), P = n * h * w;
+  if (nb <= 0 || P <= 0) return {0, 1};
+  const int64_t want = (P + kConvWgradSliceMin - 1) / kConvWgradSliceMin;
+  const int64_t s1 = want < kConvWgradSliceMax ? want : kConvWgradSliceMax, s0 = s1 < nb ? s1 : nb, B = (nb + s0 - 1) / s0;
+  return {(nb + B - 1) / B, B};
+}
+constexpr int conv_wgrad_cb(int k) { return k == 3 ? 14 : 10; } // input channels per column group: 14 * 9 | 10 * 25 columns and the bias'
+static inline int64_t conv_wgrad_cols(int c_in, int k) { return (int64_t)c_in * k * k + 1; } // a partial's row: [c_in][k^2], then the bias
+struct ConvWgradArgs {
+  const float *x;        // device: item i's [c_in, h, w] at x + i * x_item_stride
+  const float *gy, *out; // device [n, c_out, h, w] or - shuffle 2 - [n, c_out / 4, 2 h, 2 w] (out: not read with FGMM_ACT_NONE)
+  float *partial;        // device [S][c_out][c_in k^2 + 1]
+  int64_t x_item_stride;
+  int32_t c_in, c_out, h, w;
+  int32_t bh, pw;        // bands per item: ceil(h / 8); patches per band: ceil(w / 16)
+  int32_t nb, B, S;      // bands in all (n * bh), per slice, slices
+  int32_t act, shuffle;
+  float slope;
+};
+// row tiles per block: 4, 2 or 1 by ckbd_row_tiles_go's rule; blocks = S * ceil(c_in / conv_wgrad_cb(k)) * ceil(ceil(c_out / 32) / that)
+int launch_conv_wgrad(const ConvWgradArgs &args, int k, void *stream);
+int launch_conv_wgrad_finish(const float *partial, int c_out, int c_in, int k, int S, float *dweight, float *dbias_or_null, void *stream);
 
 // ---- the same layer in bf16x6 on the BF16 matrix cores (fgmm_conv16.hip; FGMM_CONV_BF16X6) ------------------------
 // packed weights: bf16 [n_rt row tiles of 32][channel tiles of 16][k^2 taps][part 3][k half 2][32 rows][8 channels] - 3072 contiguous

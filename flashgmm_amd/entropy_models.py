@@ -608,7 +608,12 @@ class ConvStack:
     use it there.  Weights outside its domain (finite, ``|w| < 0x1.FFp127``) raise here; an item with such an input is computed by the
     exact kernel.  Transposed layers have the exact form only: a stack that holds one is refused.
 
-    The weights are packed once, here.  Not MIOpen's last bits: encoder and decoder must both use it.  No gradients."""
+    The weights are packed once, here.  Not MIOpen's last bits: encoder and decoder must both use it.
+
+    Gradients (header section 5f): with grad enabled and an input or a parameter of the modules requiring it, an ``"f32"`` stack of
+    ``nn.Conv2d`` layers runs its layers through ``flashgmm_amd.ops.conv_layer`` on the modules' LIVE parameters - the same bits as the
+    packed handles give for the same weights, and differentiable.  A ``"bf16x6"`` or ``transposed`` stack has no gradients: an input that
+    requires them raises.  Under ``torch.no_grad()`` nothing changes."""
 
     @staticmethod
     def _check_transposed(m):
@@ -666,7 +671,10 @@ class ConvStack:
         if arithmetic not in ("f32", "bf16x6"):
             raise ValueError(f"ConvStack: arithmetic {arithmetic!r} (\"f32\" or \"bf16x6\")")
         self.arithmetic = arithmetic
-        layers = self.check(list(modules), transposed)
+        mods = list(modules)
+        layers = self.check(mods, transposed)
+        self._mods = nn.ModuleList(mods)  # (what a call under autograd reads: the modules' live parameters)
+        self._transposed = bool(transposed)
         for conv, *_ in layers:
             if arithmetic == "bf16x6" and isinstance(conv, nn.ConvTranspose2d):
                 raise ValueError(f"ConvStack: arithmetic \"bf16x6\" takes nn.Conv2d layers only, got {conv}")
@@ -700,12 +708,36 @@ class ConvStack:
             except Exception:  # pragma: no cover - interpreter shutdown
                 pass
 
+    @staticmethod
+    def wants_grad(modules, x: Tensor) -> bool:
+        """is a call on ``x`` one under autograd: grad enabled, and ``x`` or a parameter of ``modules`` requiring it?"""
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in modules.parameters()))
+
+    @staticmethod
+    def differentiable(modules, x: Tensor, channels: Optional[int] = None) -> Tensor:
+        """``ConvStack(modules)(x, channels)`` under autograd WITHOUT the stack: the layers as ``ops.conv_layer`` on the modules' live
+        parameters (header section 5f) - the handles' bits, no handle built.  What a training step calls: its weights change every time"""
+        from .ops import conv_layer
+
+        names = {_lib.FGMM_ACT_NONE: "none", _lib.FGMM_ACT_LEAKY: "leaky_relu", _lib.FGMM_ACT_RELU: "relu"}
+        x = x.to(torch.float32)
+        for j, (conv, act, slope, shuffle) in enumerate(ConvStack.check(list(modules))):
+            x = conv_layer(x, conv.weight.to(torch.float32), None if conv.bias is None else conv.bias.to(torch.float32), names[act], slope, shuffle, channels if j == 0 else None)
+        return x
+
     def __call__(self, x: Tensor, channels: Optional[int] = None) -> Tensor:
         """-> what the modules give for ``x`` (``channels``: for ``x[:, :channels]``, read in place through the item stride), float32, in
         the library's order.  The layers run back to back on the current stream."""
         c = x.shape[1] if channels is None and x.dim() == 4 else channels
         if x.dim() != 4 or c != self.c_in or x.shape[1] < c or x.device != self.device:
             raise RuntimeError(f"x must be [N, >= {self.c_in}, h, w] on {self.device} with channels = {self.c_in}; got {tuple(x.shape)}, channels = {c} on {x.device}")
+        if self.wants_grad(self._mods, x):
+            if self.arithmetic == "bf16x6" or self._transposed:
+                if x.requires_grad:
+                    option = 'arithmetic="bf16x6"' if self.arithmetic == "bf16x6" else "transposed=True"
+                    raise RuntimeError(f"ConvStack: no gradients with {option} (header section 5f: the exact f32 form of nn.Conv2d layers only)")
+            else:
+                return self.differentiable(self._mods, x, c)
         x = x.to(torch.float32).contiguous()
         N, C_all, h, w = x.shape
         L, cx, stream = _lib.lib(), _lib.ctx(self._dev), torch.cuda.current_stream(self.device).cuda_stream

@@ -711,8 +711,10 @@ class ChannelGroupsLatentCodec(nn.Module):
         # fuse_channel_context: group k's channel_context module - three 5x5 convolutions with ReLU, models/elic_gmm.py:151-164 - runs inside
         # the library (flashgmm_amd.ConvStack, header section 5d: one launch per layer on the matrix cores in ONE summation order) over the
         # first groups_acc[k] channels of the one full-size y_hat tensor compress / decompress hold: no merge_y.  It changes the last bits
-        # of the parameters: encoder and decoder must agree on this switch.  forward() keeps the torch modules (no gradients).
-        # fuse_channel_context="bf16x6": the same with ConvStack(arithmetic="bf16x6") (FGMM_CONV_BF16X6: the BF16 matrix cores, MI355X's bits).
+        # of the parameters: encoder and decoder must agree on this switch.  forward() computes the context through the same stack, under
+        # autograd (header section 5f): the likelihoods it reports are those of the parameters the coder uses.
+        # fuse_channel_context="bf16x6": the same with ConvStack(arithmetic="bf16x6") (FGMM_CONV_BF16X6: the BF16 matrix cores, MI355X's bits);
+        # it has no gradients: forward() keeps the torch modules.
         if isinstance(fuse_channel_context, str) and fuse_channel_context != "bf16x6":
             raise ValueError(f'fuse_channel_context: False, True or "bf16x6", got {fuse_channel_context!r}')
         self.fuse_channel_context = bool(fuse_channel_context)
@@ -734,9 +736,13 @@ class ChannelGroupsLatentCodec(nn.Module):
     def _get_ctx_params(self, k: int, side_params: Tensor, y_hat_: Tuple[Tensor, ...], y_hat: Optional[Tensor] = None) -> Tensor:
         """parameters group k is coded under: the side parameters, preceded (k > 0) by the channel context computed
         from the reconstructions of groups 0..k-1 (channel_groups.py:166-173).  ``y_hat``: the full-size tensor ``y_hat_`` are the
-        views of - with ``fuse_channel_context`` the context is the library's, read from its first ``groups_acc[k]`` channels"""
+        views of - with ``fuse_channel_context`` the context is the library's, read from its first ``groups_acc[k]`` channels.  Without
+        it (``forward()``) ``fuse_channel_context=True`` runs the same stack on the concatenated reconstructions, under autograd"""
         if k == 0:
             return side_params
+        if self.fuse_channel_context and self._cc_arith == "f32" and y_hat is None:
+            cc, x = self.channel_context[f"y{k}"], self.merge_y(*y_hat_[:k])  # (under autograd: no handle is packed for weights that change every step)
+            return self.merge_params(ConvStack.differentiable(cc, x) if ConvStack.wants_grad(cc, x) else _cached_stack(self._cc_stacks, k, cc)(x), side_params)
         if self.fuse_channel_context and y_hat is not None:
             return self.merge_params(_cached_stack(self._cc_stacks, k, self.channel_context[f"y{k}"], False, self._cc_arith)(y_hat, channels=self.groups_acc[k]), side_params)
         return self.merge_params(self.channel_context[f"y{k}"](self.merge_y(*y_hat_[:k])), side_params)
@@ -861,7 +867,8 @@ class ChannelGroupsLatentCodec(nn.Module):
     def forward(self, y: Tensor, side_params: Tensor) -> Dict[str, Any]:
         """As the reference's (channel_groups.py:89-109): group k's codec is called with its slice of ``y`` and the parameters
         ``_get_ctx_params`` builds from the side parameters and the ``y_hat`` of groups 0 .. k-1; likelihoods and ``y_hat`` are
-        concatenated along the channels."""
+        concatenated along the channels.  With ``fuse_channel_context=True`` group k's context is the library's convolution stack on
+        ``torch.cat(y_hat_[:k], 1)`` - what ``compress`` computes, differentiable (header section 5f); ``"bf16x6"`` keeps the torch modules."""
         y_ = torch.split(y, self.groups, dim=1)
         y_hat_: List[Tensor] = []
         y_likelihoods_: List[Tensor] = []
@@ -927,14 +934,21 @@ class HyperLatentCodec(nn.Module):
 
     def forward(self, y: Tensor) -> Dict[str, Any]:  # hyper.py:87-94
         """-> ``{"likelihoods": {"z": ...}, "params": h_s(z_hat)}``; ``entropy_bottleneck`` is ``flashgmm_amd.EntropyBottleneck`` (its
-        density on the GPU, include/flashgmm_amd.h section 3j) or anything callable as the reference's class.  ``h_s`` is the torch
-        module here whatever ``fuse_h_s`` says: the library's convolution has no gradients"""
+        density on the GPU, include/flashgmm_amd.h section 3j) or anything callable as the reference's class.  With ``fuse_h_s=True``
+        ``params`` is the library's convolution stack on ``z_hat`` - bit for bit what ``compress`` computes from the same ``z_hat``, and
+        differentiable (header section 5f).  ``fuse_h_s="transposed"`` and ``"bf16x6"`` have no gradients: ``h_s`` is the torch module"""
         z = self.h_a(y)
         z_hat, z_likelihoods = self.entropy_bottleneck(z)
         if self.quantizer == "ste":
             d = z - self.entropy_bottleneck._get_medians()
             z_hat = ((torch.round(d) - d).detach() + d) + self.entropy_bottleneck._get_medians()  # quantize_ste (compressai/ops/ops.py:66-80)
-        return {"likelihoods": {"z": z_likelihoods}, "params": self.h_s(z_hat)}
+        if not (self.fuse_h_s and not self._h_s_transposed and self._h_s_arith == "f32"):
+            params = self.h_s(z_hat)
+        elif ConvStack.wants_grad(self.h_s, z_hat):  # (no handle is packed for weights that change every step)
+            params = ConvStack.differentiable(self.h_s, z_hat)
+        else:
+            params = self._side_params(z_hat)
+        return {"likelihoods": {"z": z_likelihoods}, "params": params}
 
 
 class HyperpriorLatentCodec(nn.Module):

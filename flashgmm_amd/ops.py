@@ -14,6 +14,9 @@ alone.  ``ckbd_unembed`` / ``ckbd_embed`` are differentiable as well: each one's
 ``pointwise_layer`` — one 1x1 layer of the parameter network over two sources, with its activation, as a DIFFERENTIABLE operator
 (header sections 2c and 2d): forward, data gradients and weight and bias gradients on the matrix cores, each in one fixed order.
 
+``conv_layer`` — one dense 3x3 / 5x5 convolution layer with its activation and plain or ``PixelShuffle(2)`` store as a DIFFERENTIABLE
+operator (header sections 5d and 5f): forward, data gradient and weight and bias gradients on the matrix cores, each in one fixed order.
+
 ``pmf_to_quantized_cdf`` — mirror of ``compressai._CXX.pmf_to_quantized_cdf`` (compressai/cpp_exts/ops/ops.cpp:40-109),
 the table builder behind ``EntropyBottleneck.update()`` / ``GaussianConditional.update()`` (the `z` hyper-latent path).
 Runs once per model; host code in libflashgmm_amd.so."""
@@ -26,7 +29,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["pmf_to_quantized_cdf", "ckbd_unembed", "ckbd_embed", "CheckerboardContext", "checkerboard_context", "pointwise_layer"]
+__all__ = ["pmf_to_quantized_cdf", "ckbd_unembed", "ckbd_embed", "CheckerboardContext", "checkerboard_context", "pointwise_layer", "conv_layer"]
 
 
 def _ckbd(t, anchor_parity: str, embed: bool):
@@ -434,6 +437,127 @@ def pointwise_layer(ctx, side, weight, bias=None, activation: str = "none", nega
     zero gradients."""
     _pw_check(ctx, side, weight, bias, activation, negative_slope)
     return _pw_function().apply(ctx, side, weight, bias, activation, float(negative_slope))
+
+
+def _conv_check(x, weight, bias, activation, negative_slope, shuffle, channels):
+    """the refusals of ``conv_layer``: activation, slope, shuffle, device, dtype, shape -> (c_in, c_out, k)"""
+    import torch
+
+    if activation not in _ACTIVATIONS:
+        raise ValueError(f"activation {activation!r} (\"none\", \"leaky_relu\" or \"relu\")")
+    slope = float(negative_slope)
+    if slope != slope or slope in (float("inf"), float("-inf")) or (activation == "leaky_relu" and slope < 0):
+        raise ValueError(f"negative_slope {negative_slope!r}: finite, and not negative with \"leaky_relu\" (the saved output's sign is then not the pre-activation's)")
+    if shuffle not in (1, 2):
+        raise ValueError(f"shuffle {shuffle!r} (1, or 2 for PixelShuffle(2))")
+    if not (torch.is_tensor(x) and torch.is_tensor(weight)) or not (bias is None or torch.is_tensor(bias)):
+        raise TypeError("x, weight and bias must be tensors (bias may be None)")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) not in ((3, 3), (5, 5)) or weight.dtype != torch.float32:
+        raise RuntimeError(f"weight must be float32 [c_out, c_in, 3, 3] or [c_out, c_in, 5, 5]; got {weight.dtype} {tuple(weight.shape)}")
+    c_out, c_in, k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+    if c_out < 1 or c_in < 1 or (shuffle == 2 and c_out % 4):
+        raise RuntimeError(f"weight {tuple(weight.shape)}: at least one channel each way, and a multiple of 4 output channels with shuffle 2")
+    if not weight.is_cuda:
+        raise RuntimeError("flashgmm_amd operators run on the GPU only: the layer's weights must be on a HIP device")
+    c = x.shape[1] if channels is None and x.dim() == 4 else channels
+    if x.dim() != 4 or c != c_in or x.shape[1] < c_in or x.device != weight.device or x.dtype != torch.float32:
+        raise RuntimeError(f"x must be float32 [N, >= {c_in}, h, w] on {weight.device} with channels = {c_in}; got {x.dtype} {tuple(x.shape)}, channels = {c} on {x.device}")
+    if bias is not None and (tuple(bias.shape) != (c_out,) or bias.device != weight.device or bias.dtype != torch.float32):
+        raise RuntimeError(f"bias must be float32 [{c_out}] on {weight.device}; got {bias.dtype} {tuple(bias.shape)} on {bias.device}")
+    return c_in, c_out, k
+
+
+def _conv_pack(dev, stream, w, b, transposed, c_out, c_in, k):
+    """section 5f's packing of w [c_out, c_in, k, k] in torch-allocated memory, on ``stream``"""
+    import torch
+
+    L = _lib.lib()
+    floats = L.fgmm_conv_packed_floats(c_in, c_out, k) if transposed else L.fgmm_conv_packed_floats(c_out, c_in, k)
+    packed = torch.empty((int(floats),), dtype=torch.float32, device=w.device)
+    _lib.check(L.fgmm_conv_pack(_lib.ctx(dev), stream, w.data_ptr(), b.data_ptr() if b is not None else None, c_out, c_in, k, int(transposed),
+                                packed.data_ptr()), "conv_layer: pack")
+    return packed
+
+
+_conv_fn = []
+
+
+def _conv_function():
+    if not _conv_fn:
+        import torch
+
+        class ConvLayerFn(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, weight, bias, activation, negative_slope, shuffle, channels):
+                c_in, c_out, k = _conv_check(x, weight, bias, activation, negative_slope, shuffle, channels)
+                xd, w = x.detach().contiguous(), weight.detach().contiguous()  # (all of x's channels: the leading c_in are read in place)
+                b = None if bias is None else bias.detach().contiguous()
+                dev = w.device.index if w.device.index is not None else -1
+                act, slope = _ACTIVATIONS[activation], float(negative_slope)
+                N, C_all, h, wd = xd.shape
+                out = torch.empty((N, c_out // shuffle ** 2, h * shuffle, wd * shuffle), dtype=torch.float32, device=w.device)
+                with torch.cuda.device(w.device):
+                    stream = torch.cuda.current_stream(w.device).cuda_stream
+                    if N and h and wd:
+                        packed = _conv_pack(dev, stream, w, b, False, c_out, c_in, k)
+                        _lib.check(_lib.lib().fgmm_conv_apply_packed(_lib.ctx(dev), stream, packed.data_ptr(), c_out, c_in, k, act, slope, shuffle, xd.data_ptr(),
+                                                                     C_all * h * wd, out.data_ptr(), N, h, wd), "conv_layer: apply")
+                ctx.save_for_backward(xd, w, out)
+                ctx.geom = (dev, act, slope, shuffle, c_in, c_out, k, bias is not None)
+                return out
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable
+            def backward(ctx, gy):
+                xd, w, out = ctx.saved_tensors
+                dev, act, slope, shuffle, c_in, c_out, k, has_bias = ctx.geom
+                N, C_all, h, wd = xd.shape
+                gy = gy.to(torch.float32).contiguous()
+                need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+                L, empty = _lib.lib(), not (N and h and wd)
+                dx = dw = db = None
+                with torch.cuda.device(w.device):
+                    stream = torch.cuda.current_stream(w.device).cuda_stream
+                    if need_x:
+                        # the channels that were not read: +0.  (The kernel writes a dense [N, c_in, h, w]: copied into the leading channels)
+                        dx = torch.zeros(xd.shape, dtype=torch.float32, device=w.device) if empty or C_all != c_in else torch.empty_like(xd)
+                        if not empty:
+                            dense = dx if C_all == c_in else torch.empty((N, c_in, h, wd), dtype=torch.float32, device=w.device)
+                            packed_t = _conv_pack(dev, stream, w, None, True, c_out, c_in, k)
+                            _lib.check(L.fgmm_conv_dgrad(_lib.ctx(dev), stream, packed_t.data_ptr(), c_out, c_in, k, act, slope, shuffle, gy.data_ptr(), out.data_ptr(),
+                                                         dense.data_ptr(), N, h, wd), "conv_layer: dgrad")
+                            if dense is not dx:
+                                dx[:, :c_in].copy_(dense)
+                    if need_w or need_b:
+                        # (the weight gradient's call computes both; the one not asked for is dropped)
+                        dw = (torch.zeros if empty else torch.empty)(w.shape, dtype=torch.float32, device=w.device)
+                        db = (torch.zeros if empty else torch.empty)((c_out,), dtype=torch.float32, device=w.device) if need_b else None
+                        if not empty:
+                            nbytes = int(L.fgmm_conv_wgrad_workspace(c_out, c_in, k, N, h, wd))
+                            ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=w.device)
+                            _lib.check(L.fgmm_conv_wgrad(_lib.ctx(dev), stream, xd.data_ptr(), C_all * h * wd, gy.data_ptr(), out.data_ptr(), c_out, c_in, k, act, slope,
+                                                         shuffle, N, h, wd, ws.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None), "conv_layer: wgrad")
+                return dx, dw if need_w else None, db, None, None, None, None
+
+        _conv_fn.append(ConvLayerFn)
+    return _conv_fn[0]
+
+
+def conv_layer(x, weight, bias=None, activation: str = "none", negative_slope: float = 0.01, shuffle: int = 1, channels=None):
+    """One dense 3x3 / 5x5 convolution layer as a differentiable operator (include/flashgmm_amd.h sections 5d and 5f): ``x``
+    ``[N, C, h, w]`` float32, ``weight`` ``[c_out, c_in, k, k]`` (k = 3 | 5; stride 1, padding k // 2), ``bias`` ``[c_out]`` or None ->
+    ``pixel_shuffle(act(conv2d(x, weight, bias, padding=k // 2)), shuffle)``, bit for bit section 5d's ``fmaf`` chain, activation
+    (``"none"``, ``"leaky_relu"`` with ``negative_slope >= 0``, ``"relu"``) and plain (``shuffle=1``) or ``PixelShuffle(2)`` store.
+    ``channels=c_in``: the layer reads the leading ``c_in`` channels of a wider ``x`` in place, as ``ConvStack.__call__`` does.  The
+    weights are packed at every call (a training step changes them), into torch-allocated memory on the current stream.
+
+    Backward (once differentiable, only what is asked for): the activation's derivative is taken from the saved OUTPUT (nothing else is
+    kept beside ``x``); the gradient of ``x`` is the forward kernel over the flipped, transposed filters with that derivative formed as
+    it stages its input - +0 in the channels of a wider ``x`` that were not read; those of ``weight`` and ``bias`` one matrix-core
+    kernel over a torch-allocated workspace, in a summation order that depends on ``(N, h, w)`` alone - the same bits on every run,
+    device and launch geometry.  An empty batch gives zero gradients."""
+    _conv_check(x, weight, bias, activation, negative_slope, shuffle, channels)
+    return _conv_function().apply(x, weight, bias, activation, float(negative_slope), int(shuffle), channels)
 
 
 def pmf_to_quantized_cdf(pmf: Sequence[float], precision: int = 16) -> List[int]:

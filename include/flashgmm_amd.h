@@ -1445,6 +1445,75 @@ int fgmm_conv_apply_ws(fgmm_ctx *ctx, void *stream, const fgmm_conv *conv, const
 int fgmm_conv_create_transposed(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_in, int c_out, int k, int stride,
                                 int act, float slope, fgmm_conv **out);
 
+/* ---- section 5f. The dense layer of 5d as a DIFFERENTIABLE operator: the forward over caller-owned packed weights and three gradients ---
+ *    What HyperLatentCodec.forward() needs of h_s, and ChannelGroupsLatentCodec.forward() of the channel context, under autograd: a model
+ *    that is coded with section 5d's kernels sees their bits while it trains (the reason of sections 2d and 5c).  Exact binary32, Conv2d
+ *    layers only.  Notation as 5d: z = conv(x; weight, bias), out = store(act(z)) with shuffle 1 | 2.  `out` is the layer's saved, STORED
+ *    output - [n, c_out, h, w], or [n, c_out/4, 2h, 2w] with shuffle 2 - and gy the gradient with respect to it, of the same shape.
+ *    ACTIVATION DERIVATIVE  the pre-activation's gradient gz [n, c_out, h, w] is never stored.  It is section 2d's rule, one binary32
+ *    operation, read through the inverse of 5d's store:
+ *        (G, O) = (gy, out)[i][o][r][q]                                           shuffle 1
+ *               = (gy, out)[i][o >> 2][2r + ((o >> 1) & 1)][2q + (o & 1)]          shuffle 2
+ *        FGMM_ACT_NONE   gz[i][o][r][q] = G                       (`out` is not read and may be NULL)
+ *        FGMM_ACT_LEAKY  gz[i][o][r][q] = O > 0 ? G : G * slope   (a negative slope is refused by the two gradient calls, as in 2d)
+ *        FGMM_ACT_RELU   gz[i][o][r][q] = O > 0 ? G : +0
+ *    A NaN output takes the second branch.
+ *    DATA GRADIENT  on v_mfma_f32_32x32x2_f32 bit for bit - signs of zero, infinities and NaN included - section 5d's chain over gz:
+ *        acc = +0                                                  (no bias)
+ *        for o = 0 .. c_out-1 ascending:                           (the "input channels": outer)
+ *          for t = 0 .. k*k-1 ascending (t = a*k + b):             (the taps: inner)
+ *            g = gz[i][o][r + a - k/2][q + b - k/2] inside the image, else +0     (a +0 TERM of the chain, as in 5d)
+ *            acc = fmaf(weight[o][c][k*k - 1 - t], g, acc)
+ *        dx[i][c][r][q] = acc
+ *    - 5d's layer from c_out to c_in channels with the filters W'[c][o][a][b] = weight[o][c][k-1-a][k-1-b], which is what section 5e's
+ *    stride-1 packing makes of `weight` read as a transposed layer's [c_in', c_out', k, k]: fgmm_conv_pack(transposed = 1).  It runs on
+ *    5d's kernel with gz formed where the input is staged; block heights 4, 2, 1 by 5d's rule with ceil(c_in / 32) row tiles.
+ *    WEIGHT AND BIAS GRADIENTS  the reduction runs over the positions of all items.  THE ORDER of the positions: items ascending; within
+ *    an item its BANDS of 8 image rows (rows 8j .. min(8j + 8, h) - 1, the patch height of 5d) ascending; within a band its patches of 16
+ *    columns left to right; within a patch row-major.  (Positions past the image do not exist.)  THE CUT: the NB = n * ceil(h / 8) bands
+ *    of the call, in that order, into slices of whole bands - a function of (n, h, w) alone, never of the device, the grid or the block
+ *    height:
+ *        S0 = min(FGMM_CONV_WGRAD_SLICES_MAX, ceil(n*h*w / FGMM_CONV_WGRAD_SLICE_MIN), NB),   B = ceil(NB / S0),   S = ceil(NB / B)
+ *    slice j is bands [j B, min((j+1) B, NB)) and may cross item boundaries.  (n, h, w) = (1, 1, 1): NB = 1 -> S = 1, B = 1;
+ *    (1, 16, 16): 256 positions in 2 bands -> S = 1, B = 2;  (1, 9, 29): 261 positions in 2 bands -> S = 2, B = 1, the second slice one image
+ *    row;  (2, 17, 33): 1122 positions in 6 bands, S0 = 5 -> B = 2, S = 3 - a sixth and a fourth slice would be empty - and slice 1 is the
+ *    last band of item 0 and the first of item 1;  (17, 16, 32): 8704 positions in 34 bands, S0 = 16 -> B = 3, S = 12, the last slice one band.
+ *        partial_j[o][c][t] = the chain  acc = +0; for s ascending in slice j:  acc = fmaf(gz(s)[o], x(s)(c, t), acc)
+ *        dweight[o][c][t]   = ((partial_0 + partial_1) + partial_2) + ...   in binary32, ascending
+ *        dbias[o]           = the same slices in the same order with x = 1
+ *    x(s)(c, t) is the forward's tap t of channel c at position s: +0 outside the image, which takes part in the chain.  On
+ *    v_mfma_f32_32x32x2_f32 bit for bit; no float atomics: every partial has one writer.  Block heights 4, 2, 1: the first T with
+ *    S * ceil(c_in / (k == 3 ? 14 : 10)) * ceil(ceil(c_out / 32) / T) >= 256 workgroups, 1 when none has; every height gives the same bits.
+ * All six calls are STREAM-ORDERED like section 5d's apply: enqueued on `stream`, no context lock, no host wait, caller-owned memory; a
+ * refused call launches nothing and writes nothing.
+ * fgmm_conv_packed_floats: float32 elements of a packing of a layer from c_in to c_out channels (0 for sizes that are refused).
+ * fgmm_conv_pack: weight device float32 [c_out, c_in, k, k], bias [c_out] or NULL.  transposed = 0 writes the layout a handle holds into
+ *   packed[fgmm_conv_packed_floats(c_out, c_in, k)]; transposed = 1 writes the layer W' above - c_in output channels, c_out input channels
+ *   - into packed[fgmm_conv_packed_floats(c_in, c_out, k)], what fgmm_conv_dgrad runs on; it takes no bias (a bias with it is refused).
+ *   `packed` is aligned to 16 bytes.
+ * fgmm_conv_apply_packed: fgmm_conv_apply on such a buffer (transposed = 0) - bit for bit the result of a handle made of the same
+ *   weights.  Refusals as fgmm_conv_create's and fgmm_conv_apply's.
+ * fgmm_conv_dgrad: packed_t from fgmm_conv_pack(transposed = 1); gy, out as above; dx device float32 dense [n, c_in, h, w].
+ * fgmm_conv_wgrad: x as fgmm_conv_apply takes it (item i's [c_in, h, w] at x + i * x_item_stride); dweight device float32
+ *   [c_out, c_in, k, k]; dbias [c_out] or NULL.  workspace: device memory of at least fgmm_conv_wgrad_workspace(...) BYTES (S partial
+ *   copies of [c_out, c_in*k*k + 1] float32; 0 for sizes that are refused, n == 0 or h*w == 0), aligned to 16 bytes, the call's own until
+ *   the work enqueued by it has run.
+ * The gradient calls refuse what fgmm_conv_create and fgmm_conv_apply refuse, and: FGMM_ACT_LEAKY with slope < 0; a NULL gy, dx, x or
+ *   dweight (and a NULL `out` with an activation); a workspace that is NULL or not 16-byte aligned.  n*h*w == 0: success, no launch. */
+#define FGMM_HAS_CONV_GRAD 1 /* section 5f (added without a bump, as 3b - 5e) */
+#define FGMM_CONV_WGRAD_SLICE_MIN 256 /* positions the weight gradient's reduction holds before it is cut into more slices */
+#define FGMM_CONV_WGRAD_SLICES_MAX 16 /* slices at the most: the workspace holds as many partial copies of [c_out, c_in*k*k + 1] */
+size_t fgmm_conv_packed_floats(int c_out, int c_in, int k);
+int fgmm_conv_pack(fgmm_ctx *ctx, void *stream, const float *weight, const float *bias, int c_out, int c_in, int k, int transposed,
+                   float *packed);
+int fgmm_conv_apply_packed(fgmm_ctx *ctx, void *stream, const float *packed, int c_out, int c_in, int k, int act, float slope, int shuffle,
+                           const float *x, int64_t x_item_stride, float *out, int n, int h, int w);
+int fgmm_conv_dgrad(fgmm_ctx *ctx, void *stream, const float *packed_t, int c_out, int c_in, int k, int act, float slope, int shuffle,
+                    const float *gy, const float *out, float *dx, int n, int h, int w);
+size_t fgmm_conv_wgrad_workspace(int c_out, int c_in, int k, int n, int h, int w);
+int fgmm_conv_wgrad(fgmm_ctx *ctx, void *stream, const float *x, int64_t x_item_stride, const float *gy, const float *out, int c_out,
+                    int c_in, int k, int act, float slope, int shuffle, int n, int h, int w, void *workspace, float *dweight, float *dbias);
+
 /* compressai._CXX.pmf_to_quantized_cdf (compressai/cpp_exts/ops/ops.cpp:40-109): cdf_out has n + 1 entries */
 int fgmm_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *cdf_out);
 

@@ -16,7 +16,16 @@ With `--arithmetic bf16x6` the bf16x6 form (fgmm_conv16.hip; profiles/conv_bf16x
 layers: the whole call - per layer the split, conv16_kernel and the flagged-items launch - against the exact handle and torch in the same
 process, and conv16_kernel alone (the device durations torch's profiler records for it over `samples` calls, summed per call) as a share
 of the BF16 roof (419.5 TF of six part products per product, as profiles/ckbd_context_bf16x6.md).
-usage: python scripts/conv_stack_bench.py [samples=20] [inner=5] [warm=3] [--arithmetic bf16x6]"""
+With `--grad` (profiles/conv_grad.md) the script measures ONLY forward + backward under autograd - ConvStack on an input that requires
+grad (header section 5f: ops.conv_layer per layer, the weights packed at every call, fgmm_conv.hip's gradient staging and fgmm_conv_grad.hip)
+against the torch modules' forward + backward (MIOpen), gradients of the input and of every parameter - on the two h_s shapes and the
+channel context, alternating sample by sample as above; and the largest difference of a gradient of either path from float64 autograd of
+the same modules (and of the two paths from each other), relative to that gradient's largest element.
+With `--trace` (profiles/conv_grad.md, the last section) nothing is timed: on the same three workloads the script names where the library's
+binary32 forward and float64 autograd take DIFFERENT activation branches - per layer the number of such elements, and the first one's
+index, its float64 pre-activation and the library's output - and gives the gradients' largest difference from float64 twice: against
+float64 with its own branches, and against float64 made to take the library's branch at every element.
+usage: python scripts/conv_stack_bench.py [samples=20] [inner=5] [warm=3] [--arithmetic bf16x6 | --grad | --trace]"""
 import json
 import os
 import sys
@@ -35,6 +44,10 @@ if "--arithmetic" in sys.argv:
     ARITH = sys.argv[at + 1]
     del sys.argv[at:at + 2]
 assert ARITH in ("f32", "bf16x6"), ARITH
+GRAD, TRACE = "--grad" in sys.argv, "--trace" in sys.argv
+for flag in ("--grad", "--trace"):
+    if flag in sys.argv:
+        sys.argv.remove(flag)
 samples = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 inner = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 3
@@ -114,6 +127,75 @@ def flops(net, x):
 
 out = {"compute_units": torch.cuda.get_device_properties(0).multi_processor_count, "samples": samples, "calls_per_sample": inner, "warmup_samples": warm,
        "roof_tf": ROOF_TF}
+def grad_leg(name, net, shape):
+    """forward + backward of ConvStack(net) against the torch modules'; and both paths' gradients against float64 autograd of the same modules"""
+    import copy
+
+    x, op, params = torch.randn(shape, device=dev, requires_grad=True), ConvStack(net), list(net.parameters())
+    g = torch.randn_like(net(x))
+    paths = {"kernel": lambda: torch.autograd.grad(op(x), [x] + params, g), "torch": lambda: torch.autograd.grad(net(x), [x] + params, g)}
+    for _ in range(warm):
+        for fn in paths.values():
+            sample(fn)
+    t = {k: [] for k in paths}
+    for _ in range(samples):
+        for k, fn in paths.items():
+            t[k].append(sample(fn)[0])
+    res = {k: {"median_ms": round(float(np.median(v)), 5), "min_ms": round(float(np.min(v)), 5)} for k, v in t.items()}
+    res["kernel_over_torch"] = round(res["kernel"]["median_ms"] / res["torch"]["median_ms"], 4)
+    net64, x64 = copy.deepcopy(net).double(), x.detach().double().requires_grad_(True)
+    exact = torch.autograd.grad(net64(x64), [x64] + list(net64.parameters()), g.double())
+    rel = lambda a, b: float((a.double() - b.double()).abs().max() / b.abs().max())  # of a gradient's largest element
+    names = ["input"] + [n for n, _ in net.named_parameters()]
+    got = {k: fn() for k, fn in paths.items()}
+    for k in paths:  # every gradient of the path against float64: the largest, and whose it is
+        worst = max(range(len(names)), key=lambda i: rel(got[k][i], exact[i]))
+        res[k]["max_rel_grad_diff_to_float64"] = {"gradient": names[worst], "value": rel(got[k][worst], exact[worst])}
+    res["max_rel_grad_diff_to_torch"] = max(rel(a, b) for a, b in zip(got["kernel"], got["torch"]))
+    return res
+
+
+def trace_leg(net, shape):
+    """the activation branches in which the library's forward and float64 autograd differ, and the gradients with and without them"""
+    import copy
+
+    from flashgmm_amd.ops import conv_layer
+
+    layers, x = ConvStack.check(list(net)), torch.randn(shape, device=dev, requires_grad=True)
+    outs, v = [], x
+    for conv, act, slope, shuffle in layers:  # the library's layers one by one: an output's sign is its pre-activation's (slope >= 0)
+        v = conv_layer(v, conv.weight, conv.bias, ("none", "leaky_relu", "relu")[act], slope, shuffle)
+        outs.append(v.detach())
+    g = torch.randn_like(v)
+    got = torch.autograd.grad(v, [x] + list(net.parameters()), g)
+    net64 = copy.deepcopy(net).double()
+
+    def float64(branches):
+        """-> the pre-activations and the gradients of the float64 stack; branches: None = its own, else per layer the mask of the positive branch"""
+        x64, pre = x.detach().double().requires_grad_(True), []
+        v = x64
+        for j, (conv, act, slope, shuffle) in enumerate(ConvStack.check(list(net64))):
+            z = nn.functional.pixel_shuffle(nn.functional.conv2d(v, conv.weight, conv.bias, padding=conv.kernel_size[0] // 2), shuffle)
+            pre.append(z.detach())
+            v = z if act == 0 else torch.where(z > 0 if branches is None else branches[j], z, z * slope)
+        return pre, torch.autograd.grad(v, [x64] + list(net64.parameters()), g.double())
+
+    (pre, own), (_, forced) = float64(None), float64([o > 0 for o in outs])
+    rel = lambda a, b: max(float((u.double() - w).abs().max() / w.abs().max()) for u, w in zip(a, b))  # of a gradient's largest element
+    res = {"differing_branches_per_layer": [], "max_rel_grad_diff_to_float64": rel(got, own), "max_rel_grad_diff_to_float64_on_the_library_s_branches": rel(got, forced)}
+    for j, (z, o, (_, act, *_)) in enumerate(zip(pre, outs, layers)):
+        at = torch.nonzero(((z > 0) != (o > 0)).flatten() & bool(act))[:, 0]
+        res["differing_branches_per_layer"].append(int(at.numel()))
+        if at.numel() and "first" not in res:
+            res["first"] = {"layer": j, "flat_index": int(at[0]), "float64_pre_activation": float(z.flatten()[at[0]]), "library_output": float(o.flatten()[at[0]])}
+    return res
+
+
+if GRAD or TRACE:
+    for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1, N_, 8, 12)), ("channel_context", cc, (1, 128, 135, 240))):
+        out[name + (" forward+backward" if GRAD else " branches")] = grad_leg(name, net, shape) if GRAD else trace_leg(net, shape)
+    print(json.dumps(out))
+    sys.exit(0)
 for name, net, shape in (("h_s N=24", h_s, (24, N_, 8, 12)), ("h_s N=1", h_s, (1, N_, 8, 12)), ("channel_context", cc, (1, 128, 135, 240)),
                          ("elic_h_s N=1", elic_h_s, (1, N_, 34, 60)), ("elic_h_s N=16", elic_h_s, (16, N_, 34, 60)),
                          ("elic_h_s stride-2 layers N=1", elic_h_s[:4], (1, N_, 34, 60)), ("elic_h_s stride-2 layers N=16", elic_h_s[:4], (16, N_, 34, 60))):
